@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- aligned base-pairs/sec of the daligner block-vs-block hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the whole HPCdaligner block-pair plan (every block against itself and all
 lower blocks, both orientations) of ONE database:
@@ -17,17 +17,24 @@ lower blocks, both orientations) of ONE database:
 All read blocks (forward and reverse-complemented bases) are resident in HBM on every rank before the
 timed region; the timed region covers k-mer index builds, seed merge + sort, band filter +
 Local_Alignment waves, the device->host copy of the alignments, the host tail and the sorted .las files
-written to tmpfs.  After the timed region every .las of the last step is checked against the md5 of the
-file the reference daligner wrote for the same database (tests/golden/config{2,3}_ref_md5.txt).
+written to tmpfs.
 
 Prints ONE JSON line (rank 0) with the contract fields plus
   roofline      dominant kernel, HIP-event timed on the library's stream; PMC-derived fractions from profiles/
+
+A plain run does nothing else: set-up, warm-up, the K timed steps, the line.  --dump-outputs DIR writes the .las records
+of the last timed step as .npy files (dump_outputs).  --full adds everything below (each leg can be left out with its
+--no-* option):
+  ms_per_step_synced  3 more steps, each on its own between syncs
+  parity        every .las of the last step against the md5 of the file the reference daligner wrote for the same
+                database (tests/golden/config{2,3}_ref_md5.txt)
   cpu_baseline  (N == 1) the compiled reference daligner (oracle/_ref) on the host cores over the WHOLE plan
   end_to_end    (N == 1) the contract's wall of SURVEY 8(d), "DB load -> last .las closed": the plan through
                 damar_amd/bin/daligner -P from cold (process start, DB read from tmpfs, PCIe, index builds)
   one_gpu_same_workload (N > 1) rank 0 alone on the same database after the timed region: the measured
                 strong-scaling speedup, independent of the driver's N = 1 run on config 2
   trace_expand  (N == 1, not part of `value`) SURVEY 8(f)4, Compute_Trace_PTS on the block-1 file.
+  legs          (N == 1) config 4's first 24 blocks, config 3 and config 5 (datander), each a run of its own.
 """
 import argparse
 import hashlib
@@ -177,6 +184,72 @@ def sum_las(out_dir):
                 bp += b
                 tv += os.path.getsize(os.path.join(dp, f)) - 12 - 40 * n
     return nrec, bp, tv
+
+
+DUMP_RECORDS = 1 << 18            # records kept by --dump-outputs: a fixed, seeded sample where a step writes more
+DUMP_TRACE_VALUES = 1 << 23       # trace values kept at most (float32: 32 MB)
+
+
+def dump_outputs(out_dir, dst):
+    """--dump-outputs: what a caller of the timed path receives from its last step, the .las files of every block pair, as
+    .npy files under dst (the same arguments give the same inputs, so two builds can be compared file for file):
+      files.npy    float64, one row per .las (sorted by path): A block, B block, records and the sums over all of them of
+                   tlen, diffs, aepos - abpos, bepos - bbpos and the trace values
+      records.npy  float64, DUMP_RECORDS records drawn over all files with a fixed seed (every record where there are
+                   fewer), in file order: A block, B block, tlen, diffs, abpos, bbpos, aepos, bepos, flags, aread, bread
+      traces.npy   float32, the trace values of every 8th record of records.npy, one after the other (their lengths are the
+                   tlen column), up to DUMP_TRACE_VALUES values"""
+    import re
+    import struct
+    import numpy as np
+    paths = sorted(os.path.join(dp, f) for dp, _, fs in os.walk(out_dir) if "_parts" not in dp for f in fs if f.endswith(".las"))
+    counts = []
+    for p in paths:
+        with open(p, "rb") as f:
+            counts.append(struct.unpack("<q", f.read(8))[0])
+    total = sum(counts)
+    if total > DUMP_RECORDS:
+        pick = np.sort(np.random.default_rng(0).choice(total, DUMP_RECORDS, replace=False))
+    else:
+        pick = np.arange(total)
+    tpick = pick[::8]
+    files, recs, traces, ntrace, base = [], [], [], 0, 0
+    tlen_at = struct.Struct("<i").unpack_from
+    for p, n in zip(paths, counts):
+        raw = open(p, "rb").read()
+        buf = np.frombuffer(raw, np.uint8)
+        tbytes = 1 if struct.unpack_from("<i", raw, 8)[0] <= 125 else 2
+        offs = np.empty(n, np.int64)
+        off = 12
+        for i in range(n):
+            offs[i] = off
+            off += 40 + tbytes * tlen_at(raw, off)[0]
+        assert off == len(raw), (p, off, len(raw))
+        # the 40 bytes of a record: tlen, diffs, abpos, bbpos, aepos, bepos, flags, aread, bread and 4 bytes of padding
+        rec = buf[offs[:, None] + np.arange(36)].view("<i4").astype(np.int64)
+        trace = np.ones(len(buf), bool)
+        trace[:12] = False
+        trace[(offs[:, None] + np.arange(40)).ravel()] = False
+        tvals = buf[trace] if tbytes == 1 else buf[trace].view("<u2")
+        m = re.search(r"\.(\d+)\.[^./]+\.(\d+)\.las$", p)
+        ab = [int(m.group(1)), int(m.group(2))] if m else [-1, -1]
+        files.append(ab + [n, rec[:, 0].sum(), rec[:, 1].sum(), (rec[:, 4] - rec[:, 2]).sum(), (rec[:, 5] - rec[:, 3]).sum(),
+                           tvals.sum(dtype=np.int64)])
+        mine = pick[(pick >= base) & (pick < base + n)] - base
+        recs.append(np.hstack([np.tile(ab, (len(mine), 1)), rec[mine]]))
+        for i in tpick[(tpick >= base) & (tpick < base + n)] - base:
+            t = int(rec[i, 0])
+            if ntrace + t > DUMP_TRACE_VALUES:          # full: no trace of a later record either
+                tpick = tpick[:0]
+                break
+            o = int(offs[i]) + 40
+            traces.append(np.frombuffer(raw, "<u1" if tbytes == 1 else "<u2", count=t, offset=o))
+            ntrace += t
+        base += n
+    os.makedirs(dst, exist_ok=True)
+    np.save(os.path.join(dst, "files.npy"), np.array(files, np.float64).reshape(-1, 8))
+    np.save(os.path.join(dst, "records.npy"), np.vstack(recs).astype(np.float64) if recs else np.zeros((0, 11)))
+    np.save(os.path.join(dst, "traces.npy"), np.concatenate(traces).astype(np.float32) if traces else np.zeros(0, np.float32))
 
 
 def cpu_baseline(dbdir, root, nblocks, aligned_bp):
@@ -569,17 +642,21 @@ def relaunch_under_torchrun(ngpus, argv=None, run=subprocess.run):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="one rank per GPU (default: the launcher's WORLD_SIZE, else 1)")
-    ap.add_argument("--steps", type=int, default=5)       # (2 until round 4: a step is 0.25 s, and two steps are mostly the pipeline filling and draining)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps")       # (2 until round 4: a step is 0.25 s, and two steps are mostly the pipeline filling and draining)
     ap.add_argument("--warmup", type=int, default=2)      # (the second warm-up step allocates the second pinned landing buffer of the host pipeline)
     ap.add_argument("--config", type=int, default=0, help="BASELINE config of the database: 2 or 3 (default: 2 on one GPU, 3 on several)")
     ap.add_argument("--threads-param", type=int, default=16, help="daligner -j (slice rule only; the reference md5s were made with -j16)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-trace", action="store_true", help="skip the trace-expansion leg (SURVEY 8(f)4)")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end_to_end leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the .las records of the last timed step to DIR/*.npy")
+    ap.add_argument("--full", action="store_true", help="also the synced steps, the parity check and the legs below")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-trace", action="store_true", help="with --full: skip the trace-expansion leg (SURVEY 8(f)4)")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the end_to_end leg")
     ap.add_argument("--sync-steps", action="store_true", help="barrier + device sync around EVERY step (rounds 1-2), not around the K steps")
-    ap.add_argument("--no-legs", action="store_true", help="skip the config-4 (lead 24 blocks), config-3 and config-5 legs")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the config-4 (lead 24 blocks), config-3 and config-5 legs")
     ap.add_argument("--keep", action="store_true")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus is None:                 # `torchrun --nproc-per-node N bench.py`: the launcher says how many
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
@@ -640,7 +717,7 @@ def main():
         nblocks = int(open(os.path.join(work, "SIM.db")).read().split("blocks =")[1].split()[0])
         dbprefix = os.path.join(work, "SIM")
         e2e = None
-        if world == 1 and not args.no_e2e:
+        if world == 1 and args.full and not args.no_e2e:
             try:
                 e2e = end_to_end(work, "SIM", nblocks, cfg["md5"])
             except Exception as e:
@@ -725,6 +802,8 @@ def main():
         tim, cnts, last_out, nmine, builds, nmatch, nlaunch = {}, [0, 0, 0], None, 0, 0, 0, 0
         wave = [0, 0, 0]              # band cells, wave steps per alignment pass, wave-loop iterations (counted by the kernel)
         elapsed, last_out, plans, nmine = run_steps("s", args.steps, not pipelined)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(last_out, args.dump_outputs)
         for plan in plans:
             wave = [x + y for x, y in zip(wave, plan.wave)]
             builds += plan.index_builds
@@ -734,7 +813,7 @@ def main():
                 tim[k] = tim.get(k, 0.) + v
             cnts = [c + d for c, d in zip(cnts, plan.counts)]
         synced_ms = None
-        if pipelined and world == 1 and args.steps > 0:
+        if args.full and pipelined and world == 1:
             # the same measurement with every step on its own between syncs (the edge of a step exposed), 3 steps
             es, so, _, _ = run_steps("y", 3, True)
             synced_ms = 1e3 * es / 3
@@ -777,7 +856,7 @@ def main():
                                  [round(float(x), 3) for x in r.tolist()])) for r in rows]
 
         one_gpu = None
-        if world > 1:
+        if world > 1 and args.full:
             # the same database on ONE GPU (rank 0, the others wait): the measured strong-scaling reference
             barrier()
             if rank == 0:
@@ -792,7 +871,7 @@ def main():
                 shutil.rmtree(o1, ignore_errors=True)
             barrier()
 
-        if world > 1 and not args.no_e2e:
+        if world > 1 and args.full and not args.no_e2e:
             # the contract's wall on N GPUs: the C driver's node mode (rank 0 starts it, the other ranks wait; the
             # workers it forks share the GPUs with the idle ranks of this job)
             barrier()
@@ -805,7 +884,7 @@ def main():
         if rank == 0:
             steps = max(1, args.steps)
             nrec, bp, trace_vals = sum_las(last_out)
-            parity = check_against_reference(last_out, cfg["md5"])
+            parity = check_against_reference(last_out, cfg["md5"]) if args.full else None
             nmatch = float(nmatch) / steps                   # comparisons (block pair x orientation) per step, all ranks
             nlaunch = float(nlaunch) / steps                 # launches of the report kernel they took
             kern = {"report2_kernel": tim.get("report", 0.),
@@ -872,7 +951,7 @@ def main():
                             "(summed over ranks): " + ", ".join("%s=%.1f" % (k, v / steps) for k, v in sorted(tim.items()))}
             value = bp * args.steps / elapsed
             cpu = trace = None
-            if world == 1 and not args.no_cpu:
+            if world == 1 and args.full and not args.no_cpu:
                 try:
                     cpu = cpu_baseline(work, "SIM", nblocks, bp)
                 except Exception as e:           # the baseline is reported, never required
@@ -881,13 +960,13 @@ def main():
                 e2e["value"] = bp / e2e["wall_s"]
                 if cpu and cpu.get("value"):
                     e2e["vs_cpu_whole_plan"] = e2e["value"] / cpu["value"]
-            if world == 1 and not args.no_trace:
+            if world == 1 and args.full and not args.no_trace:
                 try:
                     trace = trace_expand_leg(work, "SIM", last_out, not args.no_cpu)
                 except Exception as e:
                     trace = {"error": str(e)}
             legs = None
-            if world == 1 and not args.no_legs:
+            if world == 1 and args.full and not args.no_legs:
                 for b in blocks.values():            # give the headline's blocks back before the other databases come
                     b.close()
                 blocks.clear()
@@ -941,7 +1020,7 @@ def main():
                                 "between steps; every step builds its own indexes and writes its own files)" % steps) if pipelined else
                                "every step on its own between barrier + device sync; the step times added up") +
                               "; `value` has the blocks already in HBM when the clock starts (block read, reverse complement and "
-                              "upload are NOT in it) -- the wall from the DB files on is `contract`",
+                              "upload are NOT in it) -- the wall from the DB files on is `contract` (--full)",
                     "contract": contract,
                     "higher_is_better": True, "scaling": "strong",
                     "vs_baseline": None,       # the reference publishes no number for this metric (vs the CPU: contract.vs_cpu)
@@ -978,6 +1057,9 @@ def main():
                 # the N = 1 line of a driver's scaling run is config 2: the like-for-like reference of THIS line is here
                 line["scale_ref"] = {"value": bp / one_gpu, "unit": "aligned bp/s", "n_gpus": 1,
                                      "what": "the same database and plan on ONE GPU of this job (rank 0 alone, after the timed region)"}
+            if not args.full:                # a plain run: the headline and what its timed steps counted themselves
+                for k in ("ms_per_step_synced", "contract", "parity", "cpu_baseline", "end_to_end", "trace_expand", "legs"):
+                    del line[k]
             print(json.dumps(line))
             sys.stdout.flush()
         barrier()

@@ -33,7 +33,7 @@ shutil.rmtree(work)
 for q in (None, "2", "3"):
     env = dict(os.environ)
     if q: env["GPU_MAX_HW_QUEUES"] = q
-    r = subprocess.run([sys.executable, os.path.join(bench.ROOT, "bench.py"), "--no-cpu", "--no-legs", "--no-e2e", "--no-trace"], env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
+    r = subprocess.run([sys.executable, os.path.join(bench.ROOT, "bench.py"), "--full", "--no-cpu", "--no-legs", "--no-e2e", "--no-trace"], env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
     import json
     l = [x for x in r.stdout.split("\n") if x.startswith("{")]
     d = json.loads(l[-1]) if l else {}

@@ -4,7 +4,7 @@
 #   2. SQ instruction / activity / LDS counters, separate --pmc passes         -> pmc_summary.txt
 #   3. TCC FETCH_SIZE / WRITE_SIZE of the report kernel, separate passes        -> traffic_summary.txt
 #   4. the issue-rate calibration (tools/roofcal.hip) under the same counters   -> roofcal*.txt
-#   5. the plain bench line (with cpu_baseline, end_to_end)                     -> bench.json
+#   5. the full bench line (--full: with cpu_baseline, end_to_end)             -> bench.json
 # usage: bash scripts/gpu_profile_round.sh [packed]
 set -e
 ROOT=$(pwd)
@@ -27,6 +27,6 @@ if [ -f build/prof/libdamar_hip.so ]; then
   timeout -k 10 300 python3 scripts/prof_la.py > $OUT/prof_counters.txt 2> $OUT/prof.err || echo "prof variant failed"
   echo "prof done"
 fi
-timeout -k 10 500 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 500 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 echo "bench done"
 tail -c 900 $OUT/bench.json

@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 for v in "X=1" "$@"; do
   echo "== $v"
-  env $v timeout -k 10 400 python bench.py --steps 1 --warmup 1 --no-cpu --no-trace --no-e2e 2>/dev/null | python3 -c "
+  env $v timeout -k 10 400 python bench.py --full --steps 1 --warmup 1 --no-cpu --no-trace --no-e2e 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 for k,v in d['legs'].items():

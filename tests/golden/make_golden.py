@@ -407,6 +407,39 @@ def trace_md5():
             print("%s: %d dumps" % (fixture, len(lines)))
 
 
+def simulator_md5():
+    """The reference's simulator | FA2db ; DBsplit of tests/test_host.py::test_simdb_equals_simulator_fa2db_dbsplit ->
+    simulator_ref_md5.txt (md5 per database file; of the .idx only the fields the reference defines)."""
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_host
+    with tempfile.TemporaryDirectory() as d:
+        dig = test_host.simulator_ref_digest(REF, d)
+    with open(os.path.join(HERE, "simulator_ref_md5.txt"), "w") as f:
+        for name, md5 in sorted(dig.items()):
+            f.write("%s %s\n" % (md5, name))
+    print(dig)
+
+
+def random_md5():
+    """md5 of the .las files the reference daligner writes for the 32 seeded option combinations of
+    tests/test_oracle_golden.py::test_oracle_random_option_combinations_equal_reference -> random_ref_md5.txt"""
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import conftest
+    import test_oracle_golden
+    lines = []
+    with tempfile.TemporaryDirectory() as d:
+        for n, gold, opts, blocks in test_oracle_golden.random_option_cases():
+            w = os.path.join(d, "r%d" % n)
+            conftest.link_db(os.path.join(HERE, gold), w)
+            run([os.path.join(REF, "daligner")] + opts + blocks, w, stdout=subprocess.DEVNULL)
+            lines += ["%s %d %s" % (m, n, rel) for rel, m in sorted(test_oracle_golden.las_md5s(w).items())]
+    with open(os.path.join(HERE, "random_ref_md5.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("random_ref_md5.txt: %d files" % len(lines))
+
+
 # BASELINE config 4 (`simulator 248 -c80 -m15000 -s3000 -e.15 -r4`, DBsplit -s78 -> 256 blocks) is too
 # large to run whole anywhere but on an 8-GPU node; parity is checked on seeded random samples of its
 # block pairs.  "lead": pairs among the first C4_LEAD blocks, which `simdb -N<C4_LEAD>` reproduces
@@ -508,6 +541,10 @@ def main():
         return trace_md5()
     if sys.argv[1:] == ["fa2db"]:
         return fa2db_md5()
+    if sys.argv[1:] == ["simulator"]:
+        return simulator_md5()
+    if sys.argv[1:] == ["random"]:
+        return random_md5()
     import tempfile
     dbs = {}
     only = set(sys.argv[1:])

@@ -55,23 +55,16 @@ def test_fixtures_reach_the_rare_branches(built, tmp_path, name, what):
     assert got[what] > 0, got
 
 
-def test_oracle_random_option_combinations_equal_reference(built, tmp_path):
-    """The same kind of sweep one level down: the oracle against the REAL reference binary
-    (oracle/_ref/daligner, present wherever /root/reference was at build time) over random
-    combinations of options, so that the oracle is pinned across the option space and not only on
-    the per-family golden cases."""
+def random_option_cases():
+    """[(n, golden database, options, blocks)]: the 32 seeded combinations of test_oracle_random_option_combinations_equal_reference
+    (also read by make_golden.py `random`, which writes the reference's md5s of them)."""
     import random
-    import subprocess
-    from conftest import GOLDEN, ROOT, link_db
-    ref = os.path.join(ROOT, "oracle", "_ref", "daligner")
-    if not os.path.exists(ref):
-        pytest.skip("oracle/_ref/daligner not built")
     rng = random.Random(77)
     # three databases: two blocks with mask tracks, one block of reads with tandem arrays (many seeds per pair, Bridge and
     # Fusion in the host tail), one block of long reads (wide bands); 32 combinations in all
+    out = []
     for n in range(32):
         gold = ("mask_dust", "tandem", "long", "mask_dust")[n % 4]
-        dbdir = os.path.join(GOLDEN, gold)
         # (k = 10 on the repeat-rich reads costs the reference minutes: 13 700 mutual matches per k-mer pair)
         opts = ["-k%d" % rng.choice([10, 12, 14, 16, 18] if gold == "mask_dust" else [12, 14, 16, 18]),
                 "-w%d" % rng.choice([4, 5, 6, 7]), "-h%d" % rng.choice([25, 35, 50]),
@@ -83,16 +76,44 @@ def test_oracle_random_option_combinations_equal_reference(built, tmp_path):
             opts += rng.choice([[], ["-mdust"], ["-mdust", "-mrnd"]])
         opts += ["-b"] if rng.random() < .3 else []
         blocks = ["G.2", "G.2", "G.1"] if gold == "mask_dust" else ["G.1", "G.1"]
-        rdir, odir = os.path.join(str(tmp_path), "r%d" % n), os.path.join(str(tmp_path), "o%d" % n)
-        link_db(dbdir, rdir)
+        out.append((n, gold, opts, blocks))
+    return out
+
+
+def las_md5s(d):
+    """{path relative to d: md5} of every .las under d"""
+    import hashlib
+    out = {}
+    for dp, _, fs in os.walk(d):
+        for f in fs:
+            if f.endswith(".las"):
+                out[os.path.relpath(os.path.join(dp, f), d)] = hashlib.md5(open(os.path.join(dp, f), "rb").read()).hexdigest()
+    return out
+
+
+def test_oracle_random_option_combinations_equal_reference(built, tmp_path):
+    """The same kind of sweep one level down: the oracle against the REAL reference daligner over random
+    combinations of options, so that the oracle is pinned across the option space and not only on
+    the per-family golden cases.  The reference's files are held as md5s (tests/golden/random_ref_md5.txt, made by
+    make_golden.py `random`); where oracle/_ref/daligner exists, the reference also runs live."""
+    import subprocess
+    from conftest import GOLDEN, ROOT, link_db
+    ref = os.path.join(ROOT, "oracle", "_ref", "daligner")
+    want = {}
+    for ln in open(os.path.join(GOLDEN, "random_ref_md5.txt")):
+        m, n, rel = ln.split()
+        want.setdefault(int(n), {})[rel] = m
+    for n, gold, opts, blocks in random_option_cases():
+        dbdir = os.path.join(GOLDEN, gold)
+        odir = os.path.join(str(tmp_path), "o%d" % n)
         link_db(dbdir, odir)
-        for exe, d in ((ref, rdir), (os.path.join(ROOT, "oracle", "oracle_daligner"), odir)):
-            subprocess.run([exe] + opts + blocks, cwd=d, check=True, stdout=subprocess.DEVNULL)
-        nlas = 0
-        for dp, _, fs in os.walk(rdir):
-            for f in fs:
-                if f.endswith(".las"):
-                    rel = os.path.relpath(os.path.join(dp, f), rdir)
-                    assert open(os.path.join(dp, f), "rb").read() == open(os.path.join(odir, rel), "rb").read(), (gold, opts, rel)
-                    nlas += 1
-        assert nlas >= (2 if gold == "mask_dust" else 1), (gold, opts)
+        subprocess.run([os.path.join(ROOT, "oracle", "oracle_daligner")] + opts + blocks, cwd=odir, check=True,
+                       stdout=subprocess.DEVNULL)
+        got = las_md5s(odir)
+        assert got == want[n], (gold, opts)
+        if os.path.exists(ref):
+            rdir = os.path.join(str(tmp_path), "r%d" % n)
+            link_db(dbdir, rdir)
+            subprocess.run([ref] + opts + blocks, cwd=rdir, check=True, stdout=subprocess.DEVNULL)
+            assert las_md5s(rdir) == got, (gold, opts)
+        assert len(got) >= (2 if gold == "mask_dust" else 1), (gold, opts)
