@@ -108,6 +108,11 @@ def _lib():
         L.damar_local_alignment_batch.restype = C.c_int
         L.damar_last_timings.argtypes = [C.POINTER(C.c_double)]
         L.damar_last_counters.argtypes = [C.POINTER(c_int64)]
+        L.damar_last_slabs.argtypes = [C.POINTER(C.c_int), C.POINTER(c_int64), C.c_int]
+        L.damar_last_slabs.restype = C.c_int
+        L.damar_slab_totals.argtypes = [C.POINTER(c_int64)]
+        L.damar_slab_cut.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_uint64, C.POINTER(C.c_int), C.POINTER(c_int64), C.c_int]
+        L.damar_slab_cut.restype = C.c_int
         L.damar_bench_sort_u32.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_uint32]
         L.damar_bench_sort_u32.restype = C.c_double
         _proto_done = True
@@ -167,6 +172,38 @@ def counters():
     a = (c_int64 * 8)()
     L.damar_last_counters(a)
     return list(a)
+
+
+def last_slabs():
+    """Slab table of the last damar_match: (b_lo[0 .. n], hits[0 .. n-1]); n = 1 for a comparison that was not split."""
+    L = _lib()
+    n = L.damar_last_slabs(None, None, 0)
+    b = (C.c_int * (n + 1))()
+    h = (c_int64 * n)()
+    L.damar_last_slabs(b, h, n)
+    return list(b), list(h)
+
+
+def slab_totals():
+    """(seed stages run, comparisons split) of the last damar_match / damar_match_batch."""
+    L = _lib()
+    a = (c_int64 * 2)()
+    L.damar_slab_totals(a)
+    return a[0], a[1]
+
+
+def slab_cut(hits, cap):
+    """The greedy cut of B reads into slabs (host arithmetic): (b_lo, sums), or the library's error code (< 0: read
+    -(code + 1) alone exceeds cap)."""
+    L = _lib()
+    n = len(hits)
+    h = (C.c_uint64 * max(n, 1))(*[int(x) for x in hits])
+    b = (C.c_int * (n + 2))()
+    s = (c_int64 * (n + 1))()
+    got = L.damar_slab_cut(h, n, int(cap), b, s, n + 1)
+    if got <= 0:
+        return got
+    return list(b[:got + 1]), list(s[:got])
 
 
 def daligner_binary():

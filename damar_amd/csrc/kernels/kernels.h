@@ -118,6 +118,7 @@ typedef struct
   DevBlock ablk, bblk;
   int  pbits, abits;          /* key = bread << (abits+pbits) | aread << pbits | apos, all of it << dbits */
   int  dbits;                 /* > 0: bpos rides in the key's low dbits (packed seeds, no vals array); 0: diag in vals */
+  u32  b_lo, b_hi;            /* a comparison run in slabs: the B reads of this slab (merge_range; the sweeps do not look) */
 } MergeArgs;
 
 typedef struct { u32 b0, b1, ja, ia;                   /* per tile of A entries: its piece of B, the ends of its border runs, */
@@ -132,9 +133,17 @@ u32    damar_merge_tiles(u32 alen);
 void   damar_launch_merge_count(const MergeArgs *m, void *work, unsigned long long *gram, u32 ngram, hipStream_t st);
 /* pid (optional): the read pair of every seed, bread << abits | aread, for the early cut */
 void damar_launch_merge_emit(const MergeArgs *m, void *work, u64 nhits, u64 *keys, u32 *vals, u32 *pid, hipStream_t st);
+/* A comparison run in slabs of B reads.  Both work on what a COUNT sweep (with every cap over the whole code run) has left
+   in the workspace: hist[r] += the seed pairs with bread r (hist zeroed by the caller, m->bblk.nreads entries); and, before
+   the scan of the tile counts, the counts narrowed to the B reads [m->b_lo, m->b_hi), after which the scan and EMIT yield
+   that range's seed pairs only. */
+void damar_launch_merge_bread_hist(const MergeArgs *m, void *work, unsigned long long *hist, hipStream_t st);
+void damar_launch_merge_range(const MergeArgs *m, void *work, hipStream_t st);
 /* the early cut (seed_merge.hip): heads of the runs report_thread enters, on the SORTED pair ids; their pairs into a
    bitmap over the pair ids; the seeds of those pairs out of the unsorted seeds */
-void damar_launch_pair_heads_ids(const u32 *pids, u64 nhits, int abits, int minhit, int nshift,
+/* (off, gtotal, here and below: the seeds are the stretch [off, off + nhits) of a sorted list of gtotal -- a slab of B reads;
+   the reference's thread slices are those of the whole list.  0 and nhits for a comparison in one piece) */
+void damar_launch_pair_heads_ids(const u32 *pids, u64 nhits, u64 off, u64 gtotal, int abits, int minhit, int nshift,
                                  u64 *send, u64 *bits, void *scan_work, u64 *total_dev, u32 *heads, hipStream_t st);
 void damar_launch_pair_bitmap(const u32 *pids, const u32 *heads, u32 nheads, int abits, u32 b_lo, u32 b_hi, u32 *bitmap,
                               hipStream_t st);
@@ -142,14 +151,14 @@ void damar_launch_seed_cut_count(const u64 *keys, u64 nhits, int pbits, const u3
                                  hipStream_t st);
 void damar_launch_seed_cut_scatter(const u64 *keys, const u32 *vals, u64 nhits, int pbits, const u32 *bitmap,
                                    const u32 *toff, u64 *okeys, u32 *ovals, hipStream_t st);
-void damar_launch_pair_heads(const u64 *keys, u64 nhits, int pbits, int abits, int minhit, int nshift,
+void damar_launch_pair_heads(const u64 *keys, u64 nhits, u64 off, u64 gtotal, int pbits, int abits, int minhit, int nshift,
                              u64 *send /* 64 entries of scratch */, u64 *bits, void *scan_work, u64 *total_dev,
                              u32 *heads, hipStream_t st);
 /* run heads + screen in one pass (pair_work_mark): the first half leaves the number of work items in *total_dev */
 /* (unsorted: the seed sort went over the read pair only -- the screen takes a run's seeds in any order, the caller puts the
    kept heads' runs in order of their A positions (damar_launch_order_runs) unless total_dev[1] != 0: a run too long for that,
    sort over all the bits) */
-void damar_launch_pair_work(u64 *keys, const u32 *vals, u64 nhits, int ppos, int dbits, int abits, int minhit, int nshift,
+void damar_launch_pair_work(u64 *keys, const u32 *vals, u64 nhits, u64 off, u64 gtotal, int ppos, int dbits, int abits, int minhit, int nshift,
                             u64 *send /* 64 entries of scratch */, u64 *bits, void *scan_work, u64 *total_dev /* [2] */,
                             int binshift, int kmer, int hitmin, u32 b_lo, u32 b_hi, int unsorted, hipStream_t st);
 /* (unsorted only) the runs of the work list's heads into the order of their A positions, in place */

@@ -789,6 +789,130 @@ void merge_emit(MergeArgs m, const MergeTile *__restrict__ tiles, const u32 *__r
     }
 }
 
+/***** a comparison in slabs of B reads ********************************************************************
+ * A comparison with more seed pairs than the seed arrays can hold (shim.hip match_front) is run in consecutive ranges
+ * of B reads.  Both kernels below work on what a COUNT sweep has left in the workspace -- per A entry the number of its
+ * hits and where its B run starts, under every rule of that sweep (the caps of filter.c:1248 / 1335 over the WHOLE code
+ * run, the self-comparison bounds of filter.c:1219-1246, -I) -- so neither restates a counting rule, and merge_fast,
+ * merge_sweep and merge_emit are the kernels of the comparison that is not split, instruction for instruction.
+ * The hits of an A entry are consecutive B entries of one code, and a code's entries are in (read, position) order:
+ * those of a range of B reads are a consecutive piece of them. */
+
+/* how many of bpos[jb, jb + n) -- entries of one code, reads ascending -- belong to reads below r */
+__device__ __forceinline__ u32 count_reads_below(const MergeArgs &m, u32 jb, u32 n, u32 r)
+{ if (r == 0)
+    return 0;
+  if (r >= m.bblk.nreads)
+    return n;
+  const int rp = m.bblk.rpbits;
+  if (rp == 0)
+    return count_below(m.bpos, jb, jb + n, m.bblk.boff[r]);
+  u32 a = jb, b = jb + n;
+  while (a < b)
+    { const u32 mid = (a + b) >> 1;
+      if ((m.bpos[mid] >> rp) < r) a = mid + 1; else b = mid;
+    }
+  return a - jb;
+}
+
+/* hist[r] += the seed pairs merge_emit would write with bread r: one workgroup per tile of A entries, the tile's hits
+ * dealt out to the lanes in emission order as in merge_emit.  Neighbouring hits of one A entry lie in few reads (long
+ * runs are what makes a comparison large), so a wavefront adds up each stretch of equal reads among its 64 hits before
+ * it touches memory: one 64-bit vector atomic per stretch. */
+__global__ __launch_bounds__(256)
+void merge_bread_hist(MergeArgs m, const MergeTile *__restrict__ tiles, const u32 *__restrict__ cnt, const u32 *__restrict__ jbg,
+                      unsigned long long *__restrict__ hist)
+{ SEED_PRIO(g_merge_prio);
+  __shared__ u32 loc[MT_A + 1];
+  __shared__ u32 sjb[MT_A];
+  __shared__ u32 sw4[4];
+  const int l = lane_id(), w = threadIdx.x >> 6;
+  const u32 tile = blockIdx.x;
+  const u32 a0 = tile * (u32) MT_A, a1 = min(m.alen, a0 + (u32) MT_A), nat = a1 - a0;
+  const u32 e0 = threadIdx.x * MT_PER;
+  u32 n[MT_PER], s = 0;
+  const bool packed = tiles[tile].pad[2] != 0;
+  const u32 pb0 = tiles[tile].b0;
+#pragma unroll
+  for (int k = 0; k < MT_PER; k++)
+    { const bool ok = e0 + k < nat;
+      const u32 v = ok ? cnt[a0 + e0 + k] : 0;
+      n[k] = packed ? v >> 16 : v;
+      sjb[e0 + k] = !ok ? 0 : packed ? pb0 + (v & 0xffffu) : jbg[a0 + e0 + k];
+      s += n[k];
+    }
+  u32 inc = (u32) wave_incl_scan_i((int) s);
+  if (l == 63) sw4[w] = inc;
+  __syncthreads();
+  u32 ex = inc - s;
+  for (int i = 0; i < 4; i++)
+    if (i < w) ex += sw4[i];
+#pragma unroll
+  for (int k = 0; k < MT_PER; k++)
+    { loc[e0 + k] = ex;
+      ex += n[k];
+    }
+  if (threadIdx.x == 255)
+    loc[MT_A] = ex;
+  __syncthreads();
+  const u32 T = loc[MT_A];
+  const int rp = m.bblk.rpbits;
+  for (u32 t0 = 0; t0 < T; t0 += 256)                         /* (a loop the lanes of a wavefront leave together) */
+    { const u32 t = t0 + threadIdx.x;
+      u32 rb = 0xffffffffu;
+      if (t < T)
+        { u32 lo = 0, hi = MT_A;                              /* last entry whose first hit is <= t */
+          while (hi - lo > 1)
+            { const u32 mid = (lo + hi) >> 1;
+              if (loc[mid] <= t) lo = mid; else hi = mid;
+            }
+          const u32 pb = m.bpos[sjb[lo] + (t - loc[lo])];
+          rb = rp ? pb >> rp : read_of_pos(m.bblk, pb);
+        }
+      const u32 below = (u32) __shfl_up((int) rb, 1);
+      const bool head = (l == 0) || below != rb;
+      const u64 hm = __ballot(head);
+      if (head && rb < m.bblk.nreads)
+        { const u64 above = (l == 63) ? 0ull : hm >> (l + 1);
+          const int len = above ? __ffsll((long long) above) : 64 - l;
+          atomicAdd(&hist[rb], (unsigned long long) len);
+        }
+    }
+}
+
+/* what the COUNT sweep left for an A entry, narrowed to the B reads [m.b_lo, m.b_hi), and the tile's hits added up again */
+__global__ __launch_bounds__(256)
+void merge_range(MergeArgs m, const MergeTile *__restrict__ tiles, u32 *__restrict__ tcount, u32 *__restrict__ cnt,
+                 u32 *__restrict__ jbg)
+{ SEED_PRIO(g_merge_prio);
+  __shared__ u64 red[4];
+  const u32 tile = blockIdx.x;
+  const u32 a0 = tile * (u32) MT_A, a1 = min(m.alen, a0 + (u32) MT_A);
+  const bool packed = tiles[tile].pad[2] != 0;
+  const u32 pb0 = tiles[tile].b0;
+  u64 sum = 0;
+  for (u32 i = a0 + threadIdx.x; i < a1; i += 256)
+    { const u32 v = cnt[i];
+      const u32 n = packed ? v >> 16 : v;
+      if (n == 0)
+        continue;
+      const u32 jb = packed ? pb0 + (v & 0xffffu) : jbg[i];
+      const u32 lo = count_reads_below(m, jb, n, m.b_lo), hi = count_reads_below(m, jb, n, m.b_hi);
+      const u32 nn = hi > lo ? hi - lo : 0;
+      if (packed)                                             /* (jb + lo - pb0 <= the piece's length: still 16 bits) */
+        cnt[i] = (nn << 16) | (jb + lo - pb0);
+      else
+        { cnt[i] = nn;
+          jbg[i] = jb + lo;
+        }
+      sum += nn;
+    }
+  const u64 T64 = block_sum_u64(sum, red);
+  if (threadIdx.x == 0)
+    tcount[tile] = (T64 > 0xffffffffull) ? 0xffffffffu : (u32) T64;
+}
+
+
 /* workspace: tile descriptors | tile counts (scanned in place by the caller) | cnt[alen] | jb[alen] */
 static size_t mw_tiles(u32 alen)  { return ((size_t) alen + MT_A - 1) / MT_A; }
 static size_t mw_off_counts(u32 alen) { return (mw_tiles(alen) * sizeof(MergeTile) + 255) & ~(size_t) 255; }
@@ -841,6 +965,25 @@ void damar_launch_merge_emit(const MergeArgs *m, void *work, u64 nhits, u64 *key
   hipLaunchKernelGGL(merge_emit, dim3(ntiles), dim3(256), 0, st, *m, (const MergeTile *) work, cnt, jb, toff, nhits, keys, vals, pid);
 }
 
+/* after a COUNT sweep over the whole comparison: hist[r] (zeroed by the caller, m->bblk.nreads entries) = seed pairs with bread r */
+void damar_launch_merge_bread_hist(const MergeArgs *m, void *work, unsigned long long *hist, hipStream_t st)
+{ if (m->alen == 0)
+    return;
+  const u32 ntiles = (u32) mw_tiles(m->alen);
+  const u32 *cnt = (const u32 *) ((char *) work + mw_off_cnt(m->alen)), *jb = (const u32 *) ((char *) work + mw_off_jb(m->alen));
+  hipLaunchKernelGGL(merge_bread_hist, dim3(ntiles), dim3(256), 0, st, *m, (const MergeTile *) work, cnt, jb, hist);
+}
+
+/* after a COUNT sweep, before the scan of its tile counts: the counts of the B reads [m->b_lo, m->b_hi) only */
+void damar_launch_merge_range(const MergeArgs *m, void *work, hipStream_t st)
+{ if (m->alen == 0)
+    return;
+  const u32 ntiles = (u32) mw_tiles(m->alen);
+  u32 *tcount = damar_merge_tile_counts(work, m->alen);
+  u32 *cnt = (u32 *) ((char *) work + mw_off_cnt(m->alen)), *jb = (u32 *) ((char *) work + mw_off_jb(m->alen));
+  hipLaunchKernelGGL(merge_range, dim3(ntiles), dim3(256), 0, st, *m, (const MergeTile *) work, tcount, cnt, jb);
+}
+
 /* flags[i] = 1 iff hit i starts a (bread,aread) run that report_thread would enter:
  * the run has >= minhit hits (filter.c:2215: hit i+minhit-1 is the same pair) and does
  * not start within the last minhit hits of its thread slice (filter.c:2212-2214:
@@ -848,26 +991,31 @@ void damar_launch_merge_emit(const MergeArgs *m, void *work, u64 nhits, u64 *key
  * first index >= (nhits*t)>>nshift whose bread differs from its predecessor's. */
 #define SCREEN_MAX   48
 #define SCREEN_PANEL 50000                     /* PANEL_SIZE, filter.c:73 */
-/* ends of the reference's NTHREADS slices: once per launch, not once per block */
+/* ends of the reference's NTHREADS slices: once per launch, not once per block.
+   keys holds the seeds [off, off + nhits) of a sorted list of gtotal seeds (a comparison run in slabs of B reads; off 0 and
+   gtotal = nhits otherwise) and both ends of that stretch are places where bread changes.  The slices are those of the
+   WHOLE list: an end that lies at or before the stretch's first seed is 0 here, one beyond its last seed is "never" --
+   the end of the stretch is a slice end only where the whole list has one. */
 template <typename K>
 __global__ __launch_bounds__(64)
-void slice_ends(const K *__restrict__ keys, u64 nhits, int bshift, int nshift, u64 *__restrict__ send)
+void slice_ends(const K *__restrict__ keys, u64 nhits, u64 off, u64 gtotal, int bshift, int nshift, u64 *__restrict__ send)
 { const int nthr = 1 << nshift, t = threadIdx.x;
   if (t >= nthr)
     return;
+  const u64 g = (t == nthr - 1) ? gtotal : (gtotal * (u64) (t + 1)) >> nshift;
   u64 e;
-  if (t == nthr - 1)
-    e = nhits;
+  if (g <= off)
+    e = 0;
+  else if (g > off + nhits)
+    e = ~0ull;
   else
-    { e = (nhits * (u64) (t + 1)) >> nshift;
-      if (e > 0)
-        { u64 d = keys[e - 1] >> bshift, a = e, b = nhits;     /* first index with bread != d */
-          while (a < b)
-            { u64 mid = (a + b) >> 1;
-              if ((keys[mid] >> bshift) == d) a = mid + 1; else b = mid;
-            }
-          e = a;
+    { e = g - off;
+      u64 d = keys[e - 1] >> bshift, a = e, b = nhits;         /* first index with bread != d */
+      while (a < b)
+        { u64 mid = (a + b) >> 1;
+          if ((keys[mid] >> bshift) == d) a = mid + 1; else b = mid;
         }
+      e = a;
     }
   send[t] = e;
 }
@@ -966,7 +1114,7 @@ void pair_heads_expand(const u64 *__restrict__ bits, const u32 *__restrict__ tof
 /* heads = ascending indices of the run heads; *total_dev = their number.  bits: 64 u64 words per
  * tile of DAMAR_SCAN_TILE seeds; scan_work: damar_scan_workspace_bytes(nhits) */
 template <typename K>
-static void pair_heads_impl(const K *keys, u64 nhits, int pbits, int abits, int minhit, int nshift,
+static void pair_heads_impl(const K *keys, u64 nhits, u64 off, u64 gtotal, int pbits, int abits, int minhit, int nshift,
                             u64 *send /* 64 entries of scratch */, u64 *bits, void *scan_work, u64 *total_dev,
                             u32 *heads, hipStream_t st)
 { if (nhits == 0)
@@ -978,15 +1126,15 @@ static void pair_heads_impl(const K *keys, u64 nhits, int pbits, int abits, int 
   const u32 ntiles = (u32) ((nhits + DAMAR_SCAN_TILE - 1) / DAMAR_SCAN_TILE);
   u32 *tcount = (u32 *) scan_work;
   if (nshift >= 0)
-    hipLaunchKernelGGL(slice_ends<K>, dim3(1), dim3(64), 0, st, keys, nhits, abits + pbits, nshift, send);
+    hipLaunchKernelGGL(slice_ends<K>, dim3(1), dim3(64), 0, st, keys, nhits, off, gtotal, abits + pbits, nshift, send);
   hipLaunchKernelGGL(pair_heads_mark<K>, dim3(ntiles), dim3(256), 0, st, keys, nhits, pbits, minhit, nshift, send, bits, tcount);
   damar_scan_tile_counts(tcount, ntiles, total_dev, st);
   hipLaunchKernelGGL(pair_heads_expand, dim3(ntiles), dim3(64), 0, st, bits, tcount, heads);
 }
 
-void damar_launch_pair_heads(const u64 *keys, u64 nhits, int pbits, int abits, int minhit, int nshift,
+void damar_launch_pair_heads(const u64 *keys, u64 nhits, u64 off, u64 gtotal, int pbits, int abits, int minhit, int nshift,
                              u64 *send, u64 *bits, void *scan_work, u64 *total_dev, u32 *heads, hipStream_t st)
-{ pair_heads_impl<u64>(keys, nhits, pbits, abits, minhit, nshift, send, bits, scan_work, total_dev, heads, st);
+{ pair_heads_impl<u64>(keys, nhits, off, gtotal, pbits, abits, minhit, nshift, send, bits, scan_work, total_dev, heads, st);
 }
 
 /***** the early cut ***************************************************************************************
@@ -1000,9 +1148,9 @@ void damar_launch_pair_heads(const u64 *keys, u64 nhits, int pbits, int abits, i
  * reference enters, in the reference's order. */
 
 /* heads = indices (in the sorted pair ids) of the runs report_thread enters; *total_dev = their number */
-void damar_launch_pair_heads_ids(const u32 *pids, u64 nhits, int abits, int minhit, int nshift,
+void damar_launch_pair_heads_ids(const u32 *pids, u64 nhits, u64 off, u64 gtotal, int abits, int minhit, int nshift,
                                  u64 *send, u64 *bits, void *scan_work, u64 *total_dev, u32 *heads, hipStream_t st)
-{ pair_heads_impl<u32>(pids, nhits, 0, abits, minhit, nshift, send, bits, scan_work, total_dev, heads, st);
+{ pair_heads_impl<u32>(pids, nhits, off, gtotal, 0, abits, minhit, nshift, send, bits, scan_work, total_dev, heads, st);
 }
 
 __global__ __launch_bounds__(256)
@@ -1577,7 +1725,7 @@ void damar_launch_order_runs(u64 *keys, u64 nhits, int ppos, int dbits, const u3
 
 /* first half: bit words + *total_dev = the number of work items; the caller reads the total, makes room, and calls the
    second half.  bits: 64 u64 words per tile of DAMAR_SCAN_TILE seeds; scan_work: damar_scan_workspace_bytes(nhits) */
-void damar_launch_pair_work(u64 *keys, const u32 *vals, u64 nhits, int ppos, int dbits, int abits, int minhit, int nshift,
+void damar_launch_pair_work(u64 *keys, const u32 *vals, u64 nhits, u64 off, u64 gtotal, int ppos, int dbits, int abits, int minhit, int nshift,
                             u64 *send, u64 *bits, void *scan_work, u64 *total_dev, int binshift, int kmer, int hitmin,
                             u32 b_lo, u32 b_hi, int unsorted, hipStream_t st)
 { HIP_CHECK(hipMemsetAsync(total_dev, 0, 2 * sizeof(u64), st));         /* [1]: order_runs met a run it does not sort */
@@ -1588,7 +1736,7 @@ void damar_launch_pair_work(u64 *keys, const u32 *vals, u64 nhits, int ppos, int
   const u32 ntiles = (u32) ((nhits + DAMAR_SCAN_TILE - 1) / DAMAR_SCAN_TILE);
   u32 *tcount = (u32 *) scan_work;
   if (nshift >= 0)
-    hipLaunchKernelGGL(slice_ends<u64>, dim3(1), dim3(64), 0, st, keys, nhits, abits + ppos + dbits, nshift, send);
+    hipLaunchKernelGGL(slice_ends<u64>, dim3(1), dim3(64), 0, st, keys, nhits, off, gtotal, abits + ppos + dbits, nshift, send);
   if (!unsorted)
     hipLaunchKernelGGL(pair_work_mark<false>, dim3(ntiles), dim3(256), 0, st, (const u64 *) keys, vals, nhits, ppos, dbits, abits, minhit,
                        nshift, (const u64 *) send, binshift, kmer, hitmin, b_lo, b_hi, bits, tcount);

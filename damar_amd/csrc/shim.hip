@@ -1783,7 +1783,7 @@ static void tail_worker(void)
                                job->hb->nwide ? job->hb->wmap + job->hb->wm_off[job->jobid] : (const u32 *) NULL, &job->ablock, &job->bblock,
                              job->self, job->comp, job->spec, job->jp, job->jobid, job->njobs);
           if (job->got != NULL)
-            *job->got = n;
+            *job->got += n;                    /* (summed over a comparison's slabs) */
           if (--job->hb->users == 0)
             hostbuf_put(job->hb);
           delete job;
@@ -1907,6 +1907,120 @@ static int64 sizeof_db(const HITS_DB *db)      /* db/DB.c:726 sizeof_DB without 
 }
 
 
+/* A comparison with more seed pairs than the seed arrays can hold is run in SLABS: consecutive ranges of B reads, each
+   with its own merge, seed sort, work list and place in a report launch.  The seed key is bread-major and the report
+   work is independent per (bread, aread) run (filter.c:2210-2241), so the slabs' sorted lists one after the other are
+   the list of the whole comparison; the reference's thread slices are placed from the whole list's figures (`off`,
+   `total`; kernels/seed_merge.hip slice_ends). */
+struct SlabPlan
+{ int  n;                        /* slabs (1: the comparison in one piece) */
+  bool mem_bound;                /* cap comes from the free device memory: the slabs run one at a time in one slot */
+  std::vector<int>   b_lo;       /* [n + 1] slab s holds the B reads [b_lo[s], b_lo[s + 1]) */
+  std::vector<int64> hits;       /* [n] its seed pairs */
+  std::vector<u64>   off;        /* [n] seed pairs of the slabs before it */
+  u64  total, cap;
+  u32  limit;                    /* the cap on mutual matches of the whole comparison */
+};
+static SlabPlan &G_plan = *new SlabPlan();
+static int64 G_slab_tot[2] = { 0, 0 };      /* seed stages run, comparisons split (damar_slab_totals) */
+
+/* The greedy cut: a slab takes B reads while its seed pairs stay <= cap, and always at least one.  b_lo[0 .. n] and
+   sums[0 .. n-1] for up to max_slabs slabs; returns n, -(r + 1) when read r alone has more than cap seed pairs, or 0
+   when max_slabs is too small. */
+extern "C" int damar_slab_cut(const uint64_t *hits, int nreads, uint64_t cap, int *b_lo, int64 *sums, int max_slabs)
+{ int n = 0;
+  uint64_t acc = 0;
+  if (max_slabs < 1)
+    return 0;
+  b_lo[0] = 0;
+  for (int r = 0; r < nreads; r++)
+    { if (hits[r] > cap)
+        return -(r + 1);
+      if (r > b_lo[n] && acc + hits[r] > cap)
+        { sums[n++] = (int64) acc;
+          if (n >= max_slabs)
+            return 0;
+          b_lo[n] = r;
+          acc = 0;
+        }
+      acc += hits[r];
+    }
+  sums[n++] = (int64) acc;
+  b_lo[n] = nreads;
+  return n;
+}
+
+/* What the seed stage of `n` seed pairs reserves: in the comparison's own arena, in the shared one, and -- with the early
+   cut, whose survivors are at most n -- in the shared arenas of the cut.  match_front reserves by these expressions, and
+   the number of seed pairs a seed stage can hold (seed_cap) is derived from them. */
+static size_t front_hits_bytes(u64 n)
+{ return pad256(sizeof(u64) * (size_t) n) + pad256(sizeof(u32) * (size_t) n) + 4096; }
+static size_t front_tmp_bytes(u64 n)
+{ return pad256(sizeof(u64) * (size_t) n) + 3 * pad256(sizeof(u32) * (size_t) n) +
+         pad256(damar_sort_workspace_bytes(n)) + pad256(damar_scan_workspace_bytes(n)) + 8192;
+}
+static size_t front_cut_bytes(u64 n, int minhit, size_t bmwords)
+{ return pad256(sizeof(u64) * (size_t) n) + 4 * pad256(sizeof(u32) * (size_t) n) +
+         pad256(sizeof(u32) * ((size_t) n / minhit + 64)) +
+         pad256(damar_sort_workspace_bytes(n)) + pad256(damar_scan_workspace_bytes(n)) +
+         pad256(sizeof(u32) * bmwords) + 16384;
+}
+/* what arena_reserve(a, need) would take from the device beyond what the arena holds */
+static size_t arena_growth(const Arena &a, size_t need)
+{ if (need <= a.cap)
+    return 0;
+  const size_t cap = need + (need >> 3) + (1u << 20);
+  return cap - a.cap;
+}
+/* the work list and its processing order: a work item is the head of a run of at least minhit seeds */
+static size_t front_ord_bytes(u64 n, int minhit)
+{ const u64 nw = n / (u64) minhit + 1;
+  return 5 * pad256(sizeof(u32) * (size_t) nw) + pad256(damar_sort_workspace_bytes(nw)) + 8192;
+}
+static size_t front_growth(u64 n, const Arena &hits, const Arena &ord, bool cut, int minhit, size_t bmwords)
+{ const size_t own = arena_growth(hits, front_hits_bytes(n)) + arena_growth(ord, front_ord_bytes(n, minhit));
+  if (!cut)
+    return own + arena_growth(G_tmp, front_tmp_bytes(n));
+  return own + arena_growth(G_tmp, front_cut_bytes(n, minhit, bmwords)) + arena_growth(G_tmp2, front_tmp_bytes(n));
+}
+
+/* The most seed pairs one seed stage may have: below the 32-bit seed index (work items, the tile scans), and no more
+   than the arenas of ONE comparison slot (seed pairs, work list) and the shared seed-stage arenas can be grown to hold in
+   HALF the device memory that is free now.  The other half is left to what follows a seed stage and cannot be sized
+   before it has run: the report launch's record and trace buffers, which grow with the records found.  A comparison cut
+   by this figure (*mem_bound) runs its slabs one at a time in that one slot -- each slab's launch is completed before
+   the next slab's seed stage starts (damar_match_batch) -- so no second slot's arenas grow beside it and the figure
+   holds for every slab, not only the first.
+   The device is asked only when `total` seed pairs would make an arena grow -- a comparison that fits what the arenas
+   hold costs nothing here.  Test hooks: DAMAR_TEST_SEED_CAP=<n> replaces the figure; DAMAR_TEST_FREE_BYTES=<n> stands
+   for the free device memory (and the device is not asked). */
+static u64 seed_cap(u64 total, const Arena &hits, const Arena &ord, bool cut, int minhit, size_t bmwords, bool *mem_bound)
+{ const u64 index_cap = 0xfffffff0ull - 1;
+  const char *e = getenv("DAMAR_TEST_SEED_CAP");
+  *mem_bound = false;
+  if (e != NULL && atoll(e) > 0)
+    return (u64) atoll(e);
+  const u64 top = std::min(total, index_cap);
+  if (front_growth(top, hits, ord, cut, minhit, bmwords) == 0)
+    return index_cap;
+  size_t free_b = 0, total_b = 0;
+  e = getenv("DAMAR_TEST_FREE_BYTES");
+  if (e != NULL && atoll(e) > 0)
+    free_b = (size_t) atoll(e);
+  else
+    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+  free_b /= 2;
+  if (front_growth(top, hits, ord, cut, minhit, bmwords) <= free_b)
+    return index_cap;
+  u64 lo = 0, hi = top;                        /* the largest n whose arenas fit (growth is monotone in n) */
+  while (lo < hi)
+    { const u64 mid = lo + (hi - lo + 1) / 2;
+      if (front_growth(mid, hits, ord, cut, minhit, bmwords) <= free_b) lo = mid; else hi = mid - 1;
+    }
+  *mem_bound = true;
+  return lo;
+}
+
 /* What the seed stage of one comparison leaves on the device for the report launch. */
 struct Front
 { const u64 *keys;  const u32 *vals;  u64 total;
@@ -1919,8 +2033,12 @@ struct Front
 };
 
 /* Seed stage of one comparison (filter.c:2603-2760): merge-count, scan, emit, seed sort, work list and its
-   processing order, into the arenas of job slot `slot`.  Returns false when there is nothing to report. */
-static bool match_front(damar_match_job *job, int slot, Front *f)
+   processing order, into the arenas of job slot `slot`.  Returns FRONT_NONE when there is nothing to report, FRONT_READY
+   with *f filled, or -- called with slab < 0, for the whole comparison -- FRONT_SPLIT when the comparison has more seed
+   pairs than one seed stage holds: G_plan then says how it is cut, and the caller runs the slabs (slab = 0, 1, ...),
+   each an ordinary seed stage over its range of B reads. */
+enum { FRONT_NONE = 0, FRONT_READY = 1, FRONT_SPLIT = 2 };
+static int match_front(damar_match_job *job, int slot, Front *f, int slab)
 { const HITS_DB *ablock = job->ablock, *bblock = job->bblock;
   damar_dev_index *aidx = job->aidx, *bidx = job->bidx;
   const int self = job->self, comp = job->comp;
@@ -1931,9 +2049,14 @@ static bool match_front(damar_match_job *job, int slot, Front *f)
   memset(f, 0, sizeof(*f));
   f->t_entry = t_entry;
   f->jp = params_now();
-  job->counts[0] = job->counts[1] = job->counts[2] = 0;
+  if (slab < 0)
+    { job->counts[0] = job->counts[1] = job->counts[2] = 0;
+      G_plan.n = 1;  G_plan.mem_bound = false;  G_plan.total = 0;
+      G_plan.b_lo.assign(2, 0);  G_plan.b_lo[1] = bblock->nreads;
+      G_plan.hits.assign(1, 0);  G_plan.off.assign(1, 0);
+    }
   if (aidx == NULL || bidx == NULL || aidx->n == 0 || bidx->n == 0)
-    return false;
+    return FRONT_NONE;
   if (aidx->kbits != bidx->kbits)
     { fprintf(stderr, "damar: internal error, index parameters differ\n");
       die();
@@ -1947,6 +2070,11 @@ static bool match_front(damar_match_job *job, int slot, Front *f)
   m.kbits = aidx->kbits;
   m.self = self;  m.comp = comp;  m.identity = IDENTITY;
   m.limit = (MEM_LIMIT > 0) ? MAXGRAM : 0x7fffffffu;      /* filter.c:2700-2702 */
+  m.b_lo = 0;  m.b_hi = 0xffffffffu;
+  if (slab >= 0)                                          /* the cap is the whole comparison's, the B reads the slab's */
+    { m.limit = G_plan.limit;
+      m.b_lo = (u32) G_plan.b_lo[slab];  m.b_hi = (u32) G_plan.b_lo[slab + 1];
+    }
   m.ablk = aidx->blk->d;  m.bblk = bidx->blk->d;
   m.pbits = std::max(1, ilog2_ceil((u64) ablock->maxlen + 1));
   m.abits = std::max(1, ilog2_ceil((u64) ablock->nreads));
@@ -1983,12 +2111,16 @@ static bool match_front(damar_match_job *job, int slot, Front *f)
   tot = (u64 *) arena_take(&G_work, 64);
   void *mscw = arena_take(&G_work, damar_scan_workspace_bytes(mtiles));
   damar_launch_merge_count(&m, mw, NULL, 0, G_st);
+  if (slab >= 0)
+    damar_launch_merge_range(&m, mw, G_st);
   stage("merge_count");
   damar_exclusive_scan_u32(tcount, tcount, mtiles, mscw, tot, G_st);
   stage("merge_scan");
   HIP_CHECK(hipMemcpyAsync(&total, tot, sizeof(u64), hipMemcpyDeviceToHost, G_st));
   stream_wait(G_st);
-  if (MEM_LIMIT > 0)
+  if (slab >= 0)
+    ;                                                     /* (the whole comparison's call has settled the cap) */
+  else if (MEM_LIMIT > 0)
     { /* filter.c:2634-2699.  The counts above keep every run below MAXGRAM; the reference lowers
          that cap to the first mutual count at which the kept seeds no longer fit `avail`.  That
          only happens under memory pressure, so the histogram is built only then. */
@@ -2050,17 +2182,12 @@ static bool match_front(damar_match_job *job, int slot, Front *f)
   else
     G_limit = 0x7fffffff;
   nhits = (int64) total;
-  if (VERBOSE)
+  if (VERBOSE && slab < 0)
     { printf("   Hit count = %lld\n", (long long) nhits);
       fflush(stdout);
     }
-  if (total >= 0xfffffff0ull)
-    { fprintf(stderr, "damar: FATAL: %llu seed pairs exceed the 32-bit seed index of this build\n",
-              (unsigned long long) total);
-      die();
-    }
   if (total == 0)
-    return false;
+    return FRONT_NONE;
 
   /* hits known.  The sorted seed pairs stay in this comparison's own arena until the report launch; everything else
      of the seed stage lives in arenas the comparisons share.  The sort ping-pongs: it is started from the side that
@@ -2080,6 +2207,61 @@ static bool match_front(damar_match_job *job, int slot, Front *f)
     }
   const bool ranged = P_bread_lo > 0 || P_bread_hi != 0xffffffffu;      /* one part of a block pair split over GPUs */
   const bool cut = (cut_on || ranged) && !G_keep_seeds && idbits <= 32;
+  const size_t bmwords = (((size_t) 1 << (idbits <= 32 ? idbits : 32)) + 31) / 32;      /* the early cut's bitmap over the pair ids */
+  u64 s_off = 0, s_all = total;                              /* where this seed stage's seeds lie in the whole comparison's list */
+  if (slab < 0)
+    { G_plan.total = total;  G_plan.hits[0] = nhits;  G_plan.limit = m.limit;
+      const u64 cap = seed_cap(total, G_hits, G_ord, cut, minhit, bmwords, &G_plan.mem_bound);
+      G_plan.cap = cap;
+      if (total > cap)
+        { /* seed pairs per B read from what the COUNT sweep left (built only now, like the histogram of the cap on mutual
+             matches), then the greedy cut */
+          const int nrb = bblock->nreads;
+          std::vector<unsigned long long> hist((size_t) nrb);
+          unsigned long long *dh = (unsigned long long *) dmalloc(sizeof(unsigned long long) * (size_t) nrb);
+          HIP_CHECK(hipMemsetAsync(dh, 0, sizeof(unsigned long long) * (size_t) nrb, G_st));
+          damar_launch_merge_bread_hist(&m, mw, dh, G_st);   /* (reads the entries' counts and B starts, which the scan has not touched) */
+          HIP_CHECK(hipMemcpyAsync(hist.data(), dh, sizeof(unsigned long long) * (size_t) nrb, hipMemcpyDeviceToHost, G_st));
+          tick(1);
+          HIP_CHECK(hipStreamSynchronize(G_st));
+          HIP_CHECK(hipFree(dh));
+          stage("bread_hist");
+          G_plan.b_lo.assign((size_t) nrb + 2, 0);  G_plan.hits.assign((size_t) nrb + 1, 0);
+          const int ns = damar_slab_cut((const uint64_t *) hist.data(), nrb, cap, G_plan.b_lo.data(), G_plan.hits.data(), nrb + 1);
+          if (ns < 0)
+            { fprintf(stderr, "damar: FATAL: B read %d alone has %llu seed pairs, more than the %llu one seed stage holds\n",
+                      -ns - 1, hist[(size_t) (-ns - 1)], (unsigned long long) cap);
+              die();
+            }
+          G_plan.n = ns;
+          G_plan.b_lo.resize((size_t) ns + 1);  G_plan.hits.resize((size_t) ns);
+          G_plan.off.assign((size_t) ns, 0);
+          u64 sum = 0;
+          for (int x = 0; x < ns; x++)
+            { G_plan.off[x] = sum;  sum += (u64) G_plan.hits[x]; }
+          if (sum != total)
+            { fprintf(stderr, "damar: internal error, %llu seed pairs by B read, %llu counted\n", (unsigned long long) sum,
+                      (unsigned long long) total);
+              die();
+            }
+          G_slab_tot[1] += 1;
+          if (VERBOSE)
+            { printf("   Seed stage in %d slabs of at most %llu hits\n", ns, (unsigned long long) cap);
+              fflush(stdout);
+            }
+          G_ms[DAMAR_T_MERGE] += lap(0, 1);
+          return FRONT_SPLIT;
+        }
+    }
+  else
+    { if (total != (u64) G_plan.hits[slab])
+        { fprintf(stderr, "damar: internal error, slab %d has %llu seed pairs, %lld expected\n", slab, (unsigned long long) total,
+                  (long long) G_plan.hits[slab]);
+          die();
+        }
+      s_off = G_plan.off[slab];  s_all = G_plan.total;
+    }
+  G_slab_tot[0] += 1;
   static int two_step = -1;                              /* DAMAR_WORK_TWOSTEP=1: heads, then their screen (rounds 1-5; tested) */
   if (two_step < 0)
     { const char *e = getenv("DAMAR_WORK_TWOSTEP");
@@ -2112,9 +2294,8 @@ static bool match_front(damar_match_job *job, int slot, Front *f)
   u64 *sends;
   int  hshift = P_nshift;                                     /* slices of the reference's threads in the head test */
   if (!cut)
-    { arena_reserve(&G_hits, pad256(sizeof(u64) * (size_t) total) + pad256(sizeof(u32) * (size_t) total) + 4096);
-      arena_reserve(&G_tmp,  pad256(sizeof(u64) * (size_t) total) + 3 * pad256(sizeof(u32) * (size_t) total) +
-                             pad256(damar_sort_workspace_bytes(total)) + pad256(damar_scan_workspace_bytes(total)) + 8192);
+    { arena_reserve(&G_hits, front_hits_bytes(total));
+      arena_reserve(&G_tmp,  front_tmp_bytes(total));
       u64 *pk = (u64 *) arena_take(&G_hits, sizeof(u64) * (size_t) total);
       u32 *pv = m.dbits ? NULL : (u32 *) arena_take(&G_hits, sizeof(u32) * (size_t) total);
       tk = (u64 *) arena_take(&G_tmp, sizeof(u64) * (size_t) total);
@@ -2146,11 +2327,7 @@ static bool match_front(damar_match_job *job, int slot, Front *f)
          seed sort.  The pair ids are sorted on their own (4 B per seed instead of 12, 4 passes instead of 6), the
          reference's head test runs on them, and the seeds of the surviving pairs -- a few per cent -- are compacted
          out of the unsorted seeds. */
-      const size_t bmwords = (((size_t) 1 << idbits) + 31) / 32;
-      arena_reserve(&G_tmp, pad256(sizeof(u64) * (size_t) total) + 4 * pad256(sizeof(u32) * (size_t) total) +
-                            pad256(sizeof(u32) * ((size_t) total / minhit + 64)) +
-                            pad256(damar_sort_workspace_bytes(total)) + pad256(damar_scan_workspace_bytes(total)) +
-                            pad256(sizeof(u32) * bmwords) + 16384);
+      arena_reserve(&G_tmp, front_cut_bytes(total, minhit, bmwords));
       u64 *uk   = (u64 *) arena_take(&G_tmp, sizeof(u64) * (size_t) total);
       u32 *uv   = (u32 *) arena_take(&G_tmp, sizeof(u32) * (size_t) total);
       u32 *pid0 = (u32 *) arena_take(&G_tmp, sizeof(u32) * (size_t) total);
@@ -2168,7 +2345,7 @@ static bool match_front(damar_match_job *job, int slot, Front *f)
       const u32 *spid = damar_radix_sort_keys_u32(pid0, pid1, total, idbits, sw, G_st) ? pid1 : pid0;
       sort_check(sw);
       u64 n64 = 0;
-      damar_launch_pair_heads_ids(spid, total, m.abits, minhit, P_nshift, snd, (u64 *) hbit, scc, tot, hd, G_st);
+      damar_launch_pair_heads_ids(spid, total, s_off, s_all, m.abits, minhit, P_nshift, snd, (u64 *) hbit, scc, tot, hd, G_st);
       HIP_CHECK(hipMemsetAsync(bitmap, 0, sizeof(u32) * bmwords, G_st));
       HIP_CHECK(hipMemcpyAsync(&n64, tot, sizeof(u64), hipMemcpyDeviceToHost, G_st));
       HIP_CHECK(hipStreamSynchronize(G_st));
@@ -2184,12 +2361,11 @@ static bool match_front(damar_match_job *job, int slot, Front *f)
           G_ms[DAMAR_T_MERGE] += lap(0, 1);
           G_ms[DAMAR_T_SSORT] += lap(1, 2);
           G_cnt[0] += nhits;
-          job->counts[0] = nhits;
-          return false;
+          job->counts[0] += nhits;
+          return FRONT_NONE;
         }
-      arena_reserve(&G_hits, pad256(sizeof(u64) * (size_t) nsurv) + pad256(sizeof(u32) * (size_t) nsurv) + 4096);
-      arena_reserve(&G_tmp2, pad256(sizeof(u64) * (size_t) nsurv) + 3 * pad256(sizeof(u32) * (size_t) nsurv) +
-                             pad256(damar_sort_workspace_bytes(nsurv)) + pad256(damar_scan_workspace_bytes(nsurv)) + 8192);
+      arena_reserve(&G_hits, front_hits_bytes(nsurv));
+      arena_reserve(&G_tmp2, front_tmp_bytes(nsurv));
       u64 *pk = (u64 *) arena_take(&G_hits, sizeof(u64) * (size_t) nsurv);
       u32 *pv = m.dbits ? NULL : (u32 *) arena_take(&G_hits, sizeof(u32) * (size_t) nsurv);
       tk = (u64 *) arena_take(&G_tmp2, sizeof(u64) * (size_t) nsurv);
@@ -2226,7 +2402,7 @@ static bool match_front(damar_match_job *job, int slot, Front *f)
       u64 got[2] = { 0, 0 };                               /* work items; a run order_runs would not sort */
       if (cut)
         psort = false;                                     /* (the early cut's survivors were sorted over all the bits) */
-      damar_launch_pair_work(keys, vals, total, m.pbits, m.dbits, m.abits, minhit, hshift, sends, (u64 *) foff /* bit words */,
+      damar_launch_pair_work(keys, vals, total, s_off, s_all, m.pbits, m.dbits, m.abits, minhit, hshift, sends, (u64 *) foff /* bit words */,
                              scw2, tot, P_binshift, P_kmer, P_hitmin, P_bread_lo, P_bread_hi, psort ? 1 : 0, G_st);
       stage("run_heads");
       tick(3);                                             /* (the expansion of the bits behind it is 4 us: outside the clock) */
@@ -2246,7 +2422,7 @@ static bool match_front(damar_match_job *job, int slot, Front *f)
           sort_check(resort_ws);
           if (side)
             HIP_CHECK(hipMemcpyAsync(keys, other, sizeof(u64) * (size_t) total, hipMemcpyDeviceToDevice, G_st));
-          damar_launch_pair_work(keys, vals, total, m.pbits, m.dbits, m.abits, minhit, hshift, sends, (u64 *) foff, scw2, tot,
+          damar_launch_pair_work(keys, vals, total, s_off, s_all, m.pbits, m.dbits, m.abits, minhit, hshift, sends, (u64 *) foff, scw2, tot,
                                  P_binshift, P_kmer, P_hitmin, P_bread_lo, P_bread_hi, 0, G_st);
           HIP_CHECK(hipMemcpyAsync(got, tot, 2 * sizeof(u64), hipMemcpyDeviceToHost, G_st));
           stream_wait(G_st);
@@ -2264,7 +2440,7 @@ static bool match_front(damar_match_job *job, int slot, Front *f)
     }
   else
     { u32 *heads = (u32 *) tk;                              /* the idle key buffer holds the run heads */
-      damar_launch_pair_heads(keys, total, m.pbits + m.dbits, m.abits, minhit, hshift, sends, (u64 *) foff /* bit words */,
+      damar_launch_pair_heads(keys, total, s_off, s_all, m.pbits + m.dbits, m.abits, minhit, hshift, sends, (u64 *) foff /* bit words */,
                               scw2, tot, heads, G_st);
       stage("run_heads");
       HIP_CHECK(hipMemcpyAsync(&nwork64, tot, sizeof(u64), hipMemcpyDeviceToHost, G_st));
@@ -2293,14 +2469,15 @@ static bool match_front(damar_match_job *job, int slot, Front *f)
   G_ms[DAMAR_T_SSORT] += lap(1, 2);
   G_ms[DAMAR_T_WORK]  += lap(2, 3);
   G_cnt[0] += nhits;  G_cnt[1] += nwork;
-  job->counts[0] = nhits;
+  job->counts[0] += nhits;
   prev_seeds = total;  prev_work = nwork > 0 ? nwork : 1;
 
   if (G_keep_seeds)
-    { G_seed_keys.resize(total);  G_seed_vals.resize(total);
-      HIP_CHECK(hipMemcpy(G_seed_keys.data(), keys, sizeof(u64) * (size_t) total, hipMemcpyDeviceToHost));
+    { const size_t at = slab >= 0 ? G_seed_keys.size() : 0;     /* (a slab's seeds behind those of the slabs before it: damar_match_batch clears) */
+      G_seed_keys.resize(at + total);  G_seed_vals.resize(at + total);
+      HIP_CHECK(hipMemcpy(G_seed_keys.data() + at, keys, sizeof(u64) * (size_t) total, hipMemcpyDeviceToHost));
       if (vals != NULL)
-        HIP_CHECK(hipMemcpy(G_seed_vals.data(), vals, sizeof(u32) * (size_t) total, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(G_seed_vals.data() + at, vals, sizeof(u32) * (size_t) total, hipMemcpyDeviceToHost));
       G_seed_pbits = m.pbits;  G_seed_abits = m.abits;  G_seed_dbits = m.dbits;
     }
 
@@ -2334,7 +2511,7 @@ static bool match_front(damar_match_job *job, int slot, Front *f)
   f->work = work;  f->nwork = nwork;  f->order = order;
   f->pbits = m.pbits;  f->abits = m.abits;  f->dbits = m.dbits;
   f->bytes = G_hits.cap + G_ord.cap;
-  return nwork > 0;
+  return nwork > 0 ? FRONT_READY : FRONT_NONE;
 }
 
 /* A report launch over up to DAMAR_MAX_JOBS comparisons, in two halves.  In asynchronous mode the launch goes to its own
@@ -2629,7 +2806,7 @@ static void report_finish(Pending &pd)
   for (int j = 0; j < n; j++)
     { const damar_match_job &jb = pd.job[j];
       if (pd.orig[j] != NULL)
-        pd.orig[j]->counts[1] = hc[DAMAR_CNT_NFILT + j];
+        pd.orig[j]->counts[1] += hc[DAMAR_CNT_NFILT + j];      /* (summed over a comparison's slabs) */
       G_cnt[2] += hc[DAMAR_CNT_NFILT + j];
       if (A_on)
         { { std::lock_guard<std::mutex> lk(A_mu);
@@ -2647,7 +2824,7 @@ static void report_finish(Pending &pd)
         { double t0 = now_ms();
           const int64 got = run_tail(hb->recs, hb->nrec, hb->tpool, hb->t8, hb->nwide ? hb->wmap + hb->wm_off[j] : (const u32 *) NULL, jb.ablock, jb.bblock, jb.self, jb.comp, jb.spec, pd.fr[j].jp, j, n);
           if (pd.orig[j] != NULL)
-            pd.orig[j]->counts[2] = got;
+            pd.orig[j]->counts[2] += got;
           if (--hb->users == 0)
             hostbuf_put(hb);
           G_ms[DAMAR_T_TAIL] += now_ms() - t0;
@@ -2872,6 +3049,7 @@ extern "C" void damar_match_batch(damar_match_job *jobs, int njobs)
   if (Q_exit > 0)
     Q_ms[2] += h0 - Q_exit;
   memset(G_cnt, 0, sizeof(G_cnt));
+  G_slab_tot[0] = G_slab_tot[1] = 0;
   for (int i = DAMAR_T_MERGE; i < DAMAR_T_COUNT; i++)
     G_ms[i] = 0;
   const bool defer = overlap_on();
@@ -2897,22 +3075,60 @@ extern "C" void damar_match_batch(damar_match_job *jobs, int njobs)
           if (go)
             flush_accum();
         }
-      const int slot = slot_take();               /* (may complete a launch, or launch what is held back) */
-      const int n = AC.n;
+      int slot = slot_take();                     /* (may complete a launch, or launch what is held back) */
       if (i == 0)
         Q_seg[2] += now_ms() - h0;
-      if (!match_front(&jobs[i], slot, &AC.fr[n]))
-        G_slot_busy[slot] = false;
-      else
-        { AC.job[n] = jobs[i];  AC.orig[n] = &jobs[i];  AC.slot[n] = slot;
-          AC.ablk[n] = jobs[i].aidx->blk;  AC.bblk[n] = jobs[i].bidx->blk;
-          AC.bytes += AC.fr[n].bytes;
-          AC.nwork += AC.fr[n].nwork;
-          AC.n = n + 1;
+      /* a seed stage that has something to report joins the comparisons held back, and the rules that cut a launch apply */
+      auto joined = [&](int got, int sl)
+        { const int n = AC.n;
+          if (got != FRONT_READY)
+            G_slot_busy[sl] = false;
+          else
+            { AC.job[n] = jobs[i];  AC.orig[n] = &jobs[i];  AC.slot[n] = sl;
+              AC.ablk[n] = jobs[i].aidx->blk;  AC.bblk[n] = jobs[i].bidx->blk;
+              AC.bytes += AC.fr[n].bytes;
+              AC.nwork += AC.fr[n].nwork;
+              AC.n = n + 1;
+            }
+          if (AC.n >= hard || AC.bytes > budget || (AC.n >= soft && (!defer || AC.nwork >= batch_work())))
+            flush_accum();
+        };
+      const int got = match_front(&jobs[i], slot, &AC.fr[AC.n], -1);
+      if (got != FRONT_SPLIT)
+        { H_ms[1] += now_ms() - f0;
+          joined(got, slot);
+          continue;
         }
+      /* too many seed pairs for one seed stage: slab after slab, each a comparison of its own from here on.  Slabs
+         without seeds, and those outside the caller's range of B reads (damar_set_bread_range), are not run. */
+      const int slot0 = slot;
+      bool first = true;
+      for (int sb = 0; sb < G_plan.n; sb++)
+        { if (G_plan.hits[sb] == 0)
+            continue;
+          if ((u32) G_plan.b_lo[sb + 1] <= P_bread_lo || (u32) G_plan.b_lo[sb] >= P_bread_hi)
+            { jobs[i].counts[0] += G_plan.hits[sb];          /* (not run, but seed pairs of the comparison: counts[0] and */
+              G_cnt[0] += G_plan.hits[sb];                   /*  counter 0 are the whole comparison's, as without slabs)  */
+              continue;
+            }
+          if (slot < 0 && G_plan.mem_bound)
+            { /* the figure holds for the arenas of one slot: what the slabs before this one owe is completed, and this
+                 slab runs where they ran */
+              finish_all();
+              slot = slot0;
+              G_slot_busy[slot] = true;
+            }
+          else if (slot < 0)
+            slot = slot_take();
+          if (G_keep_seeds && first)
+            { G_seed_keys.clear();  G_seed_vals.clear(); }
+          first = false;
+          joined(match_front(&jobs[i], slot, &AC.fr[AC.n], sb), slot);
+          slot = -1;
+        }
+      if (slot >= 0)
+        G_slot_busy[slot] = false;
       H_ms[1] += now_ms() - f0;
-      if (AC.n >= hard || AC.bytes > budget || (AC.n >= soft && (!defer || AC.nwork >= batch_work())))
-        flush_accum();
     }
   if (!defer)
     flush_accum();
@@ -3168,6 +3384,22 @@ extern "C" void Match_Self(char *aname, HITS_DB *ablock, Align_Spec *settings)
 }
 
 /***** test hooks ***************************************************************************************/
+
+/* slab table of the last damar_match: b_lo[0 .. n] and hits[0 .. n-1] for up to `cap` slabs; returns n (1: not split) */
+extern "C" int damar_last_slabs(int *b_lo, int64 *hits, int cap)
+{ const int n = G_plan.n;
+  for (int i = 0; i < n && i < cap; i++)
+    { if (b_lo) b_lo[i] = G_plan.b_lo[(size_t) i];
+      if (hits) hits[i] = G_plan.hits[(size_t) i];
+    }
+  if (b_lo != NULL && n <= cap && (size_t) n < G_plan.b_lo.size())
+    b_lo[n] = G_plan.b_lo[(size_t) n];
+  return n;
+}
+
+/* of the last damar_match / damar_match_batch: seed stages run (slabs, summed over its comparisons), comparisons split */
+extern "C" void damar_slab_totals(int64 *out)
+{ out[0] = G_slab_tot[0];  out[1] = G_slab_tot[1]; }
 
 extern "C" int64 damar_last_seeds(void *out, int64 cap)
 { struct SP { int diag, apos, aread, bread; } *sp = (SP *) out;

@@ -125,6 +125,8 @@ class Plan:
         self.index_builds = 0
         self.matches = 0             # comparisons (block pair x orientation) run
         self.report_launches = 0     # launches of the report kernel they took
+        self.seed_slabs = 0          # seed stages run: one per comparison, or one per slab of B reads (damar_slab_totals)
+        self.split_comparisons = 0   # comparisons with too many seed pairs for one seed stage
         self.wave = [0, 0, 0]        # band cells, wave steps per alignment pass, wave-loop iterations (damar_wave_totals)
         L.damar_set_async(1 if async_tail else 0)
 
@@ -227,6 +229,9 @@ class Plan:
             arr[q].self_, arr[q].comp, arr[q].spec = self_, comp, spec
         L.damar_match_batch(arr, len(jobs))
         self.matches += len(jobs)
+        ns, nsplit = api.slab_totals()
+        self.seed_slabs += ns
+        self.split_comparisons += nsplit
         if not self.async_tail:
             self.report_launches += api.counters()[5]
         t = api.timings()

@@ -94,7 +94,8 @@ void damar_match_batch(damar_match_job *jobs, int njobs);
 
 /* Restrict the following damar_match / Match_Filter calls to the read pairs whose B read (block-local
  * index) lies in [lo, hi); hi < 0 lifts the restriction.  The records of a range are exactly those the
- * unrestricted call writes for these B reads (the merge and the sort still cover the whole pair), so a
+ * unrestricted call writes for these B reads (the merge and the sort still cover the whole pair -- or, of a
+ * comparison run in slabs, the slabs that meet the range), so a
  * scheduler can split one block pair over several GPUs and merge the parts' files ("split big
  * pairs ... legal because report work is independent per (bread,aread) run"). */
 void damar_set_bread_range(int lo, int hi);
@@ -135,6 +136,24 @@ void Match_Self(char *aname, HITS_DB *ablock, Align_Spec *settings);
  * records {int diag, apos, aread, bread} (filter.c:128-134) in sorted order.
  * Returns the number of seed pairs; copies at most `cap` records. */
 int64 damar_last_seeds(void *out, int64 cap);
+
+/* A comparison with more seed pairs than one seed stage holds -- the 32-bit seed index, or what the seed arrays can be
+ * grown to in the device memory that is free -- is run in SLABS, consecutive ranges of B reads cut greedily: a slab takes
+ * B reads while its seed pairs stay within that figure, and at least one.  Records, counts and damar_last_seeds are those
+ * of the comparison in one piece.  damar_last_slabs: the slab table of the last damar_match, b_lo[0 .. n] (b_lo[n] = end
+ * of the last slab) and hits[0 .. n-1], at most `cap` slabs copied; returns n, 1 for a comparison that was not split.
+ * damar_slab_totals: out[0] = seed stages run (slabs, summed over the comparisons), out[1] = comparisons that were split,
+ * in the last damar_match / damar_match_batch.  damar_slab_cut is the cut itself (host arithmetic, no device): returns
+ * the number of slabs, -(r + 1) when B read r alone exceeds cap, 0 when max_slabs is too small.
+ * With damar_set_bread_range the slabs outside the range are not run; their seed pairs still count in counts[0] and in
+ * counter 0, which stay the whole comparison's as they are without slabs.  A comparison cut by the memory figure runs
+ * its slabs one at a time (each slab's report launch is completed before the next slab's seed stage).
+ * Test hooks, not options: DAMAR_TEST_SEED_CAP=<n> in the environment replaces the figure by n;
+ * DAMAR_TEST_FREE_BYTES=<n> stands for the free device memory the figure is derived from. */
+int  damar_last_slabs(int *b_lo /* [cap + 1] */, int64 *hits /* [cap] */, int cap);
+void damar_slab_totals(int64 *out /* [2] */);
+int  damar_slab_cut(const uint64_t *hits, int nreads, uint64_t cap, int *b_lo /* [max_slabs + 1] */, int64 *sums /* [max_slabs] */,
+                    int max_slabs);
 
 /* The cap on mutual k-mer matches per code that the last damar_match applied (filter.c:2634-2702:
  * 10000 unless the host memory limit forces it lower; INT32_MAX when MEM_LIMIT is 0). */
