@@ -115,6 +115,9 @@ def _lib():
         L.damar_slab_cut.restype = C.c_int
         L.damar_bench_sort_u32.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_uint32]
         L.damar_bench_sort_u32.restype = C.c_double
+        L.damar_set_check.argtypes = [C.c_int]
+        L.damar_check_totals.argtypes = [C.POINTER(c_int64)]
+        L.damar_check_note_blocks.argtypes = [C.c_void_p, C.POINTER(HITS_DB), C.POINTER(HITS_DB)]
         _proto_done = True
     return L
 
@@ -204,6 +207,31 @@ def slab_cut(hits, cap):
     if got <= 0:
         return got
     return list(b[:got + 1]), list(s[:got])
+
+
+def set_check(on):
+    """daligner -C for the in-process run: every .las file is checked by the thread that writes it (include/damar_hip.h)."""
+    _lib().damar_set_check(1 if on else 0)
+
+
+def check_totals():
+    """(files checked, records checked, violations, files checked but discarded by DAMAR_LAS_KEEP) since the process started;
+    read it after the writers have drained (driver.Plan.finish)."""
+    a = (c_int64 * 4)()
+    _lib().damar_check_totals(a)
+    return tuple(a)
+
+
+def las_check(db, las, ptp=True, sort=True, dupes=True, strict=False, ignore_discarded=False):
+    """bin/LAcheck on one file: -> (exit status, its stderr lines).  db: the WHOLE database (records carry its read numbers);
+    ptp / sort / dupes / ignore_discarded are the reference tool's -p -s -d -i, strict is -x."""
+    import subprocess
+    exe = bin_path("LAcheck")
+    if not os.path.exists(exe):
+        raise RuntimeError("%s not built" % exe)
+    opts = [o for o, on in (("-p", ptp), ("-s", sort), ("-d", dupes), ("-i", ignore_discarded), ("-x", strict)) if on]
+    r = subprocess.run([exe] + opts + [db, las], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
+    return r.returncode, r.stderr.splitlines()
 
 
 def daligner_binary():

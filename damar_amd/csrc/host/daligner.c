@@ -6,6 +6,9 @@
  * The B blocks of the line are read, checked and reverse-complemented one or two ahead on a second
  * thread while the GPU works on the current one.  Rejected explicitly: -D (dynamic mask server).
  * -H is accepted and has no effect, exactly like the reference.
+ * -C (not in the reference): every .las file is checked by the thread that writes it (include/damar_check.h: LAcheck's
+ * -p -s -d and the strict set); a violation is a line "damar: CHECK <file>: ..." on stderr, the run goes on, every file is
+ * written, and the exit status is 1 at the end.
  *
  * Plan mode, `daligner [options] -P <plan file | ->`: every `daligner ...` line of an HPCdaligner plan
  * (dalign/HPCdaligner.c:628-788) in ONE process.  The reference runs one process per line
@@ -48,7 +51,7 @@
 
 static void usage(void)
 { fprintf(stderr, "usage:\n");
-  fprintf(stderr, "daligner [-vbAIOT] [-k<int(14)>] [-w<int(6)>] [-h<int(35)>] [-t<int>] [-M<int>] [-m<track>]+\n");
+  fprintf(stderr, "daligner [-vbAIOTC] [-k<int(14)>] [-w<int(6)>] [-h<int(35)>] [-t<int>] [-M<int>] [-m<track>]+\n");
   fprintf(stderr, "         [-e<double(.70)] [-l<int(1000)>] [-s<int(100)>] [-H<int>] [-j<int>]\n");
   fprintf(stderr, "         [-r<int(1)>] [-g<gpu ordinal(0)>] <subject:db> <target:db> ...\n");
   fprintf(stderr, "daligner [options] -P <HPCdaligner plan file, or - for stdin> [-G <GPUs: n | i,j,...>] [-L]\n");
@@ -213,6 +216,7 @@ typedef struct
   char  *plan;
   char  *gpus;          /* -G: node mode */
   int    lamerge;       /* -L: run the plan's LAmerge lines too */
+  int    check;         /* -C: check every .las file as it is written */
 } Opts;
 
 static void default_opts(Opts *o)
@@ -226,7 +230,7 @@ static int parse_opts(int argc, char *argv[], Opts *o)
 { int c;
   opterr = 0;
   optind = 1;
-  while ((c = getopt(argc, argv, "vbOTAIk:w:h:t:M:e:l:s:H:D:m:r:j:g:P:G:L")) != -1)
+  while ((c = getopt(argc, argv, "vbOTAICk:w:h:t:M:e:l:s:H:D:m:r:j:g:P:G:L")) != -1)
     switch (c)
     { case 'v': o->verbose = 1; break;
       case 'T': o->notrace = 1; break;
@@ -247,6 +251,7 @@ static int parse_opts(int argc, char *argv[], Opts *o)
       case 'P': o->plan = optarg; break;
       case 'G': o->gpus = optarg; break;
       case 'L': o->lamerge = 1; break;
+      case 'C': o->check = 1; break;
       case 'M':
         o->mem_gb = atoi(optarg);
         if (o->mem_gb < 0)
@@ -301,10 +306,19 @@ static void apply_opts(const Opts *o)
   SYMMETRIC = o->symmetric;
   BIASED = o->biased;
   MINOVER = 2 * o->minover;                        /* daligner.c:861 */
+  if (o->check)
+    damar_set_check(1);
   if (Set_Filter_Params(o->kmer, o->binshift, o->maxreps, o->hitmin, o->nthreads))
     { fprintf(stderr, "Illegal combination of filter parameters\n");
       exit(1);
     }
+}
+
+/* -C: the exit status once every file is closed (the violations were counted by the writer threads, las.c) */
+static int check_status(void)
+{ int64 c[4];
+  damar_check_totals(c);
+  return c[2] > 0 ? 1 : 0;
 }
 
 static int symmetric_for(const char *afile, const char *aroot, char **bfiles, int nb)     /* daligner.c:911-946 */
@@ -415,6 +429,7 @@ int main(int argc, char *argv[])
             if (VERBOSE)
               printf("\nBuilding index for %s\n", broot);
             TIMED(1, bindex = Sort_Kmers(&it->blk, &blen));
+            damar_check_note_blocks(spec, &ablock, &it->blk);
             TIMED(2, Match_Filter(aroot, &ablock, broot, &it->blk, aindex, alen, bindex, blen, 0, spec));
             if (VERBOSE)
               printf("\nBuilding index for c(%s)\n", broot);
@@ -432,6 +447,7 @@ int main(int argc, char *argv[])
           }
         else
           { char *d1 = NULL;
+            damar_check_note_blocks(spec, &ablock, NULL);
             TIMED(2, Match_Filter(aroot, &ablock, aroot, &ablock, aindex, alen, aindex, alen, 0, spec));
             if (VERBOSE)
               printf("\nBuilding index for c(%s)\n", aroot);
@@ -472,7 +488,7 @@ int main(int argc, char *argv[])
         fprintf(stderr, " %s=%.1f", P_name[i], P_ms[i]);
       fprintf(stderr, "\n");
     }
-  return 0;
+  return check_status();
 }
 
 /* Plan mode and node mode fork their workers on the premise that this process has not touched the GPU yet.  Under
@@ -790,7 +806,7 @@ static void stats_take(int lo, int hi)               /* the last call's timings 
     S_ms[i] += t[i];
 }
 
-static void plan_stats_write(int nlines, int worker, int nworkers, double wall)
+static void plan_stats_write(int nlines, int worker, int nworkers, double wall, int check)
 { const char *dst = getenv("DAMAR_PLAN_STATS");
   static const char *nm[DAMAR_T_COUNT] = { "tuples", "ksort", "table", "merge", "ssort", "work", "report", "d2h", "tail" };
   int64  nf = 0, nl = 0, nrec = 0, las[4];
@@ -818,7 +834,14 @@ static void plan_stats_write(int nlines, int worker, int nworkers, double wall)
   fprintf(f, "\"write\": %.1f}, \"host_wall_ms\": {", wr);
   for (i = 0; i < 12; i++)
     fprintf(f, "%s\"%s\": %.1f", i ? ", " : "", P_name[i], P_ms[i]);
-  fprintf(f, "}}\n");
+  fprintf(f, "}");
+  if (check)                                          /* -C: what the writers checked (damar_check_totals) */
+    { int64 c[4];
+      damar_check_totals(c);
+      fprintf(f, ", \"checked_files\": %lld, \"checked_records\": %lld, \"check_violations\": %lld, \"checked_discarded_files\": %lld",
+              (long long) c[0], (long long) c[1], (long long) c[2], (long long) c[3]);
+    }
+  fprintf(f, "}\n");
   if (f != stderr)
     fclose(f);
 }
@@ -905,6 +928,7 @@ static void plan_line(const Opts *o, const char *afile, char **bfiles, int nb)
       jobs[0].self = jobs[1].self = same;
       jobs[0].comp = 0;  jobs[1].comp = 1;
       jobs[0].spec = jobs[1].spec = sp;
+      damar_check_note_blocks(sp, &a->blk, same ? NULL : &b->blk);
       t0 = wall_ms();
       damar_match_batch(jobs, 2);
       stats_take(DAMAR_T_MERGE, DAMAR_T_REPORT);
@@ -1138,7 +1162,7 @@ static int plan_main(const Opts *base, const char *planfile)
             got = read(pfd[0], &c, 1);
           while (got < 0 && errno == EINTR);
           if (got == 1)
-            return 0;
+            return c == 2;                         /* (2: -C found violations; every file is written all the same) */
           { int st = 0;
             waitpid(pid, &st, 0);
             if (WIFEXITED(st) && WEXITSTATUS(st) != 0)
@@ -1314,7 +1338,7 @@ static int plan_main(const Opts *base, const char *planfile)
   TIMED(5, damar_async_drain());
   mark("drained: every .las closed");
   S_loads = __atomic_load_n(&S_loads_, __ATOMIC_RELAXED);
-  plan_stats_write(nl, 0, 1, wall_ms() - t_plan0);
+  plan_stats_write(nl, 0, 1, wall_ms() - t_plan0, base->check);
   if (getenv("DAMAR_PLAN_TIDY") == NULL)
     { /* every file is closed; releasing tens of GB of HBM buffer by buffer, joining the threads and tearing the HIP context
          down costs a tenth of a second of wall time and changes nothing on disk: leave that to process exit */
@@ -1326,13 +1350,13 @@ static int plan_main(const Opts *base, const char *planfile)
         }
       fflush(NULL);
       if (PLAN_done_fd >= 0)
-        { char c = 1;
+        { char c = check_status() ? 2 : 1;
           damar_gate_hold(GATE_gpu);                 /* from here on this process is only tearing down */
           if (write(PLAN_done_fd, &c, 1) != 1)
             _exit(1);
           close(PLAN_done_fd);
         }
-      _exit(0);                                      /* (releasing buffer by buffer first was measured: the GPU is free no sooner, scripts/b2b.py) */
+      _exit(check_status());                                      /* (releasing buffer by buffer first was measured: the GPU is free no sooner, scripts/b2b.py) */
     }
   while (have_reader > 0)
     pthread_join(reader[--have_reader], NULL);
@@ -1365,7 +1389,7 @@ static int plan_main(const Opts *base, const char *planfile)
         fprintf(stderr, " %s=%.1f", P_name[i], P_ms[i]);
       fprintf(stderr, "\n");
     }
-  return 0;
+  return check_status();
 }
 
 /* ---------------------------------------------------------------------------------------------------
@@ -1391,6 +1415,7 @@ typedef struct
   struct { int units, stolen, builds, numa, cpus, tails, writers, loads;  double wall_ms;
            double phase_ms[DAMAR_T_COUNT + 1];                    /* the library's clocks (DAMAR_T_*), then the writers' */
            long long pairs, seeds, aligns, records, aligned_bp, las_bytes;
+           long long check[4];                                      /* -C: damar_check_totals of the worker */
          } stat[NODE_MAXW];
   atomic_int done[NODE_MAXW];            /* the worker has closed its last file (what it does after that is teardown) */
 } NodeShared;
@@ -1760,6 +1785,11 @@ static int node_worker(int w, int gpu, int nworkers, int sharers, const Opts *o,
     S->stat[w].pairs = S_pairs;  S->stat[w].seeds = S_seeds;  S->stat[w].aligns = nf;
     S->stat[w].records = las[2];  S->stat[w].aligned_bp = las[3];  S->stat[w].las_bytes = las[0];
     S->stat[w].loads = __atomic_load_n(&S_loads_, __ATOMIC_RELAXED);
+    { int64 c[4];
+      damar_check_totals(c);
+      for (q = 0; q < 4; q++)
+        S->stat[w].check[q] = c[q];
+    }
   }
   damar_gate_hold(GATE_gpu);                         /* from here on this worker is only tearing down (damar_gate.h) */
   atomic_store(&S->done[w], 1);
@@ -1780,6 +1810,7 @@ static int node_main(const Opts *base, const char *planfile)
   char   cwd[PATH_MAX];
   pid_t  pid[NODE_MAXW];
   int    ok = 1;
+  long long checked[4] = { 0, 0, 0, 0 };
   double t0 = wall_ms();
 
   /* -G n: GPUs 0 .. n-1; -G i,j,...: those.  DAMAR_SHARE_GPU=1 puts every worker on the first (a rehearsal on one GPU) */
@@ -2003,6 +2034,11 @@ static int node_main(const Opts *base, const char *planfile)
   }
   if (!ok)
     return 1;
+  for (i = 0; i < W; i++)                             /* -C: the workers' checks, summed (the parts of split pairs count as files) */
+    { int q;
+      for (q = 0; q < 4; q++)
+        checked[q] += S->stat[i].check[q];
+    }
 
   /* ---- the files of split pairs: every part holds the records of its B-read range, sorted; records of one
           (aread, bread) pair never span parts, so a merge on the record order restores the unsplit pair's files ---- */
@@ -2089,7 +2125,11 @@ static int node_main(const Opts *base, const char *planfile)
                 fprintf(f, "%s\"%s\": %.1f", q ? ", " : "", nm[q], S->stat[i].phase_ms[q]);
               fprintf(f, "}}");
             }
-          fprintf(f, "]}\n");
+          fprintf(f, "]");
+          if (base->check)
+            fprintf(f, ", \"checked_files\": %lld, \"checked_records\": %lld, \"check_violations\": %lld, \"checked_discarded_files\": %lld",
+                    checked[0], checked[1], checked[2], checked[3]);
+          fprintf(f, "}\n");
           if (f != stderr)
             fclose(f);
         }
@@ -2109,5 +2149,5 @@ static int node_main(const Opts *base, const char *planfile)
       }
       fprintf(stderr, "\n");
     }
-  return ok ? 0 : 1;
+  return (ok && checked[2] == 0) ? 0 : 1;
 }

@@ -56,10 +56,14 @@ void damar_emit_pair(damar_path *am, int na, damar_path *bm, int nb, damar_tpool
 int damar_append_overlap_buffer(Overlap_IO_Buffer *dst, const Overlap_IO_Buffer *src);
 
 /* Detached overlap buffers for a writer thread (las.c) */
-typedef struct { int trace_space, nthreads, symmetric, only_identity; } damar_write_params;
+typedef struct { int trace_space, nthreads, symmetric, only_identity;
+                 void *lens;            /* with checking on (damar_set_check): the read lengths noted at the spec, las.c's to free */
+               } damar_write_params;
 Overlap_IO_Buffer *damar_detach_overlap_buffers(Align_Spec *spec, damar_write_params *p);
 void damar_write_detached(const damar_write_params *p, Overlap_IO_Buffer *bufs,
                           const char *dir1, const char *dir2, const char *ablock, const char *bblock, int lastRead);
+
+int  damar_check_on(void);             /* las.c: damar_set_check(1) is in force */
 
 #ifdef __cplusplus
 }

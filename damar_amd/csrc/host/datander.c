@@ -64,7 +64,7 @@ static void *read_ahead(void *arg)
 
 
 int main(int argc, char *argv[])
-{ int    kmer = 12, hitmin = 35, binshift = 4, spacing = 100, nthreads = 4, c, i, gpu = -1;
+{ int    kmer = 12, hitmin = 35, binshift = 4, spacing = 100, nthreads = 4, c, i, gpu = -1, check = 0;
   double ecorr = .70;
   char  *outdir = "tan";
   struct stat st;
@@ -74,9 +74,10 @@ int main(int argc, char *argv[])
 
   MINOVER = 500;
   opterr = 0;
-  while ((c = getopt(argc, argv, "vk:w:h:e:l:s:o:j:g:")) != -1)
+  while ((c = getopt(argc, argv, "vCk:w:h:e:l:s:o:j:g:")) != -1)
     switch (c)
     { case 'v': VERBOSE = 1; break;
+      case 'C': check = 1; break;          /* every file checked as it is written (daligner.c, -C) */
       case 'k': kmer = atoi(optarg); break;
       case 'w': binshift = atoi(optarg); break;
       case 'h': hitmin = atoi(optarg); break;
@@ -137,7 +138,7 @@ int main(int argc, char *argv[])
             got = read(pfd[0], &b, 1);
           while (got < 0 && errno == EINTR);
           if (got == 1)
-            return 0;
+            return b == 2;                           /* (2: -C found violations) */
           { int ws = 0;
             waitpid(pid, &ws, 0);
             if (WIFEXITED(ws) && WEXITSTATUS(ws) != 0)
@@ -165,6 +166,8 @@ int main(int argc, char *argv[])
     { fprintf(stderr, "datander: cannot start the reader thread\n");
       exit(1);
     }
+  if (check)
+    damar_set_check(1);
   gpu = gpu >= 0 ? gpu : (getenv("DAMAR_DEVICE") ? atoi(getenv("DAMAR_DEVICE")) : 0);
   damar_gate_wait(gpu);                              /* not into the teardown of the command before this one (damar_gate.h) */
   damar_hip_init(gpu);                               /* beside the first read */
@@ -181,6 +184,7 @@ int main(int argc, char *argv[])
         exit(1);
       root = damar_root(R.name[i], ".db");
       spec = New_Align_Spec(ecorr, spacing, blk->freq, nthreads, 1, 0, 0, 0);
+      damar_check_note_blocks(spec, blk, NULL);
       if (R.pk[i].raw != NULL)                       /* Match_Self (scrub/tandem.c:1182) on a block that stays packed on the host */
         { damar_dev_block *dev = damar_block_upload_packed(blk, R.pk + i, 0);
           if (VERBOSE)
@@ -204,13 +208,17 @@ int main(int argc, char *argv[])
     }
   pthread_join(th, NULL);
   fflush(NULL);
+  { int64 tot[4];
+    damar_check_totals(tot);
+    check = tot[2] > 0;                              /* from here on: the exit status */
+  }
   if (done_fd >= 0)
-    { char b = 1;
+    { char b = check ? 2 : 1;
       damar_gate_hold(gpu);                          /* from here on this process is only tearing down */
       if (write(done_fd, &b, 1) != 1)
         _exit(1);
       close(done_fd);
-      _exit(0);                 /* every file is closed: what is left is teardown */
+      _exit(check);             /* every file is closed: what is left is teardown */
     }
-  return 0;
+  return check;
 }

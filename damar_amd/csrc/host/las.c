@@ -15,7 +15,12 @@
 #include <time.h>
 
 #include "damar_align.h"
+#include "damar_check.h"
 #include "damar_host.h"
+
+/* The checker is part of this translation unit: whatever is built from las.c -- the library, the CPU oracle's tools --
+   has the writer's check with it and needs no line of its own for it.  (bin/LAcheck compiles lascheck.c by itself.) */
+#include "lascheck.c"
 
 #define TRIM_BITS   15
 #define TRIM_SIZE   (1 << TRIM_BITS)
@@ -34,6 +39,8 @@ typedef struct
   Overlap_IO_Buffer *iobuf;
   int    symmetric;
   int    only_identity;
+  const struct LenTab **lens;   /* with checking on: the read lengths of the blocks compared under this specification */
+  int    nlens;
 } Spec;
 
 /* align.c:198-199: how much of the error rate a base composition leaves, by how far A+T is from one half */
@@ -123,6 +130,7 @@ void Free_Align_Spec(Align_Spec *spec)
 { Spec *s = (Spec *) spec;
   set_give(s->iobuf, s->nthreads);
   free(s->score);
+  free(s->lens);
   free(s);
 }
 
@@ -287,6 +295,118 @@ int Write_Overlap(FILE *out, Overlap *ovl, int tbytes)
   return 0;
 }
 
+/* ---- checking what is written (daligner -C, damar_set_check) ------------------------------------------------------
+ * Every file is run through the routine of lascheck.c by the thread that writes it, record by record as the records
+ * are assembled for the file: LAcheck's -p -s -d and the strict set, to the end of the file.  The bounds need the reads'
+ * lengths, which the writer does not have: the comparisons note the blocks they run on at their Align_Spec
+ * (damar_check_note_blocks), a write request takes the list along.  A table of lengths is made once per block and
+ * kept for the life of the process (4 bytes per read); a block is known by its first read, its number of reads and
+ * the lengths themselves, so that blocks of different databases in one process are told apart. */
+typedef struct LenTab { int first, n; int *len; } LenTab;
+typedef struct { int n; const LenTab *t[1]; } LenSet;
+
+static int    CHECK_on;
+static int64  CHECK_total[4];            /* files checked, records checked, violations, files checked but discarded */
+static LenTab **LT;
+static int    LT_n;
+static pthread_mutex_t LT_mu = PTHREAD_MUTEX_INITIALIZER;
+
+#define CHECK_LINES 16                   /* lines per file on stderr; the violations beyond are counted only */
+
+void damar_set_check(int on)  { __atomic_store_n(&CHECK_on, on != 0, __ATOMIC_RELAXED); }
+int  damar_check_on(void)     { return __atomic_load_n(&CHECK_on, __ATOMIC_RELAXED); }
+
+void damar_check_totals(int64 *out)
+{ int i;
+  for (i = 0; i < 4; i++)
+    out[i] = __atomic_load_n(&CHECK_total[i], __ATOMIC_RELAXED);
+}
+
+static const LenTab *lentab_of(const HITS_DB *b)            /* (LT_mu held) */
+{ LenTab *t;
+  int i, r;
+  for (i = 0; i < LT_n; i++)
+    if (LT[i]->first == b->ufirst && LT[i]->n == b->nreads)
+      { for (r = 0; r < b->nreads && LT[i]->len[r] == b->reads[r].rlen; r++)
+          ;
+        if (r == b->nreads)
+          return LT[i];
+      }
+  t = (LenTab *) malloc(sizeof(LenTab));
+  LT = (LenTab **) realloc(LT, sizeof(LenTab *) * (size_t) (LT_n + 1));
+  if (t == NULL || LT == NULL || (t->len = (int *) malloc(sizeof(int) * (size_t) (b->nreads > 0 ? b->nreads : 1))) == NULL)
+    { fprintf(stderr, "damar: out of memory (read lengths for the check)\n");
+      exit(1);
+    }
+  t->first = b->ufirst;  t->n = b->nreads;
+  for (r = 0; r < b->nreads; r++)
+    t->len[r] = b->reads[r].rlen;
+  LT[LT_n++] = t;
+  return t;
+}
+
+void damar_check_note_blocks(Align_Spec *spec, const HITS_DB *ablock, const HITS_DB *bblock)
+{ Spec *s = (Spec *) spec;
+  const HITS_DB *two[2];
+  int w, i;
+  if (!damar_check_on() || s == NULL)
+    return;
+  two[0] = ablock;  two[1] = bblock;
+  pthread_mutex_lock(&LT_mu);
+  for (w = 0; w < 2; w++)
+    if (two[w] != NULL && two[w]->reads != NULL)
+      { const LenTab *t = lentab_of(two[w]);
+        for (i = 0; i < s->nlens && s->lens[i] != t; i++)
+          ;
+        if (i == s->nlens)
+          { s->lens = (const LenTab **) realloc(s->lens, sizeof(LenTab *) * (size_t) (s->nlens + 1));
+            if (s->lens == NULL)
+              { fprintf(stderr, "damar: out of memory (read lengths for the check)\n");
+                exit(1);
+              }
+            s->lens[s->nlens++] = t;
+          }
+      }
+  pthread_mutex_unlock(&LT_mu);
+}
+
+static LenSet *lenset_of(Spec *s)                         /* the tables noted so far, for one write request (free()) */
+{ LenSet *set = NULL;
+  if (!damar_check_on())
+    return NULL;
+  pthread_mutex_lock(&LT_mu);
+  if (s->nlens > 0 && (set = (LenSet *) malloc(sizeof(LenSet) + sizeof(LenTab *) * (size_t) s->nlens)) != NULL)
+    { set->n = s->nlens;
+      memcpy(set->t, s->lens, sizeof(LenTab *) * (size_t) s->nlens);
+    }
+  pthread_mutex_unlock(&LT_mu);
+  return set;
+}
+
+static int length_of(const LenSet *set, int read, int *hint)       /* -1: of no block that was noted */
+{ int i;
+  if (set == NULL)
+    return -1;
+  if (*hint < set->n && (uint32) (read - set->t[*hint]->first) < (uint32) set->t[*hint]->n)
+    return set->t[*hint]->len[read - set->t[*hint]->first];
+  for (i = 0; i < set->n; i++)
+    if ((uint32) (read - set->t[i]->first) < (uint32) set->t[i]->n)
+      { *hint = i;
+        return set->t[i]->len[read - set->t[i]->first];
+      }
+  return -1;
+}
+
+typedef struct { const char *path; int64 said; } CheckSink;
+
+static void check_say(void *arg, int kind, const char *text)
+{ CheckSink *k = (CheckSink *) arg;
+  if (kind != DAMAR_CHECK_MESSAGE)
+    return;
+  if (k->said++ < CHECK_LINES)
+    fprintf(stderr, "damar: CHECK %s: %s\n", k->path, text);
+}
+
 typedef struct                   /* one gathered record: where it lies, its place in the gather, and its sort keys */
 { const Overlap *ovl;
   const char    *trace;          /* its trace bytes (NULL: none) */
@@ -317,7 +437,7 @@ static int by_overlap(const void *x, const void *y)
  * (4), then the records.  Records are assembled in a buffer of the writer's own and leave with one write() per 4 MB:
  * through stdio a record was two fwrite calls, which was most of a writer thread's time (1.7 M records per config-2
  * step). */
-typedef struct { int fd; char *buf; size_t fill, cap; const char *path; } LasOut;
+typedef struct { int fd; char *buf; size_t fill, cap; const char *path; int kept; } LasOut;
 
 static void las_fail(const LasOut *o, const char *what)
 { fprintf(stderr, "[ERROR] - Write_Overlap_Buffer: Cannot %s file %s\n", what, o->path);
@@ -441,7 +561,8 @@ static LasOut las_open(const char *path, int tspace)
   o.cap  = LAS_BUF;
   o.fill = 0;
   o.buf  = las_buf_take();
-  o.fd   = las_is_kept(path) ? open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666) : open("/dev/null", O_WRONLY);
+  o.kept = las_is_kept(path);
+  o.fd   = o.kept ? open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666) : open("/dev/null", O_WRONLY);
   if (o.fd < 0 || o.buf == NULL)
     las_fail(&o, "open for writing");
   las_put(&o, &none, sizeof(none));
@@ -556,21 +677,54 @@ static Keyed *sort_keyed(Keyed *all, int n)
   return out;
 }
 
-typedef struct { const char *path; int tspace, tbytes; const Keyed *recs; int n; } FilePart;
+typedef struct { const char *path; int tspace, tbytes; const Keyed *recs; int n; const LenSet *lens; int check; } FilePart;
+
+/* the same loop with every record handed to the checker as it is assembled (check: 1, or 2 for records without traces) */
+static void write_file_part_checked(const FilePart *f, LasOut *out, int64 *bp)
+{ const int opts = DAMAR_CHECK_SORT | DAMAR_CHECK_DUPES | DAMAR_CHECK_STRICT | DAMAR_CHECK_ALL |
+                   (f->check == 1 ? DAMAR_CHECK_PTP : 0);
+  damar_lascheck ck;
+  CheckSink sink;
+  int ha = 0, hb = 0, j;
+  sink.path = f->path;  sink.said = 0;
+  damar_lascheck_begin(&ck, f->tspace, opts, check_say, &sink);
+  for (j = 0; j < f->n; j++)
+    { const Keyed *k = f->recs + j;
+      if (j + 12 < f->n)
+        { __builtin_prefetch(f->recs[j + 12].ovl);
+          __builtin_prefetch(f->recs[j + 12].trace);
+        }
+      las_record(out, k, f->tbytes);
+      damar_lascheck_feed(&ck, k->ovl, (k->trace != NULL && k->ovl->path.tlen > 0) ? k->trace : NULL, f->tbytes,
+                          length_of(f->lens, k->aread, &ha), length_of(f->lens, k->bread, &hb));
+      *bp += (int64) (uint32) k->k2 - (int64) (uint32) ((k->k2 >> 32) & 0x7fffffffu);
+    }
+  damar_lascheck_end(&ck, f->n);
+  if (sink.said > CHECK_LINES)
+    fprintf(stderr, "damar: CHECK %s: %lld violations in all, the first %d shown\n", f->path, (long long) sink.said, CHECK_LINES);
+  __atomic_fetch_add(&CHECK_total[0], 1, __ATOMIC_RELAXED);
+  __atomic_fetch_add(&CHECK_total[1], ck.seen, __ATOMIC_RELAXED);
+  __atomic_fetch_add(&CHECK_total[2], ck.violations, __ATOMIC_RELAXED);
+  if (!out->kept)
+    __atomic_fetch_add(&CHECK_total[3], 1, __ATOMIC_RELAXED);
+}
 
 static void *write_file_part(void *arg)
 { const FilePart *f = (const FilePart *) arg;
   LasOut out = las_open(f->path, f->tspace);
   int64  bp = 0;
   int    j;
-  for (j = 0; j < f->n; j++)
-    { if (j + 12 < f->n)                            /* the records lie where the tails left them, in work-item order */
-        { __builtin_prefetch(f->recs[j + 12].ovl);
-          __builtin_prefetch(f->recs[j + 12].trace);
-        }
-      las_record(&out, f->recs + j, f->tbytes);
-      bp += (int64) (uint32) f->recs[j].k2 - (int64) (uint32) ((f->recs[j].k2 >> 32) & 0x7fffffffu);
-    }
+  if (f->check)
+    write_file_part_checked(f, &out, &bp);
+  else
+    for (j = 0; j < f->n; j++)
+      { if (j + 12 < f->n)                          /* the records lie where the tails left them, in work-item order */
+          { __builtin_prefetch(f->recs[j + 12].ovl);
+            __builtin_prefetch(f->recs[j + 12].trace);
+          }
+        las_record(&out, f->recs + j, f->tbytes);
+        bp += (int64) (uint32) f->recs[j].k2 - (int64) (uint32) ((f->recs[j].k2 >> 32) & 0x7fffffffu);
+      }
   __atomic_fetch_add(&LAS_total[3], bp, __ATOMIC_RELAXED);
   las_close(&out, f->n);
   return NULL;
@@ -602,6 +756,7 @@ static void write_buffers(const damar_write_params *s, Overlap_IO_Buffer *iobuf,
   char    path1[4300], path2[4300];
 
   double  w0, w1, w2;
+  const int check = damar_check_on() ? (iobuf[0].no_trace ? 2 : 1) : 0;
   pthread_mutex_lock(&W_mu);
   if (W_prof < 0)
     { W_prof = getenv("DAMAR_HOSTPROF") != NULL;
@@ -641,7 +796,7 @@ static void write_buffers(const damar_write_params *s, Overlap_IO_Buffer *iobuf,
       else
         snprintf(path1, sizeof(path1), "%s.las", ablock);
       { FilePart whole;
-        whole.path = path1;  whole.tspace = tspace;  whole.tbytes = tbytes;  whole.recs = all;  whole.n = n;
+        whole.path = path1;  whole.tspace = tspace;  whole.tbytes = tbytes;  whole.lens = (const LenSet *) s->lens;  whole.check = check;  whole.recs = all;  whole.n = n;
         write_file_part(&whole);
       }
     }
@@ -677,10 +832,10 @@ static void write_buffers(const damar_write_params *s, Overlap_IO_Buffer *iobuf,
             break;
         /* the two files are written side by side: the second by a thread of its own (the last block pair of a command
            is written with nothing else left to do: its two files one after the other were a tenth of the drain) */
-        part2.path = second;  part2.tspace = tspace;  part2.tbytes = tbytes;  part2.recs = all + j;  part2.n = n - j;
+        part2.path = second;  part2.tspace = tspace;  part2.tbytes = tbytes;  part2.lens = (const LenSet *) s->lens;  part2.check = check;  part2.recs = all + j;  part2.n = n - j;
         par = (n - j > 4096) && pthread_create(&th, NULL, write_file_part, &part2) == 0;
         { FilePart part1;
-          part1.path = first;  part1.tspace = tspace;  part1.tbytes = tbytes;  part1.recs = all;  part1.n = j;
+          part1.path = first;  part1.tspace = tspace;  part1.tbytes = tbytes;  part1.lens = (const LenSet *) s->lens;  part1.check = check;  part1.recs = all;  part1.n = j;
           write_file_part(&part1);
         }
         if (par)
@@ -704,7 +859,9 @@ void Write_Overlap_Buffer(Align_Spec *spec, char *dir1, char *dir2, char *ablock
   damar_write_params p;
   p.trace_space = s->trace_space;  p.nthreads = s->nthreads;
   p.symmetric = s->symmetric;      p.only_identity = s->only_identity;
+  p.lens = lenset_of(s);
   write_buffers(&p, s->iobuf, dir1, dir2, ablock, bblock, lastRead);
+  free(p.lens);
 }
 
 /* For a writer thread: take the filled buffers away from the Align_Spec (which continues with
@@ -774,6 +931,7 @@ Overlap_IO_Buffer *damar_detach_overlap_buffers(Align_Spec *spec, damar_write_pa
   Overlap_IO_Buffer *old = s->iobuf;
   p->trace_space = s->trace_space;  p->nthreads = s->nthreads;
   p->symmetric = s->symmetric;      p->only_identity = s->only_identity;
+  p->lens = lenset_of(s);
   s->iobuf = set_take(s->nthreads, old[0].tbytes, old[0].no_trace);
   return old;
 }
@@ -781,6 +939,7 @@ Overlap_IO_Buffer *damar_detach_overlap_buffers(Align_Spec *spec, damar_write_pa
 void damar_write_detached(const damar_write_params *p, Overlap_IO_Buffer *bufs,
                           const char *dir1, const char *dir2, const char *ablock, const char *bblock, int lastRead)
 { write_buffers(p, bufs, dir1, dir2, ablock, bblock, lastRead);
+  free(p->lens);
   set_give(bufs, p->nthreads);
 }
 

@@ -99,12 +99,14 @@ class Plan:
 
     def __init__(self, k=14, w=6, h=35, t=0, e=.70, l=1000, s=100, j=4, run=1,
                  symmetric=1, identity=0, verbose=0, async_tail=True, masks=None, biased=0,
-                 only_identity=0, no_trace=0, index_cache_bytes=None):
+                 only_identity=0, no_trace=0, index_cache_bytes=None, check=False):
         self.k, self.w, self.h, self.t, self.e, self.l, self.s, self.j, self.run = k, w, h, t, e, l, s, j, run
         self.symmetric, self.identity, self.verbose = symmetric, identity, verbose
         self.only_identity, self.no_trace = only_identity, no_trace      # daligner -O, -T (daligner.c:731-739)
         self.masks = list(masks or [])
+        self.check = bool(check)     # daligner -C: every file checked as it is written (api.check_totals after finish())
         L = api.lib()
+        L.damar_set_check(1 if check else 0)
         api.set_globals(verbose=verbose, minover=2 * l, symmetric=symmetric, identity=identity, biased=biased)
         L.damar_bias_reset()
         if L.Set_Filter_Params(k, w, t, h, j):
@@ -227,6 +229,8 @@ class Plan:
             arr[q].bblock = C.pointer(bdb)
             arr[q].aidx, arr[q].bidx = aidx, bidx
             arr[q].self_, arr[q].comp, arr[q].spec = self_, comp, spec
+            if self.check:                         # (the writer takes the reads' lengths from the blocks noted at the spec)
+                L.damar_check_note_blocks(spec, C.byref(adb), C.byref(bdb))
         L.damar_match_batch(arr, len(jobs))
         self.matches += len(jobs)
         ns, nsplit = api.slab_totals()
@@ -314,9 +318,10 @@ class Plan:
             self.run_pairs(a, bs[k:k + self.GROUP], outdir)
 
 
-def run_datander(block, outdir, k=12, w=4, h=35, e=.70, l=500, s=100, j=4, verbose=0, out="tan"):
-    """scrub/datander.c:226-258 for one block: Match_Self + tan/<blk>.<blk>.las."""
+def run_datander(block, outdir, k=12, w=4, h=35, e=.70, l=500, s=100, j=4, verbose=0, out="tan", check=False):
+    """scrub/datander.c:226-258 for one block: Match_Self + tan/<blk>.<blk>.las.  check: as datander -C."""
     L = api.lib()
+    L.damar_set_check(1 if check else 0)
     api.set_globals(verbose=verbose, minover=2 * l)
     if L.damar_tandem_set_params(k, w, h, j):
         raise ValueError("Illegal combination of filter parameters")
@@ -324,6 +329,8 @@ def run_datander(block, outdir, k=12, w=4, h=35, e=.70, l=500, s=100, j=4, verbo
     with _cwd(outdir):
         spec = L.New_Align_Spec(e, s, block.db.freq, j, 1, 0, 0, 0)
         cnt = (api.c_int64 * 3)()
+        if check:
+            L.damar_check_note_blocks(spec, C.byref(block.db), None)
         L.damar_match_self(C.byref(block.db), block.upload(), spec, cnt)
         L.Write_Overlap_Buffer(spec, out.encode(), out.encode(), block.root.encode(), block.root.encode(),
                                block.last_read())

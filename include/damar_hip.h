@@ -203,6 +203,18 @@ void damar_last_timings(double *ms /* [DAMAR_T_COUNT] */);
 /* bytes, files, records and aligned base pairs (sum of aepos - abpos) the .las writers have produced since the process started (host/las.c; with DAMAR_LAS_KEEP=<list>
    only the files whose path ends in a line of <list> reach the file system, the rest /dev/null: measurement of long plans) */
 void damar_las_totals(int64 *out /* [4] */);
+/* Checking of every .las file as it is written (daligner -C): with damar_set_check(1) the thread that writes a file runs
+   its records and trace bytes, as they go to the file, through the routine of include/damar_check.h -- LAcheck's -p -s -d
+   and the strict set, read lengths from the blocks that were compared -- files that DAMAR_LAS_KEEP discards included.  A
+   violation is one line "damar: CHECK <file>: <message>" on stderr (16 per file at most) and is counted; nothing else
+   changes, the file is written all the same.  Totals since the process started: files checked, records checked,
+   violations, files checked of those that were discarded. */
+void damar_set_check(int on);
+void damar_check_totals(int64 *out /* [4] */);
+/* The bounds (aepos <= alen, bepos <= blen) need the reads' lengths, which a write request does not carry: whoever runs
+   the comparisons notes their two blocks (bblock may be NULL) at the Align_Spec the records go to, before the files are
+   asked for.  The lengths are copied.  Without it the bounds are left out; does nothing while checking is off. */
+void damar_check_note_blocks(Align_Spec *spec, const HITS_DB *ablock, const HITS_DB *bblock);
 
 /* Counters of the last damar_match / damar_match_batch (summed over its comparisons): [0] seed pairs, [1] work items
  * (read pairs entered), [2] Local_Alignment calls, [3] records from the device, [4] trace values, [5] launches of the
