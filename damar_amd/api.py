@@ -40,6 +40,35 @@ class MatchJob(C.Structure):           # include/damar_hip.h damar_match_job
                 ("spec", C.c_void_p), ("counts", c_int64 * 3)]
 
 
+_PI = C.POINTER(C.c_int)
+
+
+class PileBatch(C.Structure):          # include/damar_hip.h damar_pile_batch
+    _fields_ = [("npiles", c_int64), ("nrec", c_int64), ("pile_off", C.POINTER(c_int64)), ("pile_aread", _PI),
+                ("abpos", _PI), ("aepos", _PI), ("bbpos", _PI), ("bepos", _PI), ("bread", _PI), ("flags", _PI),
+                ("read_len", _PI), ("read_flags", _PI), ("nreads", C.c_int), ("maxlen", C.c_int)]
+
+
+class RepeatParams(C.Structure):       # damar_repeat_params
+    _fields_ = [("xcov_enter", C.c_double), ("xcov_leave", C.c_double), ("cov", C.c_int), ("merge_dist", C.c_int),
+                ("min_aln_len", C.c_int), ("inc_identity", C.c_int), ("inccov", C.c_int), ("max_cov", C.c_int)]
+
+
+class PileTrack(C.Structure):          # damar_pile_track
+    _fields_ = [("count", _PI), ("data", _PI), ("ndata", c_int64), ("merged", c_int64), ("repeat_bases", c_int64)]
+
+
+class DbInfo(C.Structure):             # host/damar_host.h damar_dbinfo
+    _fields_ = [("nreads", C.c_int), ("maxlen", C.c_int), ("read_len", _PI), ("read_flags", _PI), ("nblocks", C.c_int),
+                ("block_first", _PI), ("path", C.c_char_p)]
+
+
+class RepeatResult(C.Structure):       # damar_repeat_result
+    _fields_ = [("histo", C.POINTER(c_int64)), ("cov_max", C.c_int), ("cov_bases", c_int64), ("cov_inactive", c_int64),
+                ("avg_rlen", C.c_int), ("cov", C.c_int), ("anno", C.POINTER(C.c_uint64)), ("data", _PI), ("ndata", c_int64),
+                ("merged", c_int64), ("bases_total", c_int64), ("bases_repeat", c_int64)]
+
+
 _proto_done = False
 
 
@@ -118,6 +147,20 @@ def _lib():
         L.damar_set_check.argtypes = [C.c_int]
         L.damar_check_totals.argtypes = [C.POINTER(c_int64)]
         L.damar_check_note_blocks.argtypes = [C.c_void_p, C.POINTER(HITS_DB), C.POINTER(HITS_DB)]
+        L.damar_pile_coverage.argtypes = [C.POINTER(PileBatch), C.POINTER(RepeatParams), C.POINTER(c_int64), C.POINTER(c_int64), C.POINTER(c_int64)]
+        L.damar_pile_repeats.argtypes = [C.POINTER(PileBatch), C.POINTER(RepeatParams), C.POINTER(PileTrack)]
+        L.damar_pile_tandem.argtypes = [C.POINTER(PileBatch), C.c_int, C.POINTER(PileTrack)]
+        L.damar_pile_last.argtypes = [C.POINTER(C.c_double), C.POINTER(c_int64)]
+        L.damar_dbinfo_open.argtypes = [C.c_char_p, C.POINTER(DbInfo)]
+        L.damar_dbinfo_close.argtypes = [C.POINTER(DbInfo)]
+        L.damar_repeat_track.argtypes = [C.POINTER(DbInfo), C.c_char_p, C.POINTER(RepeatParams), C.c_int, C.c_int, C.POINTER(RepeatResult)]
+        L.damar_repeat_result_free.argtypes = [C.POINTER(RepeatResult)]
+        L.damar_tan_track.argtypes = [C.POINTER(DbInfo), C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.POINTER(c_int64)),
+                                      C.POINTER(C.POINTER(C.c_int)), C.POINTER(c_int64), C.POINTER(c_int64)]
+        L.damar_piles_open.argtypes = [C.c_char_p, c_int64]
+        L.damar_piles_open.restype = C.c_void_p
+        L.damar_piles_next.argtypes = [C.c_void_p, C.POINTER(PileBatch)]
+        L.damar_piles_close.argtypes = [C.c_void_p]
         _proto_done = True
     return L
 
@@ -232,6 +275,208 @@ def las_check(db, las, ptp=True, sort=True, dupes=True, strict=False, ignore_dis
     opts = [o for o, on in (("-p", ptp), ("-s", sort), ("-d", dupes), ("-i", ignore_discarded), ("-x", strict)) if on]
     r = subprocess.run([exe] + opts + [db, las], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
     return r.returncode, r.stderr.splitlines()
+
+
+# ---- mask tracks from piles of overlaps (LArepeat, TANmask) -------------------------------------------------------
+
+def repeat_params(cov=-1, xcov_enter=2.0, xcov_leave=1.7, merge_dist=-1, min_aln_len=0, inc_identity=0, inccov=0, max_cov=100):
+    return RepeatParams(xcov_enter, xcov_leave, cov, merge_dist, min_aln_len, int(inc_identity), int(inccov), max_cov)
+
+
+def _batch(piles, read_len, read_flags):
+    """piles: dict of numpy arrays pile_off (int64, npiles + 1), pile_aread, abpos, aepos, bbpos, bepos, bread, flags."""
+    import numpy as np
+    keep = {}
+    b = PileBatch()
+    keep["pile_off"] = np.ascontiguousarray(piles["pile_off"], dtype=np.int64)
+    b.npiles = len(keep["pile_off"]) - 1
+    b.pile_off = keep["pile_off"].ctypes.data_as(C.POINTER(c_int64))
+    for k in ("pile_aread", "abpos", "aepos", "bbpos", "bepos", "bread", "flags"):
+        keep[k] = np.ascontiguousarray(piles[k], dtype=np.int32)
+        setattr(b, k, keep[k].ctypes.data_as(_PI))
+    b.nrec = len(keep["abpos"])
+    keep["read_len"] = np.ascontiguousarray(read_len, dtype=np.int32)
+    keep["read_flags"] = np.ascontiguousarray(read_flags, dtype=np.int32)
+    b.read_len = keep["read_len"].ctypes.data_as(_PI)
+    b.read_flags = keep["read_flags"].ctypes.data_as(_PI)
+    b.nreads = len(keep["read_len"])
+    b.maxlen = int(keep["read_len"].max()) if b.nreads else 0
+    return b, keep
+
+
+def _take_track(L, t, count):
+    import numpy as np
+    data = np.ctypeslib.as_array(t.data, shape=(max(int(t.ndata), 1),))[:int(t.ndata)].copy()
+    C.CDLL(None).free(t.data)
+    return count, data
+
+
+def pile_coverage(piles, read_len, read_flags, params):
+    """-> (histogram int64[max_cov], bases, inactive bases) of the batch (LArepeat's estimate pass)."""
+    import numpy as np
+    L = _lib()
+    b, keep = _batch(piles, read_len, read_flags)
+    histo = np.zeros(params.max_cov, dtype=np.int64)
+    bases, inactive = c_int64(0), c_int64(0)
+    if L.damar_pile_coverage(C.byref(b), C.byref(params), histo.ctypes.data_as(C.POINTER(c_int64)), C.byref(bases), C.byref(inactive)):
+        raise RuntimeError("damar_pile_coverage failed")
+    return histo, bases.value, inactive.value
+
+
+def pile_repeats(piles, read_len, read_flags, params):
+    """-> (count int32[npiles], data int32[], merged, repeat_bases) of the batch (LArepeat's repeat pass)."""
+    import numpy as np
+    L = _lib()
+    b, keep = _batch(piles, read_len, read_flags)
+    count = np.zeros(max(b.npiles, 1), dtype=np.int32)
+    t = PileTrack(count.ctypes.data_as(_PI), None, 0, 0, 0)
+    if L.damar_pile_repeats(C.byref(b), C.byref(params), C.byref(t)):
+        raise RuntimeError("damar_pile_repeats failed")
+    count, data = _take_track(L, t, count[:b.npiles])
+    return count, data, int(t.merged), int(t.repeat_bases)
+
+
+def pile_tandem(piles, read_len, read_flags, min_len=0):
+    """-> (count int32[npiles], data int32[]) of the batch (TANmask's sweep with an honest threshold)."""
+    import numpy as np
+    L = _lib()
+    b, keep = _batch(piles, read_len, read_flags)
+    count = np.zeros(max(b.npiles, 1), dtype=np.int32)
+    t = PileTrack(count.ctypes.data_as(_PI), None, 0, 0, 0)
+    if L.damar_pile_tandem(C.byref(b), int(min_len), C.byref(t)):
+        raise RuntimeError("damar_pile_tandem failed")
+    return _take_track(L, t, count[:b.npiles])
+
+
+def pile_last():
+    """Of the last device call: ({upload, sort, sweep, download} ms, events sorted, regions written)."""
+    ms, cnt = (C.c_double * 4)(), (c_int64 * 2)()
+    _lib().damar_pile_last(ms, cnt)
+    return dict(zip(("upload", "sort", "sweep", "download"), list(ms))), cnt[0], cnt[1]
+
+
+def db_info(db):
+    """-> (read_len, read_flags, block_first or None) of a database, from its stub and index alone."""
+    import numpy as np
+    L = _lib()
+    d = DbInfo()
+    if L.damar_dbinfo_open(db.encode(), C.byref(d)):
+        raise RuntimeError("cannot open database %s" % db)
+    rl = np.ctypeslib.as_array(d.read_len, shape=(d.nreads,)).copy()
+    rf = np.ctypeslib.as_array(d.read_flags, shape=(d.nreads,)).copy()
+    bf = np.ctypeslib.as_array(d.block_first, shape=(d.nblocks + 1,)).copy() if d.nblocks else None
+    L.damar_dbinfo_close(C.byref(d))
+    return rl, rf, bf
+
+
+def read_piles(las, bound=0):
+    """The batches of whole piles of a .las file, as dicts of numpy arrays (host/piles.c)."""
+    import numpy as np
+    L = _lib()
+    r = L.damar_piles_open(las.encode(), bound)
+    if not r:
+        raise RuntimeError("cannot open %s" % las)
+    out = []
+    try:
+        while True:
+            b = PileBatch()
+            got = L.damar_piles_next(r, C.byref(b))
+            if got < 0:
+                raise RuntimeError("%s is damaged" % las)
+            if got == 0:
+                break
+            d = {"pile_off": np.ctypeslib.as_array(b.pile_off, shape=(b.npiles + 1,)).copy(),
+                 "pile_aread": np.ctypeslib.as_array(b.pile_aread, shape=(b.npiles,)).copy()}
+            for k in ("abpos", "aepos", "bbpos", "bepos", "bread", "flags"):
+                d[k] = np.ctypeslib.as_array(getattr(b, k), shape=(b.nrec,)).copy()
+            out.append(d)
+    finally:
+        L.damar_piles_close(r)
+    return out
+
+
+def repeat_track(db, las, max_areads=-1, cov_only=False, **opts):
+    """LArepeat on one .las file: -> (anno uint64[nreads + 1], data int32[], stats); opts as repeat_params()."""
+    import numpy as np
+    L = _lib()
+    d = DbInfo()
+    if L.damar_dbinfo_open(db.encode(), C.byref(d)):
+        raise RuntimeError("cannot open database %s" % db)
+    p = repeat_params(**opts)
+    res = RepeatResult()
+    rc = L.damar_repeat_track(C.byref(d), las.encode(), C.byref(p), max_areads, 1 if cov_only else 0, C.byref(res))
+    try:
+        if rc:
+            raise RuntimeError("damar_repeat_track failed (%d)" % rc)
+        stats = dict(cov=res.cov, merged=int(res.merged), bases_total=int(res.bases_total), bases_repeat=int(res.bases_repeat))
+        if res.histo:
+            stats.update(histo=np.ctypeslib.as_array(res.histo, shape=(p.max_cov,)).copy(), cov_max=res.cov_max,
+                         cov_bases=int(res.cov_bases), cov_inactive=int(res.cov_inactive), avg_rlen=res.avg_rlen)
+        if cov_only:
+            return None, None, stats
+        anno = np.ctypeslib.as_array(res.anno, shape=(d.nreads + 1,)).copy()
+        data = np.ctypeslib.as_array(res.data, shape=(max(int(res.ndata), 1),))[:int(res.ndata)].copy()
+        return anno, data, stats
+    finally:
+        L.damar_repeat_result_free(C.byref(res))
+        L.damar_dbinfo_close(C.byref(d))
+
+
+def tan_track(db, las, min_len=0, block=0):
+    """TANmask's track of one .las file: -> (offsets int64[reads + 1] in bytes, data int32[]) for the reads of `block`
+    (0: the whole database)."""
+    import numpy as np
+    L = _lib()
+    d = DbInfo()
+    if L.damar_dbinfo_open(db.encode(), C.byref(d)):
+        raise RuntimeError("cannot open database %s" % db)
+    try:
+        if block < 0 or block > d.nblocks:
+            raise ValueError("block %d of a database of %d blocks" % (block, d.nblocks))
+        first, last = (d.block_first[block - 1], d.block_first[block]) if block > 0 else (0, d.nreads)
+        offs, data = C.POINTER(c_int64)(), _PI()
+        nm, mk = c_int64(0), c_int64(0)
+        rc = L.damar_tan_track(C.byref(d), las.encode(), first, last, int(min_len), C.byref(offs), C.byref(data), C.byref(nm), C.byref(mk))
+        if rc:
+            raise RuntimeError("damar_tan_track failed (%d)" % rc)
+        o = np.ctypeslib.as_array(offs, shape=(last - first + 1,)).copy()
+        n = int(o[-1]) // 4
+        v = np.ctypeslib.as_array(data, shape=(max(n, 1),))[:n].copy()
+        libc = C.CDLL(None)
+        libc.free(offs)
+        libc.free(data)
+        return o, v
+    finally:
+        L.damar_dbinfo_close(C.byref(d))
+
+
+def read_track(db, name, block=0):
+    """A track as written: {"anno", "data"} and, for the .a2/.d2 form, the header's version, size and len.  The
+    compressed form is tried first, like the loaders."""
+    import numpy as np
+    import struct
+    import zlib
+    d = os.path.dirname(os.path.abspath(db))
+    root = os.path.basename(db)
+    root = root[:-3] if root.endswith(".db") else root
+    pre = os.path.join(d, ".%s.%s%s" % (root, "%d." % block if block > 0 else "", name))
+
+    def inflate(buf):
+        out, at = [], 0
+        while at < len(buf):
+            n = struct.unpack_from("<Q", buf, at)[0]
+            out.append(zlib.decompress(buf[at + 8:at + 8 + n]))
+            at += 8 + n
+        return b"".join(out)
+    if os.path.exists(pre + ".a2"):
+        a = open(pre + ".a2", "rb").read()
+        version, size, _pad, length, clen, cdlen = struct.unpack_from("<HHIQQQ", a, 0)
+        dd = open(pre + ".d2", "rb").read()
+        return dict(version=version, size=size, len=length, anno=np.frombuffer(inflate(a[64:64 + clen]), dtype="<u8"),
+                    data=np.frombuffer(inflate(dd[:cdlen]), dtype="<i4"))
+    a = open(pre + ".anno", "rb").read()
+    length, size = struct.unpack_from("<ii", a, 0)
+    return dict(len=length, size=size, anno=np.frombuffer(a[8:], dtype="<i8"), data=np.fromfile(pre + ".data", dtype="<i4"))
 
 
 def daligner_binary():

@@ -5,6 +5,7 @@
 
 #include "damar_db.h"
 #include "damar_align.h"
+#include "damar_hip.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -64,6 +65,56 @@ void damar_write_detached(const damar_write_params *p, Overlap_IO_Buffer *bufs,
                           const char *dir1, const char *dir2, const char *ablock, const char *bblock, int lastRead);
 
 int  damar_check_on(void);             /* las.c: damar_set_check(1) is in force */
+
+/* piles.c: what the mask tools need beside the C-ABI of include/damar_hip.h */
+typedef struct
+{ int   nreads, maxlen;
+  int  *read_len, *read_flags;
+  int   nblocks;               /* 0: the database is not split */
+  int  *block_first;           /* [nblocks + 1] */
+  char *path;                  /* <dir>/.<root>, what track file names start with */
+} damar_dbinfo;
+
+int  damar_dbinfo_open(const char *name, damar_dbinfo *db);     /* stub + .idx, no bases */
+void damar_dbinfo_close(damar_dbinfo *db);
+
+typedef struct damar_pile_reader damar_pile_reader;
+damar_pile_reader *damar_piles_open(const char *las, int64 bound);     /* bound <= 0: 8 M records; DAMAR_PILE_BATCH lowers it */
+int   damar_piles_next(damar_pile_reader *r, damar_pile_batch *b);
+void  damar_piles_rewind(damar_pile_reader *r);
+int   damar_piles_tspace(const damar_pile_reader *r);
+int64 damar_piles_novl(const damar_pile_reader *r);
+void  damar_piles_close(damar_pile_reader *r);
+
+int  damar_piles_on_host(void);                                  /* DAMAR_PILES=host */
+int  damar_host_pile_coverage(const damar_pile_batch *b, const damar_repeat_params *p, int64 *histo, int64 *bases, int64 *inactive);
+int  damar_host_pile_repeats(const damar_pile_batch *b, const damar_repeat_params *p, damar_pile_track *out);
+int  damar_host_pile_tandem(const damar_pile_batch *b, int min_len, damar_pile_track *out);
+
+int  damar_track_write_a2(const char *dbpath, const char *track, int block, int nreads, const uint64 *anno, const int *data, int64 ndata);
+int  damar_track_write_anno(const char *dbpath, const char *track, int block, int len, const int64 *offs, const int *data);
+
+/* masks.c: both tools as calls (the commands and the Python interface are argument handling around them) */
+typedef struct
+{ int64 *histo;                /* [max_cov], malloc'ed, NULL when no estimate ran */
+  int    cov_max;              /* MAX: the estimate */
+  int64  cov_bases, cov_inactive;
+  int    avg_rlen;
+  int    cov;                  /* what the repeat pass used */
+  uint64 *anno;                /* [nreads + 1] byte offsets, malloc'ed */
+  int   *data;
+  int64  ndata, merged, bases_total, bases_repeat;
+} damar_repeat_result;
+
+/* LArepeat.c main: estimate pass unless p->cov > 0 (or cov_only), then the repeat pass.  max_areads < 0: all piles.
+   0, or 1 after the reference's message where the reference exits with 1. */
+int  damar_repeat_track(const damar_dbinfo *db, const char *las, const damar_repeat_params *p, int max_areads, int cov_only,
+                        damar_repeat_result *res);
+void damar_repeat_result_free(damar_repeat_result *res);
+/* TANmask.c make_a_pass for the reads [first, last): offs[last - first + 1] byte offsets and the data, both malloc'ed.
+   0, or 1 when the file's reads lie outside the range. */
+int  damar_tan_track(const damar_dbinfo *db, const char *las, int first, int last, int min_len, int64 **offs, int **data,
+                     int64 *nmasks, int64 *masked);
 
 #ifdef __cplusplus
 }

@@ -21,6 +21,31 @@ int    damar_radix_sort_u32(u32 *k0, u32 *v0, u32 *k1, u32 *v1, u64 n, int nbits
 int    damar_radix_sort_keys_u32(u32 *k0, u32 *k1, u64 n, int nbits, void *work, hipStream_t st);    /* keys only */
 int    damar_radix_sort_u64(u64 *k0, u32 *v0, u64 *k1, u32 *v1, u64 n, int nbits, void *work, hipStream_t st);
 
+/* pile_sweep.hip: mask tracks from piles of overlaps (scrub/LArepeat.c, scrub/TANmask.c) */
+enum { DAMAR_PILE_COVER = 0, DAMAR_PILE_REPEAT = 1, DAMAR_PILE_TANDEM = 2 };
+#define DAMAR_PILE_ERR_RANGE 1u      /* a coordinate does not fit the key's position bits */
+typedef struct
+{ /* the batch (include/damar_hip.h damar_pile_batch) */
+  const long long *pile_off;
+  const int *pile_aread, *abpos, *aepos, *bbpos, *bepos, *bread, *flags, *read_len, *read_flags;
+  u32   npiles;
+  int   mode, pbits;             /* event key = pile << (pbits + 1) | coordinate << 1 | tie bit */
+  int   min_len, inc_identity, inccov, enter, leave, merge_dist;
+  u64  *keys;                    /* [2 * records]: pile_events writes, pile_sweep reads them sorted */
+  u32  *kept;                    /* [npiles] records of the pile that pass the filters */
+  const u32 *koff;               /* [npiles] exclusive sums of kept */
+  u64  *bases;                   /* [npiles] COVER: summed lengths of the kept records */
+  int  *active;                  /* [npiles] COVER: length of their union */
+  int  *rb, *re, *rc;            /* [kept records] REPEAT: raw regions of pile p from koff[p] */
+  int  *out;                     /* [3 * kept records] ints of pile p from 3 * koff[p] */
+  u32  *count;                   /* [npiles] how many */
+  u64  *stats;                   /* [0] merges, [1] repeat bases */
+  u32  *err;
+} PileArgs;
+void damar_launch_pile_events(const PileArgs *a, hipStream_t st);
+void damar_launch_pile_sweep(const PileArgs *a, hipStream_t st);
+void damar_launch_pile_gather(const int *out, const u32 *koff, const u32 *count, const u32 *doff, u32 npiles, int *dst, hipStream_t st);
+
 /* A read block resident in HBM. */
 typedef struct
 { const u8  *bases;     /* byte per base 0..3, 4 = terminator; bases[-1] == 4 (reference layout) */

@@ -4000,3 +4000,257 @@ extern "C" int Compute_Trace_PTS(Alignment *align, Work_Data *work, int trace_sp
 extern "C" int Compute_Trace_MID(Alignment *align, Work_Data *work, int trace_spacing, int mode)   /* align.c:5694 */
 { return compute_trace(align, work, trace_spacing, mode, 1);
 }
+
+/***** mask tracks from piles of overlaps: scrub/LArepeat.c and scrub/TANmask.c (kernels/pile_sweep.hip) **********/
+
+static DBuf P_off, P_aread, P_col[6], P_rlen, P_rflags, P_k0, P_k1, P_kept, P_koff, P_scan, P_sortw, P_bases, P_active,
+            P_rb, P_re, P_rc, P_out, P_count, P_doff, P_dst, P_misc;
+static double P_ms[4];        /* of the last call: upload, sort, sweep, download */
+static int64  P_cnt[2];       /* events sorted, regions (TANDEM: intervals) written */
+static hipEvent_t P_ev[5];    /* made once, kept like the buffers */
+static int    P_ev_made;
+static std::vector<u64> P_hsum;       /* COVER's per-pile results on the host: grown, kept */
+static std::vector<int> P_hact;
+
+extern "C" void damar_pile_release(void)
+{ DBuf *all[] = { &P_off, &P_aread, &P_col[0], &P_col[1], &P_col[2], &P_col[3], &P_col[4], &P_col[5], &P_rlen, &P_rflags, &P_k0,
+                  &P_k1, &P_kept, &P_koff, &P_scan, &P_sortw, &P_bases, &P_active, &P_rb, &P_re, &P_rc, &P_out, &P_count,
+                  &P_doff, &P_dst, &P_misc };
+  for (DBuf *b : all) b->drop();
+  if (P_ev_made)
+    for (int i = 0; i < 5; i++) (void) hipEventDestroy(P_ev[i]);
+  P_ev_made = 0;
+  std::vector<u64>().swap(P_hsum);
+  std::vector<int>().swap(P_hact);
+}
+
+extern "C" void damar_pile_last(double *ms, int64 *cnt)
+{ for (int i = 0; i < 4; i++) ms[i] = P_ms[i];
+  cnt[0] = P_cnt[0];  cnt[1] = P_cnt[1];
+}
+
+static int bits_for(u64 v)      /* bits that hold the value v */
+{ int b = 1;
+  while (b < 63 && (v >> b) != 0) b += 1;
+  return b;
+}
+
+/* what the kernels index with: checked here, once, on the host.  The kernels hold record offsets and three ints of data per
+   kept record in 32 bits, so a batch holds fewer than 2^29 records (the reader's batches hold 2^23). */
+static int pile_batch_valid(const damar_pile_batch *b)
+{ if (b->npiles < 0 || b->nrec < 0 || b->npiles > 0x7fffffff || b->nrec > 0x1fffffff || b->nreads <= 0 || b->maxlen < 0)
+    return 0;
+  if (b->npiles == 0)
+    return b->nrec == 0;
+  if (b->pile_off[0] != 0 || b->pile_off[b->npiles] != b->nrec)
+    return 0;
+  for (int64 i = 0; i < b->npiles; i++)
+    if (b->pile_off[i] > b->pile_off[i + 1] || b->pile_aread[i] < 0 || b->pile_aread[i] >= b->nreads)
+      return 0;
+  for (int64 i = 0; i < b->nrec; i++)
+    if (b->bread[i] < 0 || b->bread[i] >= b->nreads)
+      return 0;
+  return 1;
+}
+
+/* One batch through the device.  COVER: bases_out / active_out [npiles].  REPEAT, TANDEM: out. */
+static int pile_device(int mode, const damar_pile_batch *b, const damar_repeat_params *p, int min_len,
+                       u64 *bases_out, int *active_out, damar_pile_track *out)
+{ ensure_init();
+  const u32 np = (u32) b->npiles;
+  const u64 nrec = (u64) b->nrec, nkeys = 2 * nrec;
+  int pbits = bits_for((u64) (b->maxlen > 0 ? b->maxlen : 1));
+  if (pbits > 30)
+    { fprintf(stderr, "damar: piles: reads of %d bases are beyond the event key\n", b->maxlen);
+      return 1;
+    }
+  const int hibit = pbits + 1 + bits_for(np);
+
+  if (!P_ev_made)
+    { for (int i = 0; i < 5; i++) HIP_CHECK(hipEventCreate(&P_ev[i]));
+      P_ev_made = 1;
+    }
+  struct { hipEvent_t *e; } ev = { P_ev };
+
+  PileArgs a;
+  memset(&a, 0, sizeof(a));
+  a.npiles = np;  a.mode = mode;  a.pbits = pbits;
+  a.min_len = (mode == DAMAR_PILE_TANDEM) ? min_len : p->min_aln_len;
+  if (mode != DAMAR_PILE_TANDEM)
+    { a.inc_identity = p->inc_identity;  a.inccov = p->inccov ? 1 : 0;
+      a.enter = (int) (p->cov * p->xcov_enter);  a.leave = (int) (p->cov * p->xcov_leave);     /* LArepeat.c:328-329 */
+      a.merge_dist = p->merge_dist;
+    }
+  long long *d_off = (long long *) P_off.need(sizeof(long long) * ((size_t) np + 1));
+  int *d_aread = (int *) P_aread.need(sizeof(int) * (size_t) np);
+  const int *src[6] = { b->abpos, b->aepos, b->bbpos, b->bepos, b->bread, b->flags };
+  int *d_col[6];
+  for (int i = 0; i < 6; i++) d_col[i] = (int *) P_col[i].need(sizeof(int) * (size_t) nrec + 16);
+  int *d_rlen = (int *) P_rlen.need(sizeof(int) * (size_t) b->nreads);
+  int *d_rflags = (int *) P_rflags.need(sizeof(int) * (size_t) b->nreads);
+  u64 *k0 = (u64 *) P_k0.need(sizeof(u64) * (size_t) nkeys + 64), *k1 = (u64 *) P_k1.need(sizeof(u64) * (size_t) nkeys + 64);
+  u32 *d_kept = (u32 *) P_kept.need(sizeof(u32) * (size_t) np), *d_koff = (u32 *) P_koff.need(sizeof(u32) * (size_t) np);
+  u32 *d_count = (u32 *) P_count.need(sizeof(u32) * (size_t) np), *d_doff = (u32 *) P_doff.need(sizeof(u32) * (size_t) np);
+  void *d_scan = P_scan.need(damar_scan_workspace_bytes(np));
+  void *d_sortw = P_sortw.need(damar_sort_workspace_bytes(nkeys));
+  u64 *d_misc = (u64 *) P_misc.need(256);          /* [0] total kept, [1] total data, [2..3] stats, [4] error word */
+
+  HIP_CHECK(hipEventRecord(ev.e[0], G_st));
+  HIP_CHECK(hipMemcpyAsync(d_off, b->pile_off, sizeof(long long) * ((size_t) np + 1), hipMemcpyHostToDevice, G_st));
+  HIP_CHECK(hipMemcpyAsync(d_aread, b->pile_aread, sizeof(int) * (size_t) np, hipMemcpyHostToDevice, G_st));
+  for (int i = 0; i < 6; i++)
+    HIP_CHECK(hipMemcpyAsync(d_col[i], src[i], sizeof(int) * (size_t) nrec, hipMemcpyHostToDevice, G_st));
+  HIP_CHECK(hipMemcpyAsync(d_rlen, b->read_len, sizeof(int) * (size_t) b->nreads, hipMemcpyHostToDevice, G_st));
+  HIP_CHECK(hipMemcpyAsync(d_rflags, b->read_flags, sizeof(int) * (size_t) b->nreads, hipMemcpyHostToDevice, G_st));
+  HIP_CHECK(hipMemsetAsync(d_misc, 0, 256, G_st));
+  HIP_CHECK(hipEventRecord(ev.e[1], G_st));
+
+  a.pile_off = d_off;  a.pile_aread = d_aread;
+  a.abpos = d_col[0];  a.aepos = d_col[1];  a.bbpos = d_col[2];  a.bepos = d_col[3];  a.bread = d_col[4];  a.flags = d_col[5];
+  a.read_len = d_rlen;  a.read_flags = d_rflags;
+  a.keys = k0;  a.kept = d_kept;  a.koff = d_koff;
+  a.stats = d_misc + 2;  a.err = (u32 *) (d_misc + 4);
+  a.count = d_count;
+  if (mode == DAMAR_PILE_COVER)
+    { a.bases = (u64 *) P_bases.need(sizeof(u64) * (size_t) np);
+      a.active = (int *) P_active.need(sizeof(int) * (size_t) np);
+    }
+  damar_launch_pile_events(&a, G_st);
+  damar_exclusive_scan_u32(d_kept, d_koff, np, d_scan, d_misc, G_st);
+  const int side = damar_radix_sort_keys_u64(k0, k1, nkeys, 0, hibit, d_sortw, G_st);
+  a.keys = side ? k1 : k0;
+  u64 h_misc[5];
+  u32 h_serr = 0;
+  HIP_CHECK(hipMemcpyAsync(h_misc, d_misc, sizeof(h_misc), hipMemcpyDeviceToHost, G_st));
+  HIP_CHECK(hipMemcpyAsync(&h_serr, damar_sort_error_word(d_sortw), sizeof(u32), hipMemcpyDeviceToHost, G_st));
+  HIP_CHECK(hipEventRecord(ev.e[2], G_st));
+  HIP_CHECK(hipStreamSynchronize(G_st));
+  if (h_serr != 0)
+    { fprintf(stderr, "damar: piles: the radix sort's look-back timed out\n");
+      return 1;
+    }
+  if ((u32) h_misc[4] & DAMAR_PILE_ERR_RANGE)
+    { fprintf(stderr, "damar: piles: a record's coordinates lie outside its read (longest read %d)\n", b->maxlen);
+      return 1;
+    }
+  const u64 nkept = h_misc[0];
+  P_cnt[0] = (int64) (2 * nkept);
+  if (mode == DAMAR_PILE_REPEAT)
+    { a.rb = (int *) P_rb.need(sizeof(int) * (size_t) nkept + 16);
+      a.re = (int *) P_re.need(sizeof(int) * (size_t) nkept + 16);
+      a.rc = (int *) P_rc.need(sizeof(int) * (size_t) nkept + 16);
+    }
+  if (mode != DAMAR_PILE_COVER)
+    a.out = (int *) P_out.need(sizeof(int) * 3 * (size_t) nkept + 16);
+  damar_launch_pile_sweep(&a, G_st);
+  if (mode == DAMAR_PILE_COVER)
+    { HIP_CHECK(hipEventRecord(ev.e[3], G_st));
+      HIP_CHECK(hipMemcpyAsync(bases_out, a.bases, sizeof(u64) * (size_t) np, hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipMemcpyAsync(active_out, a.active, sizeof(int) * (size_t) np, hipMemcpyDeviceToHost, G_st));
+      P_cnt[1] = 0;
+    }
+  else
+    { damar_exclusive_scan_u32(d_count, d_doff, np, d_scan, d_misc + 1, G_st);
+      HIP_CHECK(hipMemcpyAsync(h_misc, d_misc, sizeof(h_misc), hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipStreamSynchronize(G_st));
+      const u64 ndata = h_misc[1];
+      int *d_dst = (int *) P_dst.need(sizeof(int) * (size_t) ndata + 16);
+      damar_launch_pile_gather(a.out, d_koff, d_count, d_doff, np, d_dst, G_st);
+      HIP_CHECK(hipEventRecord(ev.e[3], G_st));
+      out->data = (int *) malloc(sizeof(int) * (size_t) ndata + 8);
+      if (out->data == NULL)
+        { fprintf(stderr, "damar: out of memory (piles)\n");
+          return 1;
+        }
+      out->ndata = (int64) ndata;
+      out->merged = (int64) h_misc[2];
+      out->repeat_bases = (int64) h_misc[3];
+      if (ndata > 0)
+        HIP_CHECK(hipMemcpyAsync(out->data, d_dst, sizeof(int) * (size_t) ndata, hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipMemcpyAsync(out->count, d_count, sizeof(int) * (size_t) np, hipMemcpyDeviceToHost, G_st));
+    }
+  HIP_CHECK(hipEventRecord(ev.e[4], G_st));
+  HIP_CHECK(hipStreamSynchronize(G_st));
+  if (mode != DAMAR_PILE_COVER)
+    { const int width = (mode == DAMAR_PILE_REPEAT && a.inccov) ? 3 : 2;       /* a region left open holds its begin alone */
+      int64 regions = 0;
+      for (u32 i = 0; i < np; i++)
+        regions += (out->count[i] + width - 1) / width;
+      P_cnt[1] = regions;
+    }
+  for (int i = 0; i < 4; i++)
+    { float ms = 0;
+      HIP_CHECK(hipEventElapsedTime(&ms, ev.e[i], ev.e[i + 1]));
+      P_ms[i] = ms;
+    }
+  return 0;
+}
+
+static void pile_empty(damar_pile_track *out)
+{ out->data = (int *) malloc(8);
+  out->ndata = out->merged = out->repeat_bases = 0;
+}
+
+extern "C" int damar_pile_coverage(const damar_pile_batch *b, const damar_repeat_params *p, int64 *histo, int64 *bases, int64 *inactive)
+{ if (!pile_batch_valid(b) || p->max_cov <= 0)
+    { fprintf(stderr, "damar: piles: malformed batch\n");
+      return 1;
+    }
+  if (damar_piles_on_host())
+    return damar_host_pile_coverage(b, p, histo, bases, inactive);
+  if (b->npiles == 0)
+    return 0;
+  std::vector<u64> &sum = P_hsum;
+  std::vector<int> &act = P_hact;
+  sum.assign((size_t) b->npiles, 0);
+  act.assign((size_t) b->npiles, 0);
+  if (b->nrec > 0)
+    { if (pile_device(DAMAR_PILE_COVER, b, p, 0, sum.data(), act.data(), NULL))
+        return 1;
+    }
+  for (int64 i = 0; i < b->npiles; i++)         /* LArepeat.c:208-223 */
+    { const int   alen = b->read_len[b->pile_aread[i]];
+      const int64 cov = act[i] > 0 ? (int64) sum[i] / act[i] : 0;
+      if (cov < p->max_cov)
+        histo[cov] += 1;
+      *bases += alen;
+      *inactive += alen - act[i];
+    }
+  return 0;
+}
+
+extern "C" int damar_pile_repeats(const damar_pile_batch *b, const damar_repeat_params *p, damar_pile_track *out)
+{ if (!pile_batch_valid(b) || out == NULL || (b->npiles > 0 && out->count == NULL))
+    { fprintf(stderr, "damar: piles: malformed batch\n");
+      return 1;
+    }
+  /* the state after an event is the last setting event's only while span_enter >= span_leave (LArepeat.c:609-613 refuses
+     low > high); below that the device's scan and a sequential walk would part ways */
+  if (p->xcov_enter < p->xcov_leave || (int) (p->cov * p->xcov_enter) < (int) (p->cov * p->xcov_leave))
+    { fprintf(stderr, "damar: piles: coverage %d with enter %.2f below leave %.2f\n", p->cov, p->xcov_enter, p->xcov_leave);
+      return 1;
+    }
+  if (damar_piles_on_host())
+    return damar_host_pile_repeats(b, p, out);
+  if (b->nrec == 0)
+    { for (int64 i = 0; i < b->npiles; i++) out->count[i] = 0;
+      pile_empty(out);
+      return 0;
+    }
+  return pile_device(DAMAR_PILE_REPEAT, b, p, 0, NULL, NULL, out);
+}
+
+extern "C" int damar_pile_tandem(const damar_pile_batch *b, int min_len, damar_pile_track *out)
+{ if (!pile_batch_valid(b) || out == NULL || (b->npiles > 0 && out->count == NULL))
+    { fprintf(stderr, "damar: piles: malformed batch\n");
+      return 1;
+    }
+  if (damar_piles_on_host())
+    return damar_host_pile_tandem(b, min_len, out);
+  if (b->nrec == 0)
+    { for (int64 i = 0; i < b->npiles; i++) out->count[i] = 0;
+      pile_empty(out);
+      return 0;
+    }
+  return pile_device(DAMAR_PILE_TANDEM, b, NULL, min_len, NULL, NULL, out);
+}

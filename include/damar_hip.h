@@ -195,6 +195,47 @@ int  damar_trace_mid(damar_dev_block *ablk, int afirst, damar_dev_block *bblk, i
 void damar_trace_last(double *ms, int64 *cnt);
 void damar_trace_release(void);          /* frees the cached device buffers of damar_trace_pts */
 
+/* Mask tracks from piles of overlaps (scrub/LArepeat.c, scrub/TANmask.c).  A batch is a run of whole piles -- all records
+ * of one A read, in file order -- as structure of arrays: pile i is the records [pile_off[i], pile_off[i+1]) and belongs to
+ * read pile_aread[i]; read_len / read_flags are the database's (all nreads reads, indexed by the records' read numbers).
+ * The three calls take host arrays, own the transfers and run kernels/pile_sweep.hip; with DAMAR_PILES=host in the
+ * environment they run the plain sweep of host/piles.c instead (no GPU is touched).  0 on success. */
+typedef struct
+{ int64        npiles, nrec;
+  const int64 *pile_off;                   /* [npiles + 1] */
+  const int   *pile_aread;                 /* [npiles] */
+  const int   *abpos, *aepos, *bbpos, *bepos, *bread, *flags;     /* [nrec] */
+  const int   *read_len, *read_flags;      /* [nreads] */
+  int          nreads, maxlen;             /* maxlen: the longest read (sizes the position bits of the event key) */
+} damar_pile_batch;
+
+typedef struct
+{ double xcov_enter, xcov_leave;           /* -h -l */
+  int    cov;                              /* -c, or the estimate */
+  int    merge_dist;                       /* -m (-1: none) */
+  int    min_aln_len;                      /* -o */
+  int    inc_identity;                     /* -I */
+  int    inccov;                           /* -C */
+  int    max_cov;                          /* -M: length of the coverage histogram */
+} damar_repeat_params;
+
+typedef struct
+{ int   *count;                            /* [npiles], the caller's: ints of data that pile i produced */
+  int   *data;                             /* malloc'ed by the call, the caller's to free: the piles' ints back to back */
+  int64  ndata;
+  int64  merged, repeat_bases;             /* LArepeat's MERGED and BASES_REPEAT of the batch */
+} damar_pile_track;
+
+/* LArepeat.c:168-233: histo[max_cov], *bases and *inactive are ADDED to */
+int  damar_pile_coverage(const damar_pile_batch *b, const damar_repeat_params *p, int64 *histo, int64 *bases, int64 *inactive);
+/* LArepeat.c:282-494: per pile {begin, end[, coverage]}...; a region still open at the pile's last event is its begin alone */
+int  damar_pile_repeats(const damar_pile_batch *b, const damar_repeat_params *p, damar_pile_track *out);
+/* TANmask.c:115-207 with an honest threshold: records with abpos - bepos <= 20 and aepos - bbpos > min_len */
+int  damar_pile_tandem(const damar_pile_batch *b, int min_len, damar_pile_track *out);
+void damar_pile_release(void);             /* frees the cached device buffers of the three calls */
+/* of the last call: ms[4] = upload, sort, sweep, download; cnt[2] = events sorted, regions (tandem: intervals) written */
+void damar_pile_last(double *ms, int64 *cnt);
+
 /* Phase timings (milliseconds, HIP events on the library's stream) of the last
  * damar_index_build / damar_match: see DAMAR_T_* below. */
 enum { DAMAR_T_TUPLES = 0, DAMAR_T_KSORT, DAMAR_T_TABLE, DAMAR_T_MERGE, DAMAR_T_SSORT,
