@@ -58,6 +58,20 @@ class PileTrack(C.Structure):          # damar_pile_track
     _fields_ = [("count", _PI), ("data", _PI), ("ndata", c_int64), ("merged", c_int64), ("repeat_bases", c_int64)]
 
 
+class TraceBatch(C.Structure):         # include/damar_hip.h damar_trace_batch
+    _fields_ = [("p", PileBatch), ("trace", C.POINTER(C.c_ubyte)), ("trace_off", C.POINTER(c_int64)), ("tlen", _PI),
+                ("trace_bytes", c_int64), ("tbytes", C.c_int), ("tspace", C.c_int)]
+
+
+class QParams(C.Structure):            # damar_q_params
+    _fields_ = [("segmin", C.c_int), ("segmax", C.c_int), ("ccs", C.c_int)]
+
+
+class QResult(C.Structure):            # host/damar_host.h damar_q_result
+    _fields_ = [("q_anno", C.POINTER(C.c_uint64)), ("trim_anno", C.POINTER(C.c_uint64)), ("q_data", _PI), ("trim_data", _PI),
+                ("nq", c_int64), ("ntrim", c_int64)]
+
+
 class DbInfo(C.Structure):             # host/damar_host.h damar_dbinfo
     _fields_ = [("nreads", C.c_int), ("maxlen", C.c_int), ("read_len", _PI), ("read_flags", _PI), ("nblocks", C.c_int),
                 ("block_first", _PI), ("path", C.c_char_p)]
@@ -161,6 +175,12 @@ def _lib():
         L.damar_piles_open.restype = C.c_void_p
         L.damar_piles_next.argtypes = [C.c_void_p, C.POINTER(PileBatch)]
         L.damar_piles_close.argtypes = [C.c_void_p]
+        L.damar_pile_quality.argtypes = [C.POINTER(TraceBatch), C.POINTER(QParams), _PI, C.POINTER(c_int64)]
+        L.damar_q_last.argtypes = [C.POINTER(C.c_double), C.POINTER(c_int64)]
+        L.damar_q_track.argtypes = [C.POINTER(DbInfo), C.c_char_p, C.POINTER(QParams), C.c_int, C.c_int, C.POINTER(QResult)]
+        L.damar_trim_update.argtypes = [C.POINTER(DbInfo), C.c_char_p, C.POINTER(C.c_uint64), _PI, c_int64, C.POINTER(C.c_uint64), _PI,
+                                        C.c_int, C.c_int, C.c_int, C.POINTER(QResult)]
+        L.damar_q_result_free.argtypes = [C.POINTER(QResult)]
         _proto_done = True
     return L
 
@@ -395,6 +415,41 @@ def read_piles(las, bound=0):
     return out
 
 
+def read_trace_piles(las, bound=0, tbound=0):
+    """The batches of whole piles of a .las file with their traces (the traces-on reader of host/piles.c), as the dicts
+    pile_quality takes; tbound: the trace bytes a batch holds at most (0: 1 GiB)."""
+    import numpy as np
+    L = _lib()
+    L.damar_piles_open_traces.argtypes = [C.c_char_p, c_int64, c_int64]
+    L.damar_piles_open_traces.restype = C.c_void_p
+    L.damar_piles_next_traces.argtypes = [C.c_void_p, C.POINTER(TraceBatch)]
+    r = L.damar_piles_open_traces(las.encode(), bound, tbound)
+    if not r:
+        raise RuntimeError("cannot open %s" % las)
+    out = []
+    try:
+        while True:
+            t = TraceBatch()
+            got = L.damar_piles_next_traces(r, C.byref(t))
+            if got < 0:
+                raise RuntimeError("%s is damaged" % las)
+            if got == 0:
+                break
+            b = t.p
+            d = {"pile_off": np.ctypeslib.as_array(b.pile_off, shape=(b.npiles + 1,)).copy(),
+                 "pile_aread": np.ctypeslib.as_array(b.pile_aread, shape=(b.npiles,)).copy()}
+            for k in ("abpos", "aepos", "bbpos", "bepos", "bread", "flags"):
+                d[k] = np.ctypeslib.as_array(getattr(b, k), shape=(b.nrec,)).copy()
+            d["tlen"] = np.ctypeslib.as_array(t.tlen, shape=(b.nrec,)).copy()
+            d["trace_off"] = np.ctypeslib.as_array(t.trace_off, shape=(b.nrec,)).copy()
+            d["trace"] = np.ctypeslib.as_array(t.trace, shape=(max(t.trace_bytes, 1),))[:t.trace_bytes].copy()
+            d["tbytes"], d["tspace"] = t.tbytes, t.tspace
+            out.append(d)
+    finally:
+        L.damar_piles_close(r)
+    return out
+
+
 def repeat_track(db, las, max_areads=-1, cov_only=False, **opts):
     """LArepeat on one .las file: -> (anno uint64[nreads + 1], data int32[], stats); opts as repeat_params()."""
     import numpy as np
@@ -447,6 +502,95 @@ def tan_track(db, las, min_len=0, block=0):
         libc.free(data)
         return o, v
     finally:
+        L.damar_dbinfo_close(C.byref(d))
+
+
+# ---- quality and trim tracks from the overlaps' traces (LAq) --------------------------------------------------------
+
+def pile_quality(batch, read_len, segmin=1, segmax=20, ccs=False):
+    """-> q int32[tiles]: the quality value of every tile (segment of tspace bases) of the batch's piles, pile after pile,
+    ceil(read length / tspace) tiles each.  batch: the arrays of a trace-less batch (_batch) plus `trace` (uint8, the
+    records' trace bytes back to back), `trace_off` (int64, a byte offset per record), `tlen`, `tbytes` and `tspace`."""
+    import numpy as np
+    L = _lib()
+    pb, keep = _batch(batch, read_len, np.zeros(len(read_len), dtype=np.int32))
+    t = TraceBatch()
+    t.p = pb
+    keep["trace"] = np.ascontiguousarray(batch["trace"], dtype=np.uint8)
+    keep["trace_off"] = np.ascontiguousarray(batch["trace_off"], dtype=np.int64)
+    keep["tlen"] = np.ascontiguousarray(batch["tlen"], dtype=np.int32)
+    if len(keep["trace_off"]) != pb.nrec or len(keep["tlen"]) != pb.nrec:
+        raise ValueError("trace_off and tlen hold one entry per record")
+    t.trace = keep["trace"].ctypes.data_as(C.POINTER(C.c_ubyte))
+    t.trace_off = keep["trace_off"].ctypes.data_as(C.POINTER(c_int64))
+    t.tlen = keep["tlen"].ctypes.data_as(_PI)
+    t.trace_bytes = len(keep["trace"])
+    t.tbytes, t.tspace = int(batch["tbytes"]), int(batch["tspace"])
+    p = QParams(int(segmin), int(segmax), 1 if ccs else 0)
+    nt = c_int64(0)
+    if L.damar_pile_quality(C.byref(t), C.byref(p), None, C.byref(nt)):
+        raise RuntimeError("damar_pile_quality failed")
+    q = np.zeros(max(nt.value, 1), dtype=np.int32)
+    if L.damar_pile_quality(C.byref(t), C.byref(p), q.ctypes.data_as(_PI), C.byref(nt)):
+        raise RuntimeError("damar_pile_quality failed")
+    return q[:nt.value]
+
+
+def q_last():
+    """Of the last device call of pile_quality / q_track: ({upload, count, select, download} ms, segments counted, tiles)."""
+    ms, cnt = (C.c_double * 4)(), (c_int64 * 2)()
+    _lib().damar_q_last(ms, cnt)
+    return dict(zip(("upload", "count", "select", "download"), list(ms))), cnt[0], cnt[1]
+
+
+def _take_q(res, nreads, with_q):
+    import numpy as np
+    arr = lambda ptr, n, dt: np.ctypeslib.as_array(ptr, shape=(max(int(n), 1),))[:int(n)].astype(dt)
+    out = ()
+    if with_q:
+        out = (arr(res.q_anno, nreads + 1, np.uint64), arr(res.q_data, res.nq, np.int32))
+    return out + (arr(res.trim_anno, nreads + 1, np.uint64), arr(res.trim_data, res.ntrim, np.int32))
+
+
+def q_track(db, las, segmin=1, segmax=20, trim_q=25, min_len=1000, ccs=False):
+    """LAq on one .las file: -> (q_anno uint64[nreads + 1], q_data int32[], trim_anno, trim_data), the annos in bytes."""
+    L = _lib()
+    d = DbInfo()
+    if L.damar_dbinfo_open(db.encode(), C.byref(d)):
+        raise RuntimeError("cannot open database %s" % db)
+    p = QParams(int(segmin), int(segmax), 1 if ccs else 0)
+    res = QResult()
+    try:
+        if L.damar_q_track(C.byref(d), las.encode(), C.byref(p), int(trim_q), int(min_len), C.byref(res)):
+            raise RuntimeError("damar_q_track failed")
+        return _take_q(res, d.nreads, True)
+    finally:
+        L.damar_q_result_free(C.byref(res))
+        L.damar_dbinfo_close(C.byref(d))
+
+
+def trim_update(db, las, q, trim, trim_q=25, min_len=1000, ccs=False):
+    """LAq -u: the trim track again from the records of `las` that are neither discarded nor identity overlaps.
+    q, trim: (anno, data) as q_track returns them -> (trim_anno, trim_data); reads without a pile get no entry."""
+    import numpy as np
+    L = _lib()
+    d = DbInfo()
+    if L.damar_dbinfo_open(db.encode(), C.byref(d)):
+        raise RuntimeError("cannot open database %s" % db)
+    qa, ta = (np.ascontiguousarray(x[0], dtype=np.uint64) for x in (q, trim))
+    qd, td = (np.ascontiguousarray(x[1], dtype=np.int32) for x in (q, trim))
+    res = QResult()
+    try:
+        if len(qa) != d.nreads + 1 or len(ta) != d.nreads + 1 or int(qa[-1]) != 4 * len(qd) or int(ta[-1]) != 4 * len(td) \
+                or np.any(qa[1:] < qa[:-1]) or np.any(ta[1:] < ta[:-1]) or np.any(qa % 4) or np.any(ta % 4):
+            raise ValueError("the tracks do not fit the database")
+        u64p = C.POINTER(C.c_uint64)
+        if L.damar_trim_update(C.byref(d), las.encode(), qa.ctypes.data_as(u64p), qd.ctypes.data_as(_PI), len(qd),
+                               ta.ctypes.data_as(u64p), td.ctypes.data_as(_PI), int(trim_q), int(min_len), 1 if ccs else 0, C.byref(res)):
+            raise RuntimeError("damar_trim_update failed")
+        return _take_q(res, d.nreads, False)
+    finally:
+        L.damar_q_result_free(C.byref(res))
         L.damar_dbinfo_close(C.byref(d))
 
 

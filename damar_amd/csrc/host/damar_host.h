@@ -84,6 +84,9 @@ int   damar_piles_next(damar_pile_reader *r, damar_pile_batch *b);
 void  damar_piles_rewind(damar_pile_reader *r);
 int   damar_piles_tspace(const damar_pile_reader *r);
 int64 damar_piles_novl(const damar_pile_reader *r);
+/* the reader with the traces on (LAq): tbound <= 0: 1 GiB of trace bytes per batch; DAMAR_PILE_TRACE_BYTES lowers it */
+damar_pile_reader *damar_piles_open_traces(const char *las, int64 bound, int64 tbound);
+int   damar_piles_next_traces(damar_pile_reader *r, damar_trace_batch *t);
 void  damar_piles_close(damar_pile_reader *r);
 
 int  damar_piles_on_host(void);                                  /* DAMAR_PILES=host */
@@ -93,6 +96,27 @@ int  damar_host_pile_tandem(const damar_pile_batch *b, int min_len, damar_pile_t
 
 int  damar_track_write_a2(const char *dbpath, const char *track, int block, int nreads, const uint64 *anno, const int *data, int64 ndata);
 int  damar_track_write_anno(const char *dbpath, const char *track, int block, int len, const int64 *offs, const int *data);
+
+/* quality.c: LAq (scrub/LAq.c) as calls */
+int  damar_trace_batch_valid(const damar_trace_batch *b, int64 *ntiles);     /* what both paths index with; 0 after a message */
+int  damar_host_pile_quality(const damar_trace_batch *b, const damar_q_params *p, int *q_out);
+/* trim_q_offsets: dataq[ndata] is the q data of ALL reads ([ob, oe) this read's; the walk looks at its neighbours' too, a value
+   past the end counts as 0), *tb / *te the interval to start from (0: the read's end) and the result.  0: no q data. */
+int  damar_trim_from_q(const int *dataq, int64 ndata, int64 ob, int64 oe, int rlen, int tspace, int trim_q, int min_len, int ccs,
+                       int *tb, int *te);
+typedef struct
+{ uint64 *q_anno, *trim_anno;  /* [nreads + 1] byte offsets, malloc'ed */
+  int    *q_data, *trim_data;
+  int64   nq, ntrim;
+} damar_q_result;
+/* the annotate pass over a file: q and trim of every read with a pile.  0, or 1 after a message. */
+int  damar_q_track(const damar_dbinfo *db, const char *las, const damar_q_params *p, int trim_q, int min_len, damar_q_result *res);
+/* -u: the trim track again from record headers, the q track and the trim track at hand (res->q_* stay NULL) */
+int  damar_trim_update(const damar_dbinfo *db, const char *las, const uint64 *q_anno, const int *q_data, int64 nq,
+                       const uint64 *trim_anno, const int *trim_data, int trim_q, int min_len, int ccs, damar_q_result *res);
+void damar_q_result_free(damar_q_result *res);
+/* a track of the whole database as damar_track_write_a2 writes it: anno[nreads + 1] and data, malloc'ed.  0, or 1 (no message) */
+int  damar_track_read_a2(const char *dbpath, const char *track, int nreads, uint64 **anno, int **data, int64 *ndata);
 
 /* masks.c: both tools as calls (the commands and the Python interface are argument handling around them) */
 typedef struct

@@ -1,6 +1,7 @@
 /* piles.c -- the host side of the two mask tools that turn overlaps back into tracks (scrub/LArepeat.c, scrub/TANmask.c):
  *   - the read table of a database without its bases (stub + .idx),
  *   - a streaming reader that cuts a .las file into batches of whole piles (all records of one A read, lib/pass.c:118-249),
+ *     without the records' traces (the mask tools) or with them (LAq, host/quality.c),
  *   - the plain sweep of both tools, one pile at a time (DAMAR_PILES=host; the second opinion for kernels/pile_sweep.hip),
  *   - the writers of both track forms (lib/tracks.c:180-270 .a2/.d2, TANmask.c:462-487 .anno/.data).
  * Nothing here touches the GPU runtime: the file builds into a stand-alone program as it is. */
@@ -133,14 +134,35 @@ struct damar_pile_reader
   int64 *pile_off;
   int   *pile_aread;
   int   *col[6];               /* abpos aepos bbpos bepos bread flags */
+  /* traces on (damar_piles_open_traces): the records' trace bytes as they lie in the file, back to back */
+  int    traces;
+  int64  tbound;               /* bytes of trace a batch holds at most, a pile alone in its batch excepted */
+  unsigned char *rtrace;       /* of the record read ahead */
+  int64  rtcap;
+  unsigned char *tbuf;
+  int64  tcap, ttop;
+  int64 *toff;                 /* per record: where its trace begins in tbuf */
+  int   *tlen;
 };
 
 /* 1: a record, 0: all novl records of the header are through, -1: the file ends before that, on a record boundary or not */
 static int next_record(damar_pile_reader *r)
 { if (r->seen >= r->novl)
     return 0;
-  if (fread(r->rec, 1, 40, r->f) != 40 || r->rec[0] < 0 || fseeko(r->f, (off_t) r->tbytes * r->rec[0], SEEK_CUR) != 0
-      || (int64) ftello(r->f) > r->size)
+  if (fread(r->rec, 1, 40, r->f) != 40 || r->rec[0] < 0)
+    return -1;
+  if (r->traces)
+    { const int64 n = (int64) r->tbytes * r->rec[0];
+      if ((int64) ftello(r->f) + n > r->size)
+        return -1;
+      if (n > r->rtcap)
+        { r->rtcap = n + n / 4 + 1024;
+          r->rtrace = (unsigned char *) prealloc(r->rtrace, (size_t) r->rtcap);
+        }
+      if (n > 0 && fread(r->rtrace, 1, (size_t) n, r->f) != (size_t) n)
+        return -1;
+    }
+  else if (fseeko(r->f, (off_t) r->tbytes * r->rec[0], SEEK_CUR) != 0 || (int64) ftello(r->f) > r->size)
     return -1;
   r->seen += 1;
   return 1;
@@ -174,6 +196,22 @@ damar_pile_reader *damar_piles_open(const char *las, int64 bound)
   return r;
 }
 
+/* the same reader with the traces on: batches come from damar_piles_next_traces and are bounded by records as above and by
+   trace bytes (tbound <= 0: 1 GiB; DAMAR_PILE_TRACE_BYTES lowers it) */
+damar_pile_reader *damar_piles_open_traces(const char *las, int64 bound, int64 tbound)
+{ damar_pile_reader *r = damar_piles_open(las, bound);
+  const char *e = getenv("DAMAR_PILE_TRACE_BYTES");
+  if (r == NULL)
+    return NULL;
+  if (tbound <= 0)
+    tbound = (int64) 1 << 30;
+  if (e != NULL && atoll(e) > 0 && atoll(e) < tbound)
+    tbound = atoll(e);
+  r->traces = 1;
+  r->tbound = tbound;
+  return r;
+}
+
 void damar_piles_rewind(damar_pile_reader *r)
 { fseeko(r->f, (off_t) (sizeof(int64) + sizeof(int)), SEEK_SET);
   r->seen = 0;
@@ -191,20 +229,32 @@ void damar_piles_close(damar_pile_reader *r)
   if (r->f) fclose(r->f);
   free(r->pile_off);  free(r->pile_aread);
   for (i = 0; i < 6; i++) free(r->col[i]);
+  free(r->rtrace);  free(r->tbuf);  free(r->toff);  free(r->tlen);
   free(r);
 }
 
 /* the next batch of whole piles: piles are added while the batch stays within the bound; a pile that would cross it is
    held back for the next batch, so only a pile that is larger than the bound by itself exceeds it, alone in its batch.
    The arrays belong to the reader and hold until the next call.  1: a batch, 0: no pile is left, -1: the file is damaged. */
-int damar_piles_next(damar_pile_reader *r, damar_pile_batch *b)
+static int piles_next(damar_pile_reader *r, damar_pile_batch *b)
 { int64 n = 0, np = 0, start;
   int   i, got, a;
 
   memset(b, 0, sizeof(*b));
+  r->ttop = 0;
   if (r->pend > 0)
     { for (i = 0; i < 6; i++)
         memmove(r->col[i], r->col[i] + r->pstart, sizeof(int) * (size_t) r->pend);
+      if (r->traces)
+        { const int64 t0 = r->toff[r->pstart];
+          int64 k;
+          for (k = 0; k < r->pend; k++)
+            { r->tlen[k] = r->tlen[r->pstart + k];
+              r->toff[k] = r->toff[r->pstart + k] - t0;
+            }
+          r->ttop = r->toff[r->pend - 1] + (int64) r->tbytes * r->tlen[r->pend - 1];
+          memmove(r->tbuf, r->tbuf + t0, (size_t) r->ttop);
+        }
       r->pile_off[0] = 0;  r->pile_off[1] = n = r->pend;
       r->pile_aread[0] = r->pend_aread;
       np = 1;
@@ -217,7 +267,7 @@ int damar_piles_next(damar_pile_reader *r, damar_pile_batch *b)
         return got;
       r->have = 1;
     }
-  while (r->have && n < r->bound)
+  while (r->have && n < r->bound && (!r->traces || r->ttop < r->tbound))
     { start = n;
       a = r->rec[7];
       do
@@ -225,6 +275,22 @@ int damar_piles_next(damar_pile_reader *r, damar_pile_batch *b)
             { r->cap = r->cap + r->cap / 4 + 1024;
               for (i = 0; i < 6; i++)
                 r->col[i] = (int *) prealloc(r->col[i], sizeof(int) * (size_t) r->cap);
+              if (r->traces)
+                { r->toff = (int64 *) prealloc(r->toff, sizeof(int64) * (size_t) r->cap);
+                  r->tlen = (int *) prealloc(r->tlen, sizeof(int) * (size_t) r->cap);
+                }
+            }
+          if (r->traces)
+            { const int64 nb = (int64) r->tbytes * r->rec[0];
+              if (r->ttop + nb > r->tcap)
+                { r->tcap = r->ttop + nb + r->tcap / 4 + 4096;
+                  r->tbuf = (unsigned char *) prealloc(r->tbuf, (size_t) r->tcap);
+                }
+              if (nb > 0)
+                memcpy(r->tbuf + r->ttop, r->rtrace, (size_t) nb);
+              r->toff[n] = r->ttop;
+              r->tlen[n] = r->rec[0];
+              r->ttop += nb;
             }
           r->col[0][n] = r->rec[2];  r->col[1][n] = r->rec[4];      /* abpos aepos */
           r->col[2][n] = r->rec[3];  r->col[3][n] = r->rec[5];      /* bbpos bepos */
@@ -238,7 +304,7 @@ int damar_piles_next(damar_pile_reader *r, damar_pile_batch *b)
           r->have = got;
         }
       while (r->have && r->rec[7] == a);
-      if (start > 0 && n > r->bound)
+      if (start > 0 && (n > r->bound || (r->traces && r->ttop > r->tbound)))
         { r->pstart = start;  r->pend = n - start;  r->pend_aread = a;
           n = start;
           break;
@@ -259,6 +325,30 @@ int damar_piles_next(damar_pile_reader *r, damar_pile_batch *b)
   b->pile_off = r->pile_off;  b->pile_aread = r->pile_aread;
   b->abpos = r->col[0];  b->aepos = r->col[1];  b->bbpos = r->col[2];  b->bepos = r->col[3];
   b->bread = r->col[4];  b->flags = r->col[5];
+  return 1;
+}
+
+int damar_piles_next(damar_pile_reader *r, damar_pile_batch *b)
+{ if (r->traces)
+    { fprintf(stderr, "damar: this pile reader carries traces: damar_piles_next_traces reads it\n");
+      return -1;
+    }
+  return piles_next(r, b);
+}
+
+/* the next batch with its traces: record i's tlen[i] values of tbytes bytes begin at trace + trace_off[i] */
+int damar_piles_next_traces(damar_pile_reader *r, damar_trace_batch *t)
+{ int got;
+  memset(t, 0, sizeof(*t));
+  if (!r->traces)
+    { fprintf(stderr, "damar: this pile reader was opened without traces\n");
+      return -1;
+    }
+  if ((got = piles_next(r, &t->p)) <= 0)
+    return got;
+  t->trace = r->tbuf;  t->trace_off = r->toff;  t->tlen = r->tlen;
+  t->trace_bytes = (r->pend > 0) ? r->toff[r->pstart] : r->ttop;
+  t->tbytes = r->tbytes;  t->tspace = r->tspace;
   return 1;
 }
 

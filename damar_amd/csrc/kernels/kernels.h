@@ -297,6 +297,29 @@ void damar_launch_la_batch_wide(const ReportArgs *a, const LaTask *tasks, u32 nt
 
 u64 damar_report_state_stride(int span);
 
+/* pile_quality.hip: LAq's per-tile quality from the traces of a batch of piles (scrub/LAq.c:312-409).  Tiles are numbered
+   through the batch: pile p owns [pile_tile0[p], pile_tile0[p + 1]). */
+typedef struct
+{ u32 npiles, nrec, ntiles;
+  int tspace, tbytes;
+  u32 segmin, segmax;
+  int ccs;
+  const long long *pile_off;          /* [npiles + 1] */
+  const int *pile_aread, *pile_alen;  /* [npiles] */
+  const u32 *pile_tile0;              /* [npiles + 1] */
+  const int *abpos, *aepos, *bread, *tlen;       /* [nrec] */
+  const long long *trace_off;         /* [nrec] bytes into trace */
+  const u8  *trace;
+  u32 *depth;                         /* [ntiles + 1] zeroed: segments per tile (q_count), used up again by q_scatter */
+  const u32 *off;                     /* [ntiles + 1] exclusive scan of depth */
+  u16 *vals;                          /* a run of difference counts per tile, in no order */
+  int *q;                             /* [ntiles] */
+} QArgs;
+
+void damar_launch_q_count(const QArgs *a, hipStream_t st);
+void damar_launch_q_scatter(const QArgs *a, hipStream_t st);
+void damar_launch_q_select(const QArgs *a, hipStream_t st);
+
 /* trace_pts.hip: Compute_Trace_PTS for batches of records (align.c:5577-5692, 4892-5261) */
 typedef struct
 { u32 aread, bread;       /* block-local read ids */

@@ -4254,3 +4254,121 @@ extern "C" int damar_pile_tandem(const damar_pile_batch *b, int min_len, damar_p
     }
   return pile_device(DAMAR_PILE_TANDEM, b, NULL, min_len, NULL, NULL, out);
 }
+
+/***** LAq's per-tile quality from the traces of piles: scrub/LAq.c handler_annotate (kernels/pile_quality.hip) **********/
+
+static DBuf LQ_off, LQ_aread, LQ_alen, LQ_tile0, LQ_col[4], LQ_toff, LQ_trace, LQ_depth, LQ_run, LQ_vals, LQ_q, LQ_scan, LQ_misc;
+static double LQ_ms[4];        /* of the last device call: upload, count + scan, scatter + select, download */
+static int64  LQ_cnt[2];       /* segments counted, tiles */
+static hipEvent_t LQ_ev[5];
+static int    LQ_ev_made;
+static std::vector<int> LQ_halen;       /* per pile: the read's length and where its tiles begin (host arithmetic, kept) */
+static std::vector<u32> LQ_htile0;
+
+extern "C" void damar_q_release(void)
+{ DBuf *all[] = { &LQ_off, &LQ_aread, &LQ_alen, &LQ_tile0, &LQ_col[0], &LQ_col[1], &LQ_col[2], &LQ_col[3], &LQ_toff, &LQ_trace, &LQ_depth,
+                  &LQ_run, &LQ_vals, &LQ_q, &LQ_scan, &LQ_misc };
+  for (DBuf *b : all) b->drop();
+  if (LQ_ev_made)
+    for (int i = 0; i < 5; i++) (void) hipEventDestroy(LQ_ev[i]);
+  LQ_ev_made = 0;
+  std::vector<int>().swap(LQ_halen);
+  std::vector<u32>().swap(LQ_htile0);
+}
+
+extern "C" void damar_q_last(double *ms, int64 *cnt)
+{ for (int i = 0; i < 4; i++) ms[i] = LQ_ms[i];
+  cnt[0] = LQ_cnt[0];  cnt[1] = LQ_cnt[1];
+}
+
+extern "C" int damar_pile_quality(const damar_trace_batch *t, const damar_q_params *p, int *q_out, int64 *ntiles_out)
+{ int64 ntiles = 0;
+  if (t == NULL || p == NULL || ntiles_out == NULL || !damar_trace_batch_valid(t, &ntiles))
+    return 1;
+  if (p->segmin < 1 || p->segmax < p->segmin)
+    { fprintf(stderr, "damar: quality: segmin %d and segmax %d: 1 <= segmin <= segmax is needed\n", p->segmin, p->segmax);
+      return 1;
+    }
+  *ntiles_out = ntiles;
+  if (q_out == NULL || ntiles == 0)
+    return 0;
+  if (damar_piles_on_host())
+    return damar_host_pile_quality(t, p, q_out);
+
+  ensure_init();
+  const damar_pile_batch *b = &t->p;
+  const u32 np = (u32) b->npiles, nt = (u32) ntiles;
+  const size_t nrec = (size_t) b->nrec;
+  u64 segs = 0;                                    /* what the runs hold at most: every segment of every trace */
+  for (size_t i = 0; i < nrec; i++) segs += (u64) (t->tlen[i] / 2);
+  LQ_halen.resize(np);
+  LQ_htile0.resize((size_t) np + 1);
+  LQ_htile0[0] = 0;
+  for (u32 i = 0; i < np; i++)
+    { LQ_halen[i] = b->read_len[b->pile_aread[i]];
+      LQ_htile0[i + 1] = LQ_htile0[i] + (u32) ((LQ_halen[i] + t->tspace - 1) / t->tspace);
+    }
+  if (!LQ_ev_made)
+    { for (int i = 0; i < 5; i++) HIP_CHECK(hipEventCreate(&LQ_ev[i]));
+      LQ_ev_made = 1;
+    }
+
+  QArgs a;
+  memset(&a, 0, sizeof(a));
+  a.npiles = np;  a.nrec = (u32) nrec;  a.ntiles = nt;
+  a.tspace = t->tspace;  a.tbytes = t->tbytes;
+  a.segmin = (u32) p->segmin;  a.segmax = (u32) p->segmax;  a.ccs = p->ccs ? 1 : 0;
+  long long *d_off = (long long *) LQ_off.need(sizeof(long long) * ((size_t) np + 1));
+  int *d_aread = (int *) LQ_aread.need(sizeof(int) * (size_t) np + 16);
+  int *d_alen = (int *) LQ_alen.need(sizeof(int) * (size_t) np + 16);
+  u32 *d_tile0 = (u32 *) LQ_tile0.need(sizeof(u32) * ((size_t) np + 1));
+  const int *src[4] = { b->abpos, b->aepos, b->bread, t->tlen };
+  int *d_col[4];
+  for (int i = 0; i < 4; i++) d_col[i] = (int *) LQ_col[i].need(sizeof(int) * nrec + 16);
+  long long *d_toff = (long long *) LQ_toff.need(sizeof(long long) * nrec + 16);
+  u8  *d_trace = (u8 *) LQ_trace.need((size_t) t->trace_bytes + 16);
+  u32 *d_depth = (u32 *) LQ_depth.need(sizeof(u32) * ((size_t) nt + 1));
+  u32 *d_run = (u32 *) LQ_run.need(sizeof(u32) * ((size_t) nt + 1));
+  u16 *d_vals = (u16 *) LQ_vals.need(sizeof(u16) * (size_t) segs + 16);
+  int *d_q = (int *) LQ_q.need(sizeof(int) * (size_t) nt);
+  void *d_scan = LQ_scan.need(damar_scan_workspace_bytes((u64) nt + 1));
+  u64 *d_misc = (u64 *) LQ_misc.need(64);
+
+  HIP_CHECK(hipEventRecord(LQ_ev[0], G_st));
+  HIP_CHECK(hipMemcpyAsync(d_off, b->pile_off, sizeof(long long) * ((size_t) np + 1), hipMemcpyHostToDevice, G_st));
+  HIP_CHECK(hipMemcpyAsync(d_aread, b->pile_aread, sizeof(int) * (size_t) np, hipMemcpyHostToDevice, G_st));
+  HIP_CHECK(hipMemcpyAsync(d_alen, LQ_halen.data(), sizeof(int) * (size_t) np, hipMemcpyHostToDevice, G_st));
+  HIP_CHECK(hipMemcpyAsync(d_tile0, LQ_htile0.data(), sizeof(u32) * ((size_t) np + 1), hipMemcpyHostToDevice, G_st));
+  if (nrec > 0)
+    { for (int i = 0; i < 4; i++)
+        HIP_CHECK(hipMemcpyAsync(d_col[i], src[i], sizeof(int) * nrec, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_toff, t->trace_off, sizeof(long long) * nrec, hipMemcpyHostToDevice, G_st));
+    }
+  if (t->trace_bytes > 0)
+    HIP_CHECK(hipMemcpyAsync(d_trace, t->trace, (size_t) t->trace_bytes, hipMemcpyHostToDevice, G_st));
+  HIP_CHECK(hipMemsetAsync(d_depth, 0, sizeof(u32) * ((size_t) nt + 1), G_st));
+  HIP_CHECK(hipEventRecord(LQ_ev[1], G_st));
+
+  a.pile_off = d_off;  a.pile_aread = d_aread;  a.pile_alen = d_alen;  a.pile_tile0 = d_tile0;
+  a.abpos = d_col[0];  a.aepos = d_col[1];  a.bread = d_col[2];  a.tlen = d_col[3];
+  a.trace_off = d_toff;  a.trace = d_trace;
+  a.depth = d_depth;  a.off = d_run;  a.vals = d_vals;  a.q = d_q;
+  damar_launch_q_count(&a, G_st);
+  damar_exclusive_scan_u32(d_depth, d_run, (u64) nt + 1, d_scan, d_misc, G_st);       /* d_run[nt] = d_misc[0] = segments counted */
+  HIP_CHECK(hipEventRecord(LQ_ev[2], G_st));
+  damar_launch_q_scatter(&a, G_st);
+  damar_launch_q_select(&a, G_st);
+  HIP_CHECK(hipEventRecord(LQ_ev[3], G_st));
+  u64 h_total = 0;
+  HIP_CHECK(hipMemcpyAsync(q_out, d_q, sizeof(int) * (size_t) nt, hipMemcpyDeviceToHost, G_st));
+  HIP_CHECK(hipMemcpyAsync(&h_total, d_misc, sizeof(u64), hipMemcpyDeviceToHost, G_st));
+  HIP_CHECK(hipEventRecord(LQ_ev[4], G_st));
+  HIP_CHECK(hipStreamSynchronize(G_st));
+  LQ_cnt[0] = (int64) h_total;  LQ_cnt[1] = ntiles;
+  for (int i = 0; i < 4; i++)
+    { float ms = 0;
+      HIP_CHECK(hipEventElapsedTime(&ms, LQ_ev[i], LQ_ev[i + 1]));
+      LQ_ms[i] = ms;
+    }
+  return 0;
+}

@@ -236,6 +236,32 @@ void damar_pile_release(void);             /* frees the cached device buffers of
 /* of the last call: ms[4] = upload, sort, sweep, download; cnt[2] = events sorted, regions (tandem: intervals) written */
 void damar_pile_last(double *ms, int64 *cnt);
 
+/* Per-segment quality from the traces of piles (scrub/LAq.c handler_annotate).  A trace batch is a pile batch whose records
+ * also carry their trace as it lies in the .las file: record i's tlen[i] values (diffs of a segment at even, its B length
+ * at odd positions; tbytes bytes each, 1 for tspace <= 125, else 2) begin at trace + trace_off[i].  The tiles (segments of
+ * tspace bases) of the batch's piles are numbered back to back, ceil(alen / tspace) per pile; q_out receives one value per
+ * tile and *ntiles_out their number (q_out == NULL: only the number).  Runs kernels/pile_quality.hip; with DAMAR_PILES=host
+ * the plain histogram of host/quality.c instead (no GPU is touched).  Segments and tiles of a batch stay below 2^31 each.
+ * 0 on success. */
+typedef struct
+{ damar_pile_batch     p;
+  const unsigned char *trace;              /* [trace_bytes] */
+  const int64         *trace_off;          /* [nrec] */
+  const int           *tlen;               /* [nrec] */
+  int64                trace_bytes;
+  int                  tbytes, tspace;
+} damar_trace_batch;
+
+typedef struct
+{ int segmin, segmax;                      /* -s -S: a tile's value is the mean of its segmax lowest, 0 below segmin of them */
+  int ccs;                                 /* -c: 25 instead of 0 below segmin */
+} damar_q_params;
+
+int  damar_pile_quality(const damar_trace_batch *b, const damar_q_params *p, int *q_out, int64 *ntiles_out);
+void damar_q_release(void);                /* frees the cached device buffers of damar_pile_quality */
+/* of the last device call: ms[4] = upload, count + scan, scatter + select, download; cnt[2] = segments counted, tiles */
+void damar_q_last(double *ms, int64 *cnt);
+
 /* Phase timings (milliseconds, HIP events on the library's stream) of the last
  * damar_index_build / damar_match: see DAMAR_T_* below. */
 enum { DAMAR_T_TUPLES = 0, DAMAR_T_KSORT, DAMAR_T_TABLE, DAMAR_T_MERGE, DAMAR_T_SSORT,
