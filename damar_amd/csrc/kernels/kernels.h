@@ -64,6 +64,14 @@ typedef struct
   const int *mdat;      /* j in [moff[i]/2, moff[i+1]/2); NULL when the block carries no mask      */
 } DevBlock;
 
+/* the packed index keys of a block (k <= 16) as a source of the radix sort, see KmerCursor below */
+typedef struct { DevBlock blk;  int kmer; } KmerKeys;
+/* as damar_radix_sort_split_u64 on the bits [32, 32 + 2 * kmer) of the n keys kmer_tuples would have left in k0 -- which
+   are never written: the histogram and the first pass make them from the block's 2-bit bases (k0 is still the other
+   side of the ping-pong) */
+void damar_radix_sort_split_kmers(const KmerKeys *src, u64 *k0, u64 *k1, u64 n, u32 *ohi, u32 *olo, void *work,
+                                  hipStream_t st);
+
 /* Seed-side kernels run beside a resident report launch that is bound by vector instruction issue: four report
    wavefronts and one seed wavefront share a SIMD, and at equal priority the seed wavefront -- which mostly waits for memory --
    gets a fifth of the issue slots whenever it is ready.  Raised priority lets it issue at once and go back to waiting.
@@ -101,6 +109,60 @@ __device__ __forceinline__ void pos_decode(const DevBlock &b, u32 v, u32 *r, u32
 }
 __device__ __forceinline__ u32 pos_encode(const DevBlock &b, u32 r, u32 x, u32 p)
 { return b.rpbits ? ((r << b.rpbits) | x) : p; }
+
+/* The k-mer slots of a block (k-mers in position order, kmer_index.hip): read r owns the slots
+   [kmer_slot0(boff[r], r, k), kmer_slot0(boff[r + 1], r + 1, k)) -- a read of len bases has len + 1 - k of them -- and
+   the k-mer of slot i of read r begins at block offset i + r * k. */
+__device__ __forceinline__ u32 kmer_slot0(u32 b0, u32 r, int kmer) { return b0 - r * (u32) kmer; }
+
+/* k <= 16: the code of the k-mer that begins at block offset f, out of the 2-bit copy of the block (two adjacent words,
+   base 16w in the low bits of word w) instead of k byte loads; the code wants the FIRST base in its high bits, so the
+   window is reversed pair-wise.  16 bases from f on always lie in two words, and the low 32 bits of their funnel shift
+   hold them all. */
+__device__ __forceinline__ u32 kmer_code16(const u32 *__restrict__ pk, u32 f, int kmer)
+{ const u32 wq = f >> 4, o = (f & 15) << 1;
+  const u32 win = __builtin_amdgcn_alignbit(pk[wq + 1], pk[wq], o);
+  u32 r = __brev(win);                                                 /* base j now sits at bits 30-2j, its two bits swapped */
+  r = ((r >> 1) & 0x55555555u) | ((r & 0x55555555u) << 1);
+  return r >> (32 - 2 * kmer);
+}
+
+/* The packed index keys of a block as a SOURCE of the radix sort (radix_sort.hip): the key of slot i is what
+   kmer_tuples<u64, true> stores at k0[i], code << 32 | position word, made from the 2-bit bases where the sort wants it.
+   A wavefront asks for runs of 64 consecutive slots in ascending order: it finds the read of its first slot with all
+   its lanes (a 64-ary search over the reads' first slots, three round trips for 2^18 reads), after that a lane only
+   steps to the next read when its slot has left the current one. */
+
+struct KmerCursor
+{ u32 r, ks, ke;                       /* the read, its first slot, the first slot of the next read */
+
+  /* slot: the wavefront's first slot (the same in every lane, < the number of slots; all 64 lanes are here) */
+  __device__ __forceinline__ void open(const KmerKeys &g, u32 slot)
+  { const u32 l = (u32) lane_id();
+    u32 lo = 0, hi = g.blk.nreads;                 /* the read is in [lo, hi): slot0(lo) <= slot, slot0(hi) > slot or hi past the end */
+    while (hi - lo > 1)
+      { const u32  step = (hi - lo + 63) >> 6;
+        const u32  c  = lo + l * step;
+        const bool ok = c < hi && kmer_slot0(g.blk.boff[c < hi ? c : lo], c, g.kmer) <= slot;   /* (true in lane 0; slot0 never falls) */
+        const u32  in = (u32) __popcll(wballot(ok));
+        lo += (in - 1) * step;
+        hi  = (lo + step < hi) ? lo + step : hi;
+      }
+    r  = lo;
+    ks = kmer_slot0(g.blk.boff[r], r, g.kmer);
+    ke = kmer_slot0(g.blk.boff[r + 1], r + 1, g.kmer);
+  }
+  /* the key of slot i (>= the slot of the call before, < the number of slots) */
+  __device__ __forceinline__ u64 key(const KmerKeys &g, u32 i)
+  { while (i >= ke)                                /* (reads without a k-mer are stepped over) */
+      { r += 1;
+        ks = ke;
+        ke = kmer_slot0(g.blk.boff[r + 1], r + 1, g.kmer);
+      }
+    const u32 f = i + r * (u32) g.kmer, x = i - ks + (u32) (g.kmer - 1);
+    return ((u64) kmer_code16(g.blk.pk, f, g.kmer) << 32) | (u64) pos_encode(g.blk, r, x, f + (u32) (g.kmer - 1));
+  }
+};
 #endif
 
 /* pk[w] for w in [-PK_PAD, total/16 + PK_PAD] from bases (which carry 64 padding bytes either side), then as many words

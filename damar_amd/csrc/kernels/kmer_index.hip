@@ -32,20 +32,12 @@ void kmer_tuples(DevBlock blk, int kmer, u32 nkmers, CodeT *__restrict__ codes, 
   const u32 r = read_of_pos(blk, p), b0 = blk.boff[r];
   if (p - b0 < (u32) (kmer - 1) || p + 1 == blk.boff[r + 1])       /* too close to the start / the terminator */
     return;
-  const u32 i = p - (r + 1) * (u32) kmer + 1;
+  const u32 i = kmer_slot0(b0, r, kmer) + (p - b0) - (u32) (kmer - 1);      /* the slot (kernels.h) */
   if (i >= nkmers)
     return;
   CodeT c = 0;
   if (PACK)
-    { /* k <= 16: the k-mer out of the 2-bit copy of the block (two adjacent words, base 16w in the low bits of word w)
-         instead of k byte loads; the code wants the FIRST base in its high bits, so the window is reversed pair-wise */
-      const u32 f = p - (u32) (kmer - 1), wq = f >> 4, o = (f & 15) << 1;
-      u64 win = ((u64) blk.pk[wq + 1] << 32) | (u64) blk.pk[wq];
-      win >>= o;
-      u64 r = __brevll(win);                                           /* base j now sits at bits 62-2j, its two bits swapped */
-      r = ((r >> 1) & 0x5555555555555555ull) | ((r & 0x5555555555555555ull) << 1);
-      c = (CodeT) (r >> (64 - 2 * kmer));
-    }
+    c = (CodeT) kmer_code16(blk.pk, p - (u32) (kmer - 1), kmer);         /* k <= 16: out of the 2-bit copy of the block (kernels.h) */
   else
     { const u8 *s = blk.bases + (p - (u32) (kmer - 1));
       for (int j = 0; j < kmer; j++)

@@ -24,6 +24,11 @@
  * so every earlier tile belongs to a workgroup that is already running: the look-back cannot wait for a tile that
  * has not started.  Every spin is bounded; a timeout raises the error word that the host checks.
  * 32-bit granules serve sorts of fewer than 2^30 items, 64-bit ones the rest.
+ *
+ * Where the keys come from is a compile-time choice of the histogram and of the pass (SrcT): a pointer -- every sort but
+ * one -- or KmerKeys (kernels.h), the packed k-mer index keys of a block made on the spot from its 2-bit bases.  The index
+ * build's histogram and FIRST pass take the second: the 8 bytes per k-mer that kmer_tuples wrote and these two read back
+ * are never in HBM (damar_radix_sort_split_kmers).  Later passes read what the pass before them wrote.
  */
 #include <atomic>
 #include <type_traits>
@@ -61,6 +66,9 @@ SEED_PRIO_SETTER(damar_sort_set_prio, g_sort_prio)
 #define WS_CTR     (256 + OS_MAXPASS * 256 * 4)
 #define WS_LB      16384
 
+/* the key source of a histogram or a pass (SrcT): a pointer, or keys that are made (KmerKeys, kernels.h) */
+template <typename SrcT> constexpr bool os_made = std::is_same<SrcT, KmerKeys>::value;
+
 template <typename GT> __device__ __forceinline__ GT lb_load(const GT *p)
 { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 template <typename GT> __device__ __forceinline__ void lb_store(GT *p, GT v)
@@ -89,9 +97,9 @@ __device__ __forceinline__ u32 os_scan256(u32 v, u32 *lds4)
 #define OH_THREADS 1024
 #define OH_BINMAX  61440                    /* what a 16-bit bin may receive (< 2^16) */
 
-template <typename KeyT>
+template <typename KeyT, typename SrcT = const KeyT *__restrict__>
 __global__ __launch_bounds__(OH_THREADS)
-void onesweep_hist(const KeyT *__restrict__ keys, u64 n, int lobit, int npass, u64 dsh /* a byte per pass: where its digit starts */,
+void onesweep_hist(SrcT keys, u64 n, int lobit, int npass, u64 dsh /* a byte per pass: where its digit starts */,
                    u64 dwd /* a byte per pass: its mask */, u32 *__restrict__ ghist, uint4 *__restrict__ clr, u64 clr16)
 { extern __shared__ u32 sh[];                                  /* [npass][128][32] */
   constexpr u32 nthr = OH_THREADS;
@@ -103,20 +111,42 @@ void onesweep_hist(const KeyT *__restrict__ keys, u64 n, int lobit, int npass, u
   const u64 ntile = (n + (u64) nthr * OH_ITEMS - 1) / ((u64) nthr * OH_ITEMS);
   for (u64 t = blockIdx.x; t < ntile; t += gridDim.x)
     { const u64 base = t * ((u64) nthr * OH_ITEMS);
-      KeyT k[OH_ITEMS];
+      if constexpr (!os_made<SrcT>)
+        { KeyT k[OH_ITEMS];
 #pragma unroll
-      for (int r = 0; r < OH_ITEMS; r++)
-        { const u64 i = base + (u64) r * nthr + threadIdx.x;
-          k[r] = (i < n) ? keys[i] : (KeyT) 0;
+          for (int r = 0; r < OH_ITEMS; r++)
+            { const u64 i = base + (u64) r * nthr + threadIdx.x;
+              k[r] = (i < n) ? keys[i] : (KeyT) 0;
+            }
+#pragma unroll
+          for (int r = 0; r < OH_ITEMS; r++)
+            { const u64 i = base + (u64) r * nthr + threadIdx.x;
+              if (i < n)
+                { const KeyT x = k[r] >> lobit;
+                  for (int p = 0; p < npass; p++)
+                    { const u32 d = (u32) (x >> (int) ((dsh >> (8 * p)) & 0xffu)) & (u32) ((dwd >> (8 * p)) & 0xffu);
+                      atomicAdd(&sh[((u32) p << 12) + ((d >> 1) << 5) + c], 1u << ((d & 1u) << 4));
+                    }
+                }
+            }
         }
-#pragma unroll
-      for (int r = 0; r < OH_ITEMS; r++)
-        { const u64 i = base + (u64) r * nthr + threadIdx.x;
-          if (i < n)
-            { const KeyT x = k[r] >> lobit;
-              for (int p = 0; p < npass; p++)
-                { const u32 d = (u32) (x >> (int) ((dsh >> (8 * p)) & 0xffu)) & (u32) ((dwd >> (8 * p)) & 0xffu);
-                  atomicAdd(&sh[((u32) p << 12) + ((d >> 1) << 5) + c], 1u << ((d & 1u) << 4));
+      else
+        { /* made keys: a wavefront takes 64 * OH_ITEMS consecutive slots in rounds of 64 (a bin does not care which thread
+             counts a key, and a thread still adds OH_ITEMS keys per tile) */
+          const u64 first = base + (u64) (threadIdx.x >> 6) * (64 * OH_ITEMS);
+          if (first < n)
+            { KmerCursor cur;
+              cur.open(keys, (u32) first);
+#pragma unroll 4
+              for (int r = 0; r < OH_ITEMS; r++)
+                { const u64 i = first + (u64) r * 64 + (threadIdx.x & 63u);
+                  if (i < n)
+                    { const KeyT x = cur.key(keys, (u32) i) >> lobit;
+                      for (int p = 0; p < npass; p++)
+                        { const u32 d = (u32) (x >> (int) ((dsh >> (8 * p)) & 0xffu)) & (u32) ((dwd >> (8 * p)) & 0xffu);
+                          atomicAdd(&sh[((u32) p << 12) + ((d >> 1) << 5) + c], 1u << ((d & 1u) << 4));
+                        }
+                    }
                 }
             }
         }
@@ -142,9 +172,9 @@ void onesweep_hist(const KeyT *__restrict__ keys, u64 n, int lobit, int npass, u
    the bank-private layout above wants 16 KB per place in ONE piece, which the LDS of a CU shared with report workgroups
    often cannot give (measured: launches waiting up to a whole report launch, profiles/r03_sweeps.txt). */
 #define OH_COPIES  8
-template <typename KeyT>
+template <typename KeyT, typename SrcT = const KeyT *__restrict__>
 __global__ __launch_bounds__(256)
-void onesweep_hist8(const KeyT *__restrict__ keys, u64 n, int lobit, int npass, u64 dsh /* a byte per pass: where its digit starts */,
+void onesweep_hist8(SrcT keys, u64 n, int lobit, int npass, u64 dsh /* a byte per pass: where its digit starts */,
                    u64 dwd /* a byte per pass: its mask */, u32 *__restrict__ ghist, uint4 *__restrict__ clr, u64 clr16)
 { SEED_PRIO(g_sort_prio);
   extern __shared__ u32 sh[];                                  /* [npass][256][OH_COPIES]: the bins of a digit place, OH_COPIES copies chosen by lane & 7 */
@@ -156,20 +186,41 @@ void onesweep_hist8(const KeyT *__restrict__ keys, u64 n, int lobit, int npass, 
   const u64 ntile = (n + 256 * OH_ITEMS - 1) / (256 * OH_ITEMS);
   for (u64 t = blockIdx.x; t < ntile; t += gridDim.x)
     { const u64 base = t * (256 * OH_ITEMS);
-      KeyT k[OH_ITEMS];
+      if constexpr (!os_made<SrcT>)
+        { KeyT k[OH_ITEMS];
 #pragma unroll
-      for (int r = 0; r < OH_ITEMS; r++)
-        { const u64 i = base + (u64) r * 256 + threadIdx.x;
-          k[r] = (i < n) ? keys[i] : (KeyT) 0;
+          for (int r = 0; r < OH_ITEMS; r++)
+            { const u64 i = base + (u64) r * 256 + threadIdx.x;
+              k[r] = (i < n) ? keys[i] : (KeyT) 0;
+            }
+#pragma unroll
+          for (int r = 0; r < OH_ITEMS; r++)
+            { const u64 i = base + (u64) r * 256 + threadIdx.x;
+              if (i < n)
+                { const KeyT x = k[r] >> lobit;
+                  for (int p = 0; p < npass; p++)
+                    { const u32 d = (u32) (x >> (int) ((dsh >> (8 * p)) & 0xffu)) & (u32) ((dwd >> (8 * p)) & 0xffu);
+                      atomicAdd(&sh[(((u32) p << 8) + d) * OH_COPIES + c], 1u);
+                    }
+                }
+            }
         }
-#pragma unroll
-      for (int r = 0; r < OH_ITEMS; r++)
-        { const u64 i = base + (u64) r * 256 + threadIdx.x;
-          if (i < n)
-            { const KeyT x = k[r] >> lobit;
-              for (int p = 0; p < npass; p++)
-                { const u32 d = (u32) (x >> (int) ((dsh >> (8 * p)) & 0xffu)) & (u32) ((dwd >> (8 * p)) & 0xffu);
-                  atomicAdd(&sh[(((u32) p << 8) + d) * OH_COPIES + c], 1u);
+      else
+        { /* made keys: 64 * OH_ITEMS consecutive slots per wavefront, as in onesweep_hist */
+          const u64 first = base + (u64) (threadIdx.x >> 6) * (64 * OH_ITEMS);
+          if (first < n)
+            { KmerCursor cur;
+              cur.open(keys, (u32) first);
+#pragma unroll 4
+              for (int r = 0; r < OH_ITEMS; r++)
+                { const u64 i = first + (u64) r * 64 + (threadIdx.x & 63u);
+                  if (i < n)
+                    { const KeyT x = cur.key(keys, (u32) i) >> lobit;
+                      for (int p = 0; p < npass; p++)
+                        { const u32 d = (u32) (x >> (int) ((dsh >> (8 * p)) & 0xffu)) & (u32) ((dwd >> (8 * p)) & 0xffu);
+                          atomicAdd(&sh[(((u32) p << 8) + d) * OH_COPIES + c], 1u);
+                        }
+                    }
                 }
             }
         }
@@ -195,9 +246,9 @@ void onesweep_hist8(const KeyT *__restrict__ keys, u64 n, int lobit, int npass, 
  * (wavefront, round, lane) order is input order and the ranks below make the pass stable.
  * HV: a u32 payload travels with the key.  SPLIT: the last pass of the packed k-mer index -- the key's high word
  * goes to ohi, its low word to vout (no key array is written). */
-template <typename KeyT, typename GT, bool HV, bool SPLIT, int TH, int IT>
+template <typename KeyT, typename GT, bool HV, bool SPLIT, int TH, int IT, typename SrcT = const KeyT *__restrict__>
 __global__ __launch_bounds__(TH, (IT <= 8 ? 8 : OS_MINW))      /* the small shape asks for <= 64 VGPRs: two wavefronts per SIMD beside a report launch */
-void onesweep_pass(const KeyT *__restrict__ kin, const u32 *__restrict__ vin, KeyT *__restrict__ kout,
+void onesweep_pass(SrcT kin, const u32 *__restrict__ vin, KeyT *__restrict__ kout,
                    u32 *__restrict__ vout, u32 *__restrict__ ohi, u64 n, int shift, u32 mask,
                    const u32 *__restrict__ ghist, GT *__restrict__ lb, GT *__restrict__ lbclear,
                    u32 *__restrict__ ctr, u32 *__restrict__ err)
@@ -232,14 +283,29 @@ void onesweep_pass(const KeyT *__restrict__ kin, const u32 *__restrict__ vin, Ke
   /* tile-local 32-bit indexes against lane-uniform tile pointers: one offset register per thread, 32-bit bound checks */
   const u32 have = (n - tbase < (u64) OS_TILE) ? (u32) (n - tbase) : (u32) OS_TILE;
   const u32 t0 = (u32) w * OS_WSPAN + (u32) l;
-  const KeyT *const tin = kin + tbase;
 
   KeyT key[IT];
   u32  rnk[IT];
+  if constexpr (!os_made<SrcT>)
+    { const KeyT *const tin = kin + tbase;
 #pragma unroll
-  for (int r = 0; r < IT; r++)
-    { const u32 ti = t0 + (u32) r * 64;
-      key[r] = tin[ti < have ? ti : have - 1];               /* (no branch around a load; what a lane beyond the end reads is never used) */
+      for (int r = 0; r < IT; r++)
+        { const u32 ti = t0 + (u32) r * 64;
+          key[r] = tin[ti < have ? ti : have - 1];               /* (no branch around a load; what a lane beyond the end reads is never used) */
+        }
+    }
+  else
+    { /* made keys: the tile's items are the k-mer slots from tbase on; a wavefront's rounds ascend, as the cursor wants
+         (a lane beyond the end makes the last slot's key again) */
+      static_assert(std::is_same<KeyT, u64>::value && !HV, "made keys are packed u64 index keys");
+      const u32 wfirst = (u32) w * OS_WSPAN;
+      KmerCursor cur;
+      cur.open(kin, (u32) tbase + (wfirst < have ? wfirst : have - 1));
+#pragma unroll
+      for (int r = 0; r < IT; r++)
+        { const u32 ti = t0 + (u32) r * 64;
+          key[r] = cur.key(kin, (u32) tbase + (ti < have ? ti : have - 1));
+        }
     }
 #if OS_RANK_LDS
   /* Ranking through LDS (round 5): the lanes of a wavefront that hold the same digit find each other in a 64-bit word
@@ -441,8 +507,10 @@ const u32 *damar_sort_error_word(const void *work) { return (const u32 *) work; 
 
 template <typename KeyT, typename GT, bool HV, int TH, int IT>
 static void onesweep_passes(KeyT *k0, u32 *v0, KeyT *k1, u32 *v1, u64 n, int lobit, int hibit, u32 *ohi, u32 *olo,
-                            char *ws, hipStream_t st)
+                            char *ws, hipStream_t st, const KmerKeys *made /* not NULL: k0's keys are not there, they are made */)
 { constexpr int OS_TILE = TH * IT;
+  constexpr bool MADE = std::is_same<KeyT, u64>::value && !HV;     /* (the only sort that is asked for made keys) */
+  typedef const KeyT *__restrict__ KeysAt;                         /* (named at every launch: a call would deduce the type of its argument) */
   const u32 ntiles = (u32) ((n + OS_TILE - 1) / OS_TILE);
   const int npass  = (hibit - lobit + 7) / 8;
   /* The digits of a sort are as EVEN as its bits allow -- 28 bits are four digits of 7, 43 bits one of 8 and five of 7 -- not
@@ -485,18 +553,31 @@ static void onesweep_passes(KeyT *k0, u32 *v0, KeyT *k1, u32 *v1, u64 n, int lob
         if (!(big_lds.load(std::memory_order_acquire) & bit))
           { HIP_CHECK(hipFuncSetAttribute((const void *) onesweep_hist<u32>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 16384));
             HIP_CHECK(hipFuncSetAttribute((const void *) onesweep_hist<u64>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 16384));
+            HIP_CHECK(hipFuncSetAttribute((const void *) onesweep_hist<u64, KmerKeys>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 16384));
             big_lds.fetch_or(bit, std::memory_order_release);
           }
       }
-      hipLaunchKernelGGL(onesweep_hist<KeyT>, dim3((u32) grid), dim3(OH_THREADS), lds, st,
-                         k0, n, lobit, npass, dsh, dwd, ghist, (uint4 *) lbr[0], (u64) (region / 16));
+      if (made != NULL)
+        { if constexpr (MADE)
+            hipLaunchKernelGGL((onesweep_hist<KeyT, KmerKeys>), dim3((u32) grid), dim3(OH_THREADS), lds, st,
+                               *made, n, lobit, npass, dsh, dwd, ghist, (uint4 *) lbr[0], (u64) (region / 16));
+        }
+      else
+        hipLaunchKernelGGL((onesweep_hist<KeyT, KeysAt>), dim3((u32) grid), dim3(OH_THREADS), lds, st,
+                           k0, n, lobit, npass, dsh, dwd, ghist, (uint4 *) lbr[0], (u64) (region / 16));
       HIP_CHECK(hipGetLastError());
     }
   else
     { const u64 nt = (n + 256 * OH_ITEMS - 1) / (256 * OH_ITEMS);
       const u32 grid = (u32) (nt < 2048 ? nt : 2048);
-      hipLaunchKernelGGL(onesweep_hist8<KeyT>, dim3(grid), dim3(256), (size_t) npass * 256 * OH_COPIES * sizeof(u32), st,
-                         k0, n, lobit, npass, dsh, dwd, ghist, (uint4 *) lbr[0], (u64) (region / 16));
+      if (made != NULL)
+        { if constexpr (MADE)
+            hipLaunchKernelGGL((onesweep_hist8<KeyT, KmerKeys>), dim3(grid), dim3(256), (size_t) npass * 256 * OH_COPIES * sizeof(u32), st,
+                               *made, n, lobit, npass, dsh, dwd, ghist, (uint4 *) lbr[0], (u64) (region / 16));
+        }
+      else
+        hipLaunchKernelGGL((onesweep_hist8<KeyT, KeysAt>), dim3(grid), dim3(256), (size_t) npass * 256 * OH_COPIES * sizeof(u32), st,
+                           k0, n, lobit, npass, dsh, dwd, ghist, (uint4 *) lbr[0], (u64) (region / 16));
     }
   for (int p = 0; p < npass; p++)
     { const int  side = p & 1;
@@ -504,12 +585,24 @@ static void onesweep_passes(KeyT *k0, u32 *v0, KeyT *k1, u32 *v1, u64 n, int lob
       KeyT *ki = side ? k1 : k0, *ko = side ? k0 : k1;
       u32  *vi = side ? v1 : v0, *vo = side ? v0 : v1;
       const u32 mask = (1u << dwidth[p]) - 1u;
-      if (last && ohi != NULL)
-        hipLaunchKernelGGL((onesweep_pass<KeyT, GT, false, true, TH, IT>), dim3(ntiles), dim3(TH), 0, st,
+      if (p == 0 && made != NULL)                  /* the first pass makes its keys; it writes like any other */
+        { if constexpr (MADE)
+            { if (last && ohi != NULL)
+                hipLaunchKernelGGL((onesweep_pass<KeyT, GT, false, true, TH, IT, KmerKeys>), dim3(ntiles), dim3(TH), 0, st,
+                                   *made, (const u32 *) NULL, (KeyT *) NULL, olo, ohi, n, lobit + dshift[p], mask,
+                                   ghist + 256 * p, lbr[side], lbr[side ^ 1], ctr + p, err);
+              else
+                hipLaunchKernelGGL((onesweep_pass<KeyT, GT, false, false, TH, IT, KmerKeys>), dim3(ntiles), dim3(TH), 0, st,
+                                   *made, vi, ko, vo, (u32 *) NULL, n, lobit + dshift[p], mask,
+                                   ghist + 256 * p, lbr[side], lbr[side ^ 1], ctr + p, err);
+            }
+        }
+      else if (last && ohi != NULL)
+        hipLaunchKernelGGL((onesweep_pass<KeyT, GT, false, true, TH, IT, KeysAt>), dim3(ntiles), dim3(TH), 0, st,
                            ki, (const u32 *) NULL, (KeyT *) NULL, olo, ohi, n, lobit + dshift[p], mask,
                            ghist + 256 * p, lbr[side], lbr[side ^ 1], ctr + p, err);
       else
-        hipLaunchKernelGGL((onesweep_pass<KeyT, GT, HV, false, TH, IT>), dim3(ntiles), dim3(TH), 0, st,
+        hipLaunchKernelGGL((onesweep_pass<KeyT, GT, HV, false, TH, IT, KeysAt>), dim3(ntiles), dim3(TH), 0, st,
                            ki, vi, ko, vo, (u32 *) NULL, n, lobit + dshift[p], mask,
                            ghist + 256 * p, lbr[side], lbr[side ^ 1], ctr + p, err);
     }
@@ -519,7 +612,7 @@ static void onesweep_passes(KeyT *k0, u32 *v0, KeyT *k1, u32 *v1, u64 n, int lob
  * (k0,v0), 1 if in (k1,v1).  With ohi / olo the last pass writes the two halves of the keys there instead. */
 template <typename KeyT, bool HV>
 static int onesweep_impl(KeyT *k0, u32 *v0, KeyT *k1, u32 *v1, u64 n, int lobit, int hibit, u32 *ohi, u32 *olo,
-                         void *work, hipStream_t st)
+                         void *work, hipStream_t st, const KmerKeys *made = NULL)
 { const int npass = (hibit - lobit + 7) / 8;
   if (n == 0 || npass <= 0)
     return 0;
@@ -533,12 +626,12 @@ static int onesweep_impl(KeyT *k0, u32 *v0, KeyT *k1, u32 *v1, u64 n, int lobit,
   if (lb64 < 0)
     lb64 = getenv("DAMAR_SORT_LB64") != NULL;
   if (n < (1ull << 30) && !lb64)
-    { if (shape == 1024)     onesweep_passes<KeyT, u32, HV, 1024, 8>(k0, v0, k1, v1, n, lobit, hibit, ohi, olo, (char *) work, st);
-      else if (shape == 512) onesweep_passes<KeyT, u32, HV, 512, 16>(k0, v0, k1, v1, n, lobit, hibit, ohi, olo, (char *) work, st);
-      else              onesweep_passes<KeyT, u32, HV, 256, 16>(k0, v0, k1, v1, n, lobit, hibit, ohi, olo, (char *) work, st);
+    { if (shape == 1024)     onesweep_passes<KeyT, u32, HV, 1024, 8>(k0, v0, k1, v1, n, lobit, hibit, ohi, olo, (char *) work, st, made);
+      else if (shape == 512) onesweep_passes<KeyT, u32, HV, 512, 16>(k0, v0, k1, v1, n, lobit, hibit, ohi, olo, (char *) work, st, made);
+      else              onesweep_passes<KeyT, u32, HV, 256, 16>(k0, v0, k1, v1, n, lobit, hibit, ohi, olo, (char *) work, st, made);
     }
   else                  /* 2^30 items and more: 64-bit look-back words, one shape */
-    onesweep_passes<KeyT, u64, HV, 256, 16>(k0, v0, k1, v1, n, lobit, hibit, ohi, olo, (char *) work, st);
+    onesweep_passes<KeyT, u64, HV, 256, 16>(k0, v0, k1, v1, n, lobit, hibit, ohi, olo, (char *) work, st, made);
   return npass & 1;
 }
 
@@ -561,6 +654,11 @@ int damar_radix_sort_keys_u64(u64 *k0, u64 *k1, u64 n, int lobit, int hibit, voi
 void damar_radix_sort_split_u64(u64 *k0, u64 *k1, u64 n, int lobit, int hibit, u32 *ohi, u32 *olo, void *work,
                                 hipStream_t st)
 { onesweep_impl<u64, false>(k0, NULL, k1, NULL, n, lobit, hibit, ohi, olo, work, st); }
+
+/* the packed k-mer index of a block, k <= 16: as above on the code bits of keys that are made, not read (kernels.h) */
+void damar_radix_sort_split_kmers(const KmerKeys *src, u64 *k0, u64 *k1, u64 n, u32 *ohi, u32 *olo, void *work,
+                                  hipStream_t st)
+{ onesweep_impl<u64, false>(k0, NULL, k1, NULL, n, 32, 32 + 2 * src->kmer, ohi, olo, work, st, src); }
 
 /* loads this file's code object now (a lazy load otherwise happens at the first launch, on the launching thread): called by
    the library's start-up thread, beside the caller's first uploads (shim.hip damar_hip_init) */

@@ -765,6 +765,9 @@ static int ilog2_ceil(u64 n)
   return b;
 }
 
+static int  G_index_made = 0;            /* the last index build made its keys inside the sort (damar_index_last_made) */
+extern "C" int damar_index_last_made(void) { return G_index_made; }
+
 static int  B_have = 0, B_log[4];        /* -b log weights, fixed by the first biased Sort_Kmers of the process */
 
 /* A new job in the same process (the in-process driver, tests): forget the -b weights, as a
@@ -848,6 +851,18 @@ static damar_dev_index *index_build_k(damar_dev_block *blk, int own_block, int *
       v0 = v1 = NULL;
     }
 
+  /* The plain packed build with position words (k <= 16, no mask, no -b: what a daligner run does all day) never has its
+     unsorted keys in HBM: the sort's histogram and first pass make them from the 2-bit bases (radix_sort.hip,
+     damar_radix_sort_split_kmers), so the `tuples` phase below is empty.  DAMAR_INDEX_GEN=0: kmer_tuples writes them
+     and the sort reads them, as every other build does. */
+  static int gen_on = -1;
+  if (gen_on < 0)
+    { const char *e = getenv("DAMAR_INDEX_GEN");
+      gen_on = e ? atoi(e) : 1;
+    }
+  const bool made = gen_on && !wide && !masked && !biased && blk->d.rpbits > 0;
+  G_index_made = made;
+
   tick(0);
   if (biased || masked)
     { /* filter.c:474-526 / 549-688 + the filler squeeze of :855-888: only k-mers inside one
@@ -879,7 +894,7 @@ static damar_dev_index *index_build_k(damar_dev_block *blk, int own_block, int *
       if (VERBOSE && biased)
         printf("\n   Revised kmer count = %u\n", nk);
     }
-  else
+  else if (!made)
     damar_launch_kmer_tuples(&blk->d, K, nk, k0, wide, v0, G_st);                   /* v0 == NULL: packed */
   tick(1);
   if (wide)
@@ -888,6 +903,12 @@ static damar_dev_index *index_build_k(damar_dev_block *blk, int own_block, int *
         { fprintf(stderr, "damar: internal error, sort ended on the wrong side\n");
           die();
         }
+    }
+  else if (made)
+    { KmerKeys src;
+      src.blk  = blk->d;
+      src.kmer = K;
+      damar_radix_sort_split_kmers(&src, (u64 *) k0, (u64 *) k1, nk, (u32 *) ix->codes, ix->pos, sw, G_st);
     }
   else
     damar_radix_sort_split_u64((u64 *) k0, (u64 *) k1, nk, 32, 32 + kbits, (u32 *) ix->codes, ix->pos, sw, G_st);

@@ -6,8 +6,12 @@
  *   sortbench check          correctness sweep, exit 1 on the first difference
  *   sortbench time [reps]    timings; prints GB/s against the ALGORITHMIC bytes of SURVEY 8(d)
  *                            (16-byte records, one read + one write per 8-bit digit) and the bytes moved here
+ *   sortbench index [reps]   the packed k-mer index of one config-2 block (135 Mbp of 10 kb reads, k = 14) both ways:
+ *                            kmer_tuples + sort over its keys, and the sort that makes its keys (KmerKeys); ms and bytes
+ *                            moved.  Both results are compared first, there and on a block of reads of k - 1 .. k + 6 bases.
  */
 #include "../kernels/radix_sort.hip"
+#include "../kernels/kmer_index.hip"
 #include <vector>
 #include <algorithm>
 #include <numeric>
@@ -155,9 +159,121 @@ static void report(const char *name, int kind, u64 n, int lo, int hi, int reps)
          algo / ms * 1e-6, moved / ms * 1e-6);
 }
 
+/* a block of random reads in HBM as shim.hip lays it out (boff, coarse, bases with their 4s, 2-bit copy, position words) */
+struct BenchBlock { DevBlock d;  u8 *bases;  u32 *pk, *boff, *coarse;  u32 nk; };
+
+static BenchBlock make_block(const std::vector<u32> &lens, int kmer)
+{ BenchBlock b;
+  const u32 n = (u32) lens.size();
+  std::vector<u32> boff(n + 1);
+  u32 total = 0, maxlen = 0;
+  for (u32 i = 0; i < n; i++)
+    { boff[i] = total;  total += lens[i] + 1;  maxlen = std::max(maxlen, lens[i]); }
+  boff[n] = total;
+  std::vector<u8> hb((size_t) total + 192, 4);
+  for (u32 i = 0; i < n; i++)
+    { u64 x = 0;
+      for (u32 j = 0; j < lens[i]; j++)
+        { if ((j & 31) == 0) x = rnd();
+          hb[64 + boff[i] + j] = (u8) (x & 3);  x >>= 2;
+        }
+    }
+  const size_t nq = ((size_t) total >> COARSE_SHIFT) + 2;
+  std::vector<u32> coarse(nq);
+  for (size_t q = 0, r = 0; q < nq; q++)
+    { while (r + 1 < n && (u64) boff[r + 1] <= ((u64) q << COARSE_SHIFT)) r += 1;
+      coarse[q] = (u32) r;
+    }
+  b.bases = dev<u8>(hb.size());  b.boff = dev<u32>(n + 1);  b.coarse = dev<u32>(nq);
+  b.pk = dev<u32>(2 * (size_t) damar_pack_words(total));
+  HIP_CHECK(hipMemcpy(b.bases, hb.data(), hb.size(), hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(b.boff, boff.data(), 4 * (size_t) (n + 1), hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(b.coarse, coarse.data(), 4 * nq, hipMemcpyHostToDevice));
+  damar_launch_pack_bases(b.bases + 64, total, b.pk + PK_PAD, 0);
+  HIP_CHECK(hipDeviceSynchronize());
+  memset(&b.d, 0, sizeof(b.d));
+  b.d.bases = b.bases + 64;  b.d.pk = b.pk + PK_PAD;  b.d.boff = b.boff;  b.d.coarse = b.coarse;
+  b.d.nreads = n;  b.d.total = total;  b.d.maxlen = (int) maxlen;
+  int pb = 1;
+  while ((1u << pb) < maxlen + 1) pb += 1;
+  b.d.rpbits = pb;
+  b.nk = total - (u32) kmer * n;
+  return b;
+}
+
+/* both index sorts of a block; ms[0]: kmer_tuples + sort, ms[1]: the sort that makes its keys; 1 if the results differ */
+static int index_both(const BenchBlock &b, int kmer, int reps, double ms[2])
+{ const u64 n = b.nk;
+  void *ws = dev<char>(damar_sort_workspace_bytes(n));
+  u64 *k0 = dev<u64>(n), *k1 = dev<u64>(n);
+  u32 *oh[2] = { dev<u32>(n), dev<u32>(n) }, *ol[2] = { dev<u32>(n), dev<u32>(n) };
+  KmerKeys src;
+  src.blk = b.d;  src.kmer = kmer;
+  hipEvent_t e0, e1;
+  hipEventCreate(&e0); hipEventCreate(&e1);
+  for (int way = 0; way < 2; way++)
+    { double tot = 0;
+      for (int r = 0; r < reps + 1; r++)
+        { hipEventRecord(e0, 0);
+          if (way == 0)
+            { damar_launch_kmer_tuples(&b.d, kmer, (u32) n, k0, 0, NULL, 0);
+              damar_radix_sort_split_u64(k0, k1, n, 32, 32 + 2 * kmer, oh[0], ol[0], ws, 0);
+            }
+          else
+            damar_radix_sort_split_kmers(&src, k0, k1, n, oh[1], ol[1], ws, 0);
+          hipEventRecord(e1, 0);
+          HIP_CHECK(hipEventSynchronize(e1));
+          float t; hipEventElapsedTime(&t, e0, e1);
+          if (r > 0) tot += t;
+          if (check_err(ws)) { fprintf(stderr, "look-back timeout flagged\n"); exit(1); }
+        }
+      ms[way] = reps > 0 ? tot / reps : 0;
+    }
+  int bad = 0;
+  { std::vector<u32> a(n), c(n);
+    for (int h = 0; h < 2 && !bad; h++)
+      { HIP_CHECK(hipMemcpy(a.data(), h ? ol[0] : oh[0], 4 * n, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(c.data(), h ? ol[1] : oh[1], 4 * n, hipMemcpyDeviceToHost));
+        bad = memcmp(a.data(), c.data(), 4 * n) != 0;
+      }
+  }
+  hipFree(ws); hipFree(k0); hipFree(k1); hipFree(oh[0]); hipFree(oh[1]); hipFree(ol[0]); hipFree(ol[1]);
+  return bad;
+}
+
+static void free_block(BenchBlock &b) { hipFree(b.bases); hipFree(b.pk); hipFree(b.boff); hipFree(b.coarse); }
+
+static int do_index(int reps)
+{ const int kmer = 14;
+  double ms[2];
+  { /* reads of k - 1 bases (no k-mer), k (one) ... k + 6: read borders in every round of 64 slots */
+    std::vector<u32> lens(40000);
+    for (auto &x : lens) x = (u32) (kmer - 1 + rnd() % 8);
+    BenchBlock b = make_block(lens, kmer);
+    const int bad = index_both(b, kmer, 0, ms);
+    free_block(b);
+    if (bad) { printf("index FAILED: short reads, made keys differ from kmer_tuples\n"); return 1; }
+  }
+  std::vector<u32> lens(13500);
+  for (auto &x : lens) x = (u32) (6000 + rnd() % 8000);
+  BenchBlock b = make_block(lens, kmer);
+  if (index_both(b, kmer, reps, ms))
+    { printf("index FAILED: made keys differ from kmer_tuples\n"); return 1; }
+  const int    P  = (2 * kmer + 7) / 8;
+  const double nk = b.nk, pkb = b.d.total / 4.0;
+  const double moved[2] = { pkb + 8 * nk + 8 * nk + P * 16 * nk, pkb + (pkb + 8 * nk) + (P - 1) * 16 * nk };
+  const char  *name[2]  = { "index build, kmer_tuples + sort", "index build, sort makes its keys" };
+  for (int w = 0; w < 2; w++)
+    printf("%-34s n=%9u P=%d  %7.3f ms   moved %6.2f GB = %6.0f GB/s\n", name[w], b.nk, P, ms[w], moved[w] * 1e-9, moved[w] / ms[w] * 1e-6);
+  free_block(b);
+  return 0;
+}
+
 int main(int argc, char **argv)
 { if (argc > 1 && strcmp(argv[1], "check") == 0)
     return do_check();
+  if (argc > 1 && strcmp(argv[1], "index") == 0)
+    return do_index(argc > 2 ? atoi(argv[2]) : 10);
   const int reps = argc > 2 ? atoi(argv[2]) : 10;
   printf("variant: shape %d (1024: threads x 8 keys, 512 / 256: threads x 16 keys), minw %d\n", sort_threads(), OS_MINW);
   report("kmer index, packed u64 split", 4, 135000000ull, 32, 60, reps);

@@ -69,6 +69,9 @@ void             damar_pool_trim(void);                            /* release th
 /* Test hook: copy the index back as reference-layout KmerPos records
  * {uint64 code; int rpos; int read} (filter.c:121-126), out must hold *len records. */
 void             damar_index_download(const damar_dev_index *idx, void *out);
+/* Test hook: 1 if the last damar_index_build made its unsorted keys inside the sort (packed, unmasked, unbiased, position
+ * words in use, DAMAR_INDEX_GEN not 0), 0 if kmer_tuples wrote them to HBM first. */
+int              damar_index_last_made(void);
 
 /* Device part + host tail of Match_Filter (filter.c:2519-2929); records are appended
  * to OVL_IO_Buffer(spec)[0].  counts[0..2] = seed pairs, seed hits (Local_Alignment

@@ -9,6 +9,8 @@ mkdir -p $OUT
 B=damar_amd/bin
 timeout -k 10 300 $B/sortbench check > $OUT/check.txt 2>&1 || { cat $OUT/check.txt; exit 1; }
 cat $OUT/check.txt
+# the index build of one config-2 block both ways: kmer_tuples + sort, and the sort that makes its keys
+timeout -k 10 200 $B/sortbench index 5 2>&1 | tee $OUT/index.txt
 for v in $B/sortbench $B/sortbench_*; do
   [ -x "$v" ] || continue
   echo "== $v" | tee -a $OUT/time.txt
