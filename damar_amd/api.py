@@ -149,6 +149,9 @@ def _lib():
                                                   C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int),
                                                   C.POINTER(c_int64), C.POINTER(C.c_uint16), c_int64]
         L.damar_local_alignment_batch.restype = C.c_int
+        L.damar_local_alignment_batch_opts.argtypes = L.damar_local_alignment_batch.argtypes + [C.c_int, C.POINTER(C.c_int),
+                                                                                               C.POINTER(C.c_int)]
+        L.damar_local_alignment_batch_opts.restype = C.c_int
         L.damar_last_timings.argtypes = [C.POINTER(C.c_double)]
         L.damar_last_counters.argtypes = [C.POINTER(c_int64)]
         L.damar_last_slabs.argtypes = [C.POINTER(C.c_int), C.POINTER(c_int64), C.c_int]

@@ -1094,6 +1094,12 @@ static u32 max_cells(void)                  /* (DAMAR_TEST_MAX_CELLS: a test hoo
   return m;
 }
 
+/* Blocks of a wide-kernel launch.  RS.wslots is sized when the wide pebbles are first allocated; block b of that launch also
+   takes slot b of the ordinary scratch (band state, marks, trace buffers: slot_scratch), which holds RS.nslots slots and may
+   have been rebuilt with fewer since (DAMAR_SLOTS, less free memory): never more blocks than either has. */
+static int wide_slots(void)
+{ return std::min(RS.wslots, RS.nslots); }
+
 static u32 grow_cells(u32 cell_cap)
 { if (cell_cap >= max_cells())
     { fprintf(stderr, "damar: FATAL: an alignment needs more than %u trace pebbles; use a larger trace spacing (-s)\n", max_cells());
@@ -2728,7 +2734,7 @@ static void report_finish(Pending &pd)
                 HIP_CHECK(hipMemsetAsync(ctr + DAMAR_CNT_CURSOR, 0, sizeof(u32) * DAMAR_MAX_JOBS, st));      /* the work lists once more */
                 HIP_CHECK(hipMemsetAsync(ctr + 3, 0, sizeof(u32), st));
               }
-              damar_launch_report_wide(pd.ra, n, RS.wslots, st);
+              damar_launch_report_wide(pd.ra, n, wide_slots(), st);
               HIP_CHECK(hipEventRecord(pd.done, st));
               pd.wide_done = true;
               continue;                                         /* wait for it, read the counters again */
@@ -3240,9 +3246,9 @@ static bool wide_behind(ReportArgs &ra, u32 *hc, u32 cell_cap, const int *dist, 
   HIP_CHECK(hipMemsetAsync(RS.ctr + DAMAR_CNT_CURSOR, 0, sizeof(u32) * DAMAR_MAX_JOBS, G_st));
   HIP_CHECK(hipMemsetAsync(RS.ctr + 3, 0, sizeof(u32), G_st));
   if (dist != NULL)
-    damar_launch_tandem_report_wide(&ra, dist, RS.wslots, G_st);
+    damar_launch_tandem_report_wide(&ra, dist, wide_slots(), G_st);
   else
-    damar_launch_la_batch_wide(&ra, tasks, ntasks, RS.wslots, G_st);
+    damar_launch_la_batch_wide(&ra, tasks, ntasks, wide_slots(), G_st);
   HIP_CHECK(hipMemcpyAsync(hc, RS.ctr, sizeof(u32) * DAMAR_COUNTER_WORDS, hipMemcpyDeviceToHost, G_st));
   HIP_CHECK(hipStreamSynchronize(G_st));
   HIP_CHECK(hipGetLastError());
@@ -3441,14 +3447,21 @@ extern "C" int64 damar_last_seeds(void *out, int64 cap)
   return n;
 }
 
-extern "C" int damar_local_alignment_batch(damar_dev_block *ablk, damar_dev_block *bblk, int comp,
-                                           Align_Spec *spec, const int *tasks, int ntasks,
-                                           int *paths, int64 *trace_off, uint16 *traces, int64 trace_cap)
+/* t8: the launch writes its trace values as bytes where the spacing allows it (ReportArgs.t8, what report_launch does for the
+   pipeline at -s <= 125); they are widened into `traces` here.  A value that does not fit (DAMAR_ERR_T8) repeats the launch
+   with 16-bit values: *t8_fell_back says so.  *wide_tasks: the tasks the wide kernel answered (DAMAR_CNT_WIDE). */
+extern "C" int damar_local_alignment_batch_opts(damar_dev_block *ablk, damar_dev_block *bblk, int comp,
+                                                Align_Spec *spec, const int *tasks, int ntasks,
+                                                int *paths, int64 *trace_off, uint16 *traces, int64 trace_cap,
+                                                int t8, int *t8_fell_back, int *wide_tasks)
 { finish_all();
   ensure_init();
+  if (t8_fell_back) *t8_fell_back = 0;
+  if (wide_tasks)   *wide_tasks = 0;
   if (ntasks <= 0)
     return 0;
   const int ts = Trace_Spacing(spec);
+  int use8 = (t8 != 0 && ts <= TRACE_XOVR);
   u32 cell_cap = std::min<u32>(RS.cell_cap ? RS.cell_cap : DEFAULT_CELLS, max_cells()), rec_cap = 2 * (u32) ntasks + 16,
       tp_cap = (u32) std::min<int64>(trace_cap + 1024, 0x7fffffff);
   LaTask *dt = (LaTask *) dmalloc(sizeof(LaTask) * (size_t) ntasks);
@@ -3463,6 +3476,7 @@ extern "C" int damar_local_alignment_batch(damar_dev_block *ablk, damar_dev_bloc
       stage("la_scratch");
       scratch_outputs(rec_cap, tp_cap);
       fill_report_args(&ra, ablk, bblk, comp, 0, spec, G_st, 0, 0, params_now());
+      ra.t8 = use8;
       const bool packed = use_packed(&ra, ablk->d.maxlen, bblk->d.maxlen);
       if (!packed)
         marks_must_fit(ablk->d.maxlen, bblk->d.maxlen, ts);
@@ -3496,6 +3510,10 @@ extern "C" int damar_local_alignment_batch(damar_dev_block *ablk, damar_dev_bloc
       if (hc[3] & DAMAR_ERR_WIDE)  G_ring *= 4;
       if (hc[3] & DAMAR_ERR_RECS)
         rec_cap = std::max(2 * rec_cap, hc[1] + 1024);
+      if (hc[3] & DAMAR_ERR_T8)                    /* a value above 255 (t8max): 16-bit values again, as report_launch does */
+        { use8 = 0;
+          if (t8_fell_back) *t8_fell_back = 1;
+        }
       if (hc[3] & DAMAR_ERR_TPOOL)
         { HIP_CHECK(hipFree(dt));
           if (wmap != NULL)
@@ -3507,7 +3525,16 @@ extern "C" int damar_local_alignment_batch(damar_dev_block *ablk, damar_dev_bloc
   std::vector<LaRecord> recs(hc[1]);
   std::vector<u16> tp(hc[2]);
   HIP_CHECK(hipMemcpy(recs.data(), RS.recs, sizeof(LaRecord) * (size_t) hc[1], hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(tp.data(), RS.tpool, sizeof(u16) * (size_t) hc[2], hipMemcpyDeviceToHost));
+  if (use8)
+    { std::vector<u8> tp8(hc[2]);
+      HIP_CHECK(hipMemcpy(tp8.data(), RS.tpool, sizeof(u8) * (size_t) hc[2], hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < tp8.size(); i++)
+        tp[i] = tp8[i];
+    }
+  else
+    HIP_CHECK(hipMemcpy(tp.data(), RS.tpool, sizeof(u16) * (size_t) hc[2], hipMemcpyDeviceToHost));
+  if (wide_ran && wide_tasks)
+    *wide_tasks = (int) hc[DAMAR_CNT_WIDE];
   if (wide_ran)
     wide_filter(recs, wmap, wwords);
   if (wmap != NULL)
@@ -3537,6 +3564,12 @@ extern "C" int damar_local_alignment_batch(damar_dev_block *ablk, damar_dev_bloc
       top += r.btlen;
     }
   return 0;
+}
+
+extern "C" int damar_local_alignment_batch(damar_dev_block *ablk, damar_dev_block *bblk, int comp,
+                                           Align_Spec *spec, const int *tasks, int ntasks,
+                                           int *paths, int64 *trace_off, uint16 *traces, int64 trace_cap)
+{ return damar_local_alignment_batch_opts(ablk, bblk, comp, spec, tasks, ntasks, paths, trace_off, traces, trace_cap, 0, NULL, NULL);
 }
 
 extern "C" double damar_bench_sort_u32(uint32_t n, int nbits, int reps, uint32_t seed)

@@ -175,6 +175,15 @@ void damar_bias_reset(void);
 int damar_local_alignment_batch(damar_dev_block *ablk, damar_dev_block *bblk, int comp,
                                 Align_Spec *spec, const int *tasks, int ntasks,
                                 int *paths, int64 *trace_off, uint16 *traces, int64 trace_cap);
+/* The same with the launch's switches: t8 != 0 and a trace spacing <= 125 make the device write its trace values as bytes
+ * (what the pipeline's launches do by default); they arrive widened to 16 bits in `traces`.  A value that does not fit a
+ * byte repeats the launch with 16-bit values and sets *t8_fell_back.  *wide_tasks = the tasks answered by the wide kernel
+ * (reads of more than 16 000 trace spacings, alignments that overflowed the packed pebble pool): DAMAR_CNT_WIDE of the LAST
+ * attempt's launch, set only where the wide kernel ran behind it, 0 otherwise.  Both may be NULL. */
+int damar_local_alignment_batch_opts(damar_dev_block *ablk, damar_dev_block *bblk, int comp,
+                                     Align_Spec *spec, const int *tasks, int ntasks,
+                                     int *paths, int64 *trace_off, uint16 *traces, int64 trace_cap,
+                                     int t8, int *t8_fell_back, int *wide_tasks);
 
 /* SURVEY 8(f)4, the next consumer of the records: Compute_Trace_PTS (align.c:5577-5692 + iter_np
  * :4892-5261) for every record of an Overlap array, the way utils/LAshow.c:245-262 calls it per record.

@@ -78,6 +78,8 @@ typedef struct
   int64 promotions, steps_narrow, steps_wide;
 } OWaveStats;
 
+int  oracle_wave_stats_layout(int *off /* [18]: every field's offset, in declaration order */);   /* returns sizeof(OWaveStats) */
+
 void oracle_local_alignment(const char *aseq, int alen, const char *bseq, int blen,
                             uint32 flags, int diag, int anti, Align_Spec *spec,
                             Path *apath, Path *bpath, uint16 *atrace, uint16 *btrace,

@@ -16,6 +16,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <limits.h>
+#include <stddef.h>
 
 #include "oracle.h"
 
@@ -726,6 +727,18 @@ static void reverse(const Ctx *c, Band *w, int diag, int mida,
     if (c->st)
       c->st->pebbles += w->ncell;
   }
+}
+
+/* sizeof(OWaveStats) and the offset of every field in declaration order (18), for a mirror of the struct in another
+   language to check itself */
+int oracle_wave_stats_layout(int *off)
+{ int n = 0;
+#define OFF(f) off[n++] = (int) offsetof(OWaveStats, f)
+  OFF(waves);  OFF(cells);  OFF(maxband);  OFF(pebbles);  OFF(empty_band);  OFF(bandhist);  OFF(dirs);  OFF(dirs_over31);
+  OFF(steps_after_over31);  OFF(cur_over);  OFF(pass_max);  OFF(pass_cells);  OFF(pass_n);  OFF(pass_cellsum);  OFF(pass_wide);
+  OFF(promotions);  OFF(steps_narrow);  OFF(steps_wide);
+#undef OFF
+  return (int) sizeof(OWaveStats);
 }
 
 /***** Local_Alignment: align.c:1904-2097 **************************************************/

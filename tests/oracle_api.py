@@ -23,6 +23,14 @@ class Path(C.Structure):
                 ("bbpos", C.c_int), ("aepos", C.c_int), ("bepos", C.c_int)]
 
 
+class OWaveStats(C.Structure):       # oracle/oracle.h, field for field (lib() checks its size and every offset: oracle_wave_stats_layout)
+    _fields_ = [("waves", c_int64), ("cells", c_int64), ("maxband", C.c_int), ("pebbles", c_int64),
+                ("empty_band", C.c_int), ("bandhist", c_int64 * 130), ("dirs", c_int64), ("dirs_over31", c_int64),
+                ("steps_after_over31", c_int64), ("cur_over", C.c_int), ("pass_max", C.c_int), ("pass_cells", c_int64),
+                ("pass_n", c_int64 * 5), ("pass_cellsum", c_int64 * 5), ("pass_wide", C.c_int), ("promotions", c_int64),
+                ("steps_narrow", c_int64), ("steps_wide", c_int64)]
+
+
 _L = None
 
 
@@ -45,6 +53,9 @@ def lib():
         _L.New_Align_Spec.argtypes = [C.c_double, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         _L.New_Align_Spec.restype = C.c_void_p
         _L.free.argtypes = [C.c_void_p]
+        off = (C.c_int * len(OWaveStats._fields_))()
+        assert _L.oracle_wave_stats_layout(off) == C.sizeof(OWaveStats)
+        assert list(off) == [getattr(OWaveStats, f[0]).offset for f in OWaveStats._fields_]
     return _L
 
 
@@ -86,13 +97,14 @@ def seed_pairs(adb, bdb, ap, alen, bp, blen, self_, comp, prm):
 LAST_LIMIT = 0          # the cap on mutual k-mer matches the last seed_pairs() call selected
 
 
-def local_alignment(adb, bdb, ar, br, comp, diag, anti, spec, maxtp):
+def local_alignment(adb, bdb, ar, br, comp, diag, anti, spec, maxtp, stats=None):
+    """stats: an OWaveStats the call adds to (waves, cells, pebbles) or raises (maxband, empty_band)"""
     a, b = Path(), Path()
     at = (C.c_uint16 * maxtp)()
     bt = (C.c_uint16 * maxtp)()
     ra, rb = adb.reads[ar], bdb.reads[br]
     lib().oracle_local_alignment(adb.bases + ra.boff, ra.rlen, bdb.bases + rb.boff, rb.rlen, comp, diag, anti,
-                                 spec, C.byref(a), C.byref(b), at, bt, None)
+                                 spec, C.byref(a), C.byref(b), at, bt, C.byref(stats) if stats is not None else None)
     pa = [a.abpos, a.bbpos, a.aepos, a.bepos, a.diffs, a.tlen]
     pb = [b.abpos, b.bbpos, b.aepos, b.bepos, b.diffs, b.tlen]
     return pa + pb, list(at[:a.tlen]), list(bt[:b.tlen])

@@ -31,28 +31,9 @@ TILE = 8192
 
 def _synthetic(lens, seed):
     """A HITS_DB (db/DB.h layout: a 4 in front of the first read and behind every read) of random reads."""
-    from damar_amd import api
-    lens = [int(x) for x in lens]
+    import la_shapes
     rng = np.random.RandomState(seed)
-    total = sum(lens) + len(lens)
-    buf = np.full(total + 1, 4, dtype=np.uint8)
-    reads = (api.HITS_READ * (len(lens) + 1))()
-    off = 0
-    for i, n in enumerate(lens):
-        buf[1 + off:1 + off + n] = rng.randint(0, 4, n)
-        reads[i].rlen, reads[i].boff = n, off
-        off += n + 1
-    reads[len(lens)].boff = off
-    db = api.HITS_DB()
-    db.ureads = db.nreads = len(lens)
-    db.maxlen, db.totlen = max(lens), sum(lens)
-    db.part, db.ufirst, db.loaded = 1, 0, 1
-    for i in range(4):
-        db.freq[i] = .25
-    db.bases = buf.ctypes.data + 1
-    db.reads = C.cast(reads, C.POINTER(api.HITS_READ))
-    db._keep = (buf, reads)
-    return db
+    return la_shapes.make_db([rng.randint(0, 4, int(n)).astype(np.uint8) for n in lens])
 
 
 def _lens_with_kmers(k, want, first):
