@@ -145,6 +145,8 @@ def _lib():
         L.damar_match_self.argtypes = [C.POINTER(HITS_DB), C.c_void_p, C.c_void_p, C.POINTER(c_int64)]
         L.damar_last_seeds.argtypes = [C.c_void_p, c_int64]
         L.damar_last_seeds.restype = c_int64
+        L.damar_order_runs_test.argtypes = [C.c_void_p, c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        L.damar_order_runs_test.restype = C.c_int
         L.damar_local_alignment_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                   C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int),
                                                   C.POINTER(c_int64), C.POINTER(C.c_uint16), c_int64]
@@ -241,6 +243,18 @@ def counters():
     a = (c_int64 * 8)()
     L.damar_last_counters(a)
     return list(a)
+
+
+def order_runs(keys, ppos, dbits, work):
+    """The ordering step of the seed sort over the read pair only, alone (test hook damar_order_runs_test): a copy of the
+    uint64 array `keys` with the runs whose heads `work` lists in order of their A positions."""
+    import numpy as np
+    L = _lib()
+    k = np.ascontiguousarray(keys, dtype=np.uint64).copy()
+    w = np.ascontiguousarray(work, dtype=np.uint32)
+    if L.damar_order_runs_test(k.ctypes.data, len(k), ppos, dbits, w.ctypes.data, len(w)) != 0:
+        raise RuntimeError("damar_order_runs_test failed")
+    return k
 
 
 def last_slabs():

@@ -248,8 +248,10 @@ void damar_launch_pair_heads(const u64 *keys, u64 nhits, u64 off, u64 gtotal, in
 void damar_launch_pair_work(u64 *keys, const u32 *vals, u64 nhits, u64 off, u64 gtotal, int ppos, int dbits, int abits, int minhit, int nshift,
                             u64 *send /* 64 entries of scratch */, u64 *bits, void *scan_work, u64 *total_dev /* [2] */,
                             int binshift, int kmer, int hitmin, u32 b_lo, u32 b_hi, int unsorted, hipStream_t st);
-/* (unsorted only) the runs of the work list's heads into the order of their A positions, in place */
-void damar_launch_order_runs(u64 *keys, u64 nhits, int ppos, int dbits, const u32 *work, u32 nwork, hipStream_t st);
+/* (unsorted only) the runs of the work list's heads (ascending) into the order of their A positions, in place; runs of more
+   than 2048 seeds are left as they are.  scratch: damar_order_runs_scratch_bytes(nhits) */
+size_t damar_order_runs_scratch_bytes(u64 nhits);
+void damar_launch_order_runs(u64 *keys, u64 nhits, int ppos, int dbits, const u32 *work, u32 nwork, void *scratch, hipStream_t st);
 void damar_launch_pair_work_expand(const u64 *bits, const void *scan_work, u64 nhits, u32 *work, hipStream_t st);
 #define WORK_COST_BITS 16
 #define WORK_COST_MAX  ((1u << WORK_COST_BITS) - 1)

@@ -1628,15 +1628,24 @@ void pair_work_mark(const u64 *__restrict__ keys, const u32 *__restrict__ vals, 
 
 /* The seed sort over the read pair only (4 passes instead of 6: 28 of the 43 key bits) leaves the seeds of a pair in index
  * order; only the runs the report kernel will walk -- the kept heads' -- have to be in order of their A positions, ties in
- * the order they have (what the stable sort over all the bits leaves).  order_sort, one workgroup per work item once the
- * work list exists (the rule of shim.hip match_front turns this on where the kept runs are few and long): the run's length (the lanes probe 64 seeds at a time), the run into LDS, a bitonic sort of
- * (A position << 11 | place in the run) -- a strict order, so any sort is the stable one -- and the run back where it was.
- * order_probe, before the host reads the number of work items: is any kept head's run longer than a wavefront sorts in
- * LDS (OR_MAX)?  Then the caller sorts that comparison over all the bits after all. */
-#define OR_MAX 2048
-__device__ __forceinline__ u32 run_length(const u64 *__restrict__ keys, u64 nhits, u64 i, int pshift, u32 maxrun, int l)
-{ const u64 pr = keys[i] >> pshift;
-  u32 n = 0;
+ * the order they have (what the stable sort over all the bits leaves).  What is sorted is (A position << 11 | place in the
+ * run): the place makes the order strict, no two keys are equal, so ANY correct sorting network gives the one order the
+ * stable sort gives.  The work is scheduled by the length of the run (profiles/order_runs.txt has the lengths):
+ *   order_waves   a workgroup takes a slice of consecutive work items (up to OR_SLICE; fewer where the list is short, so that
+ *                 the wavefronts of a few hundred long runs spread over the chip), a wavefront one run at a time.  The wavefront finds the
+ *                 run's length (once: 64 probes at a time, the first probe's keys are the run itself where it has up to 64
+ *                 seeds) and sorts runs of up to OR_WAVE seeds in its registers, K = 1, 2, 4 or 8 keys a lane: a bitonic
+ *                 network over index q * 64 + lane, the partner of a step in another lane (DPP, ds_swizzle, ds_bpermute)
+ *                 or in another register of the same lane.  No LDS, no barrier.  Longer runs go to a list with their length.
+ *   order_long    that list, a workgroup per run of OR_WAVE + 1 .. OR_MAX seeds, in LDS.
+ * order_probe, before the host reads the number of work items: is any kept head's run longer than OR_MAX?  Then the caller
+ * sorts that comparison over all the bits after all. */
+#define OR_MAX   2048
+#define OR_WAVE  512                                     /* the longest run a wavefront sorts in its registers (8 keys a lane) */
+#define OR_SLICE 32                                      /* work items per workgroup of order_waves, at most */
+/* seeds from i on that belong to read pair pr, counted 64 at a time by a wavefront: more than maxrun means "too many" */
+__device__ __forceinline__ u32 run_length(const u64 *keys, u64 nhits, u64 i, int pshift, u32 maxrun, int l, u64 pr)
+{ u32 n = 0;
   for (;;)                                                    /* 64 probes at a time */
     { const u64 x = i + (u64) n + (u64) l;
       const u64 same = __ballot(x < nhits && (keys[x] >> pshift) == pr);
@@ -1671,56 +1680,228 @@ void order_probe(const u64 *__restrict__ keys, u64 nhits, int ppos, int dbits, c
   const u32 n_h = nh;
   bool over = false;
   for (u32 h = threadIdx.x >> 6; h < n_h; h += 4)             /* a wavefront per kept head */
-    over |= run_length(keys, nhits, base + hl[h], ppos + dbits, maxrun, l) > maxrun;
+    { const u64 i = base + hl[h];
+      over |= run_length(keys, nhits, i, ppos + dbits, maxrun, l, keys[i] >> (ppos + dbits)) > maxrun;
+    }
   if (over && l == 0)
     atomicOr((unsigned long long *) flag, 1ull);
 }
 
+/* the value of lane (l ^ J) */
+template <u32 J>
+__device__ __forceinline__ u32 lane_xor(u32 v)
+{ if constexpr (J == 1)
+    return (u32) __builtin_amdgcn_update_dpp(0, (int) v, 0xB1, 0xf, 0xf, true);        /* quad_perm:[1,0,3,2] */
+  else if constexpr (J == 2)
+    return (u32) __builtin_amdgcn_update_dpp(0, (int) v, 0x4E, 0xf, 0xf, true);        /* quad_perm:[2,3,0,1] */
+  else if constexpr (J == 8)
+    return (u32) __builtin_amdgcn_update_dpp(0, (int) v, 0x128, 0xf, 0xf, true);       /* row_ror:8 */
+  else if constexpr (J == 4 || J == 16)
+    return (u32) __builtin_amdgcn_ds_swizzle((int) v, (int) (0x1f | (J << 10)));       /* bit mode: and 0x1f, xor J */
+  else
+    return (u32) __shfl_xor((int) v, (int) J);
+}
+
+/* one step of the network: index x = q * 64 + lane against x ^ JJ, ascending where (x & K2) == 0 */
+template <int K, u32 K2, u32 JJ>
+__device__ __forceinline__ void or_step(u32 (&c)[K], int l)
+{ if constexpr (JJ >= 64)
+    {
+#pragma unroll
+      for (int q = 0; q < K; q++)
+        if ((q & (int) (JJ >> 6)) == 0)
+          { const int  p  = q | (int) (JJ >> 6);
+            const bool up = (((u32) q << 6) & K2) == 0;
+            const u32  lo = min(c[q], c[p]), hi = max(c[q], c[p]);
+            c[q] = up ? lo : hi;
+            c[p] = up ? hi : lo;
+          }
+    }
+  else
+    {
+#pragma unroll
+      for (int q = 0; q < K; q++)
+        { const u32  o  = lane_xor<JJ>(c[q]);
+          const bool up = (((u32) q * 64u + (u32) l) & K2) == 0;
+          c[q] = (up == (((u32) l & JJ) == 0)) ? min(c[q], o) : max(c[q], o);
+        }
+    }
+}
+
+template <int K, u32 K2, u32 JJ>
+__device__ __forceinline__ void or_merge(u32 (&c)[K], int l)
+{ or_step<K, K2, JJ>(c, l);
+  if constexpr (JJ > 1)
+    or_merge<K, K2, JJ / 2>(c, l);
+}
+
+template <int K, u32 K2>
+__device__ __forceinline__ void or_network(u32 (&c)[K], int l)
+{ if constexpr (K2 > 2)
+    or_network<K, K2 / 2>(c, l);
+  or_merge<K, K2, K2 / 2>(c, l);
+}
+
+/* a run of 65 .. 64 K seeds, K keys a lane: the sorted keys' seeds are read again where they lie (they are in the cache) and
+   all of them have arrived before the first is written */
+template <int K>
+__device__ __forceinline__ void or_sort_regs(u64 *keys, u64 i, u32 n, int dbits, u64 pmask, int l)
+{ u32 c[K];
+#pragma unroll
+  for (int q = 0; q < K; q++)
+    { const u32 j = (u32) q * 64u + (u32) l;
+      c[q] = (j < n) ? (((u32) ((keys[i + j] >> dbits) & pmask) << 11) | j) : 0xffffffffu;
+    }
+  or_network<K, 64u * K>(c, l);
+  u64 v[K];
+#pragma unroll
+  for (int q = 0; q < K; q++)
+    { const u32 j = (u32) q * 64u + (u32) l;
+      v[q] = keys[i + ((j < n) ? (c[q] & 2047u) : 0u)];
+    }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+  for (int q = 0; q < K; q++)
+    { const u32 j = (u32) q * 64u + (u32) l;
+      if (j < n)
+        keys[i + j] = v[q];
+    }
+}
+
+#ifdef OR_STATS                                          /* scripts/order_runs_stats.sh: the lengths of the kept runs */
+static __device__ unsigned long long g_or_hist[16];      /* [b]: runs of up to 2 << b seeds, [12]: longer, [13]: seeds in all */
+#endif
+
 __global__ __launch_bounds__(256)
-void order_sort(u64 *__restrict__ keys, u64 nhits, int ppos, int dbits, const u32 *__restrict__ work, u32 nwork)
+void order_waves(u64 *keys, u64 nhits, int ppos, int dbits, const u32 *__restrict__ work, u32 nwork, u32 slice,
+                 u32 *__restrict__ lcount, u32 *__restrict__ llist)
+{ SEED_PRIO(g_merge_prio);
+  const int  l = lane_id(), pshift = ppos + dbits;
+  const u64  pmask = (1ull << ppos) - 1;
+  const u32  first = blockIdx.x * slice;
+  const u32  end = min(first + slice, nwork);
+  for (u32 t = first + (threadIdx.x >> 6); t < end; t += 4)
+    { const u64 i = work[t];
+      const u64 x = i + (u64) l;
+      const u64 k0 = keys[x < nhits ? x : nhits - 1];
+      const u64 pr = (u64) __shfl((long long) (k0 >> pshift), 0);
+      const u64 same = __ballot(x < nhits && (k0 >> pshift) == pr);
+      u32 n;
+      if (same != ~0ull)
+        n = (u32) __ffsll((long long) ~same) - 1u;
+      else
+        n = 64u + run_length(keys, nhits, i + 64u, pshift, OR_MAX - 64u, l, pr);
+#ifdef OR_STATS
+      if (l == 0)
+        { int b = 0;
+          while (b < 12 && (2u << b) < n) b += 1;
+          atomicAdd(&g_or_hist[n > OR_MAX ? 12 : b], 1ull);
+          atomicAdd(&g_or_hist[13], (unsigned long long) n);
+        }
+#endif
+      if (n < 2)
+        continue;
+      if (n <= 64)                                       /* the probe's keys are the run: sorted, each fetched from its lane */
+        { u32 c[1] = { (u32) l < n ? (((u32) ((k0 >> dbits) & pmask) << 11) | (u32) l) : 0xffffffffu };
+          or_network<1, 64u>(c, l);
+          const int src = (int) (c[0] & 63u);
+          const u32 lo = (u32) __shfl((int) (u32) k0, src), hi = (u32) __shfl((int) (u32) (k0 >> 32), src);
+          if ((u32) l < n)
+            keys[x] = ((u64) hi << 32) | lo;
+        }
+      else if (n <= 128)
+        or_sort_regs<2>(keys, i, n, dbits, pmask, l);
+      else if (n <= 256)
+        or_sort_regs<4>(keys, i, n, dbits, pmask, l);
+      else if (n <= OR_WAVE)
+        or_sort_regs<8>(keys, i, n, dbits, pmask, l);
+      else if (n <= OR_MAX && l == 0)                    /* (longer: order_probe has sent the comparison the other way) */
+        { const u32 at = atomicAdd(lcount, 1u);
+          llist[2 * at] = (u32) i;
+          llist[2 * at + 1] = n;
+        }
+    }
+}
+
+/* the runs of OR_WAVE + 1 .. OR_MAX seeds: llist[2 b], llist[2 b + 1] = the head and the length of run b */
+__global__ __launch_bounds__(256)
+void order_long(u64 *keys, int ppos, int dbits, const u32 *__restrict__ lcount, const u32 *__restrict__ llist)
 { SEED_PRIO(g_merge_prio);
   __shared__ u64 rk[OR_MAX];
   __shared__ u32 ck[OR_MAX];
-  const int  l = lane_id();                                  /* (every wavefront finds the run's length for itself) */
   const u64  pmask = (1ull << ppos) - 1;
-  if (blockIdx.x >= nwork)
-    return;
-  const u64 i = work[blockIdx.x];
-  const u32 n = run_length(keys, nhits, i, ppos + dbits, OR_MAX, l);
-  if (n < 2 || n > OR_MAX)                                   /* (longer: order_probe has sent the comparison the other way) */
-    return;
-  u32 P = 2;
-  while (P < n)
-    P <<= 1;
-  for (u32 j = threadIdx.x; j < P; j += 256)
-    { if (j < n)
-        { const u64 k = keys[i + j];
-          rk[j] = k;
-          ck[j] = ((u32) ((k >> dbits) & pmask) << 11) | j;
+  const u32  nl = *lcount;
+  for (u32 b = blockIdx.x; b < nl; b += gridDim.x)
+    { const u64 i = llist[2 * b];
+      const u32 n = llist[2 * b + 1];
+      u32 P = 2;
+      while (P < n)
+        P <<= 1;
+      for (u32 j = threadIdx.x; j < P; j += 256)
+        { if (j < n)
+            { const u64 k = keys[i + j];
+              rk[j] = k;
+              ck[j] = ((u32) ((k >> dbits) & pmask) << 11) | j;
+            }
+          else
+            ck[j] = 0xffffffffu;
         }
-      else
-        ck[j] = 0xffffffffu;
-    }
-  __syncthreads();
-  for (u32 k2 = 2; k2 <= P; k2 <<= 1)
-    for (u32 jj = k2 >> 1; jj > 0; jj >>= 1)
-      { for (u32 t = threadIdx.x; t < (P >> 1); t += 256)
-          { const u32 ix = ((t & ~(jj - 1)) << 1) | (t & (jj - 1)), px = ix | jj;
-            const bool up = (ix & k2) == 0;
-            const u32 a = ck[ix], c = ck[px];
-            if ((a > c) == up)
-              { ck[ix] = c;  ck[px] = a; }
+      __syncthreads();
+      for (u32 k2 = 2; k2 <= P; k2 <<= 1)
+        for (u32 jj = k2 >> 1; jj > 0; jj >>= 1)
+          { for (u32 t = threadIdx.x; t < (P >> 1); t += 256)
+              { const u32 ix = ((t & ~(jj - 1)) << 1) | (t & (jj - 1)), px = ix | jj;
+                const bool up = (ix & k2) == 0;
+                const u32 a = ck[ix], c = ck[px];
+                if ((a > c) == up)
+                  { ck[ix] = c;  ck[px] = a; }
+              }
+            __syncthreads();
           }
-        __syncthreads();
-      }
-  for (u32 j = threadIdx.x; j < n; j += 256)
-    keys[i + j] = rk[ck[j] & 2047u];
+      for (u32 j = threadIdx.x; j < n; j += 256)
+        keys[i + j] = rk[ck[j] & 2047u];
+      __syncthreads();                                   /* (the next run's seeds go where these lie) */
+    }
 }
 
-void damar_launch_order_runs(u64 *keys, u64 nhits, int ppos, int dbits, const u32 *work, u32 nwork, hipStream_t st)
+size_t damar_order_runs_scratch_bytes(u64 nhits)
+{ return sizeof(u32) * (size_t) (2 * (nhits / (OR_WAVE + 1)) + 2); }
+
+#ifdef OR_STATS
+static void or_stats_print(void)
+{ unsigned long long h[16];
+  if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_or_hist), sizeof(h)) != hipSuccess)
+    return;
+  unsigned long long runs = 0;
+  for (int b = 0; b <= 12; b++)
+    runs += h[b];
+  fprintf(stderr, "order_runs: %llu kept runs, %llu seeds in them\n", runs, h[13]);
+  for (int b = 0; b <= 12; b++)
+    if (h[b])
+      fprintf(stderr, "  runs of %5d..%-5d %9llu  (%.3f %%)\n", b == 0 ? 1 : (1 << b) + 1, b == 12 ? 1 << 30 : 2 << b, h[b], 100. * h[b] / runs);
+}
+#endif
+
+/* scratch: damar_order_runs_scratch_bytes(nhits), the count and the list of the runs a workgroup sorts */
+void damar_launch_order_runs(u64 *keys, u64 nhits, int ppos, int dbits, const u32 *work, u32 nwork, void *scratch, hipStream_t st)
 { if (nwork == 0)
     return;
-  hipLaunchKernelGGL(order_sort, dim3(nwork), dim3(256), 0, st, keys, nhits, ppos, dbits, work, nwork);
+#ifdef OR_STATS
+  static int reg = 0;
+  if (!reg)
+    { reg = 1;  atexit(or_stats_print); }
+#endif
+  u32 *lcount = (u32 *) scratch;
+  HIP_CHECK(hipMemsetAsync(lcount, 0, sizeof(u32), st));
+  /* a run per wavefront while that leaves wavefronts idle (4 a workgroup, 2048 on the chip), up to OR_SLICE / 4 then */
+  const u32 slice = std::min<u32>(OR_SLICE, 4u * std::max<u32>(1u, nwork / 2048u));
+  hipLaunchKernelGGL(order_waves, dim3((nwork + slice - 1) / slice), dim3(256), 0, st, keys, nhits, ppos, dbits, work, nwork, slice,
+                     lcount, lcount + 2);
+  if (nhits > OR_WAVE)
+    { const u64 most = nhits / (OR_WAVE + 1);
+      hipLaunchKernelGGL(order_long, dim3((u32) std::min<u64>(std::min<u64>(nwork, most), 1024)), dim3(256), 0, st, keys, ppos, dbits,
+                         (const u32 *) lcount, (const u32 *) (lcount + 2));
+    }
 }
 
 /* first half: bit words + *total_dev = the number of work items; the caller reads the total, makes room, and calls the

@@ -2298,26 +2298,21 @@ static int match_front(damar_match_job *job, int slot, Front *f, int slab)
      pair then lie in index order; the screen of the run heads takes them in any order and the runs of the kept heads -- all
      the report kernel walks -- are put in order of their A positions where they lie (kernels/seed_merge.hip order_runs).
      Not when something else reads the seeds (the tests' seed list, the two-step work list), not for the unpacked layout.
-     It pays where the seed stages are the longer side: first 300 block pairs of config 4 1.17 -> 1.11 s; config 2 gains
-     nothing (its two passes ran in the shadow of the report kernel) and config 3 loses 4 % (ordering 9 500 runs of a few
-     hundred seeds beside a report kernel that is the longer side there) -- so, like the report launch's shape (report_launch),
-     it goes by the seed pairs per work item of the comparison before this one: more than DAMAR_ADAPT_RATIO (4 000).
-     DAMAR_SORT_PAIR=0: never (the sort over all the bits, rounds 1-6), 1: always (both tested). */
+     The ordering goes by the length of a run (a wavefront's registers up to 512 seeds, a workgroup beyond), which made
+     it cheap enough to be on for every shape -- profiles/order_runs.txt has config 2, config 3 and config 4's lead both
+     ways; until then a rule by the seed pairs per work item kept it to config 4's shape.
+     DAMAR_SORT_PAIR=0: never (the sort over all the bits, rounds 1-6), 1 or unset: always (both tested). */
   static int pair_sort = -1;
-  static long long pair_ratio = 4000;
-  static u64 prev_seeds = 0, prev_work = 1;              /* of the comparison before this one */
   if (pair_sort < 0)
-    { const char *e = getenv("DAMAR_SORT_PAIR"), *r = getenv("DAMAR_ADAPT_RATIO");
-      pair_sort = e ? atoi(e) : 2;
-      if (r)
-        pair_ratio = atoll(r);
+    { const char *e = getenv("DAMAR_SORT_PAIR");
+      pair_sort = e ? atoi(e) : 1;
     }
-  const bool pair_on = pair_sort == 1 || (pair_sort == 2 && pair_ratio > 0 && prev_seeds / prev_work > (u64) pair_ratio);
+  const bool pair_on = pair_sort != 0;
   bool psort = pair_on && !cut && !two_step && !G_keep_seeds && m.dbits != 0 && m.pbits + 11 <= 32 && m.pbits >= 8;
   const int spasses_used = psort ? (sbits - m.pbits + 7) / 8 : spasses;
   u64 *keys, *tk;
   u32 *vals, *flags, *foff;
-  void *scw2, *resort_ws = NULL;
+  void *scw2, *resort_ws = NULL, *order_ws = NULL;
   u64 *sends;
   int  hshift = P_nshift;                                     /* slices of the reference's threads in the head test */
   if (!cut)
@@ -2335,6 +2330,8 @@ static int match_front(damar_match_job *job, int slot, Front *f, int slab)
       foff  = (u32 *) arena_take(&G_tmp, std::max(sizeof(u32) * (size_t) total, bit_words_bytes(total)));   /* (also the heads' bit words) */
       scw2  = arena_take(&G_tmp, damar_scan_workspace_bytes(total));
       sends = (u64 *) arena_take(&G_tmp, 64 * sizeof(u64));
+      if (psort)                                             /* (in the room of tv: the packed layout has no values) */
+        order_ws = arena_take(&G_tmp, damar_order_runs_scratch_bytes(total));
 
       damar_launch_merge_emit(&m, mw, total, k0, v0, NULL, G_st);
       stage("merge_emit");
@@ -2461,7 +2458,7 @@ static int match_front(damar_match_job *job, int slot, Front *f, int slab)
       if (nwork64 > 0)
         { damar_launch_pair_work_expand((const u64 *) foff, scw2, total, work, G_st);
           if (psort)                                       /* the runs the report kernel will walk, in the order of their A positions */
-            damar_launch_order_runs(keys, total, m.pbits, m.dbits, work, (u32) nwork64, G_st);
+            damar_launch_order_runs(keys, total, m.pbits, m.dbits, work, (u32) nwork64, order_ws, G_st);
         }
       stage("work_list");
     }
@@ -2497,7 +2494,6 @@ static int match_front(damar_match_job *job, int slot, Front *f, int slab)
   G_ms[DAMAR_T_WORK]  += lap(2, 3);
   G_cnt[0] += nhits;  G_cnt[1] += nwork;
   job->counts[0] += nhits;
-  prev_seeds = total;  prev_work = nwork > 0 ? nwork : 1;
 
   if (G_keep_seeds)
     { const size_t at = slab >= 0 ? G_seed_keys.size() : 0;     /* (a slab's seeds behind those of the slabs before it: damar_match_batch clears) */
@@ -3427,6 +3423,28 @@ extern "C" int damar_last_slabs(int *b_lo, int64 *hits, int cap)
 /* of the last damar_match / damar_match_batch: seed stages run (slabs, summed over its comparisons), comparisons split */
 extern "C" void damar_slab_totals(int64 *out)
 { out[0] = G_slab_tot[0];  out[1] = G_slab_tot[1]; }
+
+/* Test hook: the ordering of the kept runs alone (kernels/seed_merge.hip damar_launch_order_runs) on a caller's packed seeds:
+   keys[0 .. nhits) in place, work[0 .. nwork) = the heads of the runs to order, ascending.  Returns 0. */
+extern "C" int damar_order_runs_test(uint64 *keys, int64 nhits, int ppos, int dbits, const uint32 *work, int nwork)
+{ finish_all();
+  ensure_init();
+  if (nhits <= 0 || nwork <= 0)
+    return 0;
+  u64  *dk;
+  u32  *dw;
+  void *sc;
+  HIP_CHECK(hipMalloc((void **) &dk, sizeof(u64) * (size_t) nhits));
+  HIP_CHECK(hipMalloc((void **) &dw, sizeof(u32) * (size_t) nwork));
+  HIP_CHECK(hipMalloc(&sc, damar_order_runs_scratch_bytes((u64) nhits)));
+  HIP_CHECK(hipMemcpy(dk, keys, sizeof(u64) * (size_t) nhits, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(dw, work, sizeof(u32) * (size_t) nwork, hipMemcpyHostToDevice));
+  damar_launch_order_runs(dk, (u64) nhits, ppos, dbits, dw, (u32) nwork, sc, G_st);
+  HIP_CHECK(hipStreamSynchronize(G_st));
+  HIP_CHECK(hipMemcpy(keys, dk, sizeof(u64) * (size_t) nhits, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipFree(dk));  HIP_CHECK(hipFree(dw));  HIP_CHECK(hipFree(sc));
+  return 0;
+}
 
 extern "C" int64 damar_last_seeds(void *out, int64 cap)
 { struct SP { int diag, apos, aread, bread; } *sp = (SP *) out;

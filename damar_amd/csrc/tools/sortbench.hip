@@ -9,9 +9,14 @@
  *   sortbench index [reps]   the packed k-mer index of one config-2 block (135 Mbp of 10 kb reads, k = 14) both ways:
  *                            kmer_tuples + sort over its keys, and the sort that makes its keys (KmerKeys); ms and bytes
  *                            moved.  Both results are compared first, there and on a block of reads of k - 1 .. k + 6 bases.
+ *   sortbench order [reps]   the ordering of the kept runs behind the seed sort over the read pair only (kernels/seed_merge.hip
+ *                            damar_launch_order_runs) against the one it replaced, a workgroup per run: 45 000 runs of 8 seeds,
+ *                            of 100, and a mix with a tail up to 2048; both checked against std::stable_sort; ms and runs per second
  */
 #include "../kernels/radix_sort.hip"
 #include "../kernels/kmer_index.hip"
+#include "../kernels/sort_scan.hip"          /* (the scans seed_merge.hip's launchers call) */
+#include "../kernels/seed_merge.hip"
 #include <vector>
 #include <algorithm>
 #include <numeric>
@@ -269,9 +274,116 @@ static int do_index(int reps)
   return 0;
 }
 
+/* the ordering before order_waves / order_long, for the comparison: a workgroup of 256 threads per work item whatever its
+   length, every wavefront finds the length for itself, the sort in LDS with a barrier per step */
+__global__ __launch_bounds__(256)
+void order_sort_old(u64 *__restrict__ keys, u64 nhits, int ppos, int dbits, const u32 *__restrict__ work, u32 nwork)
+{ __shared__ u64 rk[OR_MAX];
+  __shared__ u32 ck[OR_MAX];
+  const int  l = lane_id();
+  const u64  pmask = (1ull << ppos) - 1;
+  if (blockIdx.x >= nwork)
+    return;
+  const u64 i = work[blockIdx.x];
+  const u32 n = run_length(keys, nhits, i, ppos + dbits, OR_MAX, l, keys[i] >> (ppos + dbits));
+  if (n < 2 || n > OR_MAX)
+    return;
+  u32 P = 2;
+  while (P < n)
+    P <<= 1;
+  for (u32 j = threadIdx.x; j < P; j += 256)
+    { if (j < n)
+        { const u64 k = keys[i + j];
+          rk[j] = k;
+          ck[j] = ((u32) ((k >> dbits) & pmask) << 11) | j;
+        }
+      else
+        ck[j] = 0xffffffffu;
+    }
+  __syncthreads();
+  for (u32 k2 = 2; k2 <= P; k2 <<= 1)
+    for (u32 jj = k2 >> 1; jj > 0; jj >>= 1)
+      { for (u32 t = threadIdx.x; t < (P >> 1); t += 256)
+          { const u32 ix = ((t & ~(jj - 1)) << 1) | (t & (jj - 1)), px = ix | jj;
+            const bool up = (ix & k2) == 0;
+            const u32 a = ck[ix], c = ck[px];
+            if ((a > c) == up)
+              { ck[ix] = c;  ck[px] = a; }
+          }
+        __syncthreads();
+      }
+  for (u32 j = threadIdx.x; j < n; j += 256)
+    keys[i + j] = rk[ck[j] & 2047u];
+}
+
+/* shape 0: runs of 8 seeds, 1: of 100, 2: 80 % of 4 .. 64, 19 % of 65 .. 512, 1 % of 513 .. 2048 */
+static int order_shape(int shape, int reps)
+{ const int ppos = 15, dbits = 15;
+  const u32 nruns = 45000;
+  std::vector<u64> hk;
+  std::vector<u32> hw(nruns);
+  for (u32 r = 0; r < nruns; r++)
+    { u32 n = shape == 0 ? 8 : 100;
+      if (shape == 2)
+        { const u32 x = (u32) (rnd() % 100);
+          n = x < 80 ? 4 + (u32) (rnd() % 61) : (x < 99 ? 65 + (u32) (rnd() % 448) : 513 + (u32) (rnd() % 1536));
+          if (r == 7) n = 2048;
+        }
+      hw[r] = (u32) hk.size();
+      for (u32 j = 0; j < n; j++)
+        hk.push_back(((u64) r << (ppos + dbits)) | (rnd() & ((1ull << (ppos + dbits)) - 1)));
+    }
+  const u64 nhits = hk.size();
+  std::vector<u64> want(hk);
+  for (u32 r = 0; r < nruns; r++)
+    std::stable_sort(want.begin() + hw[r], want.begin() + (r + 1 < nruns ? hw[r + 1] : nhits),
+                     [&](u64 a, u64 b) { return ((a >> dbits) & 0x7fff) < ((b >> dbits) & 0x7fff); });
+  u64 *src = dev<u64>(nhits), *k = dev<u64>(nhits);
+  u32 *w = dev<u32>(nruns);
+  void *sc = dev<char>(damar_order_runs_scratch_bytes(nhits));
+  HIP_CHECK(hipMemcpy(src, hk.data(), 8 * nhits, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(w, hw.data(), 4 * nruns, hipMemcpyHostToDevice));
+  hipEvent_t e0, e1;
+  hipEventCreate(&e0); hipEventCreate(&e1);
+  const char *shapes[3] = { "runs of 8", "runs of 100", "mixed, tail to 2048" };
+  int bad = 0;
+  for (int way = 0; way < 2 && !bad; way++)
+    { double tot = 0;
+      for (int r = 0; r < reps + 1; r++)
+        { HIP_CHECK(hipMemcpyAsync(k, src, 8 * nhits, hipMemcpyDeviceToDevice, 0));
+          hipEventRecord(e0, 0);
+          if (way == 0)
+            hipLaunchKernelGGL(order_sort_old, dim3(nruns), dim3(256), 0, 0, k, nhits, ppos, dbits, (const u32 *) w, nruns);
+          else
+            damar_launch_order_runs(k, nhits, ppos, dbits, w, nruns, sc, 0);
+          hipEventRecord(e1, 0);
+          HIP_CHECK(hipEventSynchronize(e1));
+          float t; hipEventElapsedTime(&t, e0, e1);
+          if (r > 0) tot += t;
+        }
+      std::vector<u64> got(nhits);
+      HIP_CHECK(hipMemcpy(got.data(), k, 8 * nhits, hipMemcpyDeviceToHost));
+      bad = memcmp(got.data(), want.data(), 8 * nhits) != 0;
+      const double ms = reps > 0 ? tot / reps : 0;
+      printf("order %-20s %5u runs, %8llu seeds  %-22s %7.3f ms  %7.1f M runs/s%s\n", shapes[shape], nruns, (unsigned long long) nhits,
+             way ? "order_waves+order_long" : "workgroup per run", ms, ms > 0 ? nruns / ms * 1e-3 : 0., bad ? "  WRONG ORDER" : "");
+    }
+  hipFree(src); hipFree(k); hipFree(w); hipFree(sc);
+  return bad;
+}
+
+static int do_order(int reps)
+{ int bad = 0;
+  for (int shape = 0; shape < 3; shape++)
+    bad |= order_shape(shape, reps);
+  return bad;
+}
+
 int main(int argc, char **argv)
 { if (argc > 1 && strcmp(argv[1], "check") == 0)
     return do_check();
+  if (argc > 1 && strcmp(argv[1], "order") == 0)
+    return do_order(argc > 2 ? atoi(argv[2]) : 20);
   if (argc > 1 && strcmp(argv[1], "index") == 0)
     return do_index(argc > 2 ? atoi(argv[2]) : 10);
   const int reps = argc > 2 ? atoi(argv[2]) : 10;

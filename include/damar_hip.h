@@ -140,6 +140,12 @@ void Match_Self(char *aname, HITS_DB *ablock, Align_Spec *settings);
  * Returns the number of seed pairs; copies at most `cap` records. */
 int64 damar_last_seeds(void *out, int64 cap);
 
+/* Test hook: the ordering step of the seed sort over the read pair only, on its own.  keys[0 .. nhits) are packed seeds
+ * (read pair | A position of ppos bits | dbits low bits), work[0 .. nwork) the ascending indices of run heads: every
+ * listed run (the seeds from its head on with the head's read pair) of up to 2048 seeds is put in order of its A positions
+ * in place, equal positions in the order they had; everything else is left as it is.  Returns 0. */
+int damar_order_runs_test(uint64 *keys, int64 nhits, int ppos, int dbits, const uint32 *work, int nwork);
+
 /* A comparison with more seed pairs than one seed stage holds -- the 32-bit seed index, or what the seed arrays can be
  * grown to in the device memory that is free -- is run in SLABS, consecutive ranges of B reads cut greedily: a slab takes
  * B reads while its seed pairs stay within that figure, and at least one.  Records, counts and damar_last_seeds are those
