@@ -1055,9 +1055,6 @@ struct ReportScratch
 };
 static ReportScratch RS = {};   /* (nslots_wanted: the slot count asked for when nslots was last sized) */
 
-static bool overlap_on(void);
-static bool corun_on(void);
-
 static int default_slots(void)
 { const char *e = getenv("DAMAR_SLOTS");
   if (e && atoi(e) > 0)
@@ -1977,32 +1974,250 @@ extern "C" int damar_slab_cut(const uint64_t *hits, int nreads, uint64_t cap, in
   return n;
 }
 
-/* What the seed stage of `n` seed pairs reserves: in the comparison's own arena, in the shared one, and -- with the early
-   cut, whose survivors are at most n -- in the shared arenas of the cut.  match_front reserves by these expressions, and
-   the number of seed pairs a seed stage can hold (seed_cap) is derived from them. */
-static size_t front_hits_bytes(u64 n)
-{ return pad256(sizeof(u64) * (size_t) n) + pad256(sizeof(u32) * (size_t) n) + 4096; }
-static size_t front_tmp_bytes(u64 n)
-{ return pad256(sizeof(u64) * (size_t) n) + 3 * pad256(sizeof(u32) * (size_t) n) +
-         pad256(damar_sort_workspace_bytes(n)) + pad256(damar_scan_workspace_bytes(n)) + 8192;
+/* What the seed stage of one comparison leaves on the device for the report launch. */
+struct Front
+{ const u64 *keys;  const u32 *vals;  u64 total;
+  const u32 *work;  u32 nwork;
+  const u32 *order;
+  int pbits, abits, dbits;
+  JobParams jp;                 /* parameters and options of the moment the seed stage ran */
+  size_t bytes;                 /* of the two arenas that hold the above */
+  double t_entry;
+};
+
+/* The switches of the seed stage.  Read from the environment once per process, by the first seed stage (front_opts). */
+struct FrontOpts
+{ int pack_seeds;   /* DAMAR_PACK_SEEDS (1): a seed is ONE u64 when position-in-B fits beside the sort key; 0 forces the
+                       diagonal into a second array (front_setup) */
+  int early_cut;    /* DAMAR_EARLY_CUT (0).  Measured on config 2: 38 % of the seed pairs belong to read pairs with >= 3 seeds
+                       (76.4 M seeds, 42.9 M read pairs, 5.8 M of them with >= 3), so the cut saves 3.7 of the 6 sort passes
+                       but costs a 4-pass sort of the pair ids and two more passes over the seeds: merge + sort + work list
+                       203 -> 209 ms per step.  Off unless asked for; with a B-read range (a pair split over GPUs) it keeps
+                       only that range's seeds. */
+  int two_step;     /* DAMAR_WORK_TWOSTEP (0): 1 = heads, then their screen (rounds 1-5; tested) */
+  int pair_sort;    /* DAMAR_SORT_PAIR (1): 0 = never sort over the read pair only (the sort over all the bits, rounds 1-6),
+                       1 or unset: always (both tested; front_setup has the rule) */
+  int order_mode;   /* DAMAR_ORDER (11): 0 = reference order, 1 = most seeds first, 2 = size classes, 9 = longest seed extent
+                       first, 10 = longest geometric overlap first, 11 = the larger of the two (default: 356 ms of report
+                       kernel per config-2 step against 370 for 1, 361 for 9, 411 for 10), other n = runs of >= n seeds first */
+};
+static const FrontOpts &front_opts(void)
+{ static FrontOpts o;
+  static bool filled = false;
+  if (!filled)
+    { const char *e;
+      o.pack_seeds = (e = getenv("DAMAR_PACK_SEEDS")) ? atoi(e) : 1;
+      o.early_cut  = (e = getenv("DAMAR_EARLY_CUT")) ? atoi(e) : 0;
+      o.two_step   = ((e = getenv("DAMAR_WORK_TWOSTEP")) && atoi(e) > 0) ? 1 : 0;
+      o.pair_sort  = (e = getenv("DAMAR_SORT_PAIR")) ? atoi(e) : 1;
+      o.order_mode = (e = getenv("DAMAR_ORDER")) ? atoi(e) : 11;
+      filled = true;
+    }
+  return o;
 }
-static size_t front_cut_bytes(u64 n, int minhit, size_t bmwords)
-{ return pad256(sizeof(u64) * (size_t) n) + 4 * pad256(sizeof(u32) * (size_t) n) +
-         pad256(sizeof(u32) * ((size_t) n / minhit + 64)) +
-         pad256(damar_sort_workspace_bytes(n)) + pad256(damar_scan_workspace_bytes(n)) +
-         pad256(sizeof(u32) * bmwords) + 16384;
+
+/* A seed stage in progress: what its steps hand to each other.  (Front, above, is what outlives the stage.) */
+struct SeedStage
+{ damar_match_job *job;
+  int    slab;                   /* < 0: the whole comparison */
+  Arena *hits, *ord;             /* the arenas of the job's slot: sorted seed pairs; work list and processing order */
+  double t_entry;
+  MergeArgs m;                   /* with the key widths pbits / abits / dbits and the cap on mutual matches */
+  int    bbits, sbits, idbits;   /* bits of a B read; of the sort key (pbits + abits + bbits); of a read pair (abits + bbits) */
+  int    minhit;                 /* seeds a run needs to be a work item */
+  bool   cut;                    /* the early cut is on for this stage */
+  size_t bmwords;                /* its bitmap over the pair ids */
+  u32    mtiles;                 /* merge workspace (G_work): */
+  void  *mw;  u32 *tcount;  u64 *tot;  void *mscw;
+  u64    total;                  /* seed pairs (after the early cut: the survivors) */
+  int64  nhits;                  /* seed pairs the merge counted */
+  u64    s_off, s_all;           /* where this stage's seeds lie in the whole comparison's list */
+  u64   *keys;  u32 *vals;       /* the sorted side (in *hits) */
+  u64   *tk;                     /* the idle side */
+  u32   *flags, *foff;  void *scw2;  u64 *sends;
+  void  *resort_ws, *order_ws;   /* only where the sort over the read pair may need them */
+  bool   psort;                  /* the seeds are sorted over the read pair only */
+  int    hshift;                 /* slices of the reference's threads in the head test (-1: applied already) */
+  u32   *work;  u32 nwork;
+  const u32 *order;
+};
+
+/* From the job to the merge's arguments and the layout of the seed key: the 64-bit check, the rule for packed seeds, the
+   slab's range of B reads and cap (G_plan), and which of the alternative paths this stage takes (cut, psort).  Resets
+   *f, and for the whole comparison (slab < 0) the job's counts and G_plan.  Leaves s.m and the widths; false when an
+   index is empty.  Host arithmetic only: no device work, no wait. */
+static bool front_setup(SeedStage &s, damar_match_job *job, int slot, Front *f, int slab)
+{ const HITS_DB *ablock = job->ablock, *bblock = job->bblock;
+  const damar_dev_index *aidx = job->aidx, *bidx = job->bidx;
+  const FrontOpts &o = front_opts();
+  memset(&s, 0, sizeof(s));
+  s.job = job;  s.slab = slab;
+  s.hits = &G_hitsJ[slot];  s.ord = &G_ordJ[slot];
+  s.t_entry = now_ms();
+  pick_sort_shape();
+  memset(f, 0, sizeof(*f));
+  f->t_entry = s.t_entry;
+  f->jp = params_now();
+  if (slab < 0)
+    { job->counts[0] = job->counts[1] = job->counts[2] = 0;
+      G_plan.n = 1;  G_plan.mem_bound = false;  G_plan.total = 0;
+      G_plan.b_lo.assign(2, 0);  G_plan.b_lo[1] = bblock->nreads;
+      G_plan.hits.assign(1, 0);  G_plan.off.assign(1, 0);
+    }
+  if (aidx == NULL || bidx == NULL || aidx->n == 0 || bidx->n == 0)
+    return false;
+  if (aidx->kbits != bidx->kbits)
+    { fprintf(stderr, "damar: internal error, index parameters differ\n");
+      die();
+    }
+  MergeArgs &m = s.m;
+  m.acode = aidx->codes;  m.apos = aidx->pos;  m.alen = aidx->n;
+  m.bcode = bidx->codes;  m.bpos = bidx->pos;  m.blen = bidx->n;
+  m.wide = aidx->wide;
+  m.kbits = aidx->kbits;
+  m.self = job->self;  m.comp = job->comp;  m.identity = IDENTITY;
+  m.limit = (MEM_LIMIT > 0) ? MAXGRAM : 0x7fffffffu;      /* filter.c:2700-2702 */
+  m.b_lo = 0;  m.b_hi = 0xffffffffu;
+  if (slab >= 0)                                          /* the cap is the whole comparison's, the B reads the slab's */
+    { m.limit = G_plan.limit;
+      m.b_lo = (u32) G_plan.b_lo[slab];  m.b_hi = (u32) G_plan.b_lo[slab + 1];
+    }
+  m.ablk = aidx->blk->d;  m.bblk = bidx->blk->d;
+  m.pbits = std::max(1, ilog2_ceil((u64) ablock->maxlen + 1));
+  m.abits = std::max(1, ilog2_ceil((u64) ablock->nreads));
+  s.bbits = std::max(1, ilog2_ceil((u64) bblock->nreads));
+  s.sbits = m.pbits + m.abits + s.bbits;
+  s.idbits = m.abits + s.bbits;                           /* a read pair as one number: bread << abits | aread */
+  if (s.sbits > 64)
+    { fprintf(stderr, "damar: FATAL: seed key needs %d bits (> 64)\n", s.sbits);
+      die();
+    }
+  /* Packed seeds: when position-in-B fits beside the sort key, a seed is ONE u64 (pair | apos | bpos) and the sort moves
+     8 bytes per seed instead of 12; otherwise the diagonal travels in a second array (DAMAR_PACK_SEEDS=0 forces that) */
+  const int db = std::max(1, ilog2_ceil((u64) bblock->maxlen + 1));
+  m.dbits = (o.pack_seeds && s.sbits + db <= 64) ? db : 0;
+
+  s.minhit = (P_hitmin - 1) / P_kmer + 1;
+  const bool ranged = P_bread_lo > 0 || P_bread_hi != 0xffffffffu;      /* one part of a block pair split over GPUs */
+  s.cut = (o.early_cut || ranged) && !G_keep_seeds && s.idbits <= 32;
+  s.bmwords = (((size_t) 1 << (s.idbits <= 32 ? s.idbits : 32)) + 31) / 32;
+  /* The seed sort over the READ PAIR only (its abits + bbits of the key's sbits: 4 passes instead of 6).  The seeds of a
+     pair then lie in index order; the screen of the run heads takes them in any order and the runs of the kept heads -- all
+     the report kernel walks -- are put in order of their A positions where they lie (kernels/seed_merge.hip order_runs).
+     Not when something else reads the seeds (the tests' seed list, the two-step work list), not for the unpacked layout,
+     not for the early cut's survivors.
+     The ordering goes by the length of a run (a wavefront's registers up to 512 seeds, a workgroup beyond), which made
+     it cheap enough to be on for every shape -- profiles/order_runs.txt has config 2, config 3 and config 4's lead both
+     ways; until then a rule by the seed pairs per work item kept it to config 4's shape. */
+  s.psort = o.pair_sort != 0 && !s.cut && !o.two_step && !G_keep_seeds && m.dbits != 0 && m.pbits + 11 <= 32 && m.pbits >= 8;
+  s.hshift = P_nshift;
+  return true;
 }
+
+/* The merge's COUNT sweep over s.m (for a slab: with merge_range behind it) and the scan of the tile totals.  Starts
+   the stage's clock (the host-profile lines, tick(0)), takes the merge workspace from G_work and leaves mw / tcount /
+   tot / mscw and s.total.  One host wait: stream_wait for the total. */
+static void front_count(SeedStage &s)
+{ MergeArgs &m = s.m;
+  s.mtiles = damar_merge_tiles(m.alen);
+  if (Q_flush > 0)
+    { Q_ms[3] += now_ms() - Q_flush;  Q_flush = 0; }
+  Q_seg[3] += now_ms() - s.t_entry;
+  tick(0);
+  arena_reserve(&G_work, pad256(damar_merge_workspace_bytes(m.alen)) + pad256(damar_scan_workspace_bytes(s.mtiles)) + 4096);
+  s.mw = arena_take(&G_work, damar_merge_workspace_bytes(m.alen));
+  s.tcount = damar_merge_tile_counts(s.mw, m.alen);
+  s.tot = (u64 *) arena_take(&G_work, 64);
+  s.mscw = arena_take(&G_work, damar_scan_workspace_bytes(s.mtiles));
+  damar_launch_merge_count(&m, s.mw, NULL, 0, G_st);
+  if (s.slab >= 0)
+    damar_launch_merge_range(&m, s.mw, G_st);
+  stage("merge_count");
+  damar_exclusive_scan_u32(s.tcount, s.tcount, s.mtiles, s.mscw, s.tot, G_st);
+  stage("merge_scan");
+  HIP_CHECK(hipMemcpyAsync(&s.total, s.tot, sizeof(u64), hipMemcpyDeviceToHost, G_st));
+  stream_wait(G_st);
+}
+
+/* The reference's words for too little memory (filter.c:2634-2699), behind `lead`. */
+static void low_memory_text(const char *lead)
+{ fputs(lead, stderr);
+  if (MEM_LIMIT == MEM_PHYSICAL)
+    fprintf(stderr, " physical memory (%.1fGb), reduce block size\n", (1. * MEM_LIMIT) / 0x40000000ll);
+  else
+    { fprintf(stderr, " memory allocation (%.1fGb),", (1. * MEM_LIMIT) / 0x40000000ll);
+      fprintf(stderr, " reduce block size or increase allocation\n");
+    }
+  fflush(stderr);
+}
+
+/* The cap on mutual matches of a whole comparison (filter.c:2634-2699; a slab runs under the cap its comparison
+   settled).  The counts of front_count keep every run below MAXGRAM; the reference lowers that cap to the first mutual
+   count at which the kept seeds no longer fit `avail`.  That only happens under memory pressure, so the histogram is
+   built only then: COUNT with the histogram and a wait, then COUNT and scan under the lower cap and a wait.  Reads
+   s.total and the merge workspace; leaves G_limit, s.m.limit and s.total. */
+static void front_adapt_limit(SeedStage &s)
+{ MergeArgs &m = s.m;
+  if (MEM_LIMIT <= 0)
+    { G_limit = 0x7fffffff;
+      return;
+    }
+  const damar_match_job *job = s.job;
+  int   limit = MAXGRAM;
+  int64 avail = (int64) (MEM_LIMIT - (uint64) (sizeof_db(job->ablock) + sizeof_db(job->bblock))) / 16;
+  if (job->aidx == job->bidx || avail > (int64) m.alen + 2 * (int64) m.blen)
+    avail = (avail - m.alen) / 2;
+  else
+    avail = avail - ((int64) m.alen + m.blen);
+  avail = (int64) (avail * .98);
+  if ((int64) s.total > avail)
+    { std::vector<unsigned long long> histo(MAXGRAM);
+      unsigned long long *dgram = (unsigned long long *) dmalloc(sizeof(unsigned long long) * MAXGRAM);
+      HIP_CHECK(hipMemsetAsync(dgram, 0, sizeof(unsigned long long) * MAXGRAM, G_st));
+      damar_launch_merge_count(&m, s.mw, dgram, MAXGRAM, G_st);          /* the same sweep, with the run histogram */
+      HIP_CHECK(hipMemcpyAsync(histo.data(), dgram, sizeof(unsigned long long) * MAXGRAM, hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipStreamSynchronize(G_st));
+      HIP_CHECK(hipFree(dgram));
+      int64 tom = 0;
+      int   j;
+      for (j = 0; j < MAXGRAM; j++)
+        { tom += (int64) j * (int64) histo[j];
+          if (tom > avail)
+            break;
+        }
+      limit = j;
+      if (limit <= 1)
+        { low_memory_text("\nError: Insufficient ");
+          exit(1);
+        }
+      if (limit < 10)
+        low_memory_text("\nWarning: Sensitivity hampered by low ");
+      /* count again with the lower cap */
+      m.limit = (u32) limit;
+      damar_launch_merge_count(&m, s.mw, NULL, 0, G_st);
+      damar_exclusive_scan_u32(s.tcount, s.tcount, s.mtiles, s.mscw, s.tot, G_st);
+      HIP_CHECK(hipMemcpyAsync(&s.total, s.tot, sizeof(u64), hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipStreamSynchronize(G_st));
+    }
+  G_limit = limit;
+  if (VERBOSE)
+    printf("\n   Capping mutual k-mer matches over %d (effectively -t%d)\n", limit, (int) sqrt(1. * limit));
+}
+
+/* What the seed stage of `n` seed pairs reserves: in the comparison's own arena (front_hits_bytes), in the shared one
+   (front_tmp_bytes), with the early cut -- whose survivors are at most n -- in the shared arenas of the cut
+   (front_cut_bytes), and for the work list (front_ord_bytes).  The steps reserve by these expressions and the number of
+   seed pairs a seed stage can hold (seed_cap) is derived from them; each stands above the step whose takes it covers. */
+static size_t front_hits_bytes(u64 n);
+static size_t front_tmp_bytes(u64 n);
+static size_t front_cut_bytes(u64 n, int minhit, size_t bmwords);
+static size_t front_ord_bytes(u64 n, int minhit);
 /* what arena_reserve(a, need) would take from the device beyond what the arena holds */
 static size_t arena_growth(const Arena &a, size_t need)
 { if (need <= a.cap)
     return 0;
   const size_t cap = need + (need >> 3) + (1u << 20);
   return cap - a.cap;
-}
-/* the work list and its processing order: a work item is the head of a run of at least minhit seeds */
-static size_t front_ord_bytes(u64 n, int minhit)
-{ const u64 nw = n / (u64) minhit + 1;
-  return 5 * pad256(sizeof(u32) * (size_t) nw) + pad256(damar_sort_workspace_bytes(nw)) + 8192;
 }
 static size_t front_growth(u64 n, const Arena &hits, const Arena &ord, bool cut, int minhit, size_t bmwords)
 { const size_t own = arena_growth(hits, front_hits_bytes(n)) + arena_growth(ord, front_ord_bytes(n, minhit));
@@ -2048,206 +2263,24 @@ static u64 seed_cap(u64 total, const Arena &hits, const Arena &ord, bool cut, in
   return lo;
 }
 
-/* What the seed stage of one comparison leaves on the device for the report launch. */
-struct Front
-{ const u64 *keys;  const u32 *vals;  u64 total;
-  const u32 *work;  u32 nwork;
-  const u32 *order;
-  int pbits, abits, dbits;
-  JobParams jp;                 /* parameters and options of the moment the seed stage ran */
-  size_t bytes;                 /* of the two arenas that hold the above */
-  double t_entry;
-};
-
-/* Seed stage of one comparison (filter.c:2603-2760): merge-count, scan, emit, seed sort, work list and its
-   processing order, into the arenas of job slot `slot`.  Returns FRONT_NONE when there is nothing to report, FRONT_READY
-   with *f filled, or -- called with slab < 0, for the whole comparison -- FRONT_SPLIT when the comparison has more seed
-   pairs than one seed stage holds: G_plan then says how it is cut, and the caller runs the slabs (slab = 0, 1, ...),
-   each an ordinary seed stage over its range of B reads. */
-enum { FRONT_NONE = 0, FRONT_READY = 1, FRONT_SPLIT = 2 };
-static int match_front(damar_match_job *job, int slot, Front *f, int slab)
-{ const HITS_DB *ablock = job->ablock, *bblock = job->bblock;
-  damar_dev_index *aidx = job->aidx, *bidx = job->bidx;
-  const int self = job->self, comp = job->comp;
-  Arena &G_hits = G_hitsJ[slot], &G_ord = G_ordJ[slot];
-  int64 nhits = 0;
-  const double t_entry = now_ms();
-  pick_sort_shape();
-  memset(f, 0, sizeof(*f));
-  f->t_entry = t_entry;
-  f->jp = params_now();
+/* Hits known: does the stage hold them?  For the whole comparison: seed_cap, and when s.total is beyond it the seed
+   pairs per B read from what the COUNT sweep left (merge_bread_hist, built only now, with tick(1) and a wait), the
+   greedy cut into G_plan, the merge lap -- and true: FRONT_SPLIT.  For a slab: its count against the plan's.  Leaves
+   s_off / s_all, and counts the stage in G_slab_tot[0] when it goes on. */
+static bool front_plan_slabs(SeedStage &s)
+{ const u64 total = s.total;
+  const int slab = s.slab;
+  s.s_off = 0;  s.s_all = total;
   if (slab < 0)
-    { job->counts[0] = job->counts[1] = job->counts[2] = 0;
-      G_plan.n = 1;  G_plan.mem_bound = false;  G_plan.total = 0;
-      G_plan.b_lo.assign(2, 0);  G_plan.b_lo[1] = bblock->nreads;
-      G_plan.hits.assign(1, 0);  G_plan.off.assign(1, 0);
-    }
-  if (aidx == NULL || bidx == NULL || aidx->n == 0 || bidx->n == 0)
-    return FRONT_NONE;
-  if (aidx->kbits != bidx->kbits)
-    { fprintf(stderr, "damar: internal error, index parameters differ\n");
-      die();
-    }
-  const u32 alen = aidx->n, blen = bidx->n;
-  MergeArgs m;
-  memset(&m, 0, sizeof(m));
-  m.acode = aidx->codes;  m.apos = aidx->pos;  m.alen = alen;
-  m.bcode = bidx->codes;  m.bpos = bidx->pos;  m.blen = blen;
-  m.wide = aidx->wide;
-  m.kbits = aidx->kbits;
-  m.self = self;  m.comp = comp;  m.identity = IDENTITY;
-  m.limit = (MEM_LIMIT > 0) ? MAXGRAM : 0x7fffffffu;      /* filter.c:2700-2702 */
-  m.b_lo = 0;  m.b_hi = 0xffffffffu;
-  if (slab >= 0)                                          /* the cap is the whole comparison's, the B reads the slab's */
-    { m.limit = G_plan.limit;
-      m.b_lo = (u32) G_plan.b_lo[slab];  m.b_hi = (u32) G_plan.b_lo[slab + 1];
-    }
-  m.ablk = aidx->blk->d;  m.bblk = bidx->blk->d;
-  m.pbits = std::max(1, ilog2_ceil((u64) ablock->maxlen + 1));
-  m.abits = std::max(1, ilog2_ceil((u64) ablock->nreads));
-  int bbits = std::max(1, ilog2_ceil((u64) bblock->nreads));
-  if (m.pbits + m.abits + bbits > 64)
-    { fprintf(stderr, "damar: FATAL: seed key needs %d bits (> 64)\n", m.pbits + m.abits + bbits);
-      die();
-    }
-  /* Packed seeds: when position-in-B fits beside the sort key, a seed is ONE u64 (pair | apos | bpos) and the sort moves
-     8 bytes per seed instead of 12; otherwise the diagonal travels in a second array (DAMAR_PACK_SEEDS=0 forces that) */
-  { static int pack_on = -1;
-    if (pack_on < 0)
-      { const char *e = getenv("DAMAR_PACK_SEEDS");
-        pack_on = e ? atoi(e) : 1;
-      }
-    const int db = std::max(1, ilog2_ceil((u64) bblock->maxlen + 1));
-    m.dbits = (pack_on && m.pbits + m.abits + bbits + db <= 64) ? db : 0;
-  }
-
-  /* ---- merge: COUNT sweep, scan of the tile totals, (lower cap and COUNT again), EMIT sweep ---- */
-  const u32 mtiles = damar_merge_tiles(alen);
-  void *mw;
-  u32  *tcount;
-  u64  *tot;
-  u64   total = 0;
-
-  if (Q_flush > 0)
-    { Q_ms[3] += now_ms() - Q_flush;  Q_flush = 0; }
-  Q_seg[3] += now_ms() - f->t_entry;
-  tick(0);
-  arena_reserve(&G_work, pad256(damar_merge_workspace_bytes(alen)) + pad256(damar_scan_workspace_bytes(mtiles)) + 4096);
-  mw = arena_take(&G_work, damar_merge_workspace_bytes(alen));
-  tcount = damar_merge_tile_counts(mw, alen);
-  tot = (u64 *) arena_take(&G_work, 64);
-  void *mscw = arena_take(&G_work, damar_scan_workspace_bytes(mtiles));
-  damar_launch_merge_count(&m, mw, NULL, 0, G_st);
-  if (slab >= 0)
-    damar_launch_merge_range(&m, mw, G_st);
-  stage("merge_count");
-  damar_exclusive_scan_u32(tcount, tcount, mtiles, mscw, tot, G_st);
-  stage("merge_scan");
-  HIP_CHECK(hipMemcpyAsync(&total, tot, sizeof(u64), hipMemcpyDeviceToHost, G_st));
-  stream_wait(G_st);
-  if (slab >= 0)
-    ;                                                     /* (the whole comparison's call has settled the cap) */
-  else if (MEM_LIMIT > 0)
-    { /* filter.c:2634-2699.  The counts above keep every run below MAXGRAM; the reference lowers
-         that cap to the first mutual count at which the kept seeds no longer fit `avail`.  That
-         only happens under memory pressure, so the histogram is built only then. */
-      int   limit = MAXGRAM;
-      int64 avail = (int64) (MEM_LIMIT - (uint64) (sizeof_db(ablock) + sizeof_db(bblock))) / 16;
-      if (aidx == bidx || avail > (int64) alen + 2 * (int64) blen)
-        avail = (avail - alen) / 2;
-      else
-        avail = avail - ((int64) alen + blen);
-      avail = (int64) (avail * .98);
-      if ((int64) total > avail)
-        { std::vector<unsigned long long> histo(MAXGRAM);
-          unsigned long long *dgram = (unsigned long long *) dmalloc(sizeof(unsigned long long) * MAXGRAM);
-          HIP_CHECK(hipMemsetAsync(dgram, 0, sizeof(unsigned long long) * MAXGRAM, G_st));
-          damar_launch_merge_count(&m, mw, dgram, MAXGRAM, G_st);          /* the same sweep, with the run histogram */
-          HIP_CHECK(hipMemcpyAsync(histo.data(), dgram, sizeof(unsigned long long) * MAXGRAM, hipMemcpyDeviceToHost, G_st));
-          HIP_CHECK(hipStreamSynchronize(G_st));
-          HIP_CHECK(hipFree(dgram));
-          int64 tom = 0;
-          int   j;
-          for (j = 0; j < MAXGRAM; j++)
-            { tom += (int64) j * (int64) histo[j];
-              if (tom > avail)
-                break;
-            }
-          limit = j;
-          if (limit <= 1)
-            { fprintf(stderr, "\nError: Insufficient ");
-              if (MEM_LIMIT == MEM_PHYSICAL)
-                fprintf(stderr, " physical memory (%.1fGb), reduce block size\n", (1. * MEM_LIMIT) / 0x40000000ll);
-              else
-                { fprintf(stderr, " memory allocation (%.1fGb),", (1. * MEM_LIMIT) / 0x40000000ll);
-                  fprintf(stderr, " reduce block size or increase allocation\n");
-                }
-              fflush(stderr);
-              exit(1);
-            }
-          if (limit < 10)
-            { fprintf(stderr, "\nWarning: Sensitivity hampered by low ");
-              if (MEM_LIMIT == MEM_PHYSICAL)
-                fprintf(stderr, " physical memory (%.1fGb), reduce block size\n", (1. * MEM_LIMIT) / 0x40000000ll);
-              else
-                { fprintf(stderr, " memory allocation (%.1fGb),", (1. * MEM_LIMIT) / 0x40000000ll);
-                  fprintf(stderr, " reduce block size or increase allocation\n");
-                }
-              fflush(stderr);
-            }
-          /* count again with the lower cap */
-          m.limit = (u32) limit;
-          damar_launch_merge_count(&m, mw, NULL, 0, G_st);
-          damar_exclusive_scan_u32(tcount, tcount, mtiles, mscw, tot, G_st);
-          HIP_CHECK(hipMemcpyAsync(&total, tot, sizeof(u64), hipMemcpyDeviceToHost, G_st));
-          HIP_CHECK(hipStreamSynchronize(G_st));
-        }
-      G_limit = limit;
-      if (VERBOSE)
-        printf("\n   Capping mutual k-mer matches over %d (effectively -t%d)\n", limit, (int) sqrt(1. * limit));
-    }
-  else
-    G_limit = 0x7fffffff;
-  nhits = (int64) total;
-  if (VERBOSE && slab < 0)
-    { printf("   Hit count = %lld\n", (long long) nhits);
-      fflush(stdout);
-    }
-  if (total == 0)
-    return FRONT_NONE;
-
-  /* hits known.  The sorted seed pairs stay in this comparison's own arena until the report launch; everything else
-     of the seed stage lives in arenas the comparisons share.  The sort ping-pongs: it is started from the side that
-     makes the result land in the comparison's arena (the number of passes is known). */
-  const int sbits = m.pbits + m.abits + bbits;
-  const int spasses = (sbits + 7) / 8;                        /* sort_scan.hip: 8 bits per pass */
-  const int minhit = (P_hitmin - 1) / P_kmer + 1;
-  const int idbits = m.abits + bbits;                         /* a read pair as one number: bread << abits | aread */
-  static int cut_on = -1;
-  if (cut_on < 0)
-    { const char *e = getenv("DAMAR_EARLY_CUT");
-      cut_on = e ? atoi(e) : 0;      /* measured on config 2: 38 % of the seed pairs belong to read pairs with >= 3 seeds
-                                        (76.4 M seeds, 42.9 M read pairs, 5.8 M of them with >= 3), so the cut saves 3.7 of
-                                        the 6 sort passes but costs a 4-pass sort of the pair ids and two more passes over
-                                        the seeds: merge + sort + work list 203 -> 209 ms per step.  Off unless asked for;
-                                        with a B-read range (a pair split over GPUs) it keeps only that range's seeds. */
-    }
-  const bool ranged = P_bread_lo > 0 || P_bread_hi != 0xffffffffu;      /* one part of a block pair split over GPUs */
-  const bool cut = (cut_on || ranged) && !G_keep_seeds && idbits <= 32;
-  const size_t bmwords = (((size_t) 1 << (idbits <= 32 ? idbits : 32)) + 31) / 32;      /* the early cut's bitmap over the pair ids */
-  u64 s_off = 0, s_all = total;                              /* where this seed stage's seeds lie in the whole comparison's list */
-  if (slab < 0)
-    { G_plan.total = total;  G_plan.hits[0] = nhits;  G_plan.limit = m.limit;
-      const u64 cap = seed_cap(total, G_hits, G_ord, cut, minhit, bmwords, &G_plan.mem_bound);
+    { G_plan.total = total;  G_plan.hits[0] = s.nhits;  G_plan.limit = s.m.limit;
+      const u64 cap = seed_cap(total, *s.hits, *s.ord, s.cut, s.minhit, s.bmwords, &G_plan.mem_bound);
       G_plan.cap = cap;
       if (total > cap)
-        { /* seed pairs per B read from what the COUNT sweep left (built only now, like the histogram of the cap on mutual
-             matches), then the greedy cut */
-          const int nrb = bblock->nreads;
+        { const int nrb = s.job->bblock->nreads;
           std::vector<unsigned long long> hist((size_t) nrb);
           unsigned long long *dh = (unsigned long long *) dmalloc(sizeof(unsigned long long) * (size_t) nrb);
           HIP_CHECK(hipMemsetAsync(dh, 0, sizeof(unsigned long long) * (size_t) nrb, G_st));
-          damar_launch_merge_bread_hist(&m, mw, dh, G_st);   /* (reads the entries' counts and B starts, which the scan has not touched) */
+          damar_launch_merge_bread_hist(&s.m, s.mw, dh, G_st);   /* (reads the entries' counts and B starts, which the scan has not touched) */
           HIP_CHECK(hipMemcpyAsync(hist.data(), dh, sizeof(unsigned long long) * (size_t) nrb, hipMemcpyDeviceToHost, G_st));
           tick(1);
           HIP_CHECK(hipStreamSynchronize(G_st));
@@ -2277,7 +2310,7 @@ static int match_front(damar_match_job *job, int slot, Front *f, int slab)
               fflush(stdout);
             }
           G_ms[DAMAR_T_MERGE] += lap(0, 1);
-          return FRONT_SPLIT;
+          return true;
         }
     }
   else
@@ -2286,255 +2319,324 @@ static int match_front(damar_match_job *job, int slot, Front *f, int slab)
                   (long long) G_plan.hits[slab]);
           die();
         }
-      s_off = G_plan.off[slab];  s_all = G_plan.total;
+      s.s_off = G_plan.off[slab];  s.s_all = G_plan.total;
     }
   G_slab_tot[0] += 1;
-  static int two_step = -1;                              /* DAMAR_WORK_TWOSTEP=1: heads, then their screen (rounds 1-5; tested) */
-  if (two_step < 0)
-    { const char *e = getenv("DAMAR_WORK_TWOSTEP");
-      two_step = (e && atoi(e) > 0) ? 1 : 0;
-    }
-  /* The seed sort over the READ PAIR only (its abits + bbits of the key's sbits: 4 passes instead of 6).  The seeds of a
-     pair then lie in index order; the screen of the run heads takes them in any order and the runs of the kept heads -- all
-     the report kernel walks -- are put in order of their A positions where they lie (kernels/seed_merge.hip order_runs).
-     Not when something else reads the seeds (the tests' seed list, the two-step work list), not for the unpacked layout.
-     The ordering goes by the length of a run (a wavefront's registers up to 512 seeds, a workgroup beyond), which made
-     it cheap enough to be on for every shape -- profiles/order_runs.txt has config 2, config 3 and config 4's lead both
-     ways; until then a rule by the seed pairs per work item kept it to config 4's shape.
-     DAMAR_SORT_PAIR=0: never (the sort over all the bits, rounds 1-6), 1 or unset: always (both tested). */
-  static int pair_sort = -1;
-  if (pair_sort < 0)
-    { const char *e = getenv("DAMAR_SORT_PAIR");
-      pair_sort = e ? atoi(e) : 1;
-    }
-  const bool pair_on = pair_sort != 0;
-  bool psort = pair_on && !cut && !two_step && !G_keep_seeds && m.dbits != 0 && m.pbits + 11 <= 32 && m.pbits >= 8;
-  const int spasses_used = psort ? (sbits - m.pbits + 7) / 8 : spasses;
-  u64 *keys, *tk;
-  u32 *vals, *flags, *foff;
-  void *scw2, *resort_ws = NULL, *order_ws = NULL;
-  u64 *sends;
-  int  hshift = P_nshift;                                     /* slices of the reference's threads in the head test */
-  if (!cut)
-    { arena_reserve(&G_hits, front_hits_bytes(total));
-      arena_reserve(&G_tmp,  front_tmp_bytes(total));
-      u64 *pk = (u64 *) arena_take(&G_hits, sizeof(u64) * (size_t) total);
-      u32 *pv = m.dbits ? NULL : (u32 *) arena_take(&G_hits, sizeof(u32) * (size_t) total);
-      tk = (u64 *) arena_take(&G_tmp, sizeof(u64) * (size_t) total);
-      u32 *tv = m.dbits ? NULL : (u32 *) arena_take(&G_tmp, sizeof(u32) * (size_t) total);
-      u64 *k0 = (spasses_used & 1) ? tk : pk, *k1 = (spasses_used & 1) ? pk : tk;
-      u32 *v0 = (spasses_used & 1) ? tv : pv, *v1 = (spasses_used & 1) ? pv : tv;
-      void *sw = arena_take(&G_tmp, damar_sort_workspace_bytes(total));
-      resort_ws = sw;
-      flags = (u32 *) arena_take(&G_tmp, sizeof(u32) * (size_t) total);
-      foff  = (u32 *) arena_take(&G_tmp, std::max(sizeof(u32) * (size_t) total, bit_words_bytes(total)));   /* (also the heads' bit words) */
-      scw2  = arena_take(&G_tmp, damar_scan_workspace_bytes(total));
-      sends = (u64 *) arena_take(&G_tmp, 64 * sizeof(u64));
-      if (psort)                                             /* (in the room of tv: the packed layout has no values) */
-        order_ws = arena_take(&G_tmp, damar_order_runs_scratch_bytes(total));
+  return false;
+}
 
-      damar_launch_merge_emit(&m, mw, total, k0, v0, NULL, G_st);
-      stage("merge_emit");
-      tick(1);
-      int side = m.dbits ? damar_radix_sort_keys_u64(k0, k1, total, m.dbits + (psort ? m.pbits : 0), m.dbits + sbits, sw, G_st)
-                         : damar_radix_sort_u64(k0, v0, k1, v1, total, sbits, sw, G_st);
-      sort_check(sw);
-      keys = side ? k1 : k0;
-      vals = side ? v1 : v0;
-      if (keys != pk)
-        { fprintf(stderr, "damar: internal error, the seed sort ended on the wrong side\n");
+/* The stage's laps and counts: merge and sort laps, G_cnt[0], the job's counts[0]; and when the stage `worked` (it got
+   as far as a work list) the work lap, G_cnt[1] and -- for the tests -- the download of the sorted seeds (a blocking
+   copy).  The stream has been waited for when this is called: the events of tick(0..3) are complete. */
+static void front_account(SeedStage &s, bool worked)
+{ G_ms[DAMAR_T_MERGE] += lap(0, 1);
+  G_ms[DAMAR_T_SSORT] += lap(1, 2);
+  G_cnt[0] += s.nhits;
+  s.job->counts[0] += s.nhits;
+  if (!worked)
+    return;
+  G_ms[DAMAR_T_WORK] += lap(2, 3);
+  G_cnt[1] += s.nwork;
+  if (G_keep_seeds)
+    { const size_t at = s.slab >= 0 ? G_seed_keys.size() : 0;   /* (a slab's seeds behind those of the slabs before it: damar_match_batch clears) */
+      G_seed_keys.resize(at + s.total);  G_seed_vals.resize(at + s.total);
+      HIP_CHECK(hipMemcpy(G_seed_keys.data() + at, s.keys, sizeof(u64) * (size_t) s.total, hipMemcpyDeviceToHost));
+      if (s.vals != NULL)
+        HIP_CHECK(hipMemcpy(G_seed_vals.data() + at, s.vals, sizeof(u32) * (size_t) s.total, hipMemcpyDeviceToHost));
+      G_seed_pbits = s.m.pbits;  G_seed_abits = s.m.abits;  G_seed_dbits = s.m.dbits;
+    }
+}
+
+/* The two sides of a seed sort: it starts on k0 / v0 and must end on `home`, in the comparison's own arena (NULL: either
+   side will do). */
+struct SortBufs { u64 *k0, *k1;  u32 *v0, *v1;  void *sw;  u64 *home; };
+
+/* The arenas of a seed sort over n seed pairs and of the work list made from its result.  arena_take starts every take
+   on a multiple of 256; pad256(x) >= x + 256 pays for that.
+     front_hits_bytes, the own arena:  pad256(8 n)  pk, the sorted keys
+                                       pad256(4 n)  pv, their values (the unpacked layout only)
+                                       4096         spare
+     front_tmp_bytes, the shared one:  pad256(8 n)  tk, the other side of the keys
+                                       pad256(4 n)  tv, of the values (unpacked only); the packed layout takes order_ws in
+                                                    its room, 8 (n / 513 + 1) bytes, as the last take (front_emit_sort_plain)
+                                       pad256(sort) sw
+                                       pad256(4 n)  flags
+                                       pad256(4 n)  foff, also the heads' bit words: max(4 n, bit_words_bytes(n)), which is
+                                                    beyond 4 n by less than 512 bytes, and only below 128 seed pairs
+                                       pad256(scan) scw2
+                                       8192         sends (512 and its 256), the 512 of foff */
+static size_t front_hits_bytes(u64 n)
+{ return pad256(sizeof(u64) * (size_t) n) + pad256(sizeof(u32) * (size_t) n) + 4096; }
+static size_t front_tmp_bytes(u64 n)
+{ return pad256(sizeof(u64) * (size_t) n) + 3 * pad256(sizeof(u32) * (size_t) n) +
+         pad256(damar_sort_workspace_bytes(n)) + pad256(damar_scan_workspace_bytes(n)) + 8192;
+}
+/* Reserves both arenas and takes the ping-pong set of a sort of `passes` passes: it is started from the side that makes
+   the result land in the own arena.  Leaves tk, flags, foff, scw2 and sends in s.  (Reserving may wait for the stream
+   and free, when an arena has to grow.) */
+static SortBufs take_sort_bufs(SeedStage &s, Arena &own, Arena &shared, u64 n, int passes)
+{ const bool packed = s.m.dbits != 0;
+  SortBufs b;
+  arena_reserve(&own, front_hits_bytes(n));
+  arena_reserve(&shared, front_tmp_bytes(n));
+  u64 *pk = (u64 *) arena_take(&own, sizeof(u64) * (size_t) n);
+  u32 *pv = packed ? NULL : (u32 *) arena_take(&own, sizeof(u32) * (size_t) n);
+  s.tk = (u64 *) arena_take(&shared, sizeof(u64) * (size_t) n);
+  u32 *tv = packed ? NULL : (u32 *) arena_take(&shared, sizeof(u32) * (size_t) n);
+  b.k0 = (passes & 1) ? s.tk : pk;  b.k1 = (passes & 1) ? pk : s.tk;
+  b.v0 = (passes & 1) ? tv : pv;    b.v1 = (passes & 1) ? pv : tv;
+  b.sw = arena_take(&shared, damar_sort_workspace_bytes(n));
+  b.home = pk;
+  s.flags = (u32 *) arena_take(&shared, sizeof(u32) * (size_t) n);
+  s.foff  = (u32 *) arena_take(&shared, std::max(sizeof(u32) * (size_t) n, bit_words_bytes(n)));   /* (also the heads' bit words) */
+  s.scw2  = arena_take(&shared, damar_scan_workspace_bytes(n));
+  s.sends = (u64 *) arena_take(&shared, 64 * sizeof(u64));
+  return b;
+}
+
+/* The seed sort of n seeds from b.k0 / b.v0: over the read pair only (`pair_only`) or over all of the key; keys alone
+   in the packed layout.  Queues the sort's error word (sort_check).  With b.home the result must lie there and becomes
+   s.keys / s.vals.  Returns the side the result is on.  No wait. */
+static int sort_seeds(SeedStage &s, const SortBufs &b, u64 n, bool pair_only)
+{ const MergeArgs &m = s.m;
+  const int side = m.dbits ? damar_radix_sort_keys_u64(b.k0, b.k1, n, m.dbits + (pair_only ? m.pbits : 0), m.dbits + s.sbits, b.sw, G_st)
+                           : damar_radix_sort_u64(b.k0, b.v0, b.k1, b.v1, n, s.sbits, b.sw, G_st);
+  sort_check(b.sw);
+  if (b.home == NULL)
+    return side;
+  s.keys = side ? b.k1 : b.k0;
+  s.vals = side ? b.v1 : b.v0;
+  if (s.keys != b.home)
+    { fprintf(stderr, "damar: internal error, the seed sort ended on the wrong side\n");
+      die();
+    }
+  return side;
+}
+
+/* EMIT and the seed sort without the early cut: the sorted seed pairs stay in the comparison's own arena until the
+   report launch, everything else lives in G_tmp, which the comparisons share.  Reads s.total and the merge workspace;
+   leaves keys / vals and the buffers of take_sort_bufs, resort_ws, and with psort order_ws.  tick(1) behind the emit.
+   No wait. */
+static void front_emit_sort_plain(SeedStage &s)
+{ const int passes = ((s.psort ? s.sbits - s.m.pbits : s.sbits) + 7) / 8;          /* sort_scan.hip: 8 bits per pass */
+  const SortBufs b = take_sort_bufs(s, *s.hits, G_tmp, s.total, passes);
+  s.resort_ws = b.sw;
+  if (s.psort)                                             /* (in the room of tv: the packed layout has no values) */
+    s.order_ws = arena_take(&G_tmp, damar_order_runs_scratch_bytes(s.total));
+  damar_launch_merge_emit(&s.m, s.mw, s.total, b.k0, b.v0, NULL, G_st);
+  stage("merge_emit");
+  tick(1);
+  sort_seeds(s, b, s.total, s.psort);
+}
+
+/* What the early cut takes from G_tmp for n seed pairs before its survivors are known, term by term:
+     pad256(8 n)                   uk, the unsorted keys
+     4 pad256(4 n)                 uv, their values; pid0 and pid1, the pair ids and the other side of their sort; hbit,
+                                   the head bits (n / 8 bytes used)
+     pad256(4 (n / minhit + 64))   hd, the heads
+     pad256(sort), pad256(scan)    sw, scc
+     pad256(4 bmwords)             bitmap
+     16384                         snd (512 and its 256) */
+static size_t front_cut_bytes(u64 n, int minhit, size_t bmwords)
+{ return pad256(sizeof(u64) * (size_t) n) + 4 * pad256(sizeof(u32) * (size_t) n) +
+         pad256(sizeof(u32) * ((size_t) n / minhit + 64)) +
+         pad256(damar_sort_workspace_bytes(n)) + pad256(damar_scan_workspace_bytes(n)) +
+         pad256(sizeof(u32) * bmwords) + 16384;
+}
+/* EMIT and the seed sort with the early cut (kernels/seed_merge.hip): only the seeds of the read pairs report_thread
+   enters go through the seed sort.  The pair ids are sorted on their own (4 B per seed instead of 12, 4 passes instead
+   of 6), the reference's head test runs on them, and the seeds of the surviving pairs -- a few per cent -- are compacted
+   out of the unsorted seeds and sorted over all the bits (take_sort_bufs in G_tmp2).  Two waits: for the number of
+   heads, for the number of survivors.  Leaves what front_emit_sort_plain leaves, with s.total the survivors and
+   hshift = -1; false when nothing survives, and the stage's account is then closed here (no work lap). */
+static bool front_emit_sort_cut(SeedStage &s)
+{ const MergeArgs &m = s.m;
+  const u64 total = s.total;
+  arena_reserve(&G_tmp, front_cut_bytes(total, s.minhit, s.bmwords));
+  u64 *uk   = (u64 *) arena_take(&G_tmp, sizeof(u64) * (size_t) total);
+  u32 *uv   = (u32 *) arena_take(&G_tmp, sizeof(u32) * (size_t) total);
+  u32 *pid0 = (u32 *) arena_take(&G_tmp, sizeof(u32) * (size_t) total);
+  u32 *pid1 = (u32 *) arena_take(&G_tmp, sizeof(u32) * (size_t) total);
+  u32 *hbit = (u32 *) arena_take(&G_tmp, sizeof(u32) * (size_t) total);          /* head bits: total / 8 bytes used */
+  u32 *hd   = (u32 *) arena_take(&G_tmp, sizeof(u32) * ((size_t) total / s.minhit + 64));
+  void *sw  = arena_take(&G_tmp, damar_sort_workspace_bytes(total));
+  void *scc = arena_take(&G_tmp, damar_scan_workspace_bytes(total));
+  u32 *bitmap = (u32 *) arena_take(&G_tmp, sizeof(u32) * s.bmwords);
+  u64 *snd  = (u64 *) arena_take(&G_tmp, 64 * sizeof(u64));
+
+  damar_launch_merge_emit(&m, s.mw, total, uk, uv, pid0, G_st);
+  stage("merge_emit");
+  tick(1);
+  const u32 *spid = damar_radix_sort_keys_u32(pid0, pid1, total, s.idbits, sw, G_st) ? pid1 : pid0;
+  sort_check(sw);
+  u64 n64 = 0;
+  damar_launch_pair_heads_ids(spid, total, s.s_off, s.s_all, m.abits, s.minhit, P_nshift, snd, (u64 *) hbit, scc, s.tot, hd, G_st);
+  HIP_CHECK(hipMemsetAsync(bitmap, 0, sizeof(u32) * s.bmwords, G_st));
+  HIP_CHECK(hipMemcpyAsync(&n64, s.tot, sizeof(u64), hipMemcpyDeviceToHost, G_st));
+  HIP_CHECK(hipStreamSynchronize(G_st));
+  damar_launch_pair_bitmap(spid, hd, (u32) n64, m.abits, P_bread_lo, P_bread_hi, bitmap, G_st);
+  damar_launch_seed_cut_count(uk, total, m.pbits + m.dbits, bitmap, (u32 *) scc, s.tot, G_st);
+  HIP_CHECK(hipMemcpyAsync(&n64, s.tot, sizeof(u64), hipMemcpyDeviceToHost, G_st));
+  HIP_CHECK(hipStreamSynchronize(G_st));
+  stage("early_cut");
+  const u64 nsurv = n64;
+  G_cnt[6] += (int64) nsurv;
+  if (nsurv == 0)
+    { tick(2);  tick(3);
+      front_account(s, false);
+      return false;
+    }
+  const SortBufs b = take_sort_bufs(s, *s.hits, G_tmp2, nsurv, (s.sbits + 7) / 8);
+  damar_launch_seed_cut_scatter(uk, m.dbits ? NULL : uv, total, m.pbits + m.dbits, bitmap, (const u32 *) scc, b.k0, b.v0, G_st);
+  sort_seeds(s, b, nsurv, false);
+  s.total  = nsurv;              /* from here on: the seeds of the read pairs that are entered, nothing else */
+  s.hshift = -1;                 /* (the slice rule of the head test has been applied on the pair ids) */
+  return true;
+}
+
+/* The work list and its processing order (the comparison's second arena: they outlive the seed stage), for nw work
+   items: pad256(4 nw) five times for `work` (nw + 1 words) and front_order's ok0, ov0, ok1, ov1; pad256(sort) for its
+   osw; 8192 spare.  A work item is the head of a run of at least minhit seeds, so n seed pairs make at most n / minhit. */
+static size_t work_list_bytes(u64 nw)
+{ return 5 * pad256(sizeof(u32) * (size_t) nw) + pad256(damar_sort_workspace_bytes(nw)) + 8192; }
+static size_t front_ord_bytes(u64 n, int minhit)
+{ return work_list_bytes(n / (u64) minhit + 1); }
+
+/* Heads and screen in one pass over the sorted seeds: a bit per seed (in foff), the work list expanded from the bits
+   once its length is known.  tick(3) behind pair_work, then the comparison's last wait: nothing after it needs the host
+   again.  When the seeds were sorted over the read pair only and a kept run is too long for order_runs (more than 2048
+   seeds: a tandem array against itself, a satellite), the seeds are sorted over all the bits after all -- from where
+   they lie, the order of equal keys has not changed -- and the work list is made again, with a second wait.  Leaves
+   work / nwork in *s.ord, the kept runs in order of their A positions, and psort as it turned out. */
+static void front_work_onepass(SeedStage &s)
+{ const MergeArgs &m = s.m;
+  u64 got[2] = { 0, 0 };                               /* work items; a run order_runs would not sort */
+  damar_launch_pair_work(s.keys, s.vals, s.total, s.s_off, s.s_all, m.pbits, m.dbits, m.abits, s.minhit, s.hshift, s.sends,
+                         (u64 *) s.foff /* bit words */, s.scw2, s.tot, P_binshift, P_kmer, P_hitmin, P_bread_lo, P_bread_hi,
+                         s.psort ? 1 : 0, G_st);
+  stage("run_heads");
+  tick(3);                                             /* (the expansion of the bits behind it is 4 us: outside the clock) */
+  HIP_CHECK(hipMemcpyAsync(got, s.tot, 2 * sizeof(u64), hipMemcpyDeviceToHost, G_st));
+  stream_wait(G_st);
+  if (s.psort && got[1] != 0)
+    { G_cnt[7] += 1;
+      if (s.keys == s.tk || s.resort_ws == NULL)
+        { fprintf(stderr, "damar: internal error, no room to sort the seeds again\n");
           die();
         }
+      const SortBufs again = { s.keys, s.tk, NULL, NULL, s.resort_ws, NULL };
+      if (sort_seeds(s, again, s.total, false))
+        HIP_CHECK(hipMemcpyAsync(s.keys, s.tk, sizeof(u64) * (size_t) s.total, hipMemcpyDeviceToDevice, G_st));
+      damar_launch_pair_work(s.keys, s.vals, s.total, s.s_off, s.s_all, m.pbits, m.dbits, m.abits, s.minhit, s.hshift, s.sends,
+                             (u64 *) s.foff, s.scw2, s.tot, P_binshift, P_kmer, P_hitmin, P_bread_lo, P_bread_hi, 0, G_st);
+      HIP_CHECK(hipMemcpyAsync(got, s.tot, 2 * sizeof(u64), hipMemcpyDeviceToHost, G_st));
+      stream_wait(G_st);
+      s.psort = false;
     }
-  else
-    { /* The early cut (kernels/seed_merge.hip): only the seeds of the read pairs report_thread enters go through the
-         seed sort.  The pair ids are sorted on their own (4 B per seed instead of 12, 4 passes instead of 6), the
-         reference's head test runs on them, and the seeds of the surviving pairs -- a few per cent -- are compacted
-         out of the unsorted seeds. */
-      arena_reserve(&G_tmp, front_cut_bytes(total, minhit, bmwords));
-      u64 *uk   = (u64 *) arena_take(&G_tmp, sizeof(u64) * (size_t) total);
-      u32 *uv   = (u32 *) arena_take(&G_tmp, sizeof(u32) * (size_t) total);
-      u32 *pid0 = (u32 *) arena_take(&G_tmp, sizeof(u32) * (size_t) total);
-      u32 *pid1 = (u32 *) arena_take(&G_tmp, sizeof(u32) * (size_t) total);
-      u32 *hbit = (u32 *) arena_take(&G_tmp, sizeof(u32) * (size_t) total);          /* head bits: total / 8 bytes used */
-      u32 *hd   = (u32 *) arena_take(&G_tmp, sizeof(u32) * ((size_t) total / minhit + 64));
-      void *sw  = arena_take(&G_tmp, damar_sort_workspace_bytes(total));
-      void *scc = arena_take(&G_tmp, damar_scan_workspace_bytes(total));
-      u32 *bitmap = (u32 *) arena_take(&G_tmp, sizeof(u32) * bmwords);
-      u64 *snd  = (u64 *) arena_take(&G_tmp, 64 * sizeof(u64));
+  const u64 nwork64 = got[0];
+  arena_reserve(s.ord, work_list_bytes(nwork64));
+  s.work = (u32 *) arena_take(s.ord, sizeof(u32) * ((size_t) nwork64 + 1));
+  if (nwork64 > 0)
+    { damar_launch_pair_work_expand((const u64 *) s.foff, s.scw2, s.total, s.work, G_st);
+      if (s.psort)                                     /* the runs the report kernel will walk, in the order of their A positions */
+        damar_launch_order_runs(s.keys, s.total, m.pbits, m.dbits, s.work, (u32) nwork64, s.order_ws, G_st);
+    }
+  stage("work_list");
+  s.nwork = (u32) nwork64;
+}
 
-      damar_launch_merge_emit(&m, mw, total, uk, uv, pid0, G_st);
-      stage("merge_emit");
-      tick(1);
-      const u32 *spid = damar_radix_sort_keys_u32(pid0, pid1, total, idbits, sw, G_st) ? pid1 : pid0;
-      sort_check(sw);
-      u64 n64 = 0;
-      damar_launch_pair_heads_ids(spid, total, s_off, s_all, m.abits, minhit, P_nshift, snd, (u64 *) hbit, scc, tot, hd, G_st);
-      HIP_CHECK(hipMemsetAsync(bitmap, 0, sizeof(u32) * bmwords, G_st));
-      HIP_CHECK(hipMemcpyAsync(&n64, tot, sizeof(u64), hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipStreamSynchronize(G_st));
-      damar_launch_pair_bitmap(spid, hd, (u32) n64, m.abits, P_bread_lo, P_bread_hi, bitmap, G_st);
-      damar_launch_seed_cut_count(uk, total, m.pbits + m.dbits, bitmap, (u32 *) scc, tot, G_st);
-      HIP_CHECK(hipMemcpyAsync(&n64, tot, sizeof(u64), hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipStreamSynchronize(G_st));
-      stage("early_cut");
-      const u64 nsurv = n64;
-      G_cnt[6] += (int64) nsurv;
-      if (nsurv == 0)
-        { tick(2);  tick(3);
-          G_ms[DAMAR_T_MERGE] += lap(0, 1);
-          G_ms[DAMAR_T_SSORT] += lap(1, 2);
-          G_cnt[0] += nhits;
-          job->counts[0] += nhits;
-          return FRONT_NONE;
-        }
-      arena_reserve(&G_hits, front_hits_bytes(nsurv));
-      arena_reserve(&G_tmp2, front_tmp_bytes(nsurv));
-      u64 *pk = (u64 *) arena_take(&G_hits, sizeof(u64) * (size_t) nsurv);
-      u32 *pv = m.dbits ? NULL : (u32 *) arena_take(&G_hits, sizeof(u32) * (size_t) nsurv);
-      tk = (u64 *) arena_take(&G_tmp2, sizeof(u64) * (size_t) nsurv);
-      u32 *tv = m.dbits ? NULL : (u32 *) arena_take(&G_tmp2, sizeof(u32) * (size_t) nsurv);
-      u64 *k0 = (spasses & 1) ? tk : pk, *k1 = (spasses & 1) ? pk : tk;
-      u32 *v0 = (spasses & 1) ? tv : pv, *v1 = (spasses & 1) ? pv : tv;
-      void *sw2 = arena_take(&G_tmp2, damar_sort_workspace_bytes(nsurv));
-      flags = (u32 *) arena_take(&G_tmp2, sizeof(u32) * (size_t) nsurv);
-      foff  = (u32 *) arena_take(&G_tmp2, std::max(sizeof(u32) * (size_t) nsurv, bit_words_bytes(nsurv)));
-      scw2  = arena_take(&G_tmp2, damar_scan_workspace_bytes(nsurv));
-      sends = (u64 *) arena_take(&G_tmp2, 64 * sizeof(u64));
-      damar_launch_seed_cut_scatter(uk, m.dbits ? NULL : uv, total, m.pbits + m.dbits, bitmap, (const u32 *) scc, k0, v0, G_st);
-      int side = m.dbits ? damar_radix_sort_keys_u64(k0, k1, nsurv, m.dbits, m.dbits + sbits, sw2, G_st)
-                         : damar_radix_sort_u64(k0, v0, k1, v1, nsurv, sbits, sw2, G_st);
-      sort_check(sw2);
-      keys = side ? k1 : k0;
-      vals = side ? v1 : v0;
-      if (keys != pk)
-        { fprintf(stderr, "damar: internal error, the seed sort ended on the wrong side\n");
-          die();
-        }
-      total  = nsurv;              /* from here on: the seeds of the read pairs that are entered, nothing else */
-      hshift = -1;                 /* (the slice rule of the head test has been applied on the pair ids) */
+/* DAMAR_WORK_TWOSTEP=1: the run heads into the idle key buffer, then their screen (dense, one thread each) and the
+   compaction of the survivors; flags / foff are reused.  Two waits: for the number of heads (the work list is reserved
+   for that many), and behind tick(3) for the number of work items.  Leaves work / nwork in *s.ord. */
+static void front_work_twostep(SeedStage &s)
+{ const MergeArgs &m = s.m;
+  u64 nwork64 = 0;
+  u32 *heads = (u32 *) s.tk;
+  damar_launch_pair_heads(s.keys, s.total, s.s_off, s.s_all, m.pbits + m.dbits, m.abits, s.minhit, s.hshift, s.sends,
+                          (u64 *) s.foff /* bit words */, s.scw2, s.tot, heads, G_st);
+  stage("run_heads");
+  HIP_CHECK(hipMemcpyAsync(&nwork64, s.tot, sizeof(u64), hipMemcpyDeviceToHost, G_st));
+  HIP_CHECK(hipStreamSynchronize(G_st));
+  const u32 nheads = (u32) nwork64;
+  arena_reserve(s.ord, work_list_bytes(nheads));
+  s.work = (u32 *) arena_take(s.ord, sizeof(u32) * ((size_t) nheads + 1));
+  nwork64 = 0;
+  if (nheads > 0)
+    { damar_launch_pair_screen(s.keys, s.vals, s.total, m.pbits, m.dbits, heads, nheads, s.minhit, P_binshift, P_kmer, P_hitmin,
+                               m.abits, P_bread_lo, P_bread_hi, s.flags, G_st);
+      damar_exclusive_scan_u32(s.flags, s.foff, nheads, s.scw2, s.tot, G_st);
+      damar_launch_compact_u32(heads, s.flags, s.foff, nheads, s.work, G_st);
+      stage("work_list");
+      HIP_CHECK(hipMemcpyAsync(&nwork64, s.tot, sizeof(u64), hipMemcpyDeviceToHost, G_st));
     }
+  tick(3);
+  HIP_CHECK(hipStreamSynchronize(G_st));
+  s.nwork = (u32) nwork64;
+}
+
+/* Largest pairs first (FrontOpts::order_mode; the order only schedules the kernel: records carry their work item's rank
+   in the reference's order): a cost per work item, and the items sorted by it.  Takes its buffers from *s.ord behind
+   the work list (front_ord_bytes covers them) and leaves s.order, NULL for the reference's order.  No wait. */
+static void front_order(SeedStage &s)
+{ const MergeArgs &m = s.m;
+  const int order_mode = front_opts().order_mode;
+  const u32 nwork = s.nwork;
+  if (nwork <= 1 || order_mode <= 0)
+    return;
+  u32 *ok0 = (u32 *) arena_take(s.ord, sizeof(u32) * (size_t) nwork);
+  u32 *ov0 = (u32 *) arena_take(s.ord, sizeof(u32) * (size_t) nwork);
+  u32 *ok1 = (u32 *) arena_take(s.ord, sizeof(u32) * (size_t) nwork);
+  u32 *ov1 = (u32 *) arena_take(s.ord, sizeof(u32) * (size_t) nwork);
+  void *osw = arena_take(s.ord, damar_sort_workspace_bytes(nwork));
+  const u32 cmode = order_mode == 2 ? 1u : order_mode == 9 ? 0xffffffffu : order_mode == 10 ? 0xfffffffeu :
+                    order_mode == 11 ? 0xfffffffdu : order_mode == 12 ? 0xfffffffcu : (order_mode > 2 ? (u32) order_mode : 0u);
+  damar_launch_work_cost(s.keys, s.vals, s.total, m.pbits, m.abits, m.dbits, m.ablk.boff, m.bblk.boff, s.work, nwork, cmode, ok0, ov0, G_st);
+  s.order = damar_radix_sort_u32(ok0, ov0, ok1, ov1, nwork, WORK_COST_BITS, osw, G_st) ? ov1 : ov0;
+  sort_check(osw);
+  stage("work_order");
+}
+
+/* Seed stage of one comparison (filter.c:2603-2760): merge-count, scan, emit, seed sort, work list and its
+   processing order, into the arenas of job slot `slot`.  Returns FRONT_NONE when there is nothing to report, FRONT_READY
+   with *f filled, or -- called with slab < 0, for the whole comparison -- FRONT_SPLIT when the comparison has more seed
+   pairs than one seed stage holds: G_plan then says how it is cut, and the caller runs the slabs (slab = 0, 1, ...),
+   each an ordinary seed stage over its range of B reads. */
+enum { FRONT_NONE = 0, FRONT_READY = 1, FRONT_SPLIT = 2 };
+static int match_front(damar_match_job *job, int slot, Front *f, int slab)
+{ SeedStage s;
+  if (!front_setup(s, job, slot, f, slab))
+    return FRONT_NONE;
+  front_count(s);
+  if (slab < 0)                                   /* (a slab: the whole comparison's call has settled the cap) */
+    front_adapt_limit(s);
+  s.nhits = (int64) s.total;
+  if (VERBOSE && slab < 0)
+    { printf("   Hit count = %lld\n", (long long) s.nhits);
+      fflush(stdout);
+    }
+  if (s.total == 0)
+    return FRONT_NONE;
+  if (front_plan_slabs(s))
+    return FRONT_SPLIT;
+  if (!s.cut)
+    front_emit_sort_plain(s);
+  else if (!front_emit_sort_cut(s))
+    return FRONT_NONE;
   stage("seed_sort");
   tick(2);
-
-  /* ---- work list ---- */
-  u64 nwork64 = 0;
-  u32 *work = NULL;
-  if (!two_step)
-    { /* heads and screen in one pass over the seeds: a bit per seed, the work list expanded from the bits once its
-         length is known (the work list and its processing order outlive the seed stage: the comparison's second arena) */
-      u64 got[2] = { 0, 0 };                               /* work items; a run order_runs would not sort */
-      if (cut)
-        psort = false;                                     /* (the early cut's survivors were sorted over all the bits) */
-      damar_launch_pair_work(keys, vals, total, s_off, s_all, m.pbits, m.dbits, m.abits, minhit, hshift, sends, (u64 *) foff /* bit words */,
-                             scw2, tot, P_binshift, P_kmer, P_hitmin, P_bread_lo, P_bread_hi, psort ? 1 : 0, G_st);
-      stage("run_heads");
-      tick(3);                                             /* (the expansion of the bits behind it is 4 us: outside the clock) */
-      HIP_CHECK(hipMemcpyAsync(got, tot, 2 * sizeof(u64), hipMemcpyDeviceToHost, G_st));
-      stream_wait(G_st);                                   /* the comparison's last wait: nothing below needs the host again */
-      if (psort && got[1] != 0)
-        { /* a run of more than 2048 seeds among the kept ones (a tandem array against itself, a satellite): this comparison's
-             seeds are sorted over all the bits after all -- from where they lie, the order of equal keys has not changed --
-             and the work list is made again */
-          G_cnt[7] += 1;
-          u64 *other = (keys == tk) ? NULL : tk;
-          if (other == NULL || resort_ws == NULL)
-            { fprintf(stderr, "damar: internal error, no room to sort the seeds again\n");
-              die();
-            }
-          int side = damar_radix_sort_keys_u64(keys, other, total, m.dbits, m.dbits + sbits, resort_ws, G_st);
-          sort_check(resort_ws);
-          if (side)
-            HIP_CHECK(hipMemcpyAsync(keys, other, sizeof(u64) * (size_t) total, hipMemcpyDeviceToDevice, G_st));
-          damar_launch_pair_work(keys, vals, total, s_off, s_all, m.pbits, m.dbits, m.abits, minhit, hshift, sends, (u64 *) foff, scw2, tot,
-                                 P_binshift, P_kmer, P_hitmin, P_bread_lo, P_bread_hi, 0, G_st);
-          HIP_CHECK(hipMemcpyAsync(got, tot, 2 * sizeof(u64), hipMemcpyDeviceToHost, G_st));
-          stream_wait(G_st);
-          psort = false;
-        }
-      nwork64 = got[0];
-      arena_reserve(&G_ord, 5 * pad256(sizeof(u32) * (size_t) nwork64) + pad256(damar_sort_workspace_bytes(nwork64)) + 8192);
-      work = (u32 *) arena_take(&G_ord, sizeof(u32) * ((size_t) nwork64 + 1));
-      if (nwork64 > 0)
-        { damar_launch_pair_work_expand((const u64 *) foff, scw2, total, work, G_st);
-          if (psort)                                       /* the runs the report kernel will walk, in the order of their A positions */
-            damar_launch_order_runs(keys, total, m.pbits, m.dbits, work, (u32) nwork64, order_ws, G_st);
-        }
-      stage("work_list");
-    }
+  if (front_opts().two_step)
+    front_work_twostep(s);
   else
-    { u32 *heads = (u32 *) tk;                              /* the idle key buffer holds the run heads */
-      damar_launch_pair_heads(keys, total, s_off, s_all, m.pbits + m.dbits, m.abits, minhit, hshift, sends, (u64 *) foff /* bit words */,
-                              scw2, tot, heads, G_st);
-      stage("run_heads");
-      HIP_CHECK(hipMemcpyAsync(&nwork64, tot, sizeof(u64), hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipStreamSynchronize(G_st));
-      const u32 nheads = (u32) nwork64;
-      /* screen the heads (dense, one thread each), compact the survivors: flags/foff are reused */
-      arena_reserve(&G_ord, 5 * pad256(sizeof(u32) * (size_t) nheads) + pad256(damar_sort_workspace_bytes(nheads)) + 8192);
-      work = (u32 *) arena_take(&G_ord, sizeof(u32) * ((size_t) nheads + 1));
-      nwork64 = 0;
-      if (nheads > 0)
-        { damar_launch_pair_screen(keys, vals, total, m.pbits, m.dbits, heads, nheads, minhit, P_binshift, P_kmer, P_hitmin, m.abits,
-                                   P_bread_lo, P_bread_hi, flags, G_st);
-          damar_exclusive_scan_u32(flags, foff, nheads, scw2, tot, G_st);
-          damar_launch_compact_u32(heads, flags, foff, nheads, work, G_st);
-          stage("work_list");
-          HIP_CHECK(hipMemcpyAsync(&nwork64, tot, sizeof(u64), hipMemcpyDeviceToHost, G_st));
-        }
-    }
-  if (two_step)
-    { tick(3);
-      HIP_CHECK(hipStreamSynchronize(G_st));
-    }
+    front_work_onepass(s);
   sort_verify();
-  const u32 nwork = (u32) nwork64;
-  G_ms[DAMAR_T_MERGE] += lap(0, 1);
-  G_ms[DAMAR_T_SSORT] += lap(1, 2);
-  G_ms[DAMAR_T_WORK]  += lap(2, 3);
-  G_cnt[0] += nhits;  G_cnt[1] += nwork;
-  job->counts[0] += nhits;
+  front_account(s, true);
+  front_order(s);
 
-  if (G_keep_seeds)
-    { const size_t at = slab >= 0 ? G_seed_keys.size() : 0;     /* (a slab's seeds behind those of the slabs before it: damar_match_batch clears) */
-      G_seed_keys.resize(at + total);  G_seed_vals.resize(at + total);
-      HIP_CHECK(hipMemcpy(G_seed_keys.data() + at, keys, sizeof(u64) * (size_t) total, hipMemcpyDeviceToHost));
-      if (vals != NULL)
-        HIP_CHECK(hipMemcpy(G_seed_vals.data() + at, vals, sizeof(u32) * (size_t) total, hipMemcpyDeviceToHost));
-      G_seed_pbits = m.pbits;  G_seed_abits = m.abits;  G_seed_dbits = m.dbits;
-    }
-
-  /* ---- largest pairs first (the order only schedules the kernel: records carry their work
-          item's rank in the reference's order) ---- */
-  const u32 *order = NULL;
-  static int order_mode = -1;
-  if (order_mode < 0)
-    { const char *e = getenv("DAMAR_ORDER");
-      order_mode = e ? atoi(e) : 11;     /* 0 = reference order, 1 = most seeds first, 2 = size classes, 9 = longest seed
-                                            extent first, 10 = longest geometric overlap first, 11 = the larger of the two
-                                            (default: 356 ms of report kernel per config-2 step against 370 for 1, 361 for
-                                            9, 411 for 10), other n = runs of >= n seeds first */
-    }
-  if (nwork > 1 && order_mode > 0)
-    { u32 *ok0 = (u32 *) arena_take(&G_ord, sizeof(u32) * (size_t) nwork);
-      u32 *ov0 = (u32 *) arena_take(&G_ord, sizeof(u32) * (size_t) nwork);
-      u32 *ok1 = (u32 *) arena_take(&G_ord, sizeof(u32) * (size_t) nwork);
-      u32 *ov1 = (u32 *) arena_take(&G_ord, sizeof(u32) * (size_t) nwork);
-      void *osw = arena_take(&G_ord, damar_sort_workspace_bytes(nwork));
-      const u32 cmode = order_mode == 2 ? 1u : order_mode == 9 ? 0xffffffffu : order_mode == 10 ? 0xfffffffeu :
-                        order_mode == 11 ? 0xfffffffdu : order_mode == 12 ? 0xfffffffcu : (order_mode > 2 ? (u32) order_mode : 0u);
-      damar_launch_work_cost(keys, vals, total, m.pbits, m.abits, m.dbits, m.ablk.boff, m.bblk.boff, work, nwork, cmode, ok0, ov0, G_st);
-      order = damar_radix_sort_u32(ok0, ov0, ok1, ov1, nwork, WORK_COST_BITS, osw, G_st) ? ov1 : ov0;
-      sort_check(osw);
-      stage("work_order");
-    }
-
-
-  f->keys = keys;  f->vals = vals;  f->total = total;
-  f->work = work;  f->nwork = nwork;  f->order = order;
-  f->pbits = m.pbits;  f->abits = m.abits;  f->dbits = m.dbits;
-  f->bytes = G_hits.cap + G_ord.cap;
-  return nwork > 0 ? FRONT_READY : FRONT_NONE;
+  f->keys = s.keys;  f->vals = s.vals;  f->total = s.total;
+  f->work = s.work;  f->nwork = s.nwork;  f->order = s.order;
+  f->pbits = s.m.pbits;  f->abits = s.m.abits;  f->dbits = s.m.dbits;
+  f->bytes = s.hits->cap + s.ord->cap;
+  return s.nwork > 0 ? FRONT_READY : FRONT_NONE;
 }
 
 /* A report launch over up to DAMAR_MAX_JOBS comparisons, in two halves.  In asynchronous mode the launch goes to its own
