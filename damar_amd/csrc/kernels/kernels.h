@@ -322,6 +322,10 @@ typedef struct
    the launch (waiting for the longest alignment) is paid once per launch, not once per comparison. */
 #define DAMAR_MAX_JOBS 32
 #define DAMAR_MAX_TSPACE 8192     /* consecutive pebbles of a chain then differ by < 2^15 diagonals and < 2^16 waves */
+#define DAMAR_CNT_RECS      1     /* counters[1]: records written (asked for, when DAMAR_ERR_RECS is up) */
+#define DAMAR_CNT_TPOOL     2     /* counters[2]: trace values written (asked for, when DAMAR_ERR_TPOOL is up) */
+#define DAMAR_CNT_FLAGS     3     /* counters[3]: the DAMAR_ERR_* flags below */
+#define DAMAR_CNT_WHERE     6     /* counters[6]: which loop gave up when DAMAR_ERR_BAND is up (report.hip GUARD) */
 #define DAMAR_CNT_CELLS     8     /* counters[8..9]   (64 bits): band cells of the launch's wave steps (packed kernel) */
 #define DAMAR_CNT_HALFSTEPS 10    /* counters[10..11] (64 bits): wave steps, counted per half-wavefront (= per alignment pass)   */
 #define DAMAR_CNT_ITERS     12    /* counters[12..13] (64 bits): iterations of the wave loop (each steps one or two halves)      */

@@ -457,6 +457,9 @@ static void stream_wait(hipStream_t st)
 static void  tick(int i)            { HIP_CHECK(hipEventRecord(G_ev[i], G_st)); }
 static void  tick_on(int i, hipStream_t st) { HIP_CHECK(hipEventRecord(G_ev[i], st)); }
 static float lap(int i, int j)      { float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, G_ev[i], G_ev[j])); return ms; }
+/* the four timer events of output set `oset` (G_ev[16 .. 23]): around its report kernel, around its download */
+enum { SET_KERNEL_BEGIN = 0, SET_KERNEL_END = 1, SET_D2H_BEGIN = 2, SET_D2H_END = 3 };
+static int   set_ev(int oset, int k) { return 16 + 4 * oset + k; }
 
 extern "C" void damar_last_timings(double *ms)  { memcpy(ms, G_ms, sizeof(G_ms)); }
 extern "C" void damar_last_counters(int64 *c)   { memcpy(c, G_cnt, sizeof(G_cnt)); }
@@ -1096,6 +1099,28 @@ static u32 max_cells(void)                  /* (DAMAR_TEST_MAX_CELLS: a test hoo
    have been rebuilt with fewer since (DAMAR_SLOTS, less free memory): never more blocks than either has. */
 static int wide_slots(void)
 { return std::min(RS.wslots, RS.nslots); }
+
+/* The wide kernel's pebble pool: 16 bytes x RS.wcell_cap pebbles x RS.wslots slots, allocated when a launch first needs
+   it (wide_pool_ensure).  When the wide kernel itself raises DAMAR_ERR_CELLS the pool gets four times the pebbles over
+   half the slots, and the caller repeats everything (wide_pool_grow; nothing may be running on the old pool: the
+   caller has synchronised). */
+static void wide_pool_ensure(void)
+{ if (RS.wcells != NULL)
+    return;
+  RS.wslots = std::min(RS.nslots, 64);
+  RS.wcell_cap = 1u << 21;
+  RS.wcells = dmalloc((size_t) 16 * RS.wcell_cap * (size_t) RS.wslots);
+}
+static void wide_pool_grow(void)
+{ if (RS.wcell_cap >= (1u << 26))
+    { fprintf(stderr, "damar: FATAL: an alignment needs more than %u trace pebbles even in the wide format\n", RS.wcell_cap);
+      die();
+    }
+  HIP_CHECK(hipFree(RS.wcells));
+  RS.wcell_cap *= 4;
+  RS.wslots = std::max(8, RS.wslots / 2);
+  RS.wcells = dmalloc((size_t) 16 * RS.wcell_cap * (size_t) RS.wslots);
+}
 
 static u32 grow_cells(u32 cell_cap)
 { if (cell_cap >= max_cells())
@@ -2647,14 +2672,17 @@ static int match_front(damar_match_job *job, int slot, Front *f, int slab)
    from one to the next without the host -- while the seed stages of later comparisons accumulate; every comparison holds
    one of DAMAR_MAX_JOBS slots (arenas of its sorted seeds and work list, its SCORE/TABLE copy) from its seed stage until
    its launch has been completed. */
+struct Comparison
+{ int  slot;
+  damar_match_job  job;                           /* a copy: the caller's array may be gone when the launch completes */
+  damar_match_job *orig;                          /* the caller's struct (counts) while its call is still running */
+  Front fr;
+  const damar_dev_block *ablk, *bblk;             /* (an index may be released before a re-launch) */
+};
 struct Pending
 { bool live;
   int  n;
-  int  slot[DAMAR_MAX_JOBS];
-  damar_match_job  job[DAMAR_MAX_JOBS];           /* copies: the caller's array may be gone when the launch completes */
-  damar_match_job *orig[DAMAR_MAX_JOBS];          /* the caller's structs (counts) while its call is still running */
-  Front fr[DAMAR_MAX_JOBS];
-  const damar_dev_block *ablk[DAMAR_MAX_JOBS], *bblk[DAMAR_MAX_JOBS];     /* (an index may be released before a re-launch) */
+  Comparison c[DAMAR_MAX_JOBS];
   int  amax, bmax, tsmin;
   u32  cell_cap, rec_cap, tp_cap;
   int  t8;                                        /* the launch's trace values leave the device as bytes (ReportArgs.t8) */
@@ -2676,45 +2704,105 @@ static bool     G_slot_busy[DAMAR_MAX_JOBS];
 /* Comparisons whose seed stages are done and whose report launch has not been made yet.  In asynchronous mode a launch is
    held back while it would be SMALL: a launch ends by waiting for its longest alignment (a 15 kb read pair is some 10 ms of
    serial wave steps), so a launch over two comparisons of a sparse block pair (config 4: ~1 600 alignments each) costs as
-   much as one over sixteen.  The comparisons of later calls join it until it holds batch_work() read pairs or its set of job
-   arenas is full; the files of the block pairs in it wait with it (damar_write_overlaps). */
+   much as one over sixteen.  The comparisons of later calls join it until it holds DAMAR_BATCH_WORK read pairs or its set of
+   job arenas is full; the files of the block pairs in it wait with it (damar_write_overlaps). */
 struct Accum
 { int    n;
-  int    slot[DAMAR_MAX_JOBS / 2];
-  damar_match_job  job[DAMAR_MAX_JOBS / 2];
-  damar_match_job *orig[DAMAR_MAX_JOBS / 2];
-  Front  fr[DAMAR_MAX_JOBS / 2];
-  const damar_dev_block *ablk[DAMAR_MAX_JOBS / 2], *bblk[DAMAR_MAX_JOBS / 2];
+  Comparison c[DAMAR_MAX_JOBS / 2];
   size_t bytes;
   u64    nwork;
   std::vector<TailJob *> writes;
 };
 static Accum &AC = *new Accum();
 
+/* The switches of the report stage.  Read from the environment once per process, by the first use (report_opts). */
+struct ReportOpts
+{ long long adapt_ratio;  /* DAMAR_ADAPT_RATIO (4000): seed pairs per work item above which a co-running launch takes fewer
+                             wavefronts per SIMD (report_slots); 0 = never */
+  int  adapt_wps;         /* DAMAR_ADAPT_WPS (3, at least 1): that many */
+  int  queue_depth;       /* DAMAR_LAUNCH_QUEUE (1; 2 = the next launch is queued behind the running one).  Two takes the host
+                             out of the hand-over, but measured SLOWER on config 2: 434 - 445 ms per step against 398 - 410
+                             with one.  With one, the host waits for the running launch before it makes the next, so the seed
+                             stream is idle during the last third of every launch -- the phase in which the kernel works
+                             through the many short read pairs, whose band filters hammer the bucket arrays; seed sorts that
+                             run beside that phase take 180 instead of 100 ms per step. */
+  int  device_t8;         /* DAMAR_DEVICE_T8 (1): trace values leave the device as bytes where every comparison of the launch
+                             writes byte traces (launch_size); 0: 16-bit values, compressed by the host tail as until round 4 */
+  int  batch;             /* DAMAR_BATCH (0 = by the mode: batch_limit; else 1 .. DAMAR_MAX_JOBS): comparisons per launch.
+                             Report ms per config-2 step: 1 -> 357, 2 -> 340, 4 -> 335.5, 16 -> 335.3; every job in flight
+                             keeps its sorted seed pairs (12 B each) in HBM, which a cold process pays for at ~25 ms per GB */
+  long long batch_work;   /* DAMAR_BATCH_WORK (32768): read pairs a held-back launch waits for, four per wave slot */
+  bool small_caps;        /* DAMAR_TEST_SMALL_CAPS, tests: the first launch starts far too small, so that the overflow flags
+                             and the re-launch are exercised */
+};
+static const ReportOpts &report_opts(void)
+{ static ReportOpts o;
+  static bool filled = false;
+  if (!filled)
+    { const char *e;
+      o.adapt_ratio = (e = getenv("DAMAR_ADAPT_RATIO")) ? atoll(e) : 4000;
+      o.adapt_wps   = std::max(1, (e = getenv("DAMAR_ADAPT_WPS")) ? atoi(e) : 3);
+      o.queue_depth = ((e = getenv("DAMAR_LAUNCH_QUEUE")) && atoi(e) == 2) ? 2 : 1;
+      o.device_t8   = (e = getenv("DAMAR_DEVICE_T8")) ? atoi(e) : 1;
+      o.batch       = (e = getenv("DAMAR_BATCH")) ? atoi(e) : 0;
+      if (o.batch != 0)
+        o.batch = std::min(std::max(o.batch, 1), DAMAR_MAX_JOBS);
+      o.batch_work  = (e = getenv("DAMAR_BATCH_WORK")) ? atoll(e) : 32768;
+      o.small_caps  = getenv("DAMAR_TEST_SMALL_CAPS") != NULL;
+      filled = true;
+    }
+  return o;
+}
 
 static int64   A_nfilt = 0;                        /* totals of the asynchronous mode (damar_async_counts) */
 static int64   W_tot[3] = { 0, 0, 0 };             /* band cells, wave steps per pass, wave-loop iterations (damar_wave_totals) */
 static double  A_report_ms = 0;
 static int64   A_launches = 0;
 
+/* How much of the machine a launch of the two-pair kernel takes (r6).  A launch that fills every wave slot keeps the seed
+   stream's next kernel waiting until its wavefronts retire; where the seed stages are the longer side -- a plan of many
+   sparse block pairs: config 4 has 9 000 seed pairs per read pair that reaches the kernel, config 2 1 300, config 3 300 --
+   a co-running launch runs on DAMAR_ADAPT_WPS wavefronts per SIMD (3) instead of all 8: it takes a quarter longer and the
+   seed kernels run beside it the whole time (first 300 block pairs of config 4: 1.69 -> 1.58 s, profiles/r06_sweeps.txt).
+   DAMAR_ADAPT_RATIO = seed pairs per work item above which that happens (4 000; 0 = never).  Returns the launch's slots. */
+static int report_slots(const Pending &pd)
+{ const ReportOpts &o = report_opts();
+  int nslots = RS.nslots;
+  if (o.adapt_ratio > 0 && corun_on() && pd.st == G_rep)
+    { u64 seeds = 0, work = 0;
+      for (int j = 0; j < pd.n; j++)
+        { seeds += pd.c[j].fr.total;  work += pd.c[j].fr.nwork; }
+      const int low = G_prop.multiProcessorCount * 4 * damar_report2_slots_per_wave() * o.adapt_wps;
+      if (work > 0 && seeds / work > (u64) o.adapt_ratio && low < nslots)
+        nslots = low;
+    }
+  return nslots;
+}
+
+/* Launches pd's comparisons on pd.st with the caps of pd into output set pd.oset: scratch and output buffers (which may
+   wait for that set's last download), the jobs' arguments, the zeroed wide map and counters, the kernel between the set's
+   two kernel timers, pd.done behind it.  Leaves pd.ra, wm_off, wide_ok and pd.live.  No wait for the launch; the host
+   waits only where a buffer has to grow (scratch_prepare, scratch_outputs, the wide map: allocations) and for a spec's
+   tables when they changed (fill_report_args: upload and hipStreamSynchronize(st)). */
 static void report_launch(Pending &pd)
 { ReportArgs *const ra = pd.ra;
   const hipStream_t st = pd.st;
   double q0 = now_ms();
   RS.cur = pd.oset;
-  scratch_prepare(pd.amax, pd.bmax, pd.fr[0].jp.binshift, pd.tsmin, pd.cell_cap, st);
+  scratch_prepare(pd.amax, pd.bmax, pd.c[0].fr.jp.binshift, pd.tsmin, pd.cell_cap, st);
   double q1 = now_ms();
   scratch_outputs(pd.rec_cap, pd.tp_cap);
   double q2 = now_ms();
   Q_ms[0] += q1 - q0;  Q_ms[1] += q2 - q1;
   bool packed = true;
   for (int j = 0; j < pd.n; j++)
-    { const damar_match_job &jb = pd.job[j];
-      fill_report_args(&ra[j], pd.ablk[j], pd.bblk[j], jb.comp, jb.self, jb.spec, st, j, pd.slot[j], pd.fr[j].jp);
-      ra[j].keys = pd.fr[j].keys;  ra[j].vals = pd.fr[j].vals;  ra[j].nhits = pd.fr[j].total;
-      ra[j].work = pd.fr[j].work;  ra[j].nwork = pd.fr[j].nwork;
-      ra[j].pbits = pd.fr[j].pbits;  ra[j].abits = pd.fr[j].abits;  ra[j].dbits = pd.fr[j].dbits;
-      ra[j].order = pd.fr[j].order;
+    { const Comparison &c = pd.c[j];
+      const Front &fr = c.fr;
+      fill_report_args(&ra[j], c.ablk, c.bblk, c.job.comp, c.job.self, c.job.spec, st, j, c.slot, fr.jp);
+      ra[j].keys = fr.keys;  ra[j].vals = fr.vals;  ra[j].nhits = fr.total;
+      ra[j].work = fr.work;  ra[j].nwork = fr.nwork;
+      ra[j].pbits = fr.pbits;  ra[j].abits = fr.abits;  ra[j].dbits = fr.dbits;
+      ra[j].order = fr.order;
       ra[j].t8 = pd.t8;
       ra[j].widemap = NULL;  ra[j].wcells = RS.wcells;  ra[j].wcell_cap = RS.wcell_cap;  ra[j].cell_max = max_cells();
       packed = packed && use_packed(&ra[j], pd.amax, pd.bmax);
@@ -2749,36 +2837,12 @@ static void report_launch(Pending &pd)
         ra[j].widemap = RS.widemap[c] + pd.wm_off[j];
     }
   HIP_CHECK(hipMemsetAsync(RS.ctr, 0, sizeof(u32) * DAMAR_COUNTER_WORDS, st));
-  tick_on(16 + 4 * pd.oset, st);
+  tick_on(set_ev(pd.oset, SET_KERNEL_BEGIN), st);
   if (packed)
-    { /* How much of the machine a launch takes (r6).  A launch that fills every wave slot keeps the seed stream's next
-         kernel waiting until its wavefronts retire; where the seed stages are the longer side -- a plan of many sparse block
-         pairs: config 4 has 9 000 seed pairs per read pair that reaches the kernel, config 2 1 300, config 3 300 -- the
-         launch runs on DAMAR_ADAPT_WPS wavefronts per SIMD (3) instead of all 8: it takes a quarter longer and the seed
-         kernels run beside it the whole time (first 300 block pairs of config 4: 1.69 -> 1.58 s, profiles/r06_sweeps.txt).
-         DAMAR_ADAPT_RATIO = seed pairs per work item above which that happens (4 000; 0 = never). */
-      static long long ratio = -1;
-      static int wps = 0;
-      if (ratio < 0)
-        { const char *e = getenv("DAMAR_ADAPT_RATIO"), *w = getenv("DAMAR_ADAPT_WPS");
-          ratio = e ? atoll(e) : 4000;
-          wps = w ? atoi(w) : 3;
-          if (wps < 1) wps = 1;
-        }
-      int nslots = RS.nslots;
-      if (ratio > 0 && corun_on() && pd.st == G_rep)
-        { u64 seeds = 0, work = 0;
-          for (int j = 0; j < pd.n; j++)
-            { seeds += pd.fr[j].total;  work += pd.fr[j].nwork; }
-          const int low = G_prop.multiProcessorCount * 4 * damar_report2_slots_per_wave() * wps;
-          if (work > 0 && seeds / work > (u64) ratio && low < nslots)
-            nslots = low;
-        }
-      damar_launch_report2(ra, pd.n, NULL, 0, nslots, st);
-    }
+    damar_launch_report2(ra, pd.n, NULL, 0, report_slots(pd), st);
   else
     damar_launch_report(ra, pd.n, RS.nslots, st);
-  tick_on(17 + 4 * pd.oset, st);
+  tick_on(set_ev(pd.oset, SET_KERNEL_END), st);
   if (pd.done == NULL)
     HIP_CHECK(hipEventCreateWithFlags(&pd.done, hipEventDisableTiming));
   HIP_CHECK(hipEventRecord(pd.done, st));
@@ -2786,113 +2850,115 @@ static void report_launch(Pending &pd)
   pd.t_launch = now_ms();
 }
 
-/* Completes the launch in flight: waits for it, re-launches with larger buffers after an overflow, starts the download
-   of the records and hands the comparisons to the host tail in job order (filter.c:2442-2483 per read pair). */
-static void report_finish(Pending &pd)
-{ if (!pd.live)
-    return;
-  u32 hc[DAMAR_COUNTER_WORDS];
-  const hipStream_t st = pd.st;
-  const int n = pd.n;
-  const double h2 = now_ms();
-  for (;;)
-    { /* this launch only: a younger one may be queued behind it on the same stream */
-      HIP_CHECK(hipEventSynchronize(pd.done));
-      late_streams();
-      HIP_CHECK(hipMemcpyAsync(hc, RS.counters + (size_t) pd.oset * DAMAR_COUNTER_WORDS, sizeof(hc), hipMemcpyDeviceToHost, G_ctl));
-      HIP_CHECK(hipStreamSynchronize(G_ctl));
-      HIP_CHECK(hipGetLastError());
-      { const float ms = lap(16 + 4 * pd.oset, 17 + 4 * pd.oset);
-        G_ms[DAMAR_T_REPORT] += ms;
-        if (A_on)
-          { std::lock_guard<std::mutex> lk(A_mu);
-            A_report_ms += ms;
-            A_launches += 1;
-          }
+/* The steps of report_finish, over the launch pd and the counters hc[DAMAR_COUNTER_WORDS] as last read behind it. */
+
+/* Waits for pd.done -- this launch only: a younger one may be queued behind it on the same stream -- and fetches the
+   set's counters into hc over G_ctl (a second, short wait).  Adds the kernel's lap to the report time and counts the
+   launch. */
+static void report_wait(Pending &pd, u32 *hc)
+{ HIP_CHECK(hipEventSynchronize(pd.done));
+  late_streams();
+  HIP_CHECK(hipMemcpyAsync(hc, RS.counters + (size_t) pd.oset * DAMAR_COUNTER_WORDS, sizeof(u32) * DAMAR_COUNTER_WORDS, hipMemcpyDeviceToHost, G_ctl));
+  HIP_CHECK(hipStreamSynchronize(G_ctl));
+  HIP_CHECK(hipGetLastError());
+  { const float ms = lap(set_ev(pd.oset, SET_KERNEL_BEGIN), set_ev(pd.oset, SET_KERNEL_END));
+    G_ms[DAMAR_T_REPORT] += ms;
+    if (A_on)
+      { std::lock_guard<std::mutex> lk(A_mu);
+        A_report_ms += ms;
+        A_launches += 1;
       }
-      G_cnt[5] += 1;
-      /* Read pairs beyond the packed pebble format (reads of more than DAMAR_MAX_MARKS trace spacings; alignments that
-         overflowed the pebble pool at its largest, 2^18): the wide kernel takes them, into the same record buffers, behind
-         the launch that is otherwise complete.  Until round 5 both were fatal. */
-      if (pd.wide_ok && !pd.wide_done && hc[DAMAR_CNT_WIDE] > 0)
-        { u32 flags = hc[3];
-          if (pd.cell_cap >= max_cells())
-            flags &= ~DAMAR_ERR_CELLS;                         /* (those pairs are in the map: nothing to repeat for them) */
-          if (flags == 0)
-            { if (RS.wcells == NULL)
-                { RS.wslots = std::min(RS.nslots, 64);
-                  RS.wcell_cap = 1u << 21;
-                  RS.wcells = dmalloc((size_t) 16 * RS.wcell_cap * (size_t) RS.wslots);
-                }
-              for (int j = 0; j < n; j++)
-                { pd.ra[j].wcells = RS.wcells;  pd.ra[j].wcell_cap = RS.wcell_cap; }
-              if (VERBOSE)
-                fprintf(stderr, "damar: %u read pair(s) beyond the packed pebble format: wide kernel\n", hc[DAMAR_CNT_WIDE]);
-              { u32 *const ctr = RS.counters + (size_t) pd.oset * DAMAR_COUNTER_WORDS;
-                HIP_CHECK(hipMemsetAsync(ctr + DAMAR_CNT_CURSOR, 0, sizeof(u32) * DAMAR_MAX_JOBS, st));      /* the work lists once more */
-                HIP_CHECK(hipMemsetAsync(ctr + 3, 0, sizeof(u32), st));
-              }
-              damar_launch_report_wide(pd.ra, n, wide_slots(), st);
-              HIP_CHECK(hipEventRecord(pd.done, st));
-              pd.wide_done = true;
-              continue;                                         /* wait for it, read the counters again */
-            }
-        }
-      if (pd.wide_done && (hc[3] & DAMAR_ERR_CELLS))
-        { /* the wide kernel's own pool: four times the pebbles, and everything once more */
-          if (RS.wcell_cap >= (1u << 26))
-            { fprintf(stderr, "damar: FATAL: an alignment needs more than %u trace pebbles even in the wide format\n", RS.wcell_cap);
-              die();
-            }
-          HIP_CHECK(hipStreamSynchronize(st));
-          HIP_CHECK(hipFree(RS.wcells));
-          RS.wcell_cap *= 4;
-          RS.wslots = std::max(8, RS.wslots / 2);
-          RS.wcells = dmalloc((size_t) 16 * RS.wcell_cap * (size_t) RS.wslots);
-          hc[3] &= ~DAMAR_ERR_CELLS;
-          hc[3] |= 0x40000000u;                                /* (something to repeat the launch for) */
-        }
-      else if (pd.wide_ok && pd.cell_cap >= max_cells() && hc[DAMAR_CNT_WIDE] > 0)
-        hc[3] &= ~DAMAR_ERR_CELLS;                             /* the packed kernel's overflows at 2^18 are the wide kernel's pairs */
-      if (hc[3] == 0)
-        break;
-      hc[3] &= ~0x40000000u;
-      if ((hc[3] & DAMAR_ERR_BAND) && !(hc[3] & (DAMAR_ERR_CELLS | DAMAR_ERR_WIDE)))
-        { fprintf(stderr, "damar: FATAL: a Local_Alignment wave exceeded its loop bound (where=%u)\n", hc[6]);
-          die();
-        }
-      if (pd.attempt >= 6)
-        { fprintf(stderr, "damar: FATAL: report kernel keeps overflowing its buffers (flags %u)\n", hc[3]);
-          die();
-        }
-      pd.attempt += 1;
-      if (hc[3] & DAMAR_ERR_CELLS) pd.cell_cap = grow_cells(pd.cell_cap);
-      if (hc[3] & DAMAR_ERR_WIDE)  G_ring *= 4;
-      if (hc[3] & DAMAR_ERR_T8)    pd.t8 = 0;     /* a value above 255: 16-bit values again, and the reference's check on what is written */
-      if (hc[3] & DAMAR_ERR_RECS)  pd.rec_cap = std::max(2 * pd.rec_cap, hc[1] + 1024);
-      if (hc[3] & DAMAR_ERR_TPOOL)
-        { if (pd.tp_cap >= 0xe0000000u)
-            { fprintf(stderr, "damar: FATAL: more than 2^32 trace values in one comparison, use smaller blocks\n");
-              die();
-            }
-          pd.tp_cap = (u32) std::min<u64>(0xe0000000ull, std::max<u64>(2ull * pd.tp_cap, (u64) hc[2] + 65536));
-        }
-      if (VERBOSE)
-        fprintf(stderr, "damar: report kernel overflow (flags %u), retrying with larger buffers\n", hc[3]);
-      report_launch(pd);
+  }
+  G_cnt[5] += 1;
+}
+
+/* Read pairs beyond the packed pebble format (reads of more than DAMAR_MAX_MARKS trace spacings; alignments that
+   overflowed the pebble pool at its largest, 2^18): the wide kernel takes them, into the same record buffers, behind
+   the launch that is otherwise complete.  Until round 5 both were fatal.  Reads hc; when the wide kernel is due and no
+   other flag is up, zeroes the jobs' cursors and the flag word, launches it on pd.st, records pd.done behind it and
+   returns true: the caller waits and reads the counters again.  No wait. */
+static bool report_wide_pass(Pending &pd, const u32 *hc)
+{ if (!pd.wide_ok || pd.wide_done || hc[DAMAR_CNT_WIDE] == 0)
+    return false;
+  u32 flags = hc[DAMAR_CNT_FLAGS];
+  if (pd.cell_cap >= max_cells())
+    flags &= ~DAMAR_ERR_CELLS;                             /* (those pairs are in the map: nothing to repeat for them) */
+  if (flags != 0)
+    return false;
+  wide_pool_ensure();
+  for (int j = 0; j < pd.n; j++)
+    { pd.ra[j].wcells = RS.wcells;  pd.ra[j].wcell_cap = RS.wcell_cap; }
+  if (VERBOSE)
+    fprintf(stderr, "damar: %u read pair(s) beyond the packed pebble format: wide kernel\n", hc[DAMAR_CNT_WIDE]);
+  u32 *const ctr = RS.counters + (size_t) pd.oset * DAMAR_COUNTER_WORDS;
+  HIP_CHECK(hipMemsetAsync(ctr + DAMAR_CNT_CURSOR, 0, sizeof(u32) * DAMAR_MAX_JOBS, pd.st));      /* the work lists once more */
+  HIP_CHECK(hipMemsetAsync(ctr + DAMAR_CNT_FLAGS, 0, sizeof(u32), pd.st));
+  damar_launch_report_wide(pd.ra, pd.n, wide_slots(), pd.st);
+  HIP_CHECK(hipEventRecord(pd.done, pd.st));
+  pd.wide_done = true;
+  return true;
+}
+
+/* From the flags in hc to the next attempt.  Returns false when the launch is complete.  Otherwise something ran over:
+   the wide kernel's own pool (grown here, behind a wait for pd.st; nothing else changes and everything runs once more),
+   or what the flags name -- pebbles, the ring, byte traces, records, trace values -- which grows in pd or G_ring; the
+   launch is made again and true returned.  Fatal: a wave past its loop bound, the seventh attempt, 2^32 trace values. */
+static bool report_retry(Pending &pd, const u32 *hc)
+{ u32 flags = hc[DAMAR_CNT_FLAGS];
+  bool repeat = false;                                     /* the launch is repeated though no flag may be left */
+  if (pd.wide_done && (flags & DAMAR_ERR_CELLS))
+    { HIP_CHECK(hipStreamSynchronize(pd.st));
+      wide_pool_grow();
+      flags &= ~DAMAR_ERR_CELLS;
+      repeat = true;
     }
-  pd.live = false;
-  tick_on(18 + 4 * pd.oset, st);
-  const double h3 = now_ms();
-  HostBuf *hb = hostbuf_get(hc[1], hc[2]);
+  else if (pd.wide_ok && pd.cell_cap >= max_cells() && hc[DAMAR_CNT_WIDE] > 0)
+    flags &= ~DAMAR_ERR_CELLS;                             /* the packed kernel's overflows at 2^18 are the wide kernel's pairs */
+  if (flags == 0 && !repeat)
+    return false;
+  if ((flags & DAMAR_ERR_BAND) && !(flags & (DAMAR_ERR_CELLS | DAMAR_ERR_WIDE)))
+    { fprintf(stderr, "damar: FATAL: a Local_Alignment wave exceeded its loop bound (where=%u)\n", hc[DAMAR_CNT_WHERE]);
+      die();
+    }
+  if (pd.attempt >= 6)
+    { fprintf(stderr, "damar: FATAL: report kernel keeps overflowing its buffers (flags %u)\n", flags);
+      die();
+    }
+  pd.attempt += 1;
+  if (flags & DAMAR_ERR_CELLS) pd.cell_cap = grow_cells(pd.cell_cap);
+  if (flags & DAMAR_ERR_WIDE)  G_ring *= 4;
+  if (flags & DAMAR_ERR_T8)    pd.t8 = 0;         /* a value above 255: 16-bit values again, and the reference's check on what is written */
+  if (flags & DAMAR_ERR_RECS)  pd.rec_cap = std::max(2 * pd.rec_cap, hc[DAMAR_CNT_RECS] + 1024);
+  if (flags & DAMAR_ERR_TPOOL)
+    { if (pd.tp_cap >= 0xe0000000u)
+        { fprintf(stderr, "damar: FATAL: more than 2^32 trace values in one comparison, use smaller blocks\n");
+          die();
+        }
+      pd.tp_cap = (u32) std::min<u64>(0xe0000000ull, std::max<u64>(2ull * pd.tp_cap, (u64) hc[DAMAR_CNT_TPOOL] + 65536));
+    }
+  if (VERBOSE)
+    fprintf(stderr, "damar: report kernel overflow (flags %u), retrying with larger buffers\n", flags);
+  report_launch(pd);
+  return true;
+}
+
+/* Starts the download of the complete launch's records, trace values and -- when the wide kernel ran -- wide map into a
+   host buffer, which it returns.  Asynchronous mode: on G_copy between the buffer's events, with the set's event
+   behind it for whatever writes the set next; no wait (but for the wide map, copied synchronously).  Otherwise on pd.st,
+   waited for here, with the d2h lap.  Then adds what was downloaded to the counts and the wave totals. */
+static HostBuf *report_download(Pending &pd, const u32 *hc)
+{ const hipStream_t st = pd.st;
+  const int n = pd.n;
+  const u32 nrec = hc[DAMAR_CNT_RECS], ntrace = hc[DAMAR_CNT_TPOOL];
+  HostBuf *hb = hostbuf_get(nrec, ntrace);
   hb->users = n;
   late_streams();
   hipStream_t cs = A_on ? G_copy : st;
   if (A_on)
     HIP_CHECK(hipEventRecord(hb->e0, cs));       /* (the report kernel has completed: the host synced on it) */
-  if (hc[1] > 0)
-    { HIP_CHECK(hipMemcpyAsync(hb->recs, RS.recs_set[pd.oset], sizeof(LaRecord) * (size_t) hc[1], hipMemcpyDeviceToHost, cs));
-      HIP_CHECK(hipMemcpyAsync(hb->tpool, RS.tpool_set[pd.oset], (pd.t8 ? sizeof(u8) : sizeof(u16)) * (size_t) hc[2], hipMemcpyDeviceToHost, cs));
+  if (nrec > 0)
+    { HIP_CHECK(hipMemcpyAsync(hb->recs, RS.recs_set[pd.oset], sizeof(LaRecord) * (size_t) nrec, hipMemcpyDeviceToHost, cs));
+      HIP_CHECK(hipMemcpyAsync(hb->tpool, RS.tpool_set[pd.oset], (pd.t8 ? sizeof(u8) : sizeof(u16)) * (size_t) ntrace, hipMemcpyDeviceToHost, cs));
     }
   hb->t8 = pd.t8;
   hb->nwide = pd.wide_done ? hc[DAMAR_CNT_WIDE] : 0;
@@ -2906,7 +2972,7 @@ static void report_finish(Pending &pd)
       memcpy(hb->wm_off, pd.wm_off, sizeof(hb->wm_off));
       HIP_CHECK(hipMemcpy(hb->wmap, RS.widemap[pd.oset], sizeof(u32) * (size_t) words, hipMemcpyDeviceToHost));
     }
-  tick_on(19 + 4 * pd.oset, st);
+  tick_on(set_ev(pd.oset, SET_D2H_END), st);
   if (A_on)
     { /* asynchronous mode: the download runs on its own stream beside the next comparison's merge and sorts; the
          tail thread waits for it, and so does the next report kernel (which would overwrite the device buffers) */
@@ -2919,19 +2985,27 @@ static void report_finish(Pending &pd)
     }
   else
     { HIP_CHECK(hipStreamSynchronize(st));
-      G_ms[DAMAR_T_D2H] += lap(18 + 4 * pd.oset, 19 + 4 * pd.oset);
+      G_ms[DAMAR_T_D2H] += lap(set_ev(pd.oset, SET_D2H_BEGIN), set_ev(pd.oset, SET_D2H_END));
     }
-  G_cnt[3] += hc[1];  G_cnt[4] += hc[2];
+  G_cnt[3] += nrec;  G_cnt[4] += ntrace;
   { std::lock_guard<std::mutex> lk(A_mu);
     W_tot[0] += (int64) (((u64) hc[DAMAR_CNT_CELLS + 1] << 32) | hc[DAMAR_CNT_CELLS]);
     W_tot[1] += (int64) (((u64) hc[DAMAR_CNT_HALFSTEPS + 1] << 32) | hc[DAMAR_CNT_HALFSTEPS]);
     W_tot[2] += (int64) (((u64) hc[DAMAR_CNT_ITERS + 1] << 32) | hc[DAMAR_CNT_ITERS]);
   }
-  const double h4 = now_ms();
+  return hb;
+}
+
+/* Hands the comparisons to the host tail in job order (filter.c:2442-2483 per read pair), each with its seed hits from
+   hc added to the caller's counts: queued behind the download in asynchronous mode, run here otherwise (hb is complete
+   then, and goes back when its last comparison is done).  Then queues the file writes that waited for these tails. */
+static void report_hand_over(Pending &pd, const u32 *hc, HostBuf *hb)
+{ const int n = pd.n;
   for (int j = 0; j < n; j++)
-    { const damar_match_job &jb = pd.job[j];
-      if (pd.orig[j] != NULL)
-        pd.orig[j]->counts[1] += hc[DAMAR_CNT_NFILT + j];      /* (summed over a comparison's slabs) */
+    { const Comparison &c = pd.c[j];
+      const damar_match_job &jb = c.job;
+      if (c.orig != NULL)
+        c.orig->counts[1] += hc[DAMAR_CNT_NFILT + j];          /* (summed over a comparison's slabs) */
       G_cnt[2] += hc[DAMAR_CNT_NFILT + j];
       if (A_on)
         { { std::lock_guard<std::mutex> lk(A_mu);
@@ -2941,15 +3015,15 @@ static void report_finish(Pending &pd)
           tj->kind = 0;
           tj->hb = hb;  tj->jobid = j;  tj->njobs = n;
           tj->ablock = *jb.ablock;  tj->bblock = *jb.bblock;
-          tj->self = jb.self;  tj->comp = jb.comp;  tj->spec = jb.spec;  tj->jp = pd.fr[j].jp;
-          tj->got = (G_tail_reports && pd.orig[j] != NULL) ? &pd.orig[j]->counts[2] : NULL;   /* (only for a caller that drains before its job struct goes: damar_match) */
+          tj->self = jb.self;  tj->comp = jb.comp;  tj->spec = jb.spec;  tj->jp = c.fr.jp;
+          tj->got = (G_tail_reports && c.orig != NULL) ? &c.orig->counts[2] : NULL;   /* (only for a caller that drains before its job struct goes: damar_match) */
           async_submit(tj);
         }
       else
         { double t0 = now_ms();
-          const int64 got = run_tail(hb->recs, hb->nrec, hb->tpool, hb->t8, hb->nwide ? hb->wmap + hb->wm_off[j] : (const u32 *) NULL, jb.ablock, jb.bblock, jb.self, jb.comp, jb.spec, pd.fr[j].jp, j, n);
-          if (pd.orig[j] != NULL)
-            pd.orig[j]->counts[2] += got;
+          const int64 got = run_tail(hb->recs, hb->nrec, hb->tpool, hb->t8, hb->nwide ? hb->wmap + hb->wm_off[j] : (const u32 *) NULL, jb.ablock, jb.bblock, jb.self, jb.comp, jb.spec, c.fr.jp, j, n);
+          if (c.orig != NULL)
+            c.orig->counts[2] += got;
           if (--hb->users == 0)
             hostbuf_put(hb);
           G_ms[DAMAR_T_TAIL] += now_ms() - t0;
@@ -2958,6 +3032,25 @@ static void report_finish(Pending &pd)
   for (TailJob *w : pd.writes)                   /* the files of these comparisons: behind their tails */
     async_submit(w);
   pd.writes.clear();
+}
+
+/* Completes the launch in flight: waits for it, lets the wide kernel run behind it, re-launches with larger buffers after
+   an overflow -- until an attempt leaves nothing to repeat -- then starts the download of the records and hands the
+   comparisons to the host tail.  Host-profile laps: 3 to the complete launch, 4 the download, 5 the hand-over. */
+static void report_finish(Pending &pd)
+{ if (!pd.live)
+    return;
+  u32 hc[DAMAR_COUNTER_WORDS];
+  const double h2 = now_ms();
+  do
+    report_wait(pd, hc);
+  while (report_wide_pass(pd, hc) || report_retry(pd, hc));
+  pd.live = false;
+  tick_on(set_ev(pd.oset, SET_D2H_BEGIN), pd.st);
+  const double h3 = now_ms();
+  HostBuf *hb = report_download(pd, hc);
+  const double h4 = now_ms();
+  report_hand_over(pd, hc, hb);
   const double h5 = now_ms();
   H_ms[3] += h3 - h2;  H_ms[4] += h4 - h3;  H_ms[5] += h5 - h4;
 }
@@ -2969,49 +3062,19 @@ static void finish_oldest(void)
   Pending &pd = PQ[PQ_head];
   report_finish(pd);
   for (int j = 0; j < pd.n; j++)
-    G_slot_busy[pd.slot[j]] = false;
+    G_slot_busy[pd.c[j].slot] = false;
   pd.n = 0;
   PQ_head ^= 1;
   PQ_n -= 1;
 }
 
-static void flush_accum(void);
-
-/* a free comparison slot; when there is none, the oldest launch is completed (or, with nothing in flight, the comparisons
-   held back are launched) */
-static int slot_take(void)
-{ for (;;)
-    { for (int i = 0; i < DAMAR_MAX_JOBS; i++)
-        if (!G_slot_busy[i])
-          { G_slot_busy[i] = true;
-            return i;
-          }
-      if (PQ_n > 0)
-        finish_oldest();
-      else
-        flush_accum();
-    }
-}
-
+/* comparisons per launch where DAMAR_BATCH does not say */
 static int batch_limit(void)
-{ static int n = 0;
-  if (n == 0)
-    { const char *e = getenv("DAMAR_BATCH");
-      n = e ? atoi(e) : 0;      /* report ms per config-2 step: 1 -> 357, 2 -> 340, 4 -> 335.5, 16 -> 335.3; every job in
-                                   flight keeps its sorted seed pairs (12 B each) in HBM, which a cold process pays for
-                                   at ~25 ms per GB */
-      if (n == 0)
-        return corun_on() ? 2 : 4;            /* overlapped launches: short ones interleave better (548 against 590 ms) */
-      if (n < 1) n = 1;
-      if (n > DAMAR_MAX_JOBS) n = DAMAR_MAX_JOBS;
-    }
-  return n;
+{ if (report_opts().batch != 0)
+    return report_opts().batch;
+  return corun_on() ? 2 : 4;                /* overlapped launches: short ones interleave better (548 against 590 ms) */
 }
 
-/* Several comparisons with ONE report launch each time their seed stages are done (kernels.h: DAMAR_MAX_JOBS): the seed
-   stages run one after the other, each into its own arena, then every wavefront of the report kernel works through all
-   the work lists.  The output is that of damar_match called for jobs[0], jobs[1], ... in this order.  Launches are cut
-   at DAMAR_BATCH jobs (default 4, at most DAMAR_MAX_JOBS) and whenever the seed arenas would pass a quarter of HBM. */
 /* Write_Overlap_Buffer + Reset_Overlap_Buffer (daligner.c:1020-1021, 1055-1056), queued behind
  * the pending tails in asynchronous mode, immediate otherwise. */
 extern "C" void damar_write_overlaps(Align_Spec *spec, const char *d1, const char *d2,
@@ -3028,14 +3091,14 @@ extern "C" void damar_write_overlaps(Align_Spec *spec, const char *d1, const cha
   if (d2) job->d2 = d2;
   job->a = ablock;  job->b = bblock;  job->last = lastRead;
   for (int j = 0; j < AC.n; j++)                 /* comparisons of this spec are still waiting for their launch */
-    if (AC.job[j].spec == spec)
+    if (AC.c[j].job.spec == spec)
       { AC.writes.push_back(job);
         return;
       }
   for (int q = PQ_n - 1; q >= 0; q--)            /* the tails of a launch in flight are not queued yet: behind them */
     { Pending &pd = PQ[(PQ_head + q) & 1];         /* (the youngest launch that holds the spec) */
       for (int j = 0; j < pd.n; j++)
-        if (pd.job[j].spec == spec)
+        if (pd.c[j].job.spec == spec)
           { pd.writes.push_back(job);
             return;
           }
@@ -3082,63 +3145,58 @@ static int overlap_mode(void)
 static bool overlap_on(void) { return overlap_mode() != 0; }
 static bool corun_on(void)   { return overlap_mode() == 1; }
 
-static u64 batch_work(void)
-{ static long long w = -1;
-  if (w < 0)
-    { const char *e = getenv("DAMAR_BATCH_WORK");
-      w = e ? atoll(e) : 32768;           /* read pairs: four per wave slot of the launch */
-    }
-  return (u64) w;
+/* The steps of flush_accum: the comparisons held back become a launch. */
+
+/* An entry of the launch queue, i.e. a set of output buffers, with AC's comparisons copied into it.  The oldest launch in
+   flight is completed first while as many are in flight as may be (ReportOpts::queue_depth: it ran beside these seed
+   stages), which waits for it.  Leaves pd.n, oset and c[]; the caller clears AC. */
+static Pending &launch_take(void)
+{ while (PQ_n >= report_opts().queue_depth)
+    finish_oldest();
+  Pending &pd = PQ[(PQ_head + PQ_n) & 1];
+  pd.n = AC.n;
+  pd.oset = (int) (&pd - PQ);
+  for (int j = 0; j < pd.n; j++)
+    pd.c[j] = AC.c[j];
+  return pd;
 }
 
+/* What a launch over pd's comparisons, nwork read pairs in all, starts with:
+     amax, bmax   the longest A and B read of any comparison;  tsmin  the smallest trace spacing
+     cell_cap     pebbles per slot: what the scratch has (DEFAULT_CELLS at first), at most max_cells()
+     rec_cap      records: what the launch's output set has, at least 2 nwork + 4096, at most 2^31 - 1
+     tp_cap       trace values: what the set has, at least 256 per record, at most 0xe0000000
+     t8           trace values as bytes off the device (align.c:3375-3396 Compress_TraceTo8, K8 of SURVEY 8a19):
+                  ReportOpts::device_t8, and 0 unless every comparison of the launch writes byte traces (-s <= 125)
+   (The set's own sizes: asking one set for the other's size plus headroom would grow both for ever.)  With
+   ReportOpts::small_caps, while neither set has been sized: 64 pebbles, 16 records, 512 trace values.  Host arithmetic only. */
+static void launch_size(Pending &pd, u64 nwork)
+{ pd.amax = pd.bmax = 0;  pd.tsmin = 0x7fffffff;
+  pd.t8 = report_opts().device_t8;
+  for (int j = 0; j < pd.n; j++)
+    { const damar_match_job &jb = pd.c[j].job;
+      pd.amax = std::max(pd.amax, jb.ablock->maxlen);  pd.bmax = std::max(pd.bmax, jb.bblock->maxlen);
+      pd.tsmin = std::min(pd.tsmin, Trace_Spacing(jb.spec));
+      if (Trace_Spacing(jb.spec) > TRACE_XOVR)
+        pd.t8 = 0;
+    }
+  const u32 rec_have = RS.rec_cap_set[pd.oset], tp_have = RS.tpool_cap_set[pd.oset];
+  pd.cell_cap = std::min<u32>(RS.cell_cap ? RS.cell_cap : DEFAULT_CELLS, max_cells());
+  pd.rec_cap  = (u32) std::min<u64>(0x7fffffffu, std::max<u64>(rec_have, 2 * nwork + 4096));
+  pd.tp_cap   = (u32) std::min<u64>(0xe0000000ull, std::max<u64>(tp_have, (u64) pd.rec_cap * 256u));
+  if (report_opts().small_caps && RS.rec_cap_set[0] == 0 && RS.rec_cap_set[1] == 0)
+    { pd.cell_cap = 64;  pd.rec_cap = 16;  pd.tp_cap = 512; }
+}
+
+/* Launches the comparisons held back: takes a queue entry, sizes the launch, orders the streams and launches.  Behind
+   the asynchronous tail (overlap_on) the launch goes to G_rep behind the seed stages on G_st (G_front_done), and at
+   DAMAR_OVERLAP=2 the next seed stages go behind it (G_rep_done); otherwise it goes to G_st and is completed here. */
 static void flush_accum(void)
 { if (AC.n == 0)
     return;
   const bool defer = overlap_on();
-  /* an entry of the launch queue, i.e. a set of output buffers: the oldest launch in flight is completed first when both
-     are taken (it ran beside these seed stages) */
-  /* How many launches may be in flight.  Two (the next one queued behind the running one) takes the host out of the
-     hand-over, but measured SLOWER on config 2: 434 - 445 ms per step against 398 - 410 with one.  With one, the host
-     waits here for the running launch, so the seed stream is idle during the last third of every launch -- the phase in
-     which the kernel works through the many short read pairs, whose band filters hammer the bucket arrays; seed sorts that
-     run beside that phase take 180 instead of 100 ms per step. */
-  static int depth = 0;
-  if (depth == 0)
-    { const char *e = getenv("DAMAR_LAUNCH_QUEUE");
-      depth = (e && atoi(e) == 2) ? 2 : 1;
-    }
-  while (PQ_n >= depth)
-    finish_oldest();
-  Pending &pd = PQ[(PQ_head + PQ_n) & 1];
-  const int n = AC.n;
-  pd.n = n;
-  pd.oset = (int) (&pd - PQ);
-  pd.amax = pd.bmax = 0;  pd.tsmin = 0x7fffffff;
-  for (int j = 0; j < n; j++)
-    { pd.job[j] = AC.job[j];  pd.orig[j] = AC.orig[j];  pd.fr[j] = AC.fr[j];  pd.slot[j] = AC.slot[j];
-      pd.ablk[j] = AC.ablk[j];  pd.bblk[j] = AC.bblk[j];
-      pd.amax = std::max(pd.amax, AC.job[j].ablock->maxlen);  pd.bmax = std::max(pd.bmax, AC.job[j].bblock->maxlen);
-      pd.tsmin = std::min(pd.tsmin, Trace_Spacing(AC.job[j].spec));
-    }
-  const u32 rec_have = RS.rec_cap_set[pd.oset], tp_have = RS.tpool_cap_set[pd.oset];     /* (of ITS set: asking one set for the
-                                                                                             other's size plus headroom would grow both for ever) */
-  pd.cell_cap = std::min<u32>(RS.cell_cap ? RS.cell_cap : DEFAULT_CELLS, max_cells());
-  pd.rec_cap  = (u32) std::min<u64>(0x7fffffffu, std::max<u64>(rec_have, 2 * AC.nwork + 4096));
-  pd.tp_cap   = (u32) std::min<u64>(0xe0000000ull, std::max<u64>(tp_have, (u64) pd.rec_cap * 256u));
-  { /* trace values as bytes off the device (align.c:3375-3396 Compress_TraceTo8, K8 of SURVEY 8a19) when every comparison
-       of the launch writes byte traces (-s <= 125); DAMAR_DEVICE_T8=0: 16-bit values, compressed by the host tail as
-       until round 4 */
-    static int want = -1;
-    if (want < 0)
-      want = getenv("DAMAR_DEVICE_T8") ? atoi(getenv("DAMAR_DEVICE_T8")) : 1;
-    pd.t8 = want;
-    for (int j = 0; j < n; j++)
-      if (Trace_Spacing(AC.job[j].spec) > TRACE_XOVR)
-        pd.t8 = 0;
-  }
-  if (getenv("DAMAR_TEST_SMALL_CAPS") && RS.rec_cap_set[0] == 0 && RS.rec_cap_set[1] == 0)        /* tests: start far too small, so that the
-                                                                  overflow flags and the re-launch are exercised */
-    { pd.cell_cap = 64;  pd.rec_cap = 16;  pd.tp_cap = 512; }
+  Pending &pd = launch_take();
+  launch_size(pd, AC.nwork);
   pd.attempt = 0;
   late_streams();
   pd.st = defer ? G_rep : G_st;
@@ -3168,6 +3226,26 @@ static void finish_all(void)
     finish_oldest();
 }
 
+/* a free comparison slot; when there is none, the oldest launch is completed (or, with nothing in flight, the comparisons
+   held back are launched) */
+static int slot_take(void)
+{ for (;;)
+    { for (int i = 0; i < DAMAR_MAX_JOBS; i++)
+        if (!G_slot_busy[i])
+          { G_slot_busy[i] = true;
+            return i;
+          }
+      if (PQ_n > 0)
+        finish_oldest();
+      else
+        flush_accum();
+    }
+}
+
+/* Several comparisons with ONE report launch each time their seed stages are done (kernels.h: DAMAR_MAX_JOBS): the seed
+   stages run one after the other, each into its own arena, then every wavefront of the report kernel works through all
+   the work lists.  The output is that of damar_match called for jobs[0], jobs[1], ... in this order.  Launches are cut
+   at DAMAR_BATCH jobs (default 4, at most DAMAR_MAX_JOBS) and whenever the seed arenas would pass a quarter of HBM. */
 extern "C" void damar_match_batch(damar_match_job *jobs, int njobs)
 { ensure_init();
   const double h0 = now_ms();
@@ -3189,8 +3267,8 @@ extern "C" void damar_match_batch(damar_match_job *jobs, int njobs)
          other options go first */
       if (AC.n > 0)
         { const JobParams now = params_now();
-          const JobParams &was = AC.fr[0].jp;
-          const int16 *s0 = damar_spec_score_table(AC.job[0].spec), *s1 = damar_spec_score_table(jobs[i].spec);
+          const JobParams &was = AC.c[0].fr.jp;
+          const int16 *s0 = damar_spec_score_table(AC.c[0].job.spec), *s1 = damar_spec_score_table(jobs[i].spec);
           bool go = now.kmer != was.kmer || now.hitmin != was.hitmin || now.binshift != was.binshift ||
                     s0[32767] != s1[32767] || s0[0] != s1[0];
           /* an Align_Spec whose files are already asked for (damar_write_overlaps) belongs to a finished block pair: a
@@ -3205,20 +3283,20 @@ extern "C" void damar_match_batch(damar_match_job *jobs, int njobs)
         Q_seg[2] += now_ms() - h0;
       /* a seed stage that has something to report joins the comparisons held back, and the rules that cut a launch apply */
       auto joined = [&](int got, int sl)
-        { const int n = AC.n;
+        { Comparison &c = AC.c[AC.n];               /* (c.fr is the seed stage's: match_front wrote it) */
           if (got != FRONT_READY)
             G_slot_busy[sl] = false;
           else
-            { AC.job[n] = jobs[i];  AC.orig[n] = &jobs[i];  AC.slot[n] = sl;
-              AC.ablk[n] = jobs[i].aidx->blk;  AC.bblk[n] = jobs[i].bidx->blk;
-              AC.bytes += AC.fr[n].bytes;
-              AC.nwork += AC.fr[n].nwork;
-              AC.n = n + 1;
+            { c.job = jobs[i];  c.orig = &jobs[i];  c.slot = sl;
+              c.ablk = jobs[i].aidx->blk;  c.bblk = jobs[i].bidx->blk;
+              AC.bytes += c.fr.bytes;
+              AC.nwork += c.fr.nwork;
+              AC.n += 1;
             }
-          if (AC.n >= hard || AC.bytes > budget || (AC.n >= soft && (!defer || AC.nwork >= batch_work())))
+          if (AC.n >= hard || AC.bytes > budget || (AC.n >= soft && (!defer || AC.nwork >= (u64) report_opts().batch_work)))
             flush_accum();
         };
-      const int got = match_front(&jobs[i], slot, &AC.fr[AC.n], -1);
+      const int got = match_front(&jobs[i], slot, &AC.c[AC.n].fr, -1);
       if (got != FRONT_SPLIT)
         { H_ms[1] += now_ms() - f0;
           joined(got, slot);
@@ -3248,7 +3326,7 @@ extern "C" void damar_match_batch(damar_match_job *jobs, int njobs)
           if (G_keep_seeds && first)
             { G_seed_keys.clear();  G_seed_vals.clear(); }
           first = false;
-          joined(match_front(&jobs[i], slot, &AC.fr[AC.n], sb), slot);
+          joined(match_front(&jobs[i], slot, &AC.c[AC.n].fr, sb), slot);
           slot = -1;
         }
       if (slot >= 0)
@@ -3258,9 +3336,9 @@ extern "C" void damar_match_batch(damar_match_job *jobs, int njobs)
   if (!defer)
     flush_accum();
   for (int j = 0; j < DAMAR_MAX_JOBS; j++)         /* the caller's job structs end with this call */
-    PQ[0].orig[j] = PQ[1].orig[j] = NULL;
+    PQ[0].c[j].orig = PQ[1].c[j].orig = NULL;
   for (int j = 0; j < DAMAR_MAX_JOBS / 2; j++)
-    AC.orig[j] = NULL;
+    AC.c[j].orig = NULL;
   Q_exit = now_ms();
   if (Q_flush > 0)
     Q_seg[0] += Q_exit - Q_flush;
@@ -3322,27 +3400,23 @@ extern "C" int damar_tandem_set_params(int kmer, int binshift, int hitmin, int n
 
 /* The wide kernel behind a two-pair launch of ONE job on G_st (datander: dist, the batch entry: tasks), for the reads /
    tasks that launch left to it (DAMAR_CNT_WIDE: reads of more than DAMAR_MAX_MARKS trace spacings, alignments that
-   overflowed the pebble pool at its largest).  hc = the counters as read behind the launch, updated; a flag left in hc[3]
-   means that the whole launch is to be repeated.  Returns whether the wide kernel ran (then the job's map says whose
-   two-pair records are to be dropped). */
+   overflowed the pebble pool at its largest).  hc = the counters as read behind the launch, updated; a flag left in
+   hc[DAMAR_CNT_FLAGS] means that the whole launch is to be repeated.  Returns whether the wide kernel ran (then the
+   job's map says whose two-pair records are to be dropped). */
 static bool wide_behind(ReportArgs &ra, u32 *hc, u32 cell_cap, const int *dist, const LaTask *tasks, u32 ntasks)
 { if (ra.widemap == NULL || hc[DAMAR_CNT_WIDE] == 0)
     return false;
-  u32 flags = hc[3];
+  u32 flags = hc[DAMAR_CNT_FLAGS];
   if (cell_cap >= max_cells())
     flags &= ~DAMAR_ERR_CELLS;                     /* (those are in the map: nothing to repeat for them) */
   if (flags != 0)
     return false;                                  /* something else ran over: the caller grows it and repeats the launch */
-  if (RS.wcells == NULL)
-    { RS.wslots = std::min(RS.nslots, 64);
-      RS.wcell_cap = 1u << 21;
-      RS.wcells = dmalloc((size_t) 16 * RS.wcell_cap * (size_t) RS.wslots);
-    }
+  wide_pool_ensure();
   ra.wcells = RS.wcells;  ra.wcell_cap = RS.wcell_cap;
   if (VERBOSE || getenv("DAMAR_TEST_MAX_CELLS") != NULL)
     fprintf(stderr, "damar: %u read(s) / task(s) beyond the packed pebble format: wide kernel\n", hc[DAMAR_CNT_WIDE]);
   HIP_CHECK(hipMemsetAsync(RS.ctr + DAMAR_CNT_CURSOR, 0, sizeof(u32) * DAMAR_MAX_JOBS, G_st));
-  HIP_CHECK(hipMemsetAsync(RS.ctr + 3, 0, sizeof(u32), G_st));
+  HIP_CHECK(hipMemsetAsync(RS.ctr + DAMAR_CNT_FLAGS, 0, sizeof(u32), G_st));
   if (dist != NULL)
     damar_launch_tandem_report_wide(&ra, dist, wide_slots(), G_st);
   else
@@ -3350,16 +3424,9 @@ static bool wide_behind(ReportArgs &ra, u32 *hc, u32 cell_cap, const int *dist, 
   HIP_CHECK(hipMemcpyAsync(hc, RS.ctr, sizeof(u32) * DAMAR_COUNTER_WORDS, hipMemcpyDeviceToHost, G_st));
   HIP_CHECK(hipStreamSynchronize(G_st));
   HIP_CHECK(hipGetLastError());
-  if (hc[3] & DAMAR_ERR_CELLS)                     /* the wide kernel's own pool: four times the pebbles, and everything once more */
-    { if (RS.wcell_cap >= (1u << 26))
-        { fprintf(stderr, "damar: FATAL: an alignment needs more than %u trace pebbles even in the wide format\n", RS.wcell_cap);
-          die();
-        }
-      HIP_CHECK(hipFree(RS.wcells));
-      RS.wcell_cap *= 4;
-      RS.wslots = std::max(8, RS.wslots / 2);
-      RS.wcells = dmalloc((size_t) 16 * RS.wcell_cap * (size_t) RS.wslots);
-      hc[3] = (hc[3] & ~DAMAR_ERR_CELLS) | 0x40000000u;
+  if (hc[DAMAR_CNT_FLAGS] & DAMAR_ERR_CELLS)       /* the wide kernel's own pool: four times the pebbles, and everything once more */
+    { wide_pool_grow();
+      hc[DAMAR_CNT_FLAGS] = (hc[DAMAR_CNT_FLAGS] & ~DAMAR_ERR_CELLS) | 0x40000000u;
     }
   return true;
 }
@@ -3438,26 +3505,26 @@ extern "C" void damar_match_self(const HITS_DB *ablock, damar_dev_block *blk, Al
         G_ms[DAMAR_T_REPORT] = lap(4, 5);
         wide_ran = packed && wide_behind(ra, hc, cell_cap, dist, NULL, 0);
         if (packed && !wide_ran && cell_cap >= max_cells() && hc[DAMAR_CNT_WIDE] > 0)
-          hc[3] &= ~DAMAR_ERR_CELLS;
-        if (hc[3] == 0)
+          hc[DAMAR_CNT_FLAGS] &= ~DAMAR_ERR_CELLS;
+        if (hc[DAMAR_CNT_FLAGS] == 0)
           break;
-        hc[3] &= ~0x40000000u;
-        if (((hc[3] & DAMAR_ERR_BAND) && !(hc[3] & (DAMAR_ERR_CELLS | DAMAR_ERR_WIDE))) || attempt >= 6)
-          { fprintf(stderr, "damar: FATAL: tandem report kernel failed (flags %u, where=%u)\n", hc[3], hc[6]);
+        hc[DAMAR_CNT_FLAGS] &= ~0x40000000u;
+        if (((hc[DAMAR_CNT_FLAGS] & DAMAR_ERR_BAND) && !(hc[DAMAR_CNT_FLAGS] & (DAMAR_ERR_CELLS | DAMAR_ERR_WIDE))) || attempt >= 6)
+          { fprintf(stderr, "damar: FATAL: tandem report kernel failed (flags %u, where=%u)\n", hc[DAMAR_CNT_FLAGS], hc[DAMAR_CNT_WHERE]);
             die();
           }
-        if (hc[3] & DAMAR_ERR_CELLS) cell_cap = grow_cells(cell_cap);
-        if (hc[3] & DAMAR_ERR_WIDE)  G_ring *= 4;
-        if (hc[3] & DAMAR_ERR_RECS)  rec_cap = std::max(2 * rec_cap, hc[1] + 1024);
-        if (hc[3] & DAMAR_ERR_TPOOL) tp_cap  = std::max(2 * tp_cap, hc[2] + 65536);
+        if (hc[DAMAR_CNT_FLAGS] & DAMAR_ERR_CELLS) cell_cap = grow_cells(cell_cap);
+        if (hc[DAMAR_CNT_FLAGS] & DAMAR_ERR_WIDE)  G_ring *= 4;
+        if (hc[DAMAR_CNT_FLAGS] & DAMAR_ERR_RECS)  rec_cap = std::max(2 * rec_cap, hc[DAMAR_CNT_RECS] + 1024);
+        if (hc[DAMAR_CNT_FLAGS] & DAMAR_ERR_TPOOL) tp_cap  = std::max(2 * tp_cap, hc[DAMAR_CNT_TPOOL] + 65536);
       }
     P_kmer = sk;  P_hitmin = sh;  P_binshift = sb;
   }
-  recs.resize(hc[1]);
-  tpool.resize(hc[2]);
-  if (hc[1] > 0)
-    { HIP_CHECK(hipMemcpy(recs.data(), RS.recs, sizeof(LaRecord) * (size_t) hc[1], hipMemcpyDeviceToHost));
-      HIP_CHECK(hipMemcpy(tpool.data(), RS.tpool, sizeof(u16) * (size_t) hc[2], hipMemcpyDeviceToHost));
+  recs.resize(hc[DAMAR_CNT_RECS]);
+  tpool.resize(hc[DAMAR_CNT_TPOOL]);
+  if (hc[DAMAR_CNT_RECS] > 0)
+    { HIP_CHECK(hipMemcpy(recs.data(), RS.recs, sizeof(LaRecord) * (size_t) hc[DAMAR_CNT_RECS], hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(tpool.data(), RS.tpool, sizeof(u16) * (size_t) hc[DAMAR_CNT_TPOOL], hipMemcpyDeviceToHost));
     }
   nfilt = hc[DAMAR_CNT_NFILT];
   if (wide_ran)
@@ -3491,7 +3558,7 @@ extern "C" void damar_match_self(const HITS_DB *ablock, damar_dev_block *blk, Al
       i = j;
     }
   free(tp.val);
-  G_cnt[0] = n;  G_cnt[2] = nfilt;  G_cnt[3] = hc[1];
+  G_cnt[0] = n;  G_cnt[2] = nfilt;  G_cnt[3] = hc[DAMAR_CNT_RECS];
   if (counts)
     { counts[0] = n;  counts[1] = nfilt;  counts[2] = ncheck; }
   if (VERBOSE)
@@ -3618,23 +3685,23 @@ extern "C" int damar_local_alignment_batch_opts(damar_dev_block *ablk, damar_dev
       HIP_CHECK(hipGetLastError());
       wide_ran = packed && wide_behind(ra, hc, cell_cap, NULL, dt, (u32) ntasks);
       if (packed && !wide_ran && cell_cap >= max_cells() && hc[DAMAR_CNT_WIDE] > 0)
-        hc[3] &= ~DAMAR_ERR_CELLS;
-      if (hc[3] == 0)
+        hc[DAMAR_CNT_FLAGS] &= ~DAMAR_ERR_CELLS;
+      if (hc[DAMAR_CNT_FLAGS] == 0)
         break;
-      hc[3] &= ~0x40000000u;
-      if (((hc[3] & DAMAR_ERR_BAND) && !(hc[3] & (DAMAR_ERR_CELLS | DAMAR_ERR_WIDE))) || attempt >= 6)
-        { fprintf(stderr, "damar: FATAL: batch Local_Alignment failed (flags %u, where=%u)\n", hc[3], hc[6]);
+      hc[DAMAR_CNT_FLAGS] &= ~0x40000000u;
+      if (((hc[DAMAR_CNT_FLAGS] & DAMAR_ERR_BAND) && !(hc[DAMAR_CNT_FLAGS] & (DAMAR_ERR_CELLS | DAMAR_ERR_WIDE))) || attempt >= 6)
+        { fprintf(stderr, "damar: FATAL: batch Local_Alignment failed (flags %u, where=%u)\n", hc[DAMAR_CNT_FLAGS], hc[DAMAR_CNT_WHERE]);
           die();
         }
-      if (hc[3] & DAMAR_ERR_CELLS) cell_cap = grow_cells(cell_cap);
-      if (hc[3] & DAMAR_ERR_WIDE)  G_ring *= 4;
-      if (hc[3] & DAMAR_ERR_RECS)
-        rec_cap = std::max(2 * rec_cap, hc[1] + 1024);
-      if (hc[3] & DAMAR_ERR_T8)                    /* a value above 255 (t8max): 16-bit values again, as report_launch does */
+      if (hc[DAMAR_CNT_FLAGS] & DAMAR_ERR_CELLS) cell_cap = grow_cells(cell_cap);
+      if (hc[DAMAR_CNT_FLAGS] & DAMAR_ERR_WIDE)  G_ring *= 4;
+      if (hc[DAMAR_CNT_FLAGS] & DAMAR_ERR_RECS)
+        rec_cap = std::max(2 * rec_cap, hc[DAMAR_CNT_RECS] + 1024);
+      if (hc[DAMAR_CNT_FLAGS] & DAMAR_ERR_T8)                    /* a value above 255 (t8max): 16-bit values again, as report_launch does */
         { use8 = 0;
           if (t8_fell_back) *t8_fell_back = 1;
         }
-      if (hc[3] & DAMAR_ERR_TPOOL)
+      if (hc[DAMAR_CNT_FLAGS] & DAMAR_ERR_TPOOL)
         { HIP_CHECK(hipFree(dt));
           if (wmap != NULL)
             HIP_CHECK(hipFree(wmap));
@@ -3642,17 +3709,17 @@ extern "C" int damar_local_alignment_batch_opts(damar_dev_block *ablk, damar_dev
         }
     }
   HIP_CHECK(hipFree(dt));
-  std::vector<LaRecord> recs(hc[1]);
-  std::vector<u16> tp(hc[2]);
-  HIP_CHECK(hipMemcpy(recs.data(), RS.recs, sizeof(LaRecord) * (size_t) hc[1], hipMemcpyDeviceToHost));
+  std::vector<LaRecord> recs(hc[DAMAR_CNT_RECS]);
+  std::vector<u16> tp(hc[DAMAR_CNT_TPOOL]);
+  HIP_CHECK(hipMemcpy(recs.data(), RS.recs, sizeof(LaRecord) * (size_t) hc[DAMAR_CNT_RECS], hipMemcpyDeviceToHost));
   if (use8)
-    { std::vector<u8> tp8(hc[2]);
-      HIP_CHECK(hipMemcpy(tp8.data(), RS.tpool, sizeof(u8) * (size_t) hc[2], hipMemcpyDeviceToHost));
+    { std::vector<u8> tp8(hc[DAMAR_CNT_TPOOL]);
+      HIP_CHECK(hipMemcpy(tp8.data(), RS.tpool, sizeof(u8) * (size_t) hc[DAMAR_CNT_TPOOL], hipMemcpyDeviceToHost));
       for (size_t i = 0; i < tp8.size(); i++)
         tp[i] = tp8[i];
     }
   else
-    HIP_CHECK(hipMemcpy(tp.data(), RS.tpool, sizeof(u16) * (size_t) hc[2], hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(tp.data(), RS.tpool, sizeof(u16) * (size_t) hc[DAMAR_CNT_TPOOL], hipMemcpyDeviceToHost));
   if (wide_ran && wide_tasks)
     *wide_tasks = (int) hc[DAMAR_CNT_WIDE];
   if (wide_ran)
