@@ -83,6 +83,16 @@ class RepeatResult(C.Structure):       # damar_repeat_result
                 ("merged", c_int64), ("bases_total", c_int64), ("bases_repeat", c_int64)]
 
 
+class BoxBatch(C.Structure):           # include/damar_hip.h damar_box_batch
+    _fields_ = [("nbox", c_int64), ("m", _PI), ("n", _PI), ("aoff", C.POINTER(c_int64)), ("boff", C.POINTER(c_int64)),
+                ("bases", C.c_void_p), ("nbases", c_int64)]
+
+
+class TrimStats(C.Structure):          # host/damar_host.h damar_trim_stats
+    _fields_ = [("novl", c_int64), ("ntrimmed", c_int64), ("novl_bases", c_int64), ("ntrim_bases", c_int64),
+                ("written", c_int64), ("discarded", c_int64), ("boxes", c_int64), ("box_a", c_int64), ("box_b", c_int64)]
+
+
 _proto_done = False
 
 
@@ -186,6 +196,10 @@ def _lib():
         L.damar_trim_update.argtypes = [C.POINTER(DbInfo), C.c_char_p, C.POINTER(C.c_uint64), _PI, c_int64, C.POINTER(C.c_uint64), _PI,
                                         C.c_int, C.c_int, C.c_int, C.POINTER(QResult)]
         L.damar_q_result_free.argtypes = [C.POINTER(QResult)]
+        L.damar_align_boxes.argtypes = [C.POINTER(BoxBatch), _PI, C.POINTER(c_int64), C.POINTER(_PI)]
+        L.damar_box_grid.restype = C.c_uint
+        L.damar_box_last.argtypes = [C.POINTER(C.c_double), C.POINTER(c_int64)]
+        L.damar_trim_las.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(TrimStats)]
         _proto_done = True
     return L
 
@@ -609,6 +623,56 @@ def trim_update(db, las, q, trim, trim_q=25, min_len=1000, ccs=False):
     finally:
         L.damar_q_result_free(C.byref(res))
         L.damar_dbinfo_close(C.byref(d))
+
+
+# ---- overlaps cut back to the trim track (LAtrim) and the exact box alignment under it -----------------------------
+
+def align_boxes(a_seqs, b_seqs):
+    """Exact alignment of box i = a_seqs[i] against b_seqs[i] (sequences of base values, one per element, neither empty)
+    as the reference's Compute_Alignment(DIFF_ALIGN) does it: -> (diffs int32[boxes], scripts: a list of int32 arrays, the
+    indels in path order, -(a + 1) for a base of B alone in front of A position a, b + 1 for a base of A alone in front of
+    B position b).  On the GPU, one wavefront per box, unless DAMAR_TRIM=host is set."""
+    import numpy as np
+    L = _lib()
+    if len(a_seqs) != len(b_seqs):
+        raise ValueError("one B sequence per A sequence")
+    nb = len(a_seqs)
+    seqs = [np.ascontiguousarray(x, dtype=np.uint8) for pair in zip(a_seqs, b_seqs) for x in pair]
+    if any(len(x) == 0 for x in seqs):
+        raise ValueError("a box has at least one base on either side")
+    lens = np.array([len(x) for x in seqs], dtype=np.int64).reshape(nb, 2)
+    offs = np.concatenate([[0], np.cumsum(lens.reshape(-1))]).astype(np.int64)
+    bases = np.concatenate(seqs) if nb else np.zeros(1, dtype=np.uint8)
+    m, n = (np.ascontiguousarray(lens[:, k], dtype=np.int32) for k in (0, 1))
+    aoff, boff = np.ascontiguousarray(offs[:-1:2]), np.ascontiguousarray(offs[1::2])
+    bb = BoxBatch(nb, m.ctypes.data_as(_PI), n.ctypes.data_as(_PI), aoff.ctypes.data_as(C.POINTER(c_int64)),
+                  boff.ctypes.data_as(C.POINTER(c_int64)), bases.ctypes.data, int(offs[-1]))
+    diffs, soff, script = np.zeros(max(nb, 1), dtype=np.int32), np.zeros(nb + 1, dtype=np.int64), _PI()
+    if L.damar_align_boxes(C.byref(bb), diffs.ctypes.data_as(_PI), soff.ctypes.data_as(C.POINTER(c_int64)), C.byref(script)):
+        raise RuntimeError("damar_align_boxes failed")
+    try:
+        total = int(soff[nb])
+        flat = np.ctypeslib.as_array(script, shape=(max(total, 1),))[:total].copy()
+    finally:
+        C.CDLL(None).free(script)
+    return diffs[:nb], [flat[soff[i]:soff[i + 1]] for i in range(nb)]
+
+
+def box_last():
+    """Of the last align_boxes / of the last batch of trim_las: ({upload, kernel, download, call} ms, boxes, boxes the host
+    routine did beside the kernel, script values)."""
+    ms, cnt = (C.c_double * 4)(), (c_int64 * 3)()
+    _lib().damar_box_last(ms, cnt)
+    return dict(zip(("upload", "kernel", "download", "call"), list(ms))), cnt[0], cnt[1], cnt[2]
+
+
+def trim_las(db, las, out, track="trim", purge=False):
+    """LAtrim on one .las file: every record cut back to what `track` keeps of both reads, written to `out` (purge: without
+    the records that end up discarded) -> the counters of the run."""
+    st = TrimStats()
+    if _lib().damar_trim_las(db.encode(), las.encode(), out.encode(), track.encode(), 1 if purge else 0, C.byref(st)):
+        raise RuntimeError("damar_trim_las failed")
+    return {k: int(getattr(st, k)) for k, _ in TrimStats._fields_}
 
 
 def read_track(db, name, block=0):

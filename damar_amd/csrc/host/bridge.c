@@ -151,6 +151,65 @@ static Meet middle(const Box *b, int *ws)
     }
 }
 
+/***** the edit script of a box ***************************************************************************/
+
+/* Exact alignment of a box into an edit script (align.c:4653-4732): the indels of one optimal path in path order, a base
+   of B alone as -(a + 1) for the A position a it stands before, a base of A alone as b + 1 for the B position b it stands
+   before, positions counted from the origin (aoff, boff are where this box lies in it).  Substitutions leave no entry.
+   Returns the differences of the box. */
+static int script_box(const char *A, int M, const char *B, int N, int aoff, int boff, int *ws, int **stop)
+{ Box  b;
+  Meet m;
+  int  i;
+  if (M <= 0)
+    { for (i = 0; i < N; i++)
+        *(*stop)++ = -aoff - 1;
+      return N;
+    }
+  if (N <= 0)
+    { for (i = 0; i < M; i++)
+        *(*stop)++ = boff + 1;
+      return M;
+    }
+  b.A = A;  b.B = B;  b.M = M;  b.N = N;
+  m = middle(&b, ws);
+  if (m.diffs >= 2)
+    { /* tie rule: the half in front of the meeting point first */
+      script_box(A, m.col, B, m.row, aoff, boff, ws, stop);
+      script_box(A + m.col, M - m.col, B + m.row, N - m.row, aoff + m.col, boff + m.row, ws, stop);
+    }
+  else if (m.diffs == 1)
+    { /* tie rule: the lone difference of a box that is not square is the indel at the meeting point; a square box holds
+         a substitution */
+      if (M > N)
+        *(*stop)++ = boff + m.row + 1;
+      else if (M < N)
+        *(*stop)++ = -(aoff + m.col) - 1;
+    }
+  return m.diffs;
+}
+
+static __thread int *g_sws = NULL;   static __thread size_t g_swsn = 0;
+
+/* Compute_Alignment(align, work, DIFF_ALIGN, ts) (align.c:4734-4869) for A[0..M) against B[0..N), M, N >= 1, positions
+   counted from the box's own corner.  script holds max(M, N) values at most; *slen receives their number. */
+int damar_exact_box(const char *A, int M, const char *B, int N, int *script, int *slen)
+{ const int big = (M > N) ? M : N;
+  const size_t need = 4 * (size_t) (2 * big + 5) + 16;
+  int *stop = script, diffs;
+  if (need > g_swsn)
+    { g_swsn = need + need / 4 + 10000;
+      g_sws = (int *) realloc(g_sws, sizeof(int) * g_swsn);
+      if (g_sws == NULL)
+        { fprintf(stderr, "damar: out of memory (box alignment)\n");
+          exit(1);
+        }
+    }
+  diffs = script_box(A, M, B, N, 0, 0, g_sws, &stop);
+  *slen = (int) (stop - script);
+  return diffs;
+}
+
 /***** the trace ledger: differences and B-length per trace interval of A ********************************/
 
 typedef struct
@@ -446,4 +505,5 @@ int damar_bridge_pair(const damar_bridge_ctx *ctx, damar_path *jp, damar_path *k
 void damar_bridge_release(void)
 { free(g_ws);  g_ws = NULL;  g_wsn = 0;
   free(g_tr);  g_tr = NULL;  g_trn = 0;
+  free(g_sws);  g_sws = NULL;  g_swsn = 0;
 }

@@ -118,6 +118,22 @@ void damar_q_result_free(damar_q_result *res);
 /* a track of the whole database as damar_track_write_a2 writes it: anno[nreads + 1] and data, malloc'ed.  0, or 1 (no message) */
 int  damar_track_read_a2(const char *dbpath, const char *track, int nreads, uint64 **anno, int **data, int64 *ndata);
 
+/* bridge.c: the exact alignment of one box with its edit script (what damar_align_boxes returns per box): A[0..M) against
+   B[0..N), M, N >= 1; script holds max(M, N) values at most, *slen receives their number; returns the differences */
+int  damar_exact_box(const char *A, int M, const char *B, int N, int *script, int *slen);
+int  damar_trim_on_host(void);                                   /* DAMAR_TRIM=host */
+void damar_piles_rest(const damar_pile_reader *r, const int **diffs, const int **last_word);
+
+/* trim.c: LAtrim (scrub/LAtrim.c, lib/trim.c) as a call: every record of `las` cut back to what the trim track keeps of
+   both reads, written to `out` in file order (purge: without the records that end up discarded).  0, or 1 after a message. */
+typedef struct
+{ int64 novl, ntrimmed;        /* records seen, records cut */
+  int64 novl_bases, ntrim_bases;
+  int64 written, discarded;    /* records written, records flagged for removal */
+  int64 boxes, box_a, box_b;   /* trace segments realigned, and the bases of A and of B in them */
+} damar_trim_stats;
+int  damar_trim_las(const char *db, const char *las, const char *out, const char *track, int purge, damar_trim_stats *st);
+
 /* masks.c: both tools as calls (the commands and the Python interface are argument handling around them) */
 typedef struct
 { int64 *histo;                /* [max_cov], malloc'ed, NULL when no estimate ran */

@@ -133,7 +133,7 @@ struct damar_pile_reader
   int    pend_aread;
   int64 *pile_off;
   int   *pile_aread;
-  int   *col[6];               /* abpos aepos bbpos bepos bread flags */
+  int   *col[8];               /* abpos aepos bbpos bepos bread flags, then diffs and the record's last word (damar_piles_rest) */
   /* traces on (damar_piles_open_traces): the records' trace bytes as they lie in the file, back to back */
   int    traces;
   int64  tbound;               /* bytes of trace a batch holds at most, a pile alone in its batch excepted */
@@ -228,7 +228,7 @@ void damar_piles_close(damar_pile_reader *r)
     return;
   if (r->f) fclose(r->f);
   free(r->pile_off);  free(r->pile_aread);
-  for (i = 0; i < 6; i++) free(r->col[i]);
+  for (i = 0; i < 8; i++) free(r->col[i]);
   free(r->rtrace);  free(r->tbuf);  free(r->toff);  free(r->tlen);
   free(r);
 }
@@ -243,7 +243,7 @@ static int piles_next(damar_pile_reader *r, damar_pile_batch *b)
   memset(b, 0, sizeof(*b));
   r->ttop = 0;
   if (r->pend > 0)
-    { for (i = 0; i < 6; i++)
+    { for (i = 0; i < 8; i++)
         memmove(r->col[i], r->col[i] + r->pstart, sizeof(int) * (size_t) r->pend);
       if (r->traces)
         { const int64 t0 = r->toff[r->pstart];
@@ -273,7 +273,7 @@ static int piles_next(damar_pile_reader *r, damar_pile_batch *b)
       do
         { if (n >= r->cap)
             { r->cap = r->cap + r->cap / 4 + 1024;
-              for (i = 0; i < 6; i++)
+              for (i = 0; i < 8; i++)
                 r->col[i] = (int *) prealloc(r->col[i], sizeof(int) * (size_t) r->cap);
               if (r->traces)
                 { r->toff = (int64 *) prealloc(r->toff, sizeof(int64) * (size_t) r->cap);
@@ -295,6 +295,7 @@ static int piles_next(damar_pile_reader *r, damar_pile_batch *b)
           r->col[0][n] = r->rec[2];  r->col[1][n] = r->rec[4];      /* abpos aepos */
           r->col[2][n] = r->rec[3];  r->col[3][n] = r->rec[5];      /* bbpos bepos */
           r->col[4][n] = r->rec[8];  r->col[5][n] = r->rec[6];      /* bread flags */
+          r->col[6][n] = r->rec[1];  r->col[7][n] = r->rec[9];      /* diffs, the word behind bread */
           n += 1;
           got = next_record(r);
           if (got < 0)
@@ -334,6 +335,13 @@ int damar_piles_next(damar_pile_reader *r, damar_pile_batch *b)
       return -1;
     }
   return piles_next(r, b);
+}
+
+/* what a batch's records hold beside the columns of damar_pile_batch, for a tool that writes records back (LAtrim): their
+   differences and the unused word that ends the 40 bytes of a record in the file */
+void damar_piles_rest(const damar_pile_reader *r, const int **diffs, const int **last_word)
+{ *diffs = r->col[6];
+  *last_word = r->col[7];
 }
 
 /* the next batch with its traces: record i's tlen[i] values of tbytes bytes begin at trace + trace_off[i] */

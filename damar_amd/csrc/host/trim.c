@@ -1,0 +1,556 @@
+/* trim.c -- LAtrim: every overlap record cut back to the part of both reads that the trim track keeps (lib/trim.c:188-470
+ * trim_overlap, around it scrub/LAtrim.c and the record loop of lib/pass.c).
+ *
+ * A cut on A drops whole trace segments and moves the A coordinates.  A cut on B that falls inside a trace segment needs
+ * that one segment aligned exactly: the cut's A coordinate and the differences on either side of it are read off the
+ * optimal path.  The reference aligns as it meets the records.  Here a batch of whole piles goes through three phases:
+ *   plan    -- from the trim track and the trace alone: each record's fate, everything of its new coordinates and trace
+ *              that no alignment decides, and the boxes (at most a left and a right one) it wants aligned;
+ *   align   -- all boxes of the batch in one damar_align_boxes call (kernels/box_align.hip, or the host routine);
+ *   settle  -- each box's script walked for the cut, the left box's values patched in before the right one's, the final
+ *              discard test and the differences summed again from the trace.
+ * Nothing here touches the GPU runtime but that one call. */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "damar_hip.h"
+#include "damar_host.h"
+
+#define OVL_COMP_FLAG    0x1              /* lib/oflags.h */
+#define OVL_DISCARD_FLAG 0x2
+#define OVL_TEMP_FLAG    0x800
+#define OVL_TRIM_FLAG    0x20000
+
+static void *tmalloc(void *q, size_t n)
+{ void *p = realloc(q, n ? n : 1);
+  if (p == NULL)
+    { fprintf(stderr, "damar: out of memory (%zu bytes, trim)\n", n);
+      exit(1);
+    }
+  return p;
+}
+
+int damar_trim_on_host(void)
+{ const char *e = getenv("DAMAR_TRIM");
+  return e != NULL && strcmp(e, "host") == 0;
+}
+
+/***** the trim track ***************************************************************************/
+
+typedef struct
+{ uint64 *anno;                /* [nreads + 1] byte offsets */
+  int    *data;
+  int64   ndata;
+} TrimTrack;
+
+/* the uncompressed form (db/DB.c Load_Track): int len, int size, len + 1 offsets of `size` bytes; the data file */
+static int read_anno_data(const damar_dbinfo *db, const char *track, TrimTrack *t)
+{ char  path[4500];
+  FILE *af, *df = NULL;
+  int   len, size, j, rc = 1;
+  snprintf(path, sizeof(path), "%s.%s.anno", db->path, track);
+  if ((af = fopen(path, "r")) == NULL)
+    return 1;
+  snprintf(path, sizeof(path), "%s.%s.data", db->path, track);
+  if (fread(&len, sizeof(int), 1, af) != 1 || fread(&size, sizeof(int), 1, af) != 1 || (size != 4 && size != 8) ||
+      len != db->nreads || (df = fopen(path, "r")) == NULL)
+    goto done;
+  t->anno = (uint64 *) tmalloc(NULL, sizeof(uint64) * ((size_t) db->nreads + 1));
+  for (j = 0; j <= db->nreads; j++)
+    { int64 v8 = 0;
+      int   v4 = 0;
+      if (fread(size == 4 ? (void *) &v4 : (void *) &v8, (size_t) size, 1, af) != 1)
+        goto done;
+      t->anno[j] = (uint64) (size == 4 ? v4 : v8);
+    }
+  t->ndata = (int64) (t->anno[db->nreads] / sizeof(int));
+  t->data = (int *) tmalloc(NULL, sizeof(int) * (size_t) t->ndata);
+  if (t->ndata > 0 && fread(t->data, sizeof(int), (size_t) t->ndata, df) != (size_t) t->ndata)
+    goto done;
+  rc = 0;
+done:
+  fclose(af);
+  if (df) fclose(df);
+  if (rc)
+    { free(t->anno);  free(t->data);
+      memset(t, 0, sizeof(*t));
+    }
+  return rc;
+}
+
+/* lib/utils.c:258-284: a read without an entry, or with an empty one, keeps nothing */
+static void trim_of(const TrimTrack *t, int rid, int *b, int *e)
+{ const uint64 ob = t->anno[rid] / sizeof(int), oe = t->anno[rid + 1] / sizeof(int);
+  *b = *e = 0;
+  if (oe - ob >= 2 && oe <= (uint64) t->ndata && t->data[ob] < t->data[ob + 1])
+    { *b = t->data[ob];
+      *e = t->data[ob + 1];
+    }
+}
+
+/***** plan *************************************************************************************/
+
+enum { FATE_ASIS = 0, FATE_GONE, FATE_CUT };
+
+typedef struct                 /* a trace segment to align: A[ab, ae) against B[bb, be), the cut at B position stop */
+{ int ab, ae, bb, be, stop;
+} Seg;
+
+typedef struct
+{ int   fate;
+  int   t0, tlen;              /* the trace values kept: [t0, t0 + tlen) of the record's */
+  int   abpos, aepos, bbpos, bepos;
+  int   a_lo, a_hi;            /* A coordinates the cuts are measured from (what the cut on A left) */
+  int   keep_lo, keep_hi;      /* what the trim track keeps of B, in the record's orientation */
+  int64 lbox, rbox;            /* the record's boxes in the batch's list, -1: none */
+  int64 known;                 /* trimmed bases that no alignment decides */
+} Plan;
+
+typedef struct
+{ Seg   *seg;
+  int64 *rec;                  /* the record a box belongs to */
+  int64  n, cap;
+} SegList;
+
+static int64 add_seg(SegList *L, int64 rec, int ab, int ae, int bb, int be, int stop)
+{ if (L->n >= L->cap)
+    { L->cap = L->cap + L->cap / 4 + 1024;
+      L->seg = (Seg *) tmalloc(L->seg, sizeof(Seg) * (size_t) L->cap);
+      L->rec = (int64 *) tmalloc(L->rec, sizeof(int64) * (size_t) L->cap);
+    }
+  L->seg[L->n].ab = ab;  L->seg[L->n].ae = ae;  L->seg[L->n].bb = bb;  L->seg[L->n].be = be;  L->seg[L->n].stop = stop;
+  L->rec[L->n] = rec;
+  return L->n++;
+}
+
+/* One record: tr is its trace, two values (differences, B length) per segment, and is patched where the new value is
+   known already.  tw: the trace spacing.  trim.c:188-424 without the two alignments. */
+static void plan_record(Plan *p, uint16 *tr, int tlen, int tw, int a_lo, int a_hi, int b_lo, int b_hi, int64 rec, SegList *L,
+                        damar_trim_stats *st)
+{ int abt, aet, bbt, bet, j;
+
+  p->lbox = p->rbox = -1;
+  p->known = 0;
+  p->t0 = 0;
+  p->tlen = tlen;
+  p->keep_lo = b_lo;  p->keep_hi = b_hi;
+  abt = (a_lo > p->abpos) ? a_lo : p->abpos;
+  aet = (a_hi < p->aepos) ? a_hi : p->aepos;
+  bbt = (b_lo > p->bbpos) ? b_lo : p->bbpos;
+  bet = (b_hi < p->bepos) ? b_hi : p->bepos;
+  if (abt >= aet || bbt >= bet)
+    { p->fate = FATE_GONE;
+      return;
+    }
+  if (abt == p->abpos && aet == p->aepos && bbt == p->bbpos && bet == p->bepos)
+    { p->fate = FATE_ASIS;
+      return;
+    }
+  p->fate = FATE_CUT;
+  st->ntrimmed += 1;
+
+  if (abt != p->abpos || aet != p->aepos)                      /* whole segments go, B follows by their lengths */
+    { int drop = abt / tw - p->abpos / tw;
+      for (j = 0; j < drop; j++)
+        p->bbpos += tr[2 * j + 1];
+      p->t0 = 2 * drop;
+      p->tlen -= 2 * drop;
+      drop = (p->aepos - 1) / tw - (aet - 1) / tw;
+      for (j = 0; j < drop; j++)
+        p->bepos -= tr[p->t0 + p->tlen - 1 - 2 * j];
+      p->tlen -= 2 * drop;
+      p->abpos = abt;
+      p->aepos = aet;
+    }
+  p->a_lo = p->abpos;
+  p->a_hi = p->aepos;
+
+  bbt = (b_lo > p->bbpos) ? b_lo : p->bbpos;
+  bet = (b_hi < p->bepos) ? b_hi : p->bepos;
+  if (bbt >= bet || (bbt == p->bbpos && bet == p->bepos))
+    return;
+
+  if (p->bbpos < bbt)                                          /* the segment the left cut falls in becomes the first */
+    { uint16 *t = tr + p->t0;
+      int sab = p->abpos, sae = (p->abpos / tw + 1) * tw, sbb = p->bbpos, sbe = p->bbpos + t[1];
+      for (j = 2; j < p->tlen; j += 2)
+        { if (sbb <= bbt && sbe > bbt)
+            break;
+          sab = sae;  sae += tw;
+          sbb = sbe;  sbe += t[j + 1];
+        }
+      if (sbb != bbt)
+        { p->lbox = add_seg(L, rec, sab, sae, sbb, sbe, bbt);
+          t[j - 1] = (uint16) (sbe - bbt);
+          p->known += bbt - p->bbpos;
+        }
+      else                                                     /* exactly on a segment's B boundary: nothing to align */
+        { p->known += (sab - p->abpos) + (sbb - p->bbpos);
+          p->abpos = sab;
+        }
+      p->bbpos = bbt;
+      p->t0 += j - 2;
+      p->tlen -= j - 2;
+    }
+
+  if (p->bepos > bet)                                          /* ... and the one of the right cut the last */
+    { uint16 *t = tr + p->t0;
+      int sae = p->aepos, sab = (sae % tw) ? sae - sae % tw : sae - tw;
+      int sbe = p->bepos, sbb = sbe - t[p->tlen - 1];          /* the first segment's B start is what the left cut set */
+      for (j = p->tlen - 4; j >= 0; j -= 2)
+        { if (sbb < bet && sbe >= bet)
+            break;
+          sae = sab;  sab -= tw;
+          sbe = sbb;  sbb -= t[j + 1];
+        }
+      if (sbe != bet)
+        { p->rbox = add_seg(L, rec, sab, sae, sbb, sbe, bet);
+          t[j + 3] = (uint16) (bet - sbb);
+          p->known += p->bepos - bet;
+        }
+      else
+        { p->known += (p->aepos - sae) + (p->bepos - sbe);
+          p->aepos = sae;
+        }
+      p->bepos = bet;
+      p->tlen = j + 4;
+    }
+}
+
+/***** settle ***********************************************************************************/
+
+/* Where the path of a box crosses B position `stop` (all positions counted from the box's corner), and the differences
+   on either side of that point: trim.c:71-158. */
+typedef struct { const char *A, *B; int a, b, diffs, stop, stop_a, left; } Walk;
+
+static void note_cut(Walk *w)
+{ if (w->b == w->stop)
+    { w->stop_a = w->a;
+      w->left = w->diffs;
+      w->diffs = 0;
+    }
+}
+
+static void walk_column(Walk *w)                               /* a base of A over a base of B */
+{ if (w->A[w->a] != w->B[w->b])
+    w->diffs += 1;
+  w->a += 1;
+  w->b += 1;
+  note_cut(w);
+}
+
+static void walk_script(const char *A, int M, const char *B, const int *script, int slen, int stop, int *stop_a, int *dl, int *dr)
+{ Walk w;
+  int  t;
+  w.A = A;  w.B = B;  w.a = w.b = w.diffs = w.stop_a = w.left = 0;  w.stop = stop;
+  for (t = 0; t < slen; t++)
+    { const int p = script[t];
+      if (p < 0)                                               /* a base of B alone, in front of A position -p - 1 */
+        { while (w.a < -p - 1)
+            walk_column(&w);
+          w.diffs += 1;
+          w.b += 1;
+          note_cut(&w);
+        }
+      else                                                     /* a base of A alone, in front of B position p - 1 */
+        { while (w.b < p - 1)
+            walk_column(&w);
+          w.diffs += 1;
+          w.a += 1;
+        }
+    }
+  while (w.a < M)
+    walk_column(&w);
+  *stop_a = w.stop_a;
+  *dl = w.left;
+  *dr = w.diffs;
+}
+
+/***** the pass *********************************************************************************/
+
+/* B read r's bases [from, to) as the alignment sees them: the read itself, or its complement */
+static void gather_b(const HITS_DB *blk, int r, int comp, int from, int to, char *dst)
+{ const char *s = (const char *) blk->bases + blk->reads[r].boff;
+  const int   len = blk->reads[r].rlen;
+  int i;
+  for (i = from; i < to; i++)
+    if (i < 0 || i >= len)
+      *dst++ = 4;
+    else
+      *dst++ = comp ? (char) (3 - s[len - 1 - i]) : s[i];
+}
+
+/* The A side of a box ends on a segment boundary, which for a cut in a read's last segment lies beyond the read's end.  The
+   reference aligns what its read buffer holds there: the end mark, then the bases of the last longer read that was loaded
+   for an alignment before.  That buffer is kept here as the reference keeps it, so that such a box sees the same bases. */
+typedef struct
+{ char *base;                  /* maxlen + one spacing of room, zero at the start */
+  int   room, holds;           /* holds: the read loaded last, -1 none */
+} ABuffer;
+
+static void load_a(ABuffer *ab, const HITS_DB *blk, int r)
+{ if (ab->holds != r)
+    { const int len = blk->reads[r].rlen;
+      memcpy(ab->base, (const char *) blk->bases + blk->reads[r].boff, (size_t) len);
+      ab->base[len] = 4;
+      ab->holds = r;
+    }
+}
+
+int damar_trim_las(const char *dbname, const char *las, const char *out, const char *track, int purge, damar_trim_stats *st)
+{ damar_dbinfo db;
+  HITS_DB   blk;
+  TrimTrack tt;
+  damar_pile_reader *r = NULL;
+  damar_trace_batch  t;
+  FILE   *fo = NULL;
+  uint16 *tr = NULL;           /* the batch's traces, two bytes a value */
+  int64  *troff = NULL;        /* per record: where its values begin in tr */
+  Plan   *plan = NULL;
+  SegList L;
+  ABuffer abuf;
+  char   *bases = NULL;
+  int    *arec = NULL;         /* per record: its A read */
+  int    *bm = NULL, *bn = NULL, *bdiffs = NULL, *script = NULL;
+  int64  *baoff = NULL, *bboff = NULL, *soff = NULL;
+  unsigned char *obuf = NULL;
+  int64   trcap = 0, rcap = 0, bcap = 0, basecap = 0, ocap = 0, written = 0, i;
+  int     got, rc = 1, have_db = 0, have_blk = 0, tw, tbytes;
+
+  memset(st, 0, sizeof(*st));
+  memset(&tt, 0, sizeof(tt));
+  memset(&L, 0, sizeof(L));
+  memset(&abuf, 0, sizeof(abuf));
+  if (damar_dbinfo_open(dbname, &db))
+    return 1;
+  have_db = 1;
+  if (damar_track_read_a2(db.path, track, db.nreads, &tt.anno, &tt.data, &tt.ndata) && read_anno_data(&db, track, &tt))
+    { /* the loader's line first, as the reference prints it: it never sets its program name */
+      fprintf(stderr, "(null): Track '%s' does not exist\n", track);
+      fprintf(stderr, "could not open trim track '%s'\n", track);
+      goto done;
+    }
+  if (damar_read_block(dbname, &blk))
+    goto done;
+  have_blk = 1;
+  if ((r = damar_piles_open_traces(las, 0, 0)) == NULL)
+    goto done;
+  if ((fo = fopen(out, "w")) == NULL)
+    { fprintf(stderr, "could not open '%s'\n", out);
+      goto done;
+    }
+  tw = damar_piles_tspace(r);
+  tbytes = (tw <= TRACE_XOVR) ? 1 : 2;
+  abuf.room = db.maxlen + (tw > 0 ? tw : 0) + 8;
+  abuf.base = (char *) tmalloc(NULL, (size_t) abuf.room);
+  memset(abuf.base, 0, (size_t) abuf.room);
+  abuf.holds = -1;
+  { const int64 zero = 0;
+    if (fwrite(&zero, sizeof(int64), 1, fo) != 1 || fwrite(&tw, sizeof(int), 1, fo) != 1)
+      goto wfail;
+  }
+
+  while ((got = damar_piles_next_traces(r, &t)) > 0)
+    { const damar_pile_batch *b = &t.p;
+      const int *rdiffs, *rlast;
+      int64 nval = 0, pi, nbase = 0, k;
+      damar_box_batch bb;
+
+      damar_piles_rest(r, &rdiffs, &rlast);
+      for (i = 0; i < b->nrec; i++) nval += t.tlen[i];
+      if (nval > trcap)
+        { trcap = nval + nval / 4 + 1024;
+          tr = (uint16 *) tmalloc(tr, sizeof(uint16) * (size_t) trcap);
+        }
+      if (b->nrec > rcap)
+        { rcap = b->nrec + b->nrec / 4 + 1024;
+          troff = (int64 *) tmalloc(troff, sizeof(int64) * (size_t) rcap);
+          plan = (Plan *) tmalloc(plan, sizeof(Plan) * (size_t) rcap);
+          arec = (int *) tmalloc(arec, sizeof(int) * (size_t) rcap);
+        }
+      for (i = 0, nval = 0; i < b->nrec; i++)
+        { const unsigned char *src = t.trace + t.trace_off[i];
+          troff[i] = nval;
+          if (tbytes == 1)
+            for (k = 0; k < t.tlen[i]; k++) tr[nval + k] = src[k];
+          else
+            memcpy(tr + nval, src, sizeof(uint16) * (size_t) t.tlen[i]);
+          nval += t.tlen[i];
+        }
+
+      /* plan */
+      L.n = 0;
+      for (pi = 0; pi < b->npiles; pi++)
+        { const int a = b->pile_aread[pi];
+          int a_lo, a_hi;
+          if (a < 0 || a >= db.nreads)
+            { fprintf(stderr, "damar: %s holds reads the database does not have\n", las);
+              goto done;
+            }
+          trim_of(&tt, a, &a_lo, &a_hi);
+          for (i = b->pile_off[pi]; i < b->pile_off[pi + 1]; i++)
+            { Plan *p = plan + i;
+              const int br = b->bread[i];
+              int b_lo, b_hi;
+              arec[i] = a;
+              if (br < 0 || br >= db.nreads || t.tlen[i] < 2 || (t.tlen[i] & 1))
+                { fprintf(stderr, "damar: %s: record %lld is malformed\n", las, (long long) (st->novl + i));
+                  goto done;
+                }
+              p->abpos = b->abpos[i];  p->aepos = b->aepos[i];  p->bbpos = b->bbpos[i];  p->bepos = b->bepos[i];
+              st->novl_bases += (p->aepos - p->abpos) + (p->bepos - p->bbpos);
+              trim_of(&tt, br, &b_lo, &b_hi);
+              if (a_lo >= a_hi || b_lo >= b_hi)
+                { p->fate = FATE_GONE;
+                  p->t0 = 0;  p->tlen = t.tlen[i];
+                  p->lbox = p->rbox = -1;
+                  continue;
+                }
+              if (b->flags[i] & OVL_COMP_FLAG)
+                { const int blen = db.read_len[br], q = b_lo;
+                  b_lo = blen - b_hi;
+                  b_hi = blen - q;
+                }
+              plan_record(p, tr + troff[i], t.tlen[i], tw, a_lo, a_hi, b_lo, b_hi, i, &L, st);
+            }
+        }
+      st->novl += b->nrec;
+
+      /* align */
+      if (L.n > bcap)
+        { bcap = L.n + L.n / 4 + 1024;
+          bm = (int *) tmalloc(bm, sizeof(int) * (size_t) bcap);
+          bn = (int *) tmalloc(bn, sizeof(int) * (size_t) bcap);
+          bdiffs = (int *) tmalloc(bdiffs, sizeof(int) * (size_t) bcap);
+          baoff = (int64 *) tmalloc(baoff, sizeof(int64) * (size_t) bcap);
+          bboff = (int64 *) tmalloc(bboff, sizeof(int64) * (size_t) bcap);
+          soff = (int64 *) tmalloc(soff, sizeof(int64) * ((size_t) bcap + 1));
+        }
+      for (k = 0; k < L.n; k++)
+        { bm[k] = L.seg[k].ae - L.seg[k].ab;
+          bn[k] = L.seg[k].be - L.seg[k].bb;
+          st->box_a += bm[k];
+          st->box_b += bn[k];
+          baoff[k] = nbase;
+          bboff[k] = nbase + bm[k];
+          nbase += bm[k] + bn[k];
+        }
+      if (nbase > basecap)
+        { basecap = nbase + nbase / 4 + 4096;
+          bases = (char *) tmalloc(bases, (size_t) basecap);
+        }
+      for (k = 0; k < L.n; k++)
+        { const int64 rec = L.rec[k];
+          load_a(&abuf, &blk, arec[rec]);
+          for (i = 0; i < bm[k]; i++)
+            bases[baoff[k] + i] = (L.seg[k].ab + i < abuf.room) ? abuf.base[L.seg[k].ab + i] : 4;
+          gather_b(&blk, b->bread[rec], b->flags[rec] & OVL_COMP_FLAG, L.seg[k].bb, L.seg[k].be, bases + bboff[k]);
+        }
+      script = NULL;
+      if (L.n > 0)
+        { bb.nbox = L.n;  bb.m = bm;  bb.n = bn;  bb.aoff = baoff;  bb.boff = bboff;  bb.bases = bases;  bb.nbases = nbase;
+          if (damar_align_boxes(&bb, bdiffs, soff, &script))
+            goto done;
+          st->boxes += L.n;
+        }
+
+      /* settle, and the records as they go to the file */
+      for (i = 0; i < b->nrec; i++)
+        { Plan   *p = plan + i;
+          uint16 *v = tr + troff[i] + p->t0;
+          int     flags = b->flags[i], diffs = rdiffs[i], rec[10];
+          int64   need;
+          if (p->fate == FATE_GONE)
+            flags |= OVL_DISCARD_FLAG | OVL_TRIM_FLAG;
+          else if (p->fate == FATE_CUT)
+            { int stop_a, dl, dr;
+              st->ntrim_bases += p->known;
+              if (p->lbox >= 0)
+                { const Seg *s = L.seg + p->lbox;
+                  walk_script(bases + baoff[p->lbox], bm[p->lbox], bases + bboff[p->lbox], script + soff[p->lbox],
+                              (int) (soff[p->lbox + 1] - soff[p->lbox]), s->stop - s->bb, &stop_a, &dl, &dr);
+                  stop_a += s->ab;
+                  v[0] = (uint16) dr;
+                  if (s->ae == stop_a)                         /* the cut would leave an empty first segment */
+                    stop_a -= 1;
+                  st->ntrim_bases += stop_a - p->a_lo;
+                  p->abpos = stop_a;
+                }
+              if (p->rbox >= 0)
+                { const Seg *s = L.seg + p->rbox;
+                  walk_script(bases + baoff[p->rbox], bm[p->rbox], bases + bboff[p->rbox], script + soff[p->rbox],
+                              (int) (soff[p->rbox + 1] - soff[p->rbox]), s->stop - s->bb, &stop_a, &dl, &dr);
+                  stop_a += s->ab;
+                  v[p->tlen - 2] = (uint16) dl;
+                  st->ntrim_bases += p->a_hi - stop_a;
+                  p->aepos = stop_a;
+                }
+              /* what is left may cover next to nothing of either read (trim.c:442) */
+              if (p->abpos >= p->aepos || p->bepos < p->keep_lo || p->bbpos > p->keep_hi)
+                flags |= OVL_DISCARD_FLAG | OVL_TRIM_FLAG;
+              else
+                { int j;
+                  diffs = 0;
+                  for (j = 0; j < p->tlen; j += 2)
+                    diffs += v[j];
+                }
+            }
+          if (flags & OVL_DISCARD_FLAG)
+            { st->discarded += 1;
+              if (purge)
+                continue;
+            }
+          rec[0] = p->tlen;  rec[1] = diffs;
+          rec[2] = (p->fate == FATE_CUT) ? p->abpos : b->abpos[i];  rec[3] = (p->fate == FATE_CUT) ? p->bbpos : b->bbpos[i];
+          rec[4] = (p->fate == FATE_CUT) ? p->aepos : b->aepos[i];  rec[5] = (p->fate == FATE_CUT) ? p->bepos : b->bepos[i];
+          rec[6] = flags & ~OVL_TEMP_FLAG;
+          rec[7] = arec[i];  rec[8] = b->bread[i];  rec[9] = rlast[i];
+          need = 40 + (int64) tbytes * p->tlen;
+          if (need > ocap)
+            { ocap = need + need / 4 + 1024;
+              obuf = (unsigned char *) tmalloc(obuf, (size_t) ocap);
+            }
+          if (tbytes == 1)
+            for (k = 0; k < p->tlen; k++)
+              { if (v[k] > 255)
+                  { fprintf(stderr, "LAtrim: Compression of trace to bytes fails, value too big\n");
+                    free(script);
+                    goto done;
+                  }
+                obuf[40 + k] = (unsigned char) v[k];
+              }
+          else
+            memcpy(obuf + 40, v, sizeof(uint16) * (size_t) p->tlen);
+          memcpy(obuf, rec, 40);
+          if (fwrite(obuf, 1, (size_t) need, fo) != (size_t) need)
+            { free(script);
+              goto wfail;
+            }
+          written += 1;
+        }
+      free(script);
+    }
+  if (got < 0)
+    goto done;
+  st->written = written;
+  rewind(fo);
+  if (fwrite(&written, sizeof(int64), 1, fo) != 1)
+    goto wfail;
+  rc = 0;
+  goto done;
+wfail:
+  fprintf(stderr, "damar: cannot write %s\n", out);
+done:
+  if (fo != NULL && fclose(fo) != 0 && rc == 0)
+    { fprintf(stderr, "damar: cannot write %s\n", out);
+      rc = 1;
+    }
+  damar_piles_close(r);
+  if (have_blk) damar_close_block(&blk);
+  if (have_db) damar_dbinfo_close(&db);
+  free(tt.anno);  free(tt.data);
+  free(tr);  free(troff);  free(plan);  free(arec);  free(L.seg);  free(L.rec);
+  free(abuf.base);  free(bases);  free(bm);  free(bn);  free(bdiffs);  free(baoff);  free(bboff);  free(soff);  free(obuf);
+  return rc;
+}

@@ -388,6 +388,25 @@ void damar_launch_q_count(const QArgs *a, hipStream_t st);
 void damar_launch_q_scatter(const QArgs *a, hipStream_t st);
 void damar_launch_q_select(const QArgs *a, hipStream_t st);
 
+/* box_align.hip: exact alignment of a batch of boxes with their edit scripts (align.c:4734 DIFF_ALIGN).  A box with
+   max(m, n) <= maxlen <= DAMAR_BOX_MAXLEN is done and leaves its differences, the length of its script (-1: it hit a bound of
+   the kernel and is the host's after all) and the script at script + coff[box], max(m, n) values of room; the others are
+   not touched. */
+#define DAMAR_BOX_MAXLEN 1000
+typedef struct
+{ u32 nbox;
+  int maxlen;
+  const int *m, *n;                   /* [nbox] */
+  const long long *aoff, *boff;       /* [nbox] bytes into bases */
+  const long long *coff;              /* [nbox] values into script */
+  const u8  *bases;
+  int *diffs, *slen;                  /* [nbox] */
+  int *script;
+} BoxArgs;
+
+void damar_launch_box_align(const BoxArgs *a, hipStream_t st);
+u32  damar_box_align_grid(void);      /* workgroups of the largest launch: beyond that many boxes a workgroup does several */
+
 /* trace_pts.hip: Compute_Trace_PTS for batches of records (align.c:5577-5692, 4892-5261) */
 typedef struct
 { u32 aread, bread;       /* block-local read ids */

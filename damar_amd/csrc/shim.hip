@@ -4613,3 +4613,122 @@ extern "C" int damar_pile_quality(const damar_trace_batch *t, const damar_q_para
     }
   return 0;
 }
+
+/***** exact alignment of a batch of boxes with their edit scripts: Compute_Alignment(DIFF_ALIGN) (kernels/box_align.hip) ******/
+
+static DBuf BX_m, BX_n, BX_aoff, BX_boff, BX_coff, BX_bases, BX_diffs, BX_slen, BX_script;
+static double BX_ms[4];        /* of the last call: upload, kernel, download (HIP events), whole call (wall) */
+static int64  BX_cnt[3];       /* boxes, boxes the host routine did beside the kernel, script values */
+static hipEvent_t BX_ev[4];
+static int    BX_ev_made;
+
+extern "C" void damar_box_release(void)
+{ DBuf *all[] = { &BX_m, &BX_n, &BX_aoff, &BX_boff, &BX_coff, &BX_bases, &BX_diffs, &BX_slen, &BX_script };
+  for (DBuf *b : all) b->drop();
+  if (BX_ev_made)
+    for (int i = 0; i < 4; i++) (void) hipEventDestroy(BX_ev[i]);
+  BX_ev_made = 0;
+}
+
+extern "C" unsigned int damar_box_grid(void) { return damar_box_align_grid(); }
+
+extern "C" void damar_box_last(double *ms, int64 *cnt)
+{ for (int i = 0; i < 4; i++) ms[i] = BX_ms[i];
+  for (int i = 0; i < 3; i++) cnt[i] = BX_cnt[i];
+}
+
+extern "C" int damar_align_boxes(const damar_box_batch *b, int *diffs, int64 *soff, int **script)
+{ const double w0 = now_ms();
+  if (b == NULL || soff == NULL || script == NULL || b->nbox < 0 || (b->nbox > 0 && diffs == NULL))
+    { fprintf(stderr, "damar: boxes: malformed batch\n");
+      return 1;
+    }
+  const size_t nb = (size_t) b->nbox;
+  if (b->nbox >= ((int64) 1 << 31))
+    { fprintf(stderr, "damar: boxes: a batch holds fewer than 2^31 boxes\n");
+      return 1;
+    }
+  for (size_t i = 0; i < nb; i++)
+    if (b->m[i] < 1 || b->n[i] < 1 || b->aoff[i] < 0 || b->boff[i] < 0 || b->aoff[i] + b->m[i] > b->nbases || b->boff[i] + b->n[i] > b->nbases)
+      { fprintf(stderr, "damar: boxes: box %zu (%d x %d) does not lie inside the %lld bases\n", i, b->m[i], b->n[i], (long long) b->nbases);
+        return 1;
+      }
+  /* every box gets max(m, n) values of room; the scripts are moved together at the end */
+  std::vector<long long> room(nb + 1);
+  room[0] = 0;
+  for (size_t i = 0; i < nb; i++)
+    room[i + 1] = room[i] + std::max(b->m[i], b->n[i]);
+  std::vector<int> wide((size_t) room[nb] + 1), slen(nb, -1);
+  for (int i = 0; i < 4; i++) BX_ms[i] = 0;
+  int64 fallback = 0;
+
+  const bool host = damar_trim_on_host();
+  int maxlen = DAMAR_BOX_MAXLEN;
+  if (getenv("DAMAR_TEST_BOX_LIMIT") && atoi(getenv("DAMAR_TEST_BOX_LIMIT")) < maxlen)
+    maxlen = atoi(getenv("DAMAR_TEST_BOX_LIMIT"));
+  if (!host && nb > 0)
+    { ensure_init();
+      /* a tool built on this call is through a few milliseconds after the library comes up: its launch, its copies and
+         the frees of damar_box_release would all run beside the start-up thread, which is inside HIP calls of its own for
+         longer than that.  The process cannot end before that thread does (helpers_join), so waiting here costs nothing. */
+      late_streams();
+      if (!BX_ev_made)
+        { for (int i = 0; i < 4; i++) HIP_CHECK(hipEventCreate(&BX_ev[i]));
+          BX_ev_made = 1;
+        }
+      BoxArgs a;
+      memset(&a, 0, sizeof(a));
+      a.nbox = (u32) nb;
+      a.maxlen = maxlen;
+      int *d_m = (int *) BX_m.need(sizeof(int) * nb), *d_n = (int *) BX_n.need(sizeof(int) * nb);
+      long long *d_aoff = (long long *) BX_aoff.need(sizeof(long long) * nb), *d_boff = (long long *) BX_boff.need(sizeof(long long) * nb);
+      long long *d_coff = (long long *) BX_coff.need(sizeof(long long) * (nb + 1));
+      u8  *d_bases = (u8 *) BX_bases.need((size_t) b->nbases + 16);
+      int *d_diffs = (int *) BX_diffs.need(sizeof(int) * nb), *d_slen = (int *) BX_slen.need(sizeof(int) * nb);
+      int *d_script = (int *) BX_script.need(sizeof(int) * ((size_t) room[nb] + 1));
+      HIP_CHECK(hipEventRecord(BX_ev[0], G_st));
+      HIP_CHECK(hipMemcpyAsync(d_m, b->m, sizeof(int) * nb, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_n, b->n, sizeof(int) * nb, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_aoff, b->aoff, sizeof(long long) * nb, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_boff, b->boff, sizeof(long long) * nb, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_coff, room.data(), sizeof(long long) * (nb + 1), hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_bases, b->bases, (size_t) b->nbases, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemsetAsync(d_slen, 0xff, sizeof(int) * nb, G_st));
+      HIP_CHECK(hipEventRecord(BX_ev[1], G_st));
+      a.m = d_m;  a.n = d_n;  a.aoff = d_aoff;  a.boff = d_boff;  a.coff = d_coff;  a.bases = d_bases;
+      a.diffs = d_diffs;  a.slen = d_slen;  a.script = d_script;
+      damar_launch_box_align(&a, G_st);
+      HIP_CHECK(hipEventRecord(BX_ev[2], G_st));
+      HIP_CHECK(hipMemcpyAsync(diffs, d_diffs, sizeof(int) * nb, hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipMemcpyAsync(slen.data(), d_slen, sizeof(int) * nb, hipMemcpyDeviceToHost, G_st));
+      if (room[nb] > 0)
+        HIP_CHECK(hipMemcpyAsync(wide.data(), d_script, sizeof(int) * (size_t) room[nb], hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipEventRecord(BX_ev[3], G_st));
+      HIP_CHECK(hipStreamSynchronize(G_st));
+      for (int i = 0; i < 3; i++)
+        { float ms = 0;
+          HIP_CHECK(hipEventElapsedTime(&ms, BX_ev[i], BX_ev[i + 1]));
+          BX_ms[i] = ms;
+        }
+    }
+  /* what the kernel left: boxes beyond its LDS budget (and all of them with DAMAR_TRIM=host) */
+  for (size_t i = 0; i < nb; i++)
+    if (slen[i] < 0)
+      { diffs[i] = damar_exact_box(b->bases + b->aoff[i], b->m[i], b->bases + b->boff[i], b->n[i], wide.data() + room[i], &slen[i]);
+        fallback += host ? 0 : 1;
+      }
+  soff[0] = 0;
+  for (size_t i = 0; i < nb; i++)
+    soff[i + 1] = soff[i] + slen[i];
+  *script = (int *) malloc(sizeof(int) * (size_t) soff[nb] + 8);
+  if (*script == NULL)
+    { fprintf(stderr, "damar: out of memory (boxes)\n");
+      return 1;
+    }
+  for (size_t i = 0; i < nb; i++)
+    if (slen[i] > 0)
+      memcpy(*script + soff[i], wide.data() + room[i], sizeof(int) * (size_t) slen[i]);
+  BX_cnt[0] = b->nbox;  BX_cnt[1] = fallback;  BX_cnt[2] = soff[nb];
+  BX_ms[3] = now_ms() - w0;
+  return 0;
+}

@@ -280,6 +280,30 @@ void damar_q_release(void);                /* frees the cached device buffers of
 /* of the last device call: ms[4] = upload, count + scan, scatter + select, download; cnt[2] = segments counted, tiles */
 void damar_q_last(double *ms, int64 *cnt);
 
+/* Exact alignment of a batch of boxes (Compute_Alignment(DIFF_ALIGN), align.c:4734 through dandc_nd and split_nd): box i is
+ * A = bases + aoff[i], m[i] >= 1 bases, against B = bases + boff[i], n[i] >= 1 bases, one base per byte, B already
+ * complemented where that is wanted.  diffs[i] receives the box's differences; its edit script -- the indels of the
+ * reference's optimal path in path order, -(a + 1) for a base of B alone in front of A position a, b + 1 for a base of A
+ * alone in front of B position b, positions counted from the box's own corner -- is the values [soff[i], soff[i + 1]) of
+ * *script (soff holds nbox + 1 entries; *script is malloc'ed, the caller's to free).  Runs kernels/box_align.hip, one
+ * wavefront per box; a box with max(m, n) above what the kernel keeps in LDS goes to the host routine of host/bridge.c
+ * (DAMAR_TEST_BOX_LIMIT lowers that bound, for tests).  With DAMAR_TRIM=host the host routine does all boxes and no GPU is
+ * touched.  0 on success. */
+typedef struct
+{ int64        nbox;
+  const int   *m, *n;                      /* [nbox] */
+  const int64 *aoff, *boff;                /* [nbox] */
+  const char  *bases;                      /* [nbases] */
+  int64        nbases;
+} damar_box_batch;
+
+int  damar_align_boxes(const damar_box_batch *b, int *diffs, int64 *soff, int **script);
+void damar_box_release(void);              /* frees the cached device buffers of damar_align_boxes */
+/* of the last call: ms[4] = upload, kernel, download (HIP events; 0 on the host path), whole call (wall);
+ * cnt[3] = boxes, boxes the host routine did beside the kernel, script values */
+void damar_box_last(double *ms, int64 *cnt);
+unsigned int damar_box_grid(void);         /* workgroups of the kernel's largest launch: a batch of more boxes gives a workgroup several */
+
 /* Phase timings (milliseconds, HIP events on the library's stream) of the last
  * damar_index_build / damar_match: see DAMAR_T_* below. */
 enum { DAMAR_T_TUPLES = 0, DAMAR_T_KSORT, DAMAR_T_TABLE, DAMAR_T_MERGE, DAMAR_T_SSORT,
