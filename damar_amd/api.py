@@ -93,6 +93,15 @@ class TrimStats(C.Structure):          # host/damar_host.h damar_trim_stats
                 ("written", c_int64), ("discarded", c_int64), ("boxes", c_int64), ("box_a", c_int64), ("box_b", c_int64)]
 
 
+class HomogParams(C.Structure):        # host/damar_host.h damar_homog_params
+    _fields_ = [("merge", C.c_int), ("ends", C.c_int), ("res", C.c_int), ("iv_anno", C.POINTER(C.c_uint64)), ("iv_data", _PI),
+                ("iv_ndata", c_int64), ("trim_anno", C.POINTER(C.c_uint64)), ("trim_data", _PI)]
+
+
+class HomogResult(C.Structure):        # host/damar_host.h damar_homog_result
+    _fields_ = [("anno", C.POINTER(C.c_uint64)), ("data", _PI), ("ndata", c_int64), ("tagged", c_int64)]
+
+
 _proto_done = False
 
 
@@ -200,6 +209,17 @@ def _lib():
         L.damar_box_grid.restype = C.c_uint
         L.damar_box_last.argtypes = [C.POINTER(C.c_double), C.POINTER(c_int64)]
         L.damar_trim_las.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(TrimStats)]
+        u64p = C.POINTER(C.c_uint64)
+        L.damar_homog_open.argtypes = [_PI, C.c_int, C.c_int]
+        L.damar_homog_open.restype = C.c_void_p
+        L.damar_homog_seed.argtypes = [C.c_void_p, u64p, _PI, c_int64]
+        L.damar_homog_add.argtypes = [C.c_void_p, C.POINTER(TraceBatch), u64p, _PI, c_int64, C.c_int, _PI]
+        L.damar_homog_finish.argtypes = [C.c_void_p, u64p, C.POINTER(_PI), C.POINTER(c_int64), C.POINTER(c_int64)]
+        L.damar_homog_close.argtypes = [C.c_void_p]
+        L.damar_homog_last.argtypes = [C.POINTER(C.c_double), C.POINTER(c_int64)]
+        L.damar_homogenize_track.argtypes = [C.POINTER(DbInfo), C.c_char_p, C.POINTER(HomogParams), C.POINTER(HomogResult)]
+        L.damar_homog_result_free.argtypes = [C.POINTER(HomogResult)]
+        L.damar_track_read_a2.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(u64p), C.POINTER(_PI), C.POINTER(c_int64)]
         _proto_done = True
     return L
 
@@ -673,6 +693,135 @@ def trim_las(db, las, out, track="trim", purge=False):
     if _lib().damar_trim_las(db.encode(), las.encode(), out.encode(), track.encode(), 1 if purge else 0, C.byref(st)):
         raise RuntimeError("damar_trim_las failed")
     return {k: int(getattr(st, k)) for k, _ in TrimStats._fields_}
+
+
+# ---- repeat intervals carried across overlaps onto the B reads (TKhomogenize) ---------------------------------------
+
+def _trace_batch(batch, read_len):
+    """a batch of the read_trace_piles form as the C structure, and what keeps its arrays alive"""
+    import numpy as np
+    pb, keep = _batch(batch, read_len, np.zeros(len(read_len), dtype=np.int32))
+    t = TraceBatch()
+    t.p = pb
+    keep["trace"] = np.ascontiguousarray(batch["trace"], dtype=np.uint8)
+    keep["trace_off"] = np.ascontiguousarray(batch["trace_off"], dtype=np.int64)
+    keep["tlen"] = np.ascontiguousarray(batch["tlen"], dtype=np.int32)
+    if len(keep["trace_off"]) != pb.nrec or len(keep["tlen"]) != pb.nrec:
+        raise ValueError("trace_off and tlen hold one entry per record")
+    t.trace = keep["trace"].ctypes.data_as(C.POINTER(C.c_ubyte))
+    t.trace_off = keep["trace_off"].ctypes.data_as(C.POINTER(c_int64))
+    t.tlen = keep["tlen"].ctypes.data_as(_PI)
+    t.trace_bytes = len(keep["trace"])
+    t.tbytes, t.tspace = int(batch["tbytes"]), int(batch["tspace"])
+    return t, keep
+
+
+def trim_pairs(trim_anno, trim_data, nreads):
+    """the trim track as one {begin, end} per read, the way the reference's get_trim reads it: (0, 0) for a read without an
+    entry or with an empty or inverted one"""
+    import numpy as np
+    anno = np.asarray(trim_anno, dtype=np.int64) // 4
+    data = np.asarray(trim_data, dtype=np.int32)
+    n = np.diff(anno)
+    if len(anno) != nreads + 1 or np.any((n != 0) & (n != 2)):
+        raise ValueError("a trim track holds one interval per read at most")
+    pairs = np.zeros((nreads, 2), dtype=np.int32)
+    has = np.flatnonzero(n == 2)
+    b, e = data[anno[has]], data[anno[has] + 1]
+    ok = b < e
+    pairs[has[ok], 0], pairs[has[ok], 1] = b[ok], e[ok]
+    return pairs
+
+
+def pile_homogenize(batches, read_len, rep_anno, rep_data, merge=False, ends=-1, trim=None, res=1):
+    """TKhomogenize on arrays: the intervals of the track (rep_anno uint64[nreads + 1] byte offsets, rep_data {begin, end}
+    pairs) carried across the records of `batches` -- a LIST of batches of the read_trace_piles form, added to one session
+    in order -- onto the B reads.  merge: -m; ends: -e, with trim = (anno, data) of the trim track; res: -r.
+    -> (anno uint64[nreads + 1], data int32[], tagged).  The mask lives on the GPU unless DAMAR_PILES=host is set."""
+    import numpy as np
+    L = _lib()
+    rl = np.ascontiguousarray(read_len, dtype=np.int32)
+    nreads = len(rl)
+    ra = np.ascontiguousarray(rep_anno, dtype=np.uint64)
+    rd = np.ascontiguousarray(rep_data, dtype=np.int32)
+    if len(ra) != nreads + 1:
+        raise ValueError("the interval track holds an offset per read and one more")
+    pairs = None
+    if ends != -1:
+        if trim is None:
+            raise ValueError("ends needs the trim track")
+        pairs = np.ascontiguousarray(trim_pairs(trim[0], trim[1], nreads))
+    u64p = C.POINTER(C.c_uint64)
+    h = L.damar_homog_open(rl.ctypes.data_as(_PI), nreads, int(res))
+    if not h:
+        raise RuntimeError("damar_homog_open failed")
+    try:
+        if merge and L.damar_homog_seed(h, ra.ctypes.data_as(u64p), rd.ctypes.data_as(_PI), len(rd)):
+            raise RuntimeError("damar_homog_seed failed")
+        for batch in batches:
+            t, keep = _trace_batch(batch, rl)
+            if L.damar_homog_add(h, C.byref(t), ra.ctypes.data_as(u64p), rd.ctypes.data_as(_PI), len(rd), int(ends),
+                                 pairs.ctypes.data_as(_PI) if pairs is not None else None):
+                raise RuntimeError("damar_homog_add failed")
+        anno = np.zeros(nreads + 1, dtype=np.uint64)
+        data, ndata, tagged = _PI(), c_int64(0), c_int64(0)
+        if L.damar_homog_finish(h, anno.ctypes.data_as(u64p), C.byref(data), C.byref(ndata), C.byref(tagged)):
+            raise RuntimeError("damar_homog_finish failed")
+        try:
+            out = np.ctypeslib.as_array(data, shape=(max(ndata.value, 1),))[:ndata.value].copy()
+        finally:
+            C.CDLL(None).free(data)
+        return anno, out, tagged.value
+    finally:
+        L.damar_homog_close(h)
+
+
+def homog_last():
+    """Of the last session of pile_homogenize / homogenize_track, summed over its calls: ({upload, mark, readout, download}
+    ms, records seen, ranges set in the mask, intervals read out)."""
+    ms, cnt = (C.c_double * 4)(), (c_int64 * 3)()
+    _lib().damar_homog_last(ms, cnt)
+    return dict(zip(("upload", "mark", "readout", "download"), list(ms))), cnt[0], cnt[1], cnt[2]
+
+
+def _load_a2(L, d, name):
+    import numpy as np
+    anno, data, n = C.POINTER(C.c_uint64)(), _PI(), c_int64(0)
+    if L.damar_track_read_a2(d.path, name.encode(), d.nreads, C.byref(anno), C.byref(data), C.byref(n)):
+        raise RuntimeError("cannot read track %s" % name)
+    try:
+        return (np.ctypeslib.as_array(anno, shape=(d.nreads + 1,)).copy(),
+                np.ctypeslib.as_array(data, shape=(max(n.value, 1),))[:n.value].copy())
+    finally:
+        libc = C.CDLL(None)
+        libc.free(anno)
+        libc.free(data)
+
+
+def homogenize_track(db, las, track_in="repeats", merge=False, ends=-1, trim="trim", res=1):
+    """TKhomogenize on one .las file: the track `track_in` of the database carried across the overlaps
+    -> (anno uint64[nreads + 1] in bytes, data int32[], tagged)."""
+    import numpy as np
+    L = _lib()
+    d = DbInfo()
+    if L.damar_dbinfo_open(db.encode(), C.byref(d)):
+        raise RuntimeError("cannot open database %s" % db)
+    res_c = HomogResult()
+    try:
+        ia, idt = _load_a2(L, d, track_in)
+        u64p = C.POINTER(C.c_uint64)
+        p = HomogParams(1 if merge else 0, int(ends), int(res), ia.ctypes.data_as(u64p), idt.ctypes.data_as(_PI), len(idt), None, None)
+        if ends != -1:
+            ta, td = _load_a2(L, d, trim)
+            p.trim_anno, p.trim_data = ta.ctypes.data_as(u64p), td.ctypes.data_as(_PI)
+        if L.damar_homogenize_track(C.byref(d), las.encode(), C.byref(p), C.byref(res_c)):
+            raise RuntimeError("damar_homogenize_track failed")
+        anno = np.ctypeslib.as_array(res_c.anno, shape=(d.nreads + 1,)).copy()
+        data = np.ctypeslib.as_array(res_c.data, shape=(max(int(res_c.ndata), 1),))[:int(res_c.ndata)].copy()
+        return anno, data, int(res_c.tagged)
+    finally:
+        L.damar_homog_result_free(C.byref(res_c))
+        L.damar_dbinfo_close(C.byref(d))
 
 
 def read_track(db, name, block=0):

@@ -134,6 +134,37 @@ typedef struct
 } damar_trim_stats;
 int  damar_trim_las(const char *db, const char *las, const char *out, const char *track, int purge, damar_trim_stats *st);
 
+/* homogenize.c: TKhomogenize (scrub/TKhomogenize.c).  The plain routine behind the session calls of include/damar_hip.h
+   (DAMAR_PILES=host), the checks both paths share, and the pass over a file. */
+typedef struct damar_host_homog damar_host_homog;
+void damar_bits_set_range(unsigned char *bits, int64 nbits, int64 beg, int64 end);          /* ba_assign_range(.., 1), held to nbits */
+int  damar_trim_pairs(const uint64 *anno, const int *data, int nreads, int *pairs);         /* get_trim of every read; 1: not a trim track */
+int  damar_homog_seed_valid(const int *read_len, int nreads, const uint64 *anno, const int *data, int64 ndata);     /* 0 after a message */
+int  damar_homog_inputs_valid(const damar_trace_batch *t, int nreads, const int *read_len, const uint64 *anno, const int *data,
+                              int64 ndata, int ends, const int *trim);
+damar_host_homog *damar_host_homog_open(const int *read_len, int nreads, int res);
+int  damar_host_homog_seed(damar_host_homog *h, const uint64 *anno, const int *data);
+int  damar_host_homog_add(damar_host_homog *h, const damar_trace_batch *t, const uint64 *anno, const int *data, int ends, const int *trim);
+int  damar_host_homog_finish(damar_host_homog *h, uint64 *anno, int **data, int64 *ndata, int64 *tagged);
+void damar_host_homog_counts(const damar_host_homog *h, int64 *cnt /* [3] */);
+void damar_host_homog_close(damar_host_homog *h);
+typedef struct
+{ int merge, ends, res;        /* -m, -e (-1: none), -r */
+  const uint64 *iv_anno;       /* -i: the interval track of the whole database, byte offsets */
+  const int    *iv_data;
+  int64         iv_ndata;
+  const uint64 *trim_anno;     /* -t, looked at when ends != -1 */
+  const int    *trim_data;
+} damar_homog_params;
+typedef struct
+{ uint64 *anno;                /* [nreads + 1] byte offsets, malloc'ed */
+  int    *data;
+  int64   ndata, tagged;
+} damar_homog_result;
+/* the pass over a file: open, seed (-m), add per batch of whole piles, finish.  0, or 1 after a message. */
+int  damar_homogenize_track(const damar_dbinfo *db, const char *las, const damar_homog_params *p, damar_homog_result *res);
+void damar_homog_result_free(damar_homog_result *res);
+
 /* masks.c: both tools as calls (the commands and the Python interface are argument handling around them) */
 typedef struct
 { int64 *histo;                /* [max_cov], malloc'ed, NULL when no estimate ran */

@@ -388,6 +388,35 @@ void damar_launch_q_count(const QArgs *a, hipStream_t st);
 void damar_launch_q_scatter(const QArgs *a, hipStream_t st);
 void damar_launch_q_select(const QArgs *a, hipStream_t st);
 
+/* homogenize.hip: repeat intervals carried across overlaps into a bit mask of the whole database (scrub/TKhomogenize.c).
+   Read r owns the words [woff[r], woff[r + 1]) of `words`: bit j of the read is bit j % 32 of word j / 32, one bit per `res`
+   bases, alen = (res > 1 ? ceil(rlen / res) : rlen) of them are read back and one spare bit follows. */
+typedef struct
+{ u32 npiles, nrec, nreads;
+  int tspace, tbytes;
+  int res, ends;                      /* ends: -1, or -e's n (trim is set then) */
+  const long long *pile_off;          /* [npiles + 1] */
+  const int *pile_aread;              /* [npiles] */
+  const int *abpos, *aepos, *bbpos, *bepos, *bread, *flags, *tlen;       /* [nrec] */
+  const long long *trace_off;         /* [nrec] bytes into trace */
+  const u8  *trace;
+  const u64 *iv_anno;                 /* [nreads + 1] byte offsets into iv_data */
+  const int *iv_data;                 /* {begin, end} pairs */
+  const int *trim;                    /* [2 * nreads] or NULL */
+  const int *read_len;                /* [nreads] */
+  const u64 *woff;                    /* [nreads + 1] */
+  u32 *words;
+  u64 *nranges;                       /* added to: ranges set */
+  u32 *count;                         /* [nreads] intervals of a read (hom_count) */
+  const u32 *off;                     /* [nreads] exclusive scan of count */
+  int *out;                           /* {begin, end} pairs, read r's from 2 * off[r] */
+} HomArgs;
+
+void damar_launch_hom_mark(const HomArgs *a, hipStream_t st);
+void damar_launch_hom_seed(const HomArgs *a, hipStream_t st);
+void damar_launch_hom_count(const HomArgs *a, hipStream_t st);
+void damar_launch_hom_emit(const HomArgs *a, hipStream_t st);
+
 /* box_align.hip: exact alignment of a batch of boxes with their edit scripts (align.c:4734 DIFF_ALIGN).  A box with
    max(m, n) <= maxlen <= DAMAR_BOX_MAXLEN is done and leaves its differences, the length of its script (-1: it hit a bound of
    the kernel and is the host's after all) and the script at script + coff[box], max(m, n) values of room; the others are

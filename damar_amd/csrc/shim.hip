@@ -4614,6 +4614,261 @@ extern "C" int damar_pile_quality(const damar_trace_batch *t, const damar_q_para
   return 0;
 }
 
+/***** TKhomogenize's mask of the whole database, kept in HBM across batches of piles (kernels/homogenize.hip) ****************/
+
+struct damar_homog
+{ int   nreads, res;
+  damar_host_homog *hs;          /* DAMAR_PILES=host: the plain routine's state, nothing below is used */
+  std::vector<int> rlen;
+  u32  *d_words;                 /* the mask, nwords of them */
+  u64  *d_woff, *d_cnt;          /* [nreads + 1] word offsets; [0] ranges set */
+  int  *d_rlen;
+  u64   nwords;
+  DBuf  off, aread, col[7], toff, trace, ianno, idata, trim, count, doff, scan, out;
+  hipEvent_t ev[3];
+};
+static double HM_ms[4];          /* of the last session so far: upload, mark, read-out, download */
+static int64  HM_cnt[3];         /* records seen by add, ranges set, intervals read out */
+
+extern "C" void damar_homog_last(double *ms, int64 *cnt)
+{ for (int i = 0; i < 4; i++) ms[i] = HM_ms[i];
+  for (int i = 0; i < 3; i++) cnt[i] = HM_cnt[i];
+}
+
+extern "C" void damar_homog_close(damar_homog *h)
+{ if (h == NULL)
+    return;
+  if (h->hs != NULL)
+    damar_host_homog_close(h->hs);
+  else
+    { DBuf *all[] = { &h->off, &h->aread, &h->col[0], &h->col[1], &h->col[2], &h->col[3], &h->col[4], &h->col[5], &h->col[6], &h->toff,
+                      &h->trace, &h->ianno, &h->idata, &h->trim, &h->count, &h->doff, &h->scan, &h->out };
+      for (DBuf *b : all) b->drop();
+      void *own[] = { h->d_words, h->d_woff, h->d_cnt, h->d_rlen };
+      for (void *p : own)
+        if (p != NULL) HIP_CHECK(hipFree(p));
+      for (int i = 0; i < 3; i++)
+        if (h->ev[i] != NULL) (void) hipEventDestroy(h->ev[i]);
+    }
+  delete h;
+}
+
+extern "C" damar_homog *damar_homog_open(const int *read_len, int nreads, int res)
+{ if (read_len == NULL || nreads <= 0 || res < 1)
+    { fprintf(stderr, "damar: homogenize: %d reads at resolution %d\n", nreads, res);
+      return NULL;
+    }
+  for (int r = 0; r < nreads; r++)
+    if (read_len[r] < 0)
+      { fprintf(stderr, "damar: homogenize: read %d has length %d\n", r, read_len[r]);
+        return NULL;
+      }
+  damar_homog *h = new damar_homog();
+  h->nreads = nreads;  h->res = res;  h->hs = NULL;
+  h->d_words = NULL;  h->d_woff = NULL;  h->d_cnt = NULL;  h->d_rlen = NULL;
+  for (int i = 0; i < 3; i++) h->ev[i] = NULL;
+  for (int i = 0; i < 4; i++) HM_ms[i] = 0;
+  for (int i = 0; i < 3; i++) HM_cnt[i] = 0;
+  h->rlen.assign(read_len, read_len + nreads);
+  if (damar_piles_on_host())
+    { if ((h->hs = damar_host_homog_open(read_len, nreads, res)) == NULL)
+        { delete h;
+          return NULL;
+        }
+      return h;
+    }
+  ensure_init();
+  late_streams();                  /* a tool built on these calls is through soon after the library comes up: see damar_align_boxes */
+  std::vector<u64> woff((size_t) nreads + 1);
+  woff[0] = 0;
+  for (int r = 0; r < nreads; r++)
+    { const u64 bits = (u64) (res > 1 ? (read_len[r] + res - 1) / res : read_len[r]) + 1;
+      woff[(size_t) r + 1] = woff[r] + (bits + 31) / 32;
+    }
+  h->nwords = woff[nreads];
+  const hipError_t e = hipMalloc((void **) &h->d_words, sizeof(u32) * (size_t) h->nwords + 64);
+  if (e != hipSuccess)             /* no smaller mask would do, and there is no other path */
+    { (void) hipGetLastError();
+      fprintf(stderr, "damar: homogenize: no device memory for a mask of %llu bytes (%s)\n", (unsigned long long) (4 * h->nwords),
+              hipGetErrorString(e));
+      h->d_words = NULL;
+      damar_homog_close(h);
+      return NULL;
+    }
+  HIP_CHECK(hipMalloc((void **) &h->d_woff, sizeof(u64) * ((size_t) nreads + 1)));
+  HIP_CHECK(hipMalloc((void **) &h->d_rlen, sizeof(int) * (size_t) nreads));
+  HIP_CHECK(hipMalloc((void **) &h->d_cnt, 64));
+  for (int i = 0; i < 3; i++) HIP_CHECK(hipEventCreate(&h->ev[i]));
+  HIP_CHECK(hipEventRecord(h->ev[0], G_st));
+  HIP_CHECK(hipMemsetAsync(h->d_words, 0, sizeof(u32) * (size_t) h->nwords + 64, G_st));
+  HIP_CHECK(hipMemsetAsync(h->d_cnt, 0, 64, G_st));
+  HIP_CHECK(hipMemcpyAsync(h->d_woff, woff.data(), sizeof(u64) * ((size_t) nreads + 1), hipMemcpyHostToDevice, G_st));
+  HIP_CHECK(hipMemcpyAsync(h->d_rlen, read_len, sizeof(int) * (size_t) nreads, hipMemcpyHostToDevice, G_st));
+  HIP_CHECK(hipEventRecord(h->ev[1], G_st));
+  HIP_CHECK(hipStreamSynchronize(G_st));
+  float ms = 0;
+  HIP_CHECK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+  HM_ms[0] += ms;
+  return h;
+}
+
+/* the interval track goes up with every call: a few ints per read, next to a batch's trace bytes it does not count */
+static void homog_track_up(damar_homog *h, HomArgs *a, const uint64 *anno, const int *data, int64 ndata)
+{ u64 *d_anno = (u64 *) h->ianno.need(sizeof(u64) * ((size_t) h->nreads + 1));
+  int *d_data = (int *) h->idata.need(sizeof(int) * (size_t) ndata + 16);
+  HIP_CHECK(hipMemcpyAsync(d_anno, anno, sizeof(u64) * ((size_t) h->nreads + 1), hipMemcpyHostToDevice, G_st));
+  if (ndata > 0)
+    HIP_CHECK(hipMemcpyAsync(d_data, data, sizeof(int) * (size_t) ndata, hipMemcpyHostToDevice, G_st));
+  memset(a, 0, sizeof(*a));
+  a->nreads = (u32) h->nreads;  a->res = h->res;  a->ends = -1;
+  a->iv_anno = d_anno;  a->iv_data = d_data;
+  a->read_len = h->d_rlen;  a->woff = h->d_woff;  a->words = h->d_words;  a->nranges = h->d_cnt;
+}
+
+static void homog_marked(damar_homog *h)           /* after the kernel: its time and the running count of ranges */
+{ u64 ranges = 0;
+  HIP_CHECK(hipMemcpyAsync(&ranges, h->d_cnt, sizeof(u64), hipMemcpyDeviceToHost, G_st));
+  HIP_CHECK(hipStreamSynchronize(G_st));
+  HM_cnt[1] = (int64) ranges;
+  for (int i = 0; i < 2; i++)
+    { float ms = 0;
+      HIP_CHECK(hipEventElapsedTime(&ms, h->ev[i], h->ev[i + 1]));
+      HM_ms[i] += ms;
+    }
+}
+
+extern "C" int damar_homog_seed(damar_homog *h, const uint64 *anno, const int *data, int64 ndata)
+{ if (h == NULL)
+    return 1;
+  if (!damar_homog_seed_valid(h->rlen.data(), h->nreads, anno, data, ndata))
+    return 1;
+  if (h->hs != NULL)
+    { if (damar_host_homog_seed(h->hs, anno, data))
+        return 1;
+      damar_host_homog_counts(h->hs, HM_cnt);
+      return 0;
+    }
+  HomArgs a;
+  HIP_CHECK(hipEventRecord(h->ev[0], G_st));
+  homog_track_up(h, &a, anno, data, ndata);
+  HIP_CHECK(hipEventRecord(h->ev[1], G_st));
+  damar_launch_hom_seed(&a, G_st);
+  HIP_CHECK(hipEventRecord(h->ev[2], G_st));
+  homog_marked(h);
+  return 0;
+}
+
+extern "C" int damar_homog_add(damar_homog *h, const damar_trace_batch *t, const uint64 *anno, const int *data, int64 ndata, int ends,
+                               const int *trim)
+{ if (h == NULL || t == NULL)
+    return 1;
+  if (!damar_homog_inputs_valid(t, h->nreads, h->rlen.data(), anno, data, ndata, ends, trim))
+    return 1;
+  if (h->hs != NULL)
+    { if (damar_host_homog_add(h->hs, t, anno, data, ends, trim))
+        return 1;
+      damar_host_homog_counts(h->hs, HM_cnt);
+      return 0;
+    }
+  const damar_pile_batch *b = &t->p;
+  HM_cnt[0] += b->nrec;
+  if (b->nrec == 0)
+    return 0;
+  const u32 np = (u32) b->npiles;
+  const size_t nrec = (size_t) b->nrec;
+  HomArgs a;
+  HIP_CHECK(hipEventRecord(h->ev[0], G_st));
+  homog_track_up(h, &a, anno, data, ndata);
+  a.npiles = np;  a.nrec = (u32) nrec;  a.tspace = t->tspace;  a.tbytes = t->tbytes;  a.ends = ends;
+  long long *d_off = (long long *) h->off.need(sizeof(long long) * ((size_t) np + 1));
+  int *d_aread = (int *) h->aread.need(sizeof(int) * (size_t) np + 16);
+  const int *src[7] = { b->abpos, b->aepos, b->bbpos, b->bepos, b->bread, b->flags, t->tlen };
+  int *d_col[7];
+  for (int i = 0; i < 7; i++) d_col[i] = (int *) h->col[i].need(sizeof(int) * nrec + 16);
+  long long *d_toff = (long long *) h->toff.need(sizeof(long long) * nrec + 16);
+  u8 *d_trace = (u8 *) h->trace.need((size_t) t->trace_bytes + 16);
+  HIP_CHECK(hipMemcpyAsync(d_off, b->pile_off, sizeof(long long) * ((size_t) np + 1), hipMemcpyHostToDevice, G_st));
+  HIP_CHECK(hipMemcpyAsync(d_aread, b->pile_aread, sizeof(int) * (size_t) np, hipMemcpyHostToDevice, G_st));
+  for (int i = 0; i < 7; i++)
+    HIP_CHECK(hipMemcpyAsync(d_col[i], src[i], sizeof(int) * nrec, hipMemcpyHostToDevice, G_st));
+  HIP_CHECK(hipMemcpyAsync(d_toff, t->trace_off, sizeof(long long) * nrec, hipMemcpyHostToDevice, G_st));
+  if (t->trace_bytes > 0)
+    HIP_CHECK(hipMemcpyAsync(d_trace, t->trace, (size_t) t->trace_bytes, hipMemcpyHostToDevice, G_st));
+  if (ends != -1)
+    { int *d_trim = (int *) h->trim.need(sizeof(int) * 2 * (size_t) h->nreads);
+      HIP_CHECK(hipMemcpyAsync(d_trim, trim, sizeof(int) * 2 * (size_t) h->nreads, hipMemcpyHostToDevice, G_st));
+      a.trim = d_trim;
+    }
+  HIP_CHECK(hipEventRecord(h->ev[1], G_st));
+  a.pile_off = d_off;  a.pile_aread = d_aread;
+  a.abpos = d_col[0];  a.aepos = d_col[1];  a.bbpos = d_col[2];  a.bepos = d_col[3];  a.bread = d_col[4];  a.flags = d_col[5];
+  a.tlen = d_col[6];  a.trace_off = d_toff;  a.trace = d_trace;
+  damar_launch_hom_mark(&a, G_st);
+  HIP_CHECK(hipEventRecord(h->ev[2], G_st));
+  homog_marked(h);
+  return 0;
+}
+
+extern "C" int damar_homog_finish(damar_homog *h, uint64 *anno, int **data, int64 *ndata, int64 *tagged)
+{ if (h == NULL || anno == NULL || data == NULL || ndata == NULL || tagged == NULL)
+    return 1;
+  if (h->hs != NULL)
+    { if (damar_host_homog_finish(h->hs, anno, data, ndata, tagged))
+        return 1;
+      damar_host_homog_counts(h->hs, HM_cnt);
+      return 0;
+    }
+  const size_t nr = (size_t) h->nreads;
+  HomArgs a;
+  memset(&a, 0, sizeof(a));
+  a.nreads = (u32) h->nreads;  a.res = h->res;
+  a.read_len = h->d_rlen;  a.woff = h->d_woff;  a.words = h->d_words;
+  u32 *d_count = (u32 *) h->count.need(sizeof(u32) * nr), *d_doff = (u32 *) h->doff.need(sizeof(u32) * nr);
+  void *d_scan = h->scan.need(damar_scan_workspace_bytes(nr));
+  a.count = d_count;  a.off = d_doff;
+  HIP_CHECK(hipEventRecord(h->ev[0], G_st));
+  damar_launch_hom_count(&a, G_st);
+  damar_exclusive_scan_u32(d_count, d_doff, nr, d_scan, h->d_cnt + 1, G_st);
+  u64 total = 0;
+  HIP_CHECK(hipMemcpyAsync(&total, h->d_cnt + 1, sizeof(u64), hipMemcpyDeviceToHost, G_st));
+  HIP_CHECK(hipStreamSynchronize(G_st));
+  if (total >= ((u64) 1 << 30))
+    { fprintf(stderr, "damar: homogenize: %llu intervals, 2^30 - 1 is the most a track of ints holds here\n", (unsigned long long) total);
+      return 1;
+    }
+  a.out = (int *) h->out.need(sizeof(int) * 2 * (size_t) total + 16);
+  damar_launch_hom_emit(&a, G_st);
+  HIP_CHECK(hipEventRecord(h->ev[1], G_st));
+  std::vector<u32> cnt(nr);
+  int *out = (int *) malloc(sizeof(int) * 2 * (size_t) total + 8);
+  if (out == NULL)
+    { fprintf(stderr, "damar: out of memory (homogenize)\n");
+      return 1;
+    }
+  HIP_CHECK(hipMemcpyAsync(cnt.data(), d_count, sizeof(u32) * nr, hipMemcpyDeviceToHost, G_st));
+  if (total > 0)
+    HIP_CHECK(hipMemcpyAsync(out, a.out, sizeof(int) * 2 * (size_t) total, hipMemcpyDeviceToHost, G_st));
+  HIP_CHECK(hipEventRecord(h->ev[2], G_st));
+  HIP_CHECK(hipStreamSynchronize(G_st));
+  uint64 off = 0;
+  for (size_t r = 0; r < nr; r++)
+    { anno[r] = off;
+      off += 2 * sizeof(int) * (uint64) cnt[r];
+    }
+  anno[nr] = off;
+  int64 sum = 0;
+  for (u64 k = 0; k < total; k++)
+    sum += out[2 * k + 1] - out[2 * k];
+  *data = out;  *ndata = (int64) (2 * total);  *tagged = sum;
+  HM_cnt[2] = (int64) total;
+  for (int i = 0; i < 2; i++)
+    { float ms = 0;
+      HIP_CHECK(hipEventElapsedTime(&ms, h->ev[i], h->ev[i + 1]));
+      HM_ms[2 + i] += ms;
+    }
+  return 0;
+}
+
 /***** exact alignment of a batch of boxes with their edit scripts: Compute_Alignment(DIFF_ALIGN) (kernels/box_align.hip) ******/
 
 static DBuf BX_m, BX_n, BX_aoff, BX_boff, BX_coff, BX_bases, BX_diffs, BX_slen, BX_script;

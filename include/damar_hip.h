@@ -304,6 +304,31 @@ void damar_box_release(void);              /* frees the cached device buffers of
 void damar_box_last(double *ms, int64 *cnt);
 unsigned int damar_box_grid(void);         /* workgroups of the kernel's largest launch: a batch of more boxes gives a workgroup several */
 
+/* Repeat intervals carried across overlaps (scrub/TKhomogenize.c): for every record of a trace batch that is not an identity
+ * overlap, the A read's intervals of at least 500 bases that the record covers are projected through its trace points onto
+ * the B read and set in a bit mask of the whole database, one bit per `res` bases and one spare bit per read.  The mask is
+ * indexed by the B read, so it outlives the batch: a session.
+ *   open    the mask of all nreads reads, all zero, resident in HBM (totlen / 8 bytes at res 1); NULL after a message when
+ *           it cannot be had -- there is no fallback;
+ *   seed    -m: every interval of the track of at least 500 bases set in its own read;
+ *   add     one trace batch (its read_len / nreads are the session's) against the interval track: anno[nreads + 1] byte
+ *           offsets into data[ndata], a read's intervals as {begin, end} pairs in the order the reference walks them.
+ *           ends = -1, or -e's n with trim[2 * nreads] = {begin, end} per read (0, 0 for a read the trim track leaves out);
+ *   finish  the mask read out as a track: anno[nreads + 1] (the caller's) receives byte offsets, *data (malloc'ed, the
+ *           caller's to free) the {begin, end} pairs, *tagged the sum of end - begin.  The mask stays as it is.
+ * Runs kernels/homogenize.hip; with DAMAR_PILES=host the bit array of host/homogenize.c instead (no GPU is touched).
+ * 0 on success, 1 after a message. */
+typedef struct damar_homog damar_homog;
+damar_homog *damar_homog_open(const int *read_len, int nreads, int res);
+int  damar_homog_seed(damar_homog *h, const uint64 *anno, const int *data, int64 ndata);
+int  damar_homog_add(damar_homog *h, const damar_trace_batch *b, const uint64 *anno, const int *data, int64 ndata, int ends,
+                     const int *trim);
+int  damar_homog_finish(damar_homog *h, uint64 *anno, int **data, int64 *ndata, int64 *tagged);
+void damar_homog_close(damar_homog *h);
+/* of the last session, summed over its calls so far: ms[4] = upload, mark (seed and add), read-out, download (HIP events; 0
+ * on the host path); cnt[3] = records seen by add, ranges set in the mask (seed and add), intervals read out */
+void damar_homog_last(double *ms, int64 *cnt);
+
 /* Phase timings (milliseconds, HIP events on the library's stream) of the last
  * damar_index_build / damar_match: see DAMAR_T_* below. */
 enum { DAMAR_T_TUPLES = 0, DAMAR_T_KSORT, DAMAR_T_TABLE, DAMAR_T_MERGE, DAMAR_T_SSORT,
