@@ -166,6 +166,9 @@ def _lib():
         L.damar_last_seeds.restype = c_int64
         L.damar_order_runs_test.argtypes = [C.c_void_p, c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int]
         L.damar_order_runs_test.restype = C.c_int
+        L.damar_pair_work_test.argtypes = [C.c_void_p, C.c_void_p, c_int64, c_int64, c_int64] + [C.c_int] * 8 + \
+                                          [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, c_int64, C.POINTER(c_int64)]
+        L.damar_pair_work_test.restype = c_int64
         L.damar_local_alignment_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                   C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int),
                                                   C.POINTER(c_int64), C.POINTER(C.c_uint16), c_int64]
@@ -289,6 +292,30 @@ def order_runs(keys, ppos, dbits, work):
     if L.damar_order_runs_test(k.ctypes.data, len(k), ppos, dbits, w.ctypes.data, len(w)) != 0:
         raise RuntimeError("damar_order_runs_test failed")
     return k
+
+
+def pair_work(keys, vals, off, gtotal, ppos, dbits, abits, minhit, nshift, binshift, kmer, hitmin, b_lo, b_hi, mode):
+    """The work list of a comparison alone (test hook damar_pair_work_test) over the packed seeds `keys` (uint64; `vals` =
+    their diagonals as uint32 where dbits == 0, None otherwise), the stretch [off, off + len(keys)) of a list of gtotal
+    seeds.  mode 0: one pass over sorted seeds, 1: one pass over seeds sorted by read pair only, 2: heads, then screen.
+    Returns (work, flag): the ascending seed indices of the work items (uint32) and, as an int64 array of one entry, whether
+    mode 1 met a kept run too long to order."""
+    import numpy as np
+    L = _lib()
+    k = np.ascontiguousarray(keys, dtype=np.uint64)
+    v = None if vals is None else np.ascontiguousarray(vals, dtype=np.uint32)
+    if v is not None and len(v) != len(k):
+        raise ValueError("vals and keys differ in length")
+    flag = c_int64(0)
+    work = np.zeros(len(k) // max(1, minhit) + 1, dtype=np.uint32)          # (a work item heads a run of at least minhit seeds)
+    n = L.damar_pair_work_test(k.ctypes.data if len(k) else None, None if v is None else v.ctypes.data, len(k), off, gtotal,
+                               ppos, dbits, abits, minhit, nshift, binshift, kmer, hitmin, b_lo, b_hi, mode,
+                               work.ctypes.data, len(work), C.byref(flag))
+    if n < 0:
+        raise ValueError("damar_pair_work_test refused its arguments")
+    if n > len(work):
+        raise RuntimeError("damar_pair_work_test: %d work items over %d seeds with minhit %d" % (n, len(k), minhit))
+    return work[:n].copy(), np.array([flag.value], dtype=np.int64)
 
 
 def last_slabs():

@@ -3615,6 +3615,83 @@ extern "C" int damar_order_runs_test(uint64 *keys, int64 nhits, int ppos, int db
   return 0;
 }
 
+/* Test hook: the work list alone on a caller's seeds -- keys[0 .. nhits) is the stretch [off, off + nhits) of a sorted list of
+   gtotal seeds, vals (the diagonals) is NULL unless dbits == 0.  mode 0: one pass over sorted seeds (damar_launch_pair_work,
+   then damar_launch_pair_work_expand); mode 1: the same with the seeds of a read pair in no particular order, *flag_out =
+   "a kept run is too long to order" (the ordering itself is not run: keys are never written); mode 2: the calls of
+   front_work_twostep.  At most cap ascending seed indices go to work_out.  Returns the number of work items, -1 for
+   arguments it refuses (mode 1 never sees dbits == 0: SeedStage sorts those comparisons over all the bits). */
+extern "C" int64 damar_pair_work_test(const uint64 *keys, const uint32 *vals, int64 nhits, int64 off, int64 gtotal, int ppos,
+                                      int dbits, int abits, int minhit, int nshift, int binshift, int kmer, int hitmin,
+                                      uint32 b_lo, uint32 b_hi, int mode, uint32 *work_out, int64 cap, int64 *flag_out)
+{ if (flag_out)
+    *flag_out = 0;
+  if (nhits < 0 || nhits > 0x7fffffffll || off < 0 || gtotal < off + nhits || mode < 0 || mode > 2 || cap < 0 ||
+      (cap > 0 && work_out == NULL) || ppos < 1 || dbits < 0 || abits < 0 || ppos + dbits + abits > 63 || ppos > 31 ||
+      minhit < 1 || kmer < 1 || hitmin < 1 || binshift < 0 || binshift > 31 || nshift > 6 ||
+      (dbits == 0) != (vals != NULL) || (mode == 1 && dbits == 0) || (nhits > 0 && keys == NULL))
+    return -1;
+  finish_all();
+  ensure_init();
+  if (nhits == 0)
+    return 0;
+  const size_t n = (size_t) nhits, ntiles = (n + DAMAR_SCAN_TILE - 1) / DAMAR_SCAN_TILE;
+  u64  *dk, *bits, *send, *tot;
+  u32  *dv = NULL, *heads = NULL, *flags = NULL, *work = NULL;
+  void *scw;
+  HIP_CHECK(hipMalloc((void **) &dk, sizeof(u64) * n));
+  HIP_CHECK(hipMalloc((void **) &bits, std::max(sizeof(u64) * 64 * ntiles, sizeof(u32) * n)));   /* (mode 2: foff after the heads) */
+  HIP_CHECK(hipMalloc((void **) &send, sizeof(u64) * 64));
+  HIP_CHECK(hipMalloc((void **) &tot, 64));
+  HIP_CHECK(hipMalloc(&scw, damar_scan_workspace_bytes((u64) nhits)));
+  HIP_CHECK(hipMemcpy(dk, keys, sizeof(u64) * n, hipMemcpyHostToDevice));
+  if (vals != NULL)
+    { HIP_CHECK(hipMalloc((void **) &dv, sizeof(u32) * n));
+      HIP_CHECK(hipMemcpy(dv, vals, sizeof(u32) * n, hipMemcpyHostToDevice));
+    }
+  u64 got[2] = { 0, 0 };
+  if (mode < 2)
+    { damar_launch_pair_work(dk, dv, (u64) nhits, (u64) off, (u64) gtotal, ppos, dbits, abits, minhit, nshift, send, bits, scw, tot,
+                             binshift, kmer, hitmin, b_lo, b_hi, mode, G_st);
+      HIP_CHECK(hipMemcpyAsync(got, tot, 2 * sizeof(u64), hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipStreamSynchronize(G_st));
+      if (got[0] > 0)
+        { HIP_CHECK(hipMalloc((void **) &work, sizeof(u32) * ((size_t) got[0] + 1)));
+          damar_launch_pair_work_expand(bits, scw, (u64) nhits, work, G_st);
+        }
+    }
+  else
+    { HIP_CHECK(hipMalloc((void **) &heads, sizeof(u32) * n));
+      HIP_CHECK(hipMalloc((void **) &flags, sizeof(u32) * n));
+      damar_launch_pair_heads(dk, (u64) nhits, (u64) off, (u64) gtotal, ppos + dbits, abits, minhit, nshift, send, bits, scw, tot,
+                              heads, G_st);
+      HIP_CHECK(hipMemcpyAsync(got, tot, sizeof(u64), hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipStreamSynchronize(G_st));
+      const u32 nheads = (u32) got[0];
+      got[0] = 0;
+      if (nheads > 0)
+        { HIP_CHECK(hipMalloc((void **) &work, sizeof(u32) * ((size_t) nheads + 1)));
+          damar_launch_pair_screen(dk, dv, (u64) nhits, ppos, dbits, heads, nheads, minhit, binshift, kmer, hitmin, abits, b_lo, b_hi,
+                                   flags, G_st);
+          damar_exclusive_scan_u32(flags, (u32 *) bits, nheads, scw, tot, G_st);
+          damar_launch_compact_u32(heads, flags, (const u32 *) bits, nheads, work, G_st);
+          HIP_CHECK(hipMemcpyAsync(got, tot, sizeof(u64), hipMemcpyDeviceToHost, G_st));
+        }
+    }
+  HIP_CHECK(hipStreamSynchronize(G_st));
+  const u64 nw = got[0];
+  if (nw > 0 && cap > 0)
+    HIP_CHECK(hipMemcpy(work_out, work, sizeof(u32) * (size_t) std::min<u64>(nw, (u64) cap), hipMemcpyDeviceToHost));
+  if (flag_out)
+    *flag_out = (int64) got[1];
+  HIP_CHECK(hipFree(dk));  HIP_CHECK(hipFree(bits));  HIP_CHECK(hipFree(send));  HIP_CHECK(hipFree(tot));  HIP_CHECK(hipFree(scw));
+  if (dv)    HIP_CHECK(hipFree(dv));
+  if (heads) HIP_CHECK(hipFree(heads));
+  if (flags) HIP_CHECK(hipFree(flags));
+  if (work)  HIP_CHECK(hipFree(work));
+  return (int64) nw;
+}
+
 extern "C" int64 damar_last_seeds(void *out, int64 cap)
 { struct SP { int diag, apos, aread, bread; } *sp = (SP *) out;
   if (out == NULL)

@@ -146,6 +146,18 @@ int64 damar_last_seeds(void *out, int64 cap);
  * in place, equal positions in the order they had; everything else is left as it is.  Returns 0. */
 int damar_order_runs_test(uint64 *keys, int64 nhits, int ppos, int dbits, const uint32 *work, int nwork);
 
+/* Test hook: the work list of a comparison on its own -- the heads of the (bread, aread) runs report_thread enters that
+ * survive the screen of the bucket sums.  keys[0 .. nhits) are seeds packed as ((bread << abits | aread) << ppos | apos) <<
+ * dbits | bpos, the stretch [off, off + nhits) of a sorted list of gtotal seeds whose thread slices (1 << nshift of them;
+ * nshift < 0: none) are those of the whole list; with dbits == 0 the diagonals are in vals, which is NULL otherwise.
+ * minhit = (hitmin - 1) / kmer + 1; only B reads in [b_lo, b_hi) are kept.  mode 0: one pass over sorted seeds; mode 1: one
+ * pass over seeds sorted by read pair only (refused with dbits == 0), *flag_out = 1 when a kept run has more than 2048 seeds;
+ * mode 2: heads, then screen, scan and compaction.  Writes at most cap ascending seed indices to work_out and returns the
+ * number of work items, or -1 for arguments it refuses. */
+int64 damar_pair_work_test(const uint64 *keys, const uint32 *vals, int64 nhits, int64 off, int64 gtotal, int ppos, int dbits,
+                           int abits, int minhit, int nshift, int binshift, int kmer, int hitmin, uint32 b_lo, uint32 b_hi,
+                           int mode, uint32 *work_out, int64 cap, int64 *flag_out);
+
 /* A comparison with more seed pairs than one seed stage holds -- the 32-bit seed index, or what the seed arrays can be
  * grown to in the device memory that is free -- is run in SLABS, consecutive ranges of B reads cut greedily: a slab takes
  * B reads while its seed pairs stay within that figure, and at least one.  Records, counts and damar_last_seeds are those
