@@ -88,6 +88,22 @@ class BoxBatch(C.Structure):           # include/damar_hip.h damar_box_batch
                 ("bases", C.c_void_p), ("nbases", c_int64)]
 
 
+class TBoxBatch(C.Structure):          # include/damar_hip.h damar_tbox_batch
+    _fields_ = [("nbox", c_int64), ("m", _PI), ("n", _PI), ("abpos", _PI), ("aoff", C.POINTER(c_int64)), ("boff", C.POINTER(c_int64)),
+                ("bases", C.c_void_p), ("nbases", c_int64), ("tspace", C.c_int)]
+
+
+class StitchParams(C.Structure):       # host/damar_host.h damar_stitch_params
+    _fields_ = [("fuzz", C.c_int), ("purge", C.c_int), ("anchor", C.c_int), ("merge", C.c_int), ("min_len", C.c_int),
+                ("min_merge", C.c_int), ("gap_diff", C.c_double), ("lc_track", C.c_char_p), ("rep_track", C.c_char_p)]
+
+
+class StitchStats(C.Structure):        # host/damar_host.h damar_stitch_stats
+    _fields_ = [("novl", c_int64), ("written", c_int64), ("discarded", c_int64), ("stitched", c_int64), ("stitched_lc", c_int64),
+                ("candidates", c_int64), ("no_box", c_int64), ("widened", c_int64), ("boxes", c_int64), ("box_a", c_int64), ("box_b", c_int64), ("refused", c_int64),
+                ("rounds", c_int64), ("round_boxes", c_int64 * 16)]
+
+
 class TrimStats(C.Structure):          # host/damar_host.h damar_trim_stats
     _fields_ = [("novl", c_int64), ("ntrimmed", c_int64), ("novl_bases", c_int64), ("ntrim_bases", c_int64),
                 ("written", c_int64), ("discarded", c_int64), ("boxes", c_int64), ("box_a", c_int64), ("box_b", c_int64)]
@@ -211,6 +227,10 @@ def _lib():
         L.damar_align_boxes.argtypes = [C.POINTER(BoxBatch), _PI, C.POINTER(c_int64), C.POINTER(_PI)]
         L.damar_box_grid.restype = C.c_uint
         L.damar_box_last.argtypes = [C.POINTER(C.c_double), C.POINTER(c_int64)]
+        L.damar_trace_boxes.argtypes = [C.POINTER(TBoxBatch), _PI, C.POINTER(c_int64), C.POINTER(C.POINTER(C.c_uint16))]
+        L.damar_tbox_grid.restype = C.c_uint
+        L.damar_tbox_last.argtypes = [C.POINTER(C.c_double), C.POINTER(c_int64)]
+        L.damar_stitch_las.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(StitchParams), C.POINTER(StitchStats)]
         L.damar_trim_las.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(TrimStats)]
         u64p = C.POINTER(C.c_uint64)
         L.damar_homog_open.argtypes = [_PI, C.c_int, C.c_int]
@@ -720,6 +740,70 @@ def trim_las(db, las, out, track="trim", purge=False):
     if _lib().damar_trim_las(db.encode(), las.encode(), out.encode(), track.encode(), 1 if purge else 0, C.byref(st)):
         raise RuntimeError("damar_trim_las failed")
     return {k: int(getattr(st, k)) for k, _ in TrimStats._fields_}
+
+
+# ---- split overlaps rejoined (LAstitch) and the exact box alignment into trace pairs under it -----------------------
+
+def trace_boxes(a_seqs, b_seqs, a_starts, tspace):
+    """Exact alignment of box i = a_seqs[i] against b_seqs[i] (sequences of base values, one per element, neither empty)
+    into trace pairs as the reference's Compute_Alignment(DIFF_TRACE) does it, a_starts[i] being where the box begins in A
+    (the pairs are cut on A's grid of tspace): -> (diffs int32[boxes], a list of uint16 arrays: differences and B length of
+    every interval the box touches).  On the GPU, one wavefront per box, unless DAMAR_STITCH=host is set."""
+    import numpy as np
+    L = _lib()
+    if len(a_seqs) != len(b_seqs) or len(a_seqs) != len(a_starts):
+        raise ValueError("one B sequence and one start per A sequence")
+    if int(tspace) < 1:
+        raise ValueError("the trace spacing is at least 1")
+    nb = len(a_seqs)
+    seqs = [np.ascontiguousarray(x, dtype=np.uint8) for pair in zip(a_seqs, b_seqs) for x in pair]
+    if any(len(x) == 0 for x in seqs):
+        raise ValueError("a box has at least one base on either side")
+    lens = np.array([len(x) for x in seqs], dtype=np.int64).reshape(nb, 2)
+    offs = np.concatenate([[0], np.cumsum(lens.reshape(-1))]).astype(np.int64)
+    bases = np.concatenate(seqs) if nb else np.zeros(1, dtype=np.uint8)
+    m, n = (np.ascontiguousarray(lens[:, k], dtype=np.int32) for k in (0, 1))
+    ab = np.ascontiguousarray(a_starts, dtype=np.int32).reshape(nb)
+    if nb and ab.min() < 0:
+        raise ValueError("a box begins at or behind position 0 of A")
+    aoff, boff = np.ascontiguousarray(offs[:-1:2]), np.ascontiguousarray(offs[1::2])
+    i64p = C.POINTER(c_int64)
+    tb = TBoxBatch(nb, m.ctypes.data_as(_PI), n.ctypes.data_as(_PI), ab.ctypes.data_as(_PI), aoff.ctypes.data_as(i64p),
+                   boff.ctypes.data_as(i64p), bases.ctypes.data, int(offs[-1]), int(tspace))
+    diffs, toff, trace = np.zeros(max(nb, 1), dtype=np.int32), np.zeros(nb + 1, dtype=np.int64), C.POINTER(C.c_uint16)()
+    if L.damar_trace_boxes(C.byref(tb), diffs.ctypes.data_as(_PI), toff.ctypes.data_as(i64p), C.byref(trace)):
+        raise RuntimeError("damar_trace_boxes failed")
+    try:
+        total = int(toff[nb])
+        flat = np.ctypeslib.as_array(trace, shape=(max(total, 1),))[:total].copy()
+    finally:
+        C.CDLL(None).free(trace)
+    return diffs[:nb], [flat[toff[i]:toff[i + 1]] for i in range(nb)]
+
+
+def tbox_last():
+    """Of the last trace_boxes / of the last round of stitch_las: ({upload, kernel, download, call} ms, boxes, boxes the host
+    routine did beside the kernel, trace values)."""
+    ms, cnt = (C.c_double * 4)(), (c_int64 * 3)()
+    _lib().damar_tbox_last(ms, cnt)
+    return dict(zip(("upload", "kernel", "download", "call"), list(ms))), cnt[0], cnt[1], cnt[2]
+
+
+def stitch_las(db, las, out, fuzz=40, purge=False, track=None, repeats=None, anchor=500, merge=10, min_len=500, min_merge=200,
+               gap_diff=0.3):
+    """LAstitch on one .las file: the records of one (A read, B read) that the overlapper split are rejoined, the joint
+    realigned, the superfluous record flagged; written to `out` (purge: without the discarded records) -> the counters of
+    the run, round_boxes a list of the boxes per round."""
+    p = StitchParams(int(fuzz), 1 if purge else 0, int(anchor), int(merge), int(min_len), int(min_merge), float(gap_diff),
+                     track.encode() if track else None, repeats.encode() if repeats else None)
+    st = StitchStats()
+    if int(fuzz) < 0:
+        raise ValueError("invalid fuzzing value of %d" % int(fuzz))
+    if _lib().damar_stitch_las(db.encode(), las.encode(), out.encode(), C.byref(p), C.byref(st)):
+        raise RuntimeError("damar_stitch_las failed")
+    res = {k: int(getattr(st, k)) for k, _ in StitchStats._fields_ if k != "round_boxes"}
+    res["round_boxes"] = [int(x) for x in st.round_boxes][:max(res["rounds"], 1)]
+    return res
 
 
 # ---- repeat intervals carried across overlaps onto the B reads (TKhomogenize) ---------------------------------------

@@ -214,14 +214,15 @@ int damar_exact_box(const char *A, int M, const char *B, int N, int *script, int
 
 typedef struct
 { uint16     *cell;       /* cell[2 i] differences, cell[2 i + 1] B-length of interval i (i counted from A's origin) */
-  const char *origin;     /* position 0 of the A coordinates the intervals are cut in */
+  const char *origin;     /* the box's first base of A ... */
+  int         org;        /* ... and its position in the A coordinates the intervals are cut in */
   int         ts;
   int        *ws;
 } Ledger;
 
-static int interval_of(const Ledger *L, const char *a) { return (int) (a - L->origin) / L->ts; }
+static int interval_of(const Ledger *L, const char *a) { return (L->org + (int) (a - L->origin)) / L->ts; }
 static int room_in_interval(const Ledger *L, const char *a)       /* bases from a to the end of its interval */
-{ const int at = (int) (a - L->origin);
+{ const int at = L->org + (int) (a - L->origin);
   return (at / L->ts + 1) * L->ts - at;
 }
 
@@ -311,7 +312,14 @@ static __thread uint16 *g_tr = NULL;   static __thread size_t g_trn = 0;
 
 /* Compute_Alignment(align, work, DIFF_TRACE, ts) (align.c:4734-4869) for the box in p: fills p->diffs, p->tlen, p->trace
    (the thread's buffer, valid until the next call) */
+static void realign_at(const char *abox, int aorg, const char *bseq, BPath *p, int ts);
+
 static void realign_box(const char *aseq, const char *bseq, BPath *p, int ts)
+{ realign_at(aseq + p->abpos, p->abpos, bseq, p, ts);
+}
+
+/* the same with A given by the box's own first base: abox[0] is position aorg == p->abpos of A's coordinates */
+static void realign_at(const char *abox, int aorg, const char *bseq, BPath *p, int ts)
 { const int asub = p->aepos - p->abpos, bsub = p->bepos - p->bbpos;
   const int big = (asub > bsub) ? asub : bsub;
   const size_t need_ws = 4 * (size_t) (2 * big + 5) + 16;
@@ -331,16 +339,30 @@ static void realign_box(const char *aseq, const char *bseq, BPath *p, int ts)
     }
   memset(g_tr, 0, sizeof(uint16) * (size_t) ncell);
   L.cell = g_tr - 2 * (p->abpos / ts);
-  L.origin = aseq;
+  L.origin = abox;
+  L.org = aorg;
   L.ts = ts;
   L.ws = g_ws;
-  p->diffs = settle(&L, aseq + p->abpos, asub, bseq + p->bbpos, bsub);
+  p->diffs = settle(&L, abox, asub, bseq + p->bbpos, bsub);
   if (g_tr[ncell - 1] != 0)             /* insertions booked exactly on the last boundary belong to the interval before it */
     { g_tr[ncell - 3] += g_tr[ncell - 1];
       g_tr[ncell - 4] += g_tr[ncell - 2];
     }
   p->tlen = ncell - 2;
   p->trace = g_tr;
+}
+
+/* The same for a caller outside this file (what damar_trace_boxes returns per box, stitch.c through it): A[0..M) against
+   B[0..N), A's position 0 lying abpos bases into the grid of ts; trace receives 2 * ((abpos + M + ts - 1) / ts - abpos / ts)
+   values, *tlen their number; returns the differences */
+int damar_trace_box(const char *A, int M, const char *B, int N, int abpos, int ts, uint16 *trace, int *tlen)
+{ BPath p;
+  p.abpos = abpos % ts;  p.aepos = p.abpos + M;
+  p.bbpos = 0;           p.bepos = N;
+  realign_at(A, p.abpos, B, &p, ts);
+  memcpy(trace, p.trace, sizeof(uint16) * (size_t) p.tlen);
+  *tlen = p.tlen;
+  return p.diffs;
 }
 
 /***** trace points of a path ***************************************************************************/

@@ -134,6 +134,36 @@ typedef struct
 } damar_trim_stats;
 int  damar_trim_las(const char *db, const char *las, const char *out, const char *track, int purge, damar_trim_stats *st);
 
+/* bridge.c: the exact alignment of one box into trace pairs (what damar_trace_boxes returns per box): A[0..M) against
+   B[0..N), M, N >= 1, A's position 0 lying abpos >= 0 bases into the grid of ts; trace holds
+   2 * ((abpos + M + ts - 1) / ts - abpos / ts) values, *tlen receives their number; returns the differences.  Works in the
+   calling thread's buffers (damar_bridge_release frees them). */
+int  damar_trace_box(const char *A, int M, const char *B, int N, int abpos, int ts, uint16 *trace, int *tlen);
+int  damar_stitch_on_host(void);                                 /* DAMAR_STITCH=host */
+
+/* stitch.c: LAstitch (scrub/LAstitch.c stitch_handler2) as a call: the records of one (A read, B read) run that the
+   overlapper split are rejoined, the joint realigned exactly, the superfluous record flagged; written to `out` in file
+   order (purge: without the discarded records).  0, or 1 after a message. */
+typedef struct
+{ int    fuzz, purge;          /* -f -p */
+  int    anchor, merge, min_len, min_merge;      /* -a -m -l -M */
+  double gap_diff;             /* -d */
+  const char *lc_track, *rep_track;              /* -t -r, NULL: none */
+} damar_stitch_params;
+#define DAMAR_STITCH_ROUNDS 16
+typedef struct
+{ int64 novl, written, discarded;
+  int64 stitched, stitched_lc; /* joins by the fuzz test, joins by a low-complexity break */
+  int64 candidates;            /* pairs that passed the candidate tests: boxes + no_box */
+  int64 no_box;                /* candidates Compute_Bridge_Path gave up on (a widening ran off a record, or bout < bin) */
+  int64 widened;               /* boxes whose joint took at least one widening step */
+  int64 boxes, box_a, box_b;   /* boxes realigned, and the bases of A and of B in them */
+  int64 refused;               /* boxes Check_Bridge turned down */
+  int64 rounds;                /* the most rounds a batch of piles took */
+  int64 round_boxes[DAMAR_STITCH_ROUNDS];        /* boxes per round, summed over the batches; the last entry takes the rest */
+} damar_stitch_stats;
+int  damar_stitch_las(const char *db, const char *las, const char *out, const damar_stitch_params *p, damar_stitch_stats *st);
+
 /* homogenize.c: TKhomogenize (scrub/TKhomogenize.c).  The plain routine behind the session calls of include/damar_hip.h
    (DAMAR_PILES=host), the checks both paths share, and the pass over a file. */
 typedef struct damar_host_homog damar_host_homog;

@@ -436,6 +436,28 @@ typedef struct
 void damar_launch_box_align(const BoxArgs *a, hipStream_t st);
 u32  damar_box_align_grid(void);      /* workgroups of the largest launch: beyond that many boxes a workgroup does several */
 
+/* box_trace.hip: exact alignment of a batch of boxes into trace pairs (align.c:4734 DIFF_TRACE).  Box i is m[i] bases of A
+   against n[i] of B, its A side beginning abpos[i] bases into A's grid of tspace.  A box with max(m, n) <= maxlen <=
+   DAMAR_TBOX_MAXLEN and no more intervals than the kernel's ledger holds is done and leaves its differences, the number
+   of its values (-1: it hit a bound of the kernel and is the host's after all) and the values at trace + toff[box],
+   2 * ((abpos % tspace + m + tspace - 1) / tspace) of them; the others are not touched. */
+#define DAMAR_TBOX_MAXLEN 4096
+typedef struct
+{ u32 nbox, nlarge;                   /* nlarge: boxes above what the first launch takes (0: the second is not made) */
+  const u32 *large;                   /* [nlarge] which they are */
+  int maxlen, tspace;
+  const int *m, *n, *abpos;           /* [nbox] */
+  const long long *aoff, *boff;       /* [nbox] bytes into bases */
+  const long long *toff;              /* [nbox] values into trace */
+  const u8  *bases;
+  int *diffs, *tlen;                  /* [nbox] */
+  u16 *trace;
+} TBoxArgs;
+
+void damar_launch_box_trace(const TBoxArgs *a, hipStream_t st);
+u32  damar_box_trace_grid(void);      /* workgroups of the largest launch: beyond that many boxes a workgroup does several */
+u32  damar_box_trace_small(void);     /* the largest box of the first of the two launches */
+
 /* trace_pts.hip: Compute_Trace_PTS for batches of records (align.c:5577-5692, 4892-5261) */
 typedef struct
 { u32 aread, bread;       /* block-local read ids */

@@ -5064,3 +5064,134 @@ extern "C" int damar_align_boxes(const damar_box_batch *b, int *diffs, int64 *so
   BX_ms[3] = now_ms() - w0;
   return 0;
 }
+
+/***** exact alignment of a batch of boxes into trace pairs: Compute_Alignment(DIFF_TRACE) (kernels/box_trace.hip) ******/
+
+static DBuf TB_large, TB_m, TB_n, TB_abpos, TB_aoff, TB_boff, TB_toff, TB_bases, TB_diffs, TB_tlen, TB_trace;
+static double TB_ms[4];        /* of the last call: upload, kernel, download (HIP events), whole call (wall) */
+static int64  TB_cnt[3];       /* boxes, boxes the host routine did beside the kernel, trace values */
+static hipEvent_t TB_ev[4];
+static int    TB_ev_made;
+
+extern "C" void damar_tbox_release(void)
+{ DBuf *all[] = { &TB_large, &TB_m, &TB_n, &TB_abpos, &TB_aoff, &TB_boff, &TB_toff, &TB_bases, &TB_diffs, &TB_tlen, &TB_trace };
+  for (DBuf *b : all) b->drop();
+  if (TB_ev_made)
+    for (int i = 0; i < 4; i++) (void) hipEventDestroy(TB_ev[i]);
+  TB_ev_made = 0;
+}
+
+extern "C" unsigned int damar_tbox_grid(void) { return damar_box_trace_grid(); }
+
+extern "C" void damar_tbox_last(double *ms, int64 *cnt)
+{ for (int i = 0; i < 4; i++) ms[i] = TB_ms[i];
+  for (int i = 0; i < 3; i++) cnt[i] = TB_cnt[i];
+}
+
+extern "C" int damar_trace_boxes(const damar_tbox_batch *b, int *diffs, int64 *toff, uint16 **trace)
+{ const double w0 = now_ms();
+  if (b == NULL || toff == NULL || trace == NULL || b->nbox < 0 || b->tspace < 1 || (b->nbox > 0 && diffs == NULL))
+    { fprintf(stderr, "damar: trace boxes: malformed batch\n");
+      return 1;
+    }
+  const size_t nb = (size_t) b->nbox;
+  const int    ts = b->tspace;
+  if (b->nbox >= ((int64) 1 << 31))
+    { fprintf(stderr, "damar: trace boxes: a batch holds fewer than 2^31 boxes\n");
+      return 1;
+    }
+  for (size_t i = 0; i < nb; i++)
+    if (b->m[i] < 1 || b->n[i] < 1 || b->abpos[i] < 0 || b->aoff[i] < 0 || b->boff[i] < 0 || b->aoff[i] + b->m[i] > b->nbases ||
+        b->boff[i] + b->n[i] > b->nbases)
+      { fprintf(stderr, "damar: trace boxes: box %zu (%d x %d at %d) does not lie inside the %lld bases\n", i, b->m[i], b->n[i], b->abpos[i],
+                (long long) b->nbases);
+        return 1;
+      }
+  /* a box's number of values follows from where it lies on A's grid: the pairs go straight to their place */
+  toff[0] = 0;
+  for (size_t i = 0; i < nb; i++)
+    toff[i + 1] = toff[i] + 2 * (int64) ((b->abpos[i] % ts + b->m[i] + ts - 1) / ts);
+  *trace = (uint16 *) malloc(sizeof(uint16) * (size_t) toff[nb] + 8);
+  if (*trace == NULL)
+    { fprintf(stderr, "damar: out of memory (trace boxes)\n");
+      return 1;
+    }
+  std::vector<int> tlen(nb, -1);
+  for (int i = 0; i < 4; i++) TB_ms[i] = 0;
+  int64 fallback = 0;
+
+  const bool host = damar_stitch_on_host();
+  int maxlen = DAMAR_TBOX_MAXLEN;
+  if (getenv("DAMAR_TEST_BOX_LIMIT") && atoi(getenv("DAMAR_TEST_BOX_LIMIT")) < maxlen)
+    maxlen = atoi(getenv("DAMAR_TEST_BOX_LIMIT"));
+  if (!host && nb > 0)
+    { ensure_init();
+      late_streams();              /* a tool built on this call is through soon after the library comes up: see damar_align_boxes */
+      if (!TB_ev_made)
+        { for (int i = 0; i < 4; i++) HIP_CHECK(hipEventCreate(&TB_ev[i]));
+          TB_ev_made = 1;
+        }
+      TBoxArgs a;
+      memset(&a, 0, sizeof(a));
+      a.nbox = (u32) nb;
+      a.maxlen = maxlen;
+      a.tspace = ts;
+      std::vector<u32> large;
+      for (size_t i = 0; i < nb; i++)
+        if ((u32) std::max(b->m[i], b->n[i]) > damar_box_trace_small())
+          large.push_back((u32) i);
+      a.nlarge = (u32) large.size();
+      u32 *d_large = (u32 *) TB_large.need(sizeof(u32) * (large.size() + 1));
+      int *d_m = (int *) TB_m.need(sizeof(int) * nb), *d_n = (int *) TB_n.need(sizeof(int) * nb);
+      int *d_abpos = (int *) TB_abpos.need(sizeof(int) * nb);
+      long long *d_aoff = (long long *) TB_aoff.need(sizeof(long long) * nb), *d_boff = (long long *) TB_boff.need(sizeof(long long) * nb);
+      long long *d_toff = (long long *) TB_toff.need(sizeof(long long) * (nb + 1));
+      u8  *d_bases = (u8 *) TB_bases.need((size_t) b->nbases + 16);
+      int *d_diffs = (int *) TB_diffs.need(sizeof(int) * nb), *d_tlen = (int *) TB_tlen.need(sizeof(int) * nb);
+      u16 *d_trace = (u16 *) TB_trace.need(sizeof(u16) * ((size_t) toff[nb] + 4));
+      HIP_CHECK(hipEventRecord(TB_ev[0], G_st));
+      HIP_CHECK(hipMemcpyAsync(d_m, b->m, sizeof(int) * nb, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_n, b->n, sizeof(int) * nb, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_abpos, b->abpos, sizeof(int) * nb, hipMemcpyHostToDevice, G_st));
+      if (a.nlarge > 0)
+        HIP_CHECK(hipMemcpyAsync(d_large, large.data(), sizeof(u32) * large.size(), hipMemcpyHostToDevice, G_st));
+      a.large = d_large;
+      HIP_CHECK(hipMemcpyAsync(d_aoff, b->aoff, sizeof(long long) * nb, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_boff, b->boff, sizeof(long long) * nb, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_toff, toff, sizeof(long long) * (nb + 1), hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_bases, b->bases, (size_t) b->nbases, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemsetAsync(d_tlen, 0xff, sizeof(int) * nb, G_st));
+      HIP_CHECK(hipEventRecord(TB_ev[1], G_st));
+      a.m = d_m;  a.n = d_n;  a.abpos = d_abpos;  a.aoff = d_aoff;  a.boff = d_boff;  a.toff = d_toff;  a.bases = d_bases;
+      a.diffs = d_diffs;  a.tlen = d_tlen;  a.trace = d_trace;
+      damar_launch_box_trace(&a, G_st);
+      HIP_CHECK(hipEventRecord(TB_ev[2], G_st));
+      HIP_CHECK(hipMemcpyAsync(diffs, d_diffs, sizeof(int) * nb, hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipMemcpyAsync(tlen.data(), d_tlen, sizeof(int) * nb, hipMemcpyDeviceToHost, G_st));
+      if (toff[nb] > 0)
+        HIP_CHECK(hipMemcpyAsync(*trace, d_trace, sizeof(u16) * (size_t) toff[nb], hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipEventRecord(TB_ev[3], G_st));
+      HIP_CHECK(hipStreamSynchronize(G_st));
+      for (int i = 0; i < 3; i++)
+        { float ms = 0;
+          HIP_CHECK(hipEventElapsedTime(&ms, TB_ev[i], TB_ev[i + 1]));
+          TB_ms[i] = ms;
+        }
+    }
+  /* what the kernel left: boxes beyond its LDS budget (and all of them with DAMAR_STITCH=host) */
+  for (size_t i = 0; i < nb; i++)
+    if (tlen[i] < 0)
+      { diffs[i] = damar_trace_box(b->bases + b->aoff[i], b->m[i], b->bases + b->boff[i], b->n[i], b->abpos[i], ts, *trace + toff[i], &tlen[i]);
+        fallback += host ? 0 : 1;
+      }
+  for (size_t i = 0; i < nb; i++)
+    if (tlen[i] != toff[i + 1] - toff[i])
+      { fprintf(stderr, "damar: trace boxes: box %zu came back with %d values for %lld\n", i, tlen[i], (long long) (toff[i + 1] - toff[i]));
+        free(*trace);
+        *trace = NULL;
+        return 1;
+      }
+  TB_cnt[0] = b->nbox;  TB_cnt[1] = fallback;  TB_cnt[2] = toff[nb];
+  TB_ms[3] = now_ms() - w0;
+  return 0;
+}

@@ -316,6 +316,32 @@ void damar_box_release(void);              /* frees the cached device buffers of
 void damar_box_last(double *ms, int64 *cnt);
 unsigned int damar_box_grid(void);         /* workgroups of the kernel's largest launch: a batch of more boxes gives a workgroup several */
 
+/* Exact alignment of a batch of boxes into trace pairs (Compute_Alignment(DIFF_TRACE), align.c:4734 through trace_nd and
+ * split_nd): box i is A = bases + aoff[i], m[i] >= 1 bases, against B = bases + boff[i], n[i] >= 1 bases, one base per
+ * byte, B already complemented where that is wanted.  abpos[i] >= 0 is where the box begins in A (or that position modulo
+ * tspace): the pairs are cut on A's own grid of tspace.  diffs[i] receives the box's differences; its pairs -- the
+ * differences and the B length of every interval of the grid that the box touches, what the reference leaves in
+ * path->trace, the cell beyond the last boundary folded into the one before it -- are the values [toff[i], toff[i + 1])
+ * of *trace, 2 * ((abpos + m + tspace - 1) / tspace - abpos / tspace) of them (toff holds nbox + 1 entries; *trace is
+ * malloc'ed, the caller's to free).  Runs kernels/box_trace.hip, one wavefront per box; a box with max(m, n) above 4096,
+ * or with more than 255 intervals, goes to the host routine of host/bridge.c (DAMAR_TEST_BOX_LIMIT lowers the first bound,
+ * for tests).  With DAMAR_STITCH=host the host routine does all boxes and no GPU is touched.  0 on success. */
+typedef struct
+{ int64        nbox;
+  const int   *m, *n, *abpos;              /* [nbox] */
+  const int64 *aoff, *boff;                /* [nbox] */
+  const char  *bases;                      /* [nbases] */
+  int64        nbases;
+  int          tspace;
+} damar_tbox_batch;
+
+int  damar_trace_boxes(const damar_tbox_batch *b, int *diffs, int64 *toff, uint16 **trace);
+void damar_tbox_release(void);             /* frees the cached device buffers of damar_trace_boxes */
+/* of the last call: ms[4] = upload, kernel, download (HIP events; 0 on the host path), whole call (wall);
+ * cnt[3] = boxes, boxes the host routine did beside the kernel, trace values */
+void damar_tbox_last(double *ms, int64 *cnt);
+unsigned int damar_tbox_grid(void);        /* workgroups of the kernel's largest launch: a batch of more boxes gives a workgroup several */
+
 /* Repeat intervals carried across overlaps (scrub/TKhomogenize.c): for every record of a trace batch that is not an identity
  * overlap, the A read's intervals of at least 500 bases that the record covers are projected through its trace points onto
  * the B read and set in a bit mask of the whole database, one bit per `res` bases and one spare bit per read.  The mask is
