@@ -143,6 +143,60 @@ def tboxes():
     return _TBOXES
 
 
+TBOX_MAX = 4096                         # DAMAR_TBOX_MAXLEN: the largest box kernels/box_trace.hip keeps
+TB_SMALL = 1024                         # the largest box of its first build
+TB_CELLS = 512                          # the ledger cells of a box
+_TBOXES_WIDE = None
+
+
+def tboxes_wide():
+    """the box cases of tests/golden/make_box_edges_golden.py, loaded once: the layout of tboxes(), and run_tspace[j], the
+    spacing run j was made at"""
+    global _TBOXES_WIDE
+    if _TBOXES_WIDE is None:
+        z = np.load(os.path.join(SDIR, "tboxes_wide.npz"))
+        _TBOXES_WIDE = {k: z[k] for k in z.files}
+        for v in _TBOXES_WIDE.values():
+            v.setflags(write=False)
+    return _TBOXES_WIDE
+
+
+def family_runs(bx, name):
+    return np.flatnonzero(bx["family"][bx["run_box"]] == list(bx["families"]).index(name))
+
+
+def run_spacing(bx, runs):
+    """the spacing of every run: a file without run_tspace was made at TW throughout"""
+    return bx["run_tspace"][runs] if "run_tspace" in bx else np.full(len(runs), TW, dtype=np.int32)
+
+
+def run_cells(bx, runs):
+    """the ledger cells kernels/box_trace.hip needs for every run: two per interval the box touches and a spare pair"""
+    ts = run_spacing(bx, runs).astype(np.int64)
+    return 2 * ((bx["run_abpos"][runs] % ts + bx["m"][bx["run_box"][runs]] + ts - 1) // ts + 1)
+
+
+def trace_runs(bx, runs, limit=TBOX_MAX):
+    """api.trace_boxes on the runs, one call per spacing among them, against the fixture: -> (the device's kernel time in ms,
+    boxes the host routine did beside the kernel, and how many of the runs lie beyond what the kernel keeps: a side above
+    `limit`, or more ledger cells than it has) summed over the calls"""
+    from damar_amd import api
+    runs = np.asarray(runs)
+    spacing = run_spacing(bx, runs)
+    kernel_ms, fallback = 0., 0
+    for ts in sorted(set(spacing.tolist())):
+        part = runs[spacing == ts]
+        a, b, at = run_seqs(bx, part)
+        diffs, traces = api.trace_boxes(a, b, at, ts)
+        check_runs(bx, part, diffs, traces)
+        ms, boxes, fb, _ = api.tbox_last()
+        assert boxes == len(part)
+        kernel_ms += ms["kernel"]
+        fallback += fb
+    big = np.maximum(bx["m"], bx["n"])[bx["run_box"][runs]]
+    return kernel_ms, fallback, int(np.sum((big > limit) | (run_cells(bx, runs) > TB_CELLS)))
+
+
 def run_seqs(bx, runs):
     a = [bx["bases"][bx["aoff"][i]:bx["aoff"][i] + bx["m"][i]] for i in bx["run_box"][runs]]
     b = [bx["bases"][bx["boff"][i]:bx["boff"][i] + bx["n"][i]] for i in bx["run_box"][runs]]

@@ -27,6 +27,45 @@ def test_box_runs():
     assert (boxes, fallback, values) == (len(runs), 0, len(bx["trace"]))
 
 
+WIDE_FAMILIES = ("build_border", "middle", "worst", "spacing", "ledger")
+
+
+@pytest.mark.parametrize("family", WIDE_FAMILIES)
+def test_wide_box_runs(family):
+    """tboxes_wide.npz (tests/golden/make_box_edges_golden.py): the border between the kernel's two builds, the sizes
+    between the old fixtures, the most differences a box can hold, other spacings than 100 and the ledger's bound"""
+    bx = sc.tboxes_wide()
+    _, fallback, _ = sc.trace_runs(bx, sc.family_runs(bx, family))
+    assert fallback == 0
+
+
+def test_wide_families_hold_what_they_were_planted_for():
+    bx = sc.tboxes_wide()
+    assert sorted(bx["families"]) == sorted(WIDE_FAMILIES)
+    runs = np.arange(len(bx["run_box"]))
+    m, n = bx["m"][bx["run_box"]], bx["n"][bx["run_box"]]
+    big, ts, cells = np.maximum(m, n), sc.run_spacing(bx, runs), sc.run_cells(bx, runs)
+    assert big.max() == sc.TBOX_MAX
+    worst = sc.family_runs(bx, "worst")
+    assert len(worst) == 8 and np.all(bx["diffs"][worst] == big[worst]) and set(bx["run_abpos"][worst] % sc.TW) == {0, 99}
+    assert set(big[worst].tolist()) == {sc.TB_SMALL, sc.TBOX_MAX} and set((m - n)[worst].tolist()) > {0}
+    border = sc.family_runs(bx, "build_border")
+    for side in (m, n):                                      # either side the larger one, related and unrelated
+        for size in (1023, 1024, 1025, 1026):
+            at_size = border[(side[border] == size) & (big[border] == size)]
+            assert np.any(bx["diffs"][at_size] < size // 3) and np.any(bx["diffs"][at_size] > size // 3)
+    middle = sc.family_runs(bx, "middle")
+    assert np.all((m[middle] > 700) & (m[middle] <= 2000)) and np.any(big[middle] <= sc.TB_SMALL) and np.any(big[middle] > sc.TB_SMALL)
+    assert np.all(ts[np.concatenate([worst, border, middle])] == sc.TW)
+    spacing = sc.family_runs(bx, "spacing")
+    assert set(ts[spacing].tolist()) == {16, 64, 126, 255, 1000}
+    for t in (16, 64, 126, 255, 1000):
+        assert set((bx["run_abpos"] % ts)[spacing[ts[spacing] == t]].tolist()) == {0, 1, t - 1, 7}
+    ledger = sc.family_runs(bx, "ledger")
+    assert sorted(cells[ledger].tolist()) == [sc.TB_CELLS, sc.TB_CELLS + 2, sc.TB_CELLS + 2] and np.all(ts[ledger] == 16)
+    assert np.all(cells[np.setdiff1d(runs, ledger)] <= sc.TB_CELLS)
+
+
 def test_start_modulo_spacing_is_enough():
     from damar_amd import api
     bx = sc.tboxes()

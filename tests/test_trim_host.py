@@ -32,6 +32,40 @@ def test_box_cases():
     assert (boxes, fallback, values) == (len(a), 0, len(bx["script"]))
 
 
+WIDE_FAMILIES = ("limit", "worst", "ladder", "skew", "ties", "random")
+
+
+@pytest.mark.parametrize("family", WIDE_FAMILIES)
+def test_wide_box_cases(family):
+    """boxes_wide.npz (tests/golden/make_box_edges_golden.py): boxes of every size up to the kernel's 1000 and just beyond"""
+    from damar_amd import api
+    bx = tc.boxes_wide()
+    idx = tc.family_rows(bx, family)
+    a, b = tc.box_seqs(bx, idx)
+    diffs, scripts = api.align_boxes(a, b)
+    tc.check_boxes(bx, diffs, scripts, idx)
+    assert api.box_last()[1:3] == (len(idx), 0)
+
+
+def test_wide_families_hold_what_they_were_planted_for():
+    bx = tc.boxes_wide()
+    assert sorted(bx["families"]) == sorted(WIDE_FAMILIES)
+    big = np.maximum(bx["m"], bx["n"])
+    worst = tc.family_rows(bx, "worst")
+    assert len(worst) == 5 and np.all(bx["diffs"][worst] == big[worst]) and big[worst].max() == tc.BOX_MAX
+    ladder = tc.family_rows(bx, "ladder")
+    pure = ladder[bx["planted"][ladder] >= 0]
+    assert np.array_equal(bx["diffs"][pure], bx["planted"][pure])
+    assert sorted(bx["planted"][pure]) == list(range(61, 68)) + list(range(125, 132)) + list(range(253, 260)) + [300]
+    assert len(ladder) == 2 * len(pure) and np.all(bx["soff"][pure + 1] == bx["soff"][pure])        # substitutions leave no entry
+    limit = tc.family_rows(bx, "limit")
+    assert np.sum(big[limit] == tc.BOX_MAX) == 14 and np.sum(big[limit] > tc.BOX_MAX) == 3
+    assert np.sum(big > tc.BOX_MAX) == 3 and np.sum((big >= 256) & (big <= tc.BOX_MAX)) >= 300
+    skew = tc.family_rows(bx, "skew")
+    assert set(np.abs(bx["m"] - bx["n"])[skew].tolist()) == {70, 130, 200, 450, 700}
+    assert set(np.sign(bx["m"] - bx["n"])[skew].tolist()) == {-1, 1}
+
+
 def test_no_boxes():
     from damar_amd import api
     diffs, scripts = api.align_boxes([], [])

@@ -134,6 +134,26 @@ def boxes():
     return np.load(os.path.join(TDIR, "boxes.npz"))
 
 
+BOX_MAX = 1000                          # DAMAR_BOX_MAXLEN: the largest box kernels/box_align.hip keeps
+_WIDE = None
+
+
+def boxes_wide():
+    """the box cases of tests/golden/make_box_edges_golden.py, loaded once: the layout of boxes(), and family[i] (an index
+    into families) and planted[i] (the substitutions planted into a ladder box, -1 elsewhere) of every box"""
+    global _WIDE
+    if _WIDE is None:
+        z = np.load(os.path.join(TDIR, "boxes_wide.npz"))
+        _WIDE = {k: z[k] for k in z.files}
+        for v in _WIDE.values():
+            v.setflags(write=False)
+    return _WIDE
+
+
+def family_rows(bx, name):
+    return np.flatnonzero(bx["family"] == list(bx["families"]).index(name))
+
+
 def box_seqs(bx, idx=None):
     idx = range(len(bx["m"])) if idx is None else idx
     a = [bx["bases"][bx["aoff"][i]:bx["aoff"][i] + bx["m"][i]] for i in idx]
