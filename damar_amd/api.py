@@ -109,6 +109,20 @@ class TrimStats(C.Structure):          # host/damar_host.h damar_trim_stats
                 ("written", c_int64), ("discarded", c_int64), ("boxes", c_int64), ("box_a", c_int64), ("box_b", c_int64)]
 
 
+class GapParams(C.Structure):          # include/damar_hip.h damar_gap_params
+    _fields_ = [("stitch", C.c_int), ("ex_anno", C.POINTER(C.c_uint64)), ("ex_data", _PI), ("ex_ndata", c_int64), ("purge", C.c_int),
+                ("trim_track", C.c_char_p)]
+
+
+class GapEvents(C.Structure):          # include/damar_hip.h damar_gap_events
+    _fields_ = [("count", _PI), ("ev", _PI), ("nev", c_int64), ("contained", c_int64), ("breaks", c_int64), ("dropped", c_int64)]
+
+
+class GapStats(C.Structure):           # host/damar_host.h damar_gap_stats
+    _fields_ = [("novl", c_int64), ("written", c_int64), ("discarded", c_int64), ("contained", c_int64), ("breaks", c_int64),
+                ("dropped", c_int64), ("piles", c_int64), ("host_piles", c_int64), ("events", c_int64), ("trim", TrimStats)]
+
+
 class HomogParams(C.Structure):        # host/damar_host.h damar_homog_params
     _fields_ = [("merge", C.c_int), ("ends", C.c_int), ("res", C.c_int), ("iv_anno", C.POINTER(C.c_uint64)), ("iv_data", _PI),
                 ("iv_ndata", c_int64), ("trim_anno", C.POINTER(C.c_uint64)), ("trim_data", _PI)]
@@ -243,6 +257,11 @@ def _lib():
         L.damar_homogenize_track.argtypes = [C.POINTER(DbInfo), C.c_char_p, C.POINTER(HomogParams), C.POINTER(HomogResult)]
         L.damar_homog_result_free.argtypes = [C.POINTER(HomogResult)]
         L.damar_track_read_a2.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(u64p), C.POINTER(_PI), C.POINTER(c_int64)]
+        L.damar_track_read_any.argtypes = [C.POINTER(DbInfo), C.c_char_p, C.POINTER(u64p), C.POINTER(_PI), C.POINTER(c_int64)]
+        L.damar_pile_gaps.argtypes = [C.POINTER(PileBatch), C.POINTER(GapParams), _PI, C.POINTER(GapEvents)]
+        L.damar_gap_limits.argtypes = [_PI, _PI]
+        L.damar_gap_last.argtypes = [C.POINTER(C.c_double), C.POINTER(c_int64)]
+        L.damar_gap_las.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(GapParams), C.POINTER(GapStats)]
         _proto_done = True
     return L
 
@@ -803,6 +822,102 @@ def stitch_las(db, las, out, fuzz=40, purge=False, track=None, repeats=None, anc
         raise RuntimeError("damar_stitch_las failed")
     res = {k: int(getattr(st, k)) for k, _ in StitchStats._fields_ if k != "round_boxes"}
     res["round_boxes"] = [int(x) for x in st.round_boxes][:max(res["rounds"], 1)]
+    return res
+
+
+# ---- containments, gaps and breaks of piles (LAgap) -----------------------------------------------------------------
+
+GAP_KINDS = ("masked", "stitchable", "drop_L", "drop_R", "drop_none")
+GAP_TRAILING = 0x100
+
+
+def gap_limits():
+    """(bins, events) a pile may have for kernels/pile_gaps.hip to do it: DAMAR_GAP_MAXBINS, DAMAR_GAP_MAXEVENTS"""
+    bins, events = C.c_int(0), C.c_int(0)
+    _lib().damar_gap_limits(C.byref(bins), C.byref(events))
+    return bins.value, events.value
+
+
+def _gap_params(stitch, exclude, keep):
+    import numpy as np
+    p = GapParams(int(stitch), None, None, 0, 0, None)
+    if exclude is not None:
+        keep["ex_anno"] = np.ascontiguousarray(exclude[0], dtype=np.uint64)
+        keep["ex_data"] = np.ascontiguousarray(exclude[1], dtype=np.int32)
+        p.ex_anno = keep["ex_anno"].ctypes.data_as(C.POINTER(C.c_uint64))
+        p.ex_data = keep["ex_data"].ctypes.data_as(_PI)
+        p.ex_ndata = len(keep["ex_data"])
+    return p
+
+
+def pile_gaps(piles, read_len, stitch=0, exclude=None):
+    """LAgap's work on a batch of whole piles (the dict of _batch; exclude: (anno, data) of a track of the whole database,
+    byte offsets and {begin, end} pairs): -> (flags int32[nrec], OVL_TEMP included, and per pile the list of its events
+    (first bin, bin after the run, kind, v0, v1, records dropped), kind as include/damar_hip.h has it).  On the GPU, one
+    wavefront per pile, unless DAMAR_PILES=host is set."""
+    import numpy as np
+    L = _lib()
+    b, keep = _batch(piles, read_len, np.zeros(len(read_len), dtype=np.int32))
+    p = _gap_params(stitch, exclude, keep)
+    if exclude is not None and len(keep["ex_anno"]) != b.nreads + 1:
+        raise ValueError("the exclude track holds one offset per read and one more")
+    flags = np.zeros(max(b.nrec, 1), dtype=np.int32)
+    count = np.zeros(max(b.npiles, 1), dtype=np.int32)
+    ev = GapEvents(count.ctypes.data_as(_PI), None, 0, 0, 0, 0)
+    if L.damar_pile_gaps(C.byref(b), C.byref(p), flags.ctypes.data_as(_PI), C.byref(ev)):
+        raise RuntimeError("damar_pile_gaps failed")
+    try:
+        flat = np.ctypeslib.as_array(ev.ev, shape=(max(6 * int(ev.nev), 1),))[:6 * int(ev.nev)].copy().reshape(-1, 6)
+    finally:
+        C.CDLL(None).free(ev.ev)
+    at, events = 0, []
+    for n in count[:b.npiles]:
+        events.append([tuple(int(x) for x in row) for row in flat[at:at + n]])
+        at += int(n)
+    return flags[:b.nrec], events
+
+
+def gap_last():
+    """Of the last pile_gaps / of the last batch of gap_las: ({upload, kernel, download, call} ms, piles, piles the host
+    routine did beside the kernel, break events)."""
+    ms, cnt = (C.c_double * 4)(), (c_int64 * 3)()
+    _lib().damar_gap_last(ms, cnt)
+    return dict(zip(("upload", "kernel", "download", "call"), list(ms))), cnt[0], cnt[1], cnt[2]
+
+
+def gap_las(db, las, out, stitch=0, purge=False, trim=None, exclude=None, repeats=None):
+    """LAgap on one .las file: contained records and the records across gaps and breaks flagged, written to `out` (purge:
+    without the discarded records); trim: the trim track the records are cut to first, exclude: the track whose intervals
+    mask breaks, repeats: loaded and not used, as in the reference.  The reference's lines go to stdout.  -> the counters of
+    the run (host_piles: piles the host routine did beside the kernel)."""
+    import numpy as np
+    L = _lib()
+    d = DbInfo()
+    if L.damar_dbinfo_open(db.encode(), C.byref(d)):
+        raise RuntimeError("cannot open database %s" % db)
+    try:
+        got = {}
+        for name in (exclude, repeats):
+            if name is None:
+                continue
+            anno, data, ndata = C.POINTER(C.c_uint64)(), _PI(), c_int64(0)
+            if L.damar_track_read_any(C.byref(d), name.encode(), C.byref(anno), C.byref(data), C.byref(ndata)):
+                raise RuntimeError("could not open track '%s'" % name)
+            got[name] = (np.ctypeslib.as_array(anno, shape=(d.nreads + 1,)).copy(),
+                         np.ctypeslib.as_array(data, shape=(max(ndata.value, 1),))[:ndata.value].copy())
+            C.CDLL(None).free(anno)
+            C.CDLL(None).free(data)
+    finally:
+        L.damar_dbinfo_close(C.byref(d))
+    keep = {}
+    p = _gap_params(stitch, got.get(exclude) if exclude is not None else None, keep)
+    p.purge = 1 if purge else 0
+    p.trim_track = trim.encode() if trim else None
+    st = GapStats()
+    if L.damar_gap_las(db.encode(), las.encode(), out.encode(), C.byref(p), C.byref(st)):
+        raise RuntimeError("damar_gap_las failed")
+    res = {k: int(getattr(st, k)) for k, _ in GapStats._fields_ if k != "trim"}
+    res["trim"] = {k: int(getattr(st.trim, k)) for k, _ in TrimStats._fields_}
     return res
 
 

@@ -3,6 +3,8 @@
 #ifndef DAMAR_HOST_H
 #define DAMAR_HOST_H
 
+#include <stdio.h>
+
 #include "damar_db.h"
 #include "damar_align.h"
 #include "damar_hip.h"
@@ -133,6 +135,45 @@ typedef struct
   int64 boxes, box_a, box_b;   /* trace segments realigned, and the bases of A and of B in them */
 } damar_trim_stats;
 int  damar_trim_las(const char *db, const char *las, const char *out, const char *track, int purge, damar_trim_stats *st);
+/* The same per batch of whole piles in memory (what damar_trim_las and gap.c run): open loads the trim track and the bases
+   (NULL; *no_track set and no message when the track is not there), batch runs plan / align / settle on the batches of one
+   file in file order and leaves every record's new coordinates, flags, differences and trace values (record i's are the
+   tlen[i] values at trace + toff[i]) in arrays of the trimmer's, good until the next call; st is added to. */
+typedef struct damar_trimmer damar_trimmer;
+typedef struct
+{ const int    *abpos, *aepos, *bbpos, *bepos, *flags, *diffs, *tlen;     /* [nrec] */
+  const int64  *toff;
+  const uint16 *trace;
+} damar_trimmed;
+damar_trimmer *damar_trimmer_open(const char *dbname, const damar_dbinfo *db, const char *track, int *no_track);
+int  damar_trimmer_batch(damar_trimmer *tm, const damar_trace_batch *t, const int *rdiffs, const char *las, int64 first,
+                         damar_trim_stats *st, damar_trimmed *res);
+int  damar_trimmer_aread(const damar_trimmer *tm, int64 rec);
+void damar_trimmer_close(damar_trimmer *tm);
+/* one record as it lies in a .las file: the ten words of rec (rec[0]: the number of trace values), then v at tbytes bytes a
+   value.  0; 1 (no message) when the write fails; 2 after "<tool>: Compression of trace to bytes fails, value too big" */
+int  damar_write_record(FILE *fo, const int *rec, const uint16 *v, int tbytes, const char *tool, unsigned char **obuf, int64 *ocap);
+
+/* a track of the whole database in either form, the compressed one first: as damar_track_read_a2.  0, or 1 (no message) */
+int  damar_track_read_any(const damar_dbinfo *db, const char *track, uint64 **anno, int **data, int64 *ndata);
+
+/* gap.c: LAgap (scrub/LAgap.c) -- the plain routine behind damar_pile_gaps (DAMAR_PILES=host, and the piles the kernel
+   leaves), the checks both paths share, and the pass over a file. */
+typedef struct { int *ev; int64 n, cap; } damar_gap_list;       /* DAMAR_GAP_EVENT_INTS ints per event, n events */
+int  damar_gap_inputs_valid(const damar_pile_batch *b, const damar_gap_params *p);          /* 0 after a message */
+/* one pile: flags_out[the pile's records] from the batch's flags, its events appended to L, cnt[3] (contained, breaks,
+   records dropped) added to */
+void damar_host_gap_pile(const damar_pile_batch *b, int64 pile, const damar_gap_params *p, int *flags_out, damar_gap_list *L, int64 *cnt);
+typedef struct
+{ int64 novl, written, discarded;
+  int64 contained, breaks, dropped;        /* the reference's closing counters */
+  int64 piles, host_piles, events;         /* summed over the batches: damar_gap_last's counts */
+  damar_trim_stats trim;                   /* -t */
+} damar_gap_stats;
+/* the pass over a file: per batch of whole piles the trim (p->trim_track), damar_pile_gaps, the reference's lines on stdout,
+   and the records written to `out` in file order (p->purge: without the discarded ones).  0, or 1 after a message. */
+void damar_gap_no_track(const char *track);      /* the reference's two lines for a track that cannot be loaded */
+int  damar_gap_las(const char *db, const char *las, const char *out, const damar_gap_params *p, damar_gap_stats *st);
 
 /* bridge.c: the exact alignment of one box into trace pairs (what damar_trace_boxes returns per box): A[0..M) against
    B[0..N), M, N >= 1, A's position 0 lying abpos >= 0 bases into the grid of ts; trace holds

@@ -9,6 +9,8 @@
  *   align   -- all boxes of the batch in one damar_align_boxes call (kernels/box_align.hip, or the host routine);
  *   settle  -- each box's script walked for the cut, the left box's values patched in before the right one's, the final
  *              discard test and the differences summed again from the trace.
+ * The three phases are damar_trimmer_batch, on one batch in memory; damar_trim_las is the file loop around it, and gap.c
+ * (LAgap -t) runs the same routine on its batches.
  * Nothing here touches the GPU runtime but that one call. */
 #include <stdio.h>
 #include <stdlib.h>
@@ -77,6 +79,15 @@ done:
       memset(t, 0, sizeof(*t));
     }
   return rc;
+}
+
+int damar_track_read_any(const damar_dbinfo *db, const char *track, uint64 **anno, int **data, int64 *ndata)
+{ TrimTrack t;
+  memset(&t, 0, sizeof(t));
+  if (damar_track_read_a2(db->path, track, db->nreads, &t.anno, &t.data, &t.ndata) && read_anno_data(db, track, &t))
+    return 1;
+  *anno = t.anno;  *data = t.data;  *ndata = t.ndata;
+  return 0;
 }
 
 /* lib/utils.c:258-284: a read without an entry, or with an empty one, keeps nothing */
@@ -298,42 +309,287 @@ static void load_a(ABuffer *ab, const HITS_DB *blk, int r)
     }
 }
 
-int damar_trim_las(const char *dbname, const char *las, const char *out, const char *track, int purge, damar_trim_stats *st)
-{ damar_dbinfo db;
+/* What a batch needs beyond its records: the track, the bases, and every buffer the three phases work in.  One trimmer
+   serves all batches of a file, in file order (the A buffer above depends on that order). */
+struct damar_trimmer
+{ const damar_dbinfo *db;
   HITS_DB   blk;
   TrimTrack tt;
-  damar_pile_reader *r = NULL;
-  damar_trace_batch  t;
-  FILE   *fo = NULL;
-  uint16 *tr = NULL;           /* the batch's traces, two bytes a value */
-  int64  *troff = NULL;        /* per record: where its values begin in tr */
-  Plan   *plan = NULL;
+  int       have_blk;
+  uint16 *tr;                  /* the batch's traces, two bytes a value */
+  int64  *troff;               /* per record: where its values begin in tr */
+  Plan   *plan;
   SegList L;
   ABuffer abuf;
-  char   *bases = NULL;
-  int    *arec = NULL;         /* per record: its A read */
-  int    *bm = NULL, *bn = NULL, *bdiffs = NULL, *script = NULL;
-  int64  *baoff = NULL, *bboff = NULL, *soff = NULL;
+  char   *bases;
+  int    *arec;                /* per record: its A read */
+  int    *bm, *bn, *bdiffs;
+  int64  *baoff, *bboff, *soff;
+  int    *o[7];                /* the result's columns */
+  int64  *otoff;
+  int64   trcap, rcap, bcap, basecap;
+};
+
+void damar_trimmer_close(damar_trimmer *tm)
+{ int k;
+  if (tm == NULL)
+    return;
+  if (tm->have_blk) damar_close_block(&tm->blk);
+  free(tm->tt.anno);  free(tm->tt.data);
+  free(tm->tr);  free(tm->troff);  free(tm->plan);  free(tm->arec);  free(tm->L.seg);  free(tm->L.rec);
+  free(tm->abuf.base);  free(tm->bases);  free(tm->bm);  free(tm->bn);  free(tm->bdiffs);  free(tm->baoff);  free(tm->bboff);
+  free(tm->soff);  free(tm->otoff);
+  for (k = 0; k < 7; k++) free(tm->o[k]);
+  free(tm);
+}
+
+damar_trimmer *damar_trimmer_open(const char *dbname, const damar_dbinfo *db, const char *track, int *no_track)
+{ damar_trimmer *tm = (damar_trimmer *) calloc(1, sizeof(*tm));
+  *no_track = 0;
+  if (tm == NULL)
+    return NULL;
+  tm->db = db;
+  tm->abuf.holds = -1;
+  if (damar_track_read_a2(db->path, track, db->nreads, &tm->tt.anno, &tm->tt.data, &tm->tt.ndata) && read_anno_data(db, track, &tm->tt))
+    { *no_track = 1;
+      damar_trimmer_close(tm);
+      return NULL;
+    }
+  if (damar_read_block(dbname, &tm->blk))
+    { damar_trimmer_close(tm);
+      return NULL;
+    }
+  tm->have_blk = 1;
+  return tm;
+}
+
+/* plan, align, settle for one batch of whole piles: rdiffs are the records' differences as the file has them, `first` the
+   number of the batch's first record in the file (for messages), st is added to.  0, or 1 after a message. */
+int damar_trimmer_batch(damar_trimmer *tm, const damar_trace_batch *tb, const int *rdiffs, const char *las, int64 first,
+                        damar_trim_stats *st, damar_trimmed *res)
+{ const damar_pile_batch *b = &tb->p;
+  const damar_dbinfo *db = tm->db;
+  const damar_trace_batch t = *tb;
+  const int tw = t.tspace, tbytes = t.tbytes;
+  uint16 *tr;
+  int64  *troff;
+  Plan   *plan;
+  int    *arec, *bm, *bn, *bdiffs, *script = NULL;
+  int64  *baoff, *bboff, *soff;
+  char   *bases;
+  SegList *Lp = &tm->L;
+  ABuffer *abuf = &tm->abuf;
+  int64 nval = 0, pi, nbase = 0, k, i;
+  damar_box_batch bb;
+
+  if (abuf->base == NULL || abuf->room < db->maxlen + (tw > 0 ? tw : 0) + 8)
+    { abuf->room = db->maxlen + (tw > 0 ? tw : 0) + 8;
+      abuf->base = (char *) tmalloc(abuf->base, (size_t) abuf->room);
+      memset(abuf->base, 0, (size_t) abuf->room);
+      abuf->holds = -1;
+    }
+  for (i = 0; i < b->nrec; i++) nval += t.tlen[i];
+  if (nval > tm->trcap)
+    { tm->trcap = nval + nval / 4 + 1024;
+      tm->tr = (uint16 *) tmalloc(tm->tr, sizeof(uint16) * (size_t) tm->trcap);
+    }
+  if (b->nrec > tm->rcap || tm->plan == NULL)
+    { tm->rcap = b->nrec + b->nrec / 4 + 1024;
+      tm->troff = (int64 *) tmalloc(tm->troff, sizeof(int64) * (size_t) tm->rcap);
+      tm->otoff = (int64 *) tmalloc(tm->otoff, sizeof(int64) * (size_t) tm->rcap);
+      tm->plan = (Plan *) tmalloc(tm->plan, sizeof(Plan) * (size_t) tm->rcap);
+      tm->arec = (int *) tmalloc(tm->arec, sizeof(int) * (size_t) tm->rcap);
+      for (k = 0; k < 7; k++)
+        tm->o[k] = (int *) tmalloc(tm->o[k], sizeof(int) * (size_t) tm->rcap);
+    }
+  tr = tm->tr;  troff = tm->troff;  plan = tm->plan;  arec = tm->arec;
+  for (i = 0, nval = 0; i < b->nrec; i++)
+    { const unsigned char *src = t.trace + t.trace_off[i];
+      troff[i] = nval;
+      if (tbytes == 1)
+        for (k = 0; k < t.tlen[i]; k++) tr[nval + k] = src[k];
+      else
+        memcpy(tr + nval, src, sizeof(uint16) * (size_t) t.tlen[i]);
+      nval += t.tlen[i];
+    }
+
+  /* plan */
+  Lp->n = 0;
+  for (pi = 0; pi < b->npiles; pi++)
+    { const int a = b->pile_aread[pi];
+      int a_lo, a_hi;
+      if (a < 0 || a >= db->nreads)
+        { fprintf(stderr, "damar: %s holds reads the database does not have\n", las);
+          return 1;
+        }
+      trim_of(&tm->tt, a, &a_lo, &a_hi);
+      for (i = b->pile_off[pi]; i < b->pile_off[pi + 1]; i++)
+        { Plan *p = plan + i;
+          const int br = b->bread[i];
+          int b_lo, b_hi;
+          arec[i] = a;
+          if (br < 0 || br >= db->nreads || t.tlen[i] < 2 || (t.tlen[i] & 1))
+            { fprintf(stderr, "damar: %s: record %lld is malformed\n", las, (long long) (first + i));
+              return 1;
+            }
+          p->abpos = b->abpos[i];  p->aepos = b->aepos[i];  p->bbpos = b->bbpos[i];  p->bepos = b->bepos[i];
+          st->novl_bases += (p->aepos - p->abpos) + (p->bepos - p->bbpos);
+          trim_of(&tm->tt, br, &b_lo, &b_hi);
+          if (a_lo >= a_hi || b_lo >= b_hi)
+            { p->fate = FATE_GONE;
+              p->t0 = 0;  p->tlen = t.tlen[i];
+              p->lbox = p->rbox = -1;
+              continue;
+            }
+          if (b->flags[i] & OVL_COMP_FLAG)
+            { const int blen = db->read_len[br], q = b_lo;
+              b_lo = blen - b_hi;
+              b_hi = blen - q;
+            }
+          plan_record(p, tr + troff[i], t.tlen[i], tw, a_lo, a_hi, b_lo, b_hi, i, Lp, st);
+        }
+    }
+  st->novl += b->nrec;
+
+  /* align */
+  if (Lp->n > tm->bcap || tm->bm == NULL)
+    { tm->bcap = Lp->n + Lp->n / 4 + 1024;
+      tm->bm = (int *) tmalloc(tm->bm, sizeof(int) * (size_t) tm->bcap);
+      tm->bn = (int *) tmalloc(tm->bn, sizeof(int) * (size_t) tm->bcap);
+      tm->bdiffs = (int *) tmalloc(tm->bdiffs, sizeof(int) * (size_t) tm->bcap);
+      tm->baoff = (int64 *) tmalloc(tm->baoff, sizeof(int64) * (size_t) tm->bcap);
+      tm->bboff = (int64 *) tmalloc(tm->bboff, sizeof(int64) * (size_t) tm->bcap);
+      tm->soff = (int64 *) tmalloc(tm->soff, sizeof(int64) * ((size_t) tm->bcap + 1));
+    }
+  bm = tm->bm;  bn = tm->bn;  bdiffs = tm->bdiffs;  baoff = tm->baoff;  bboff = tm->bboff;  soff = tm->soff;
+  for (k = 0; k < Lp->n; k++)
+    { bm[k] = Lp->seg[k].ae - Lp->seg[k].ab;
+      bn[k] = Lp->seg[k].be - Lp->seg[k].bb;
+      st->box_a += bm[k];
+      st->box_b += bn[k];
+      baoff[k] = nbase;
+      bboff[k] = nbase + bm[k];
+      nbase += bm[k] + bn[k];
+    }
+  if (nbase > tm->basecap || tm->bases == NULL)
+    { tm->basecap = nbase + nbase / 4 + 4096;
+      tm->bases = (char *) tmalloc(tm->bases, (size_t) tm->basecap);
+    }
+  bases = tm->bases;
+  for (k = 0; k < Lp->n; k++)
+    { const int64 rec = Lp->rec[k];
+      load_a(abuf, &tm->blk, arec[rec]);
+      for (i = 0; i < bm[k]; i++)
+        bases[baoff[k] + i] = (Lp->seg[k].ab + i < abuf->room) ? abuf->base[Lp->seg[k].ab + i] : 4;
+      gather_b(&tm->blk, b->bread[rec], b->flags[rec] & OVL_COMP_FLAG, Lp->seg[k].bb, Lp->seg[k].be, bases + bboff[k]);
+    }
+  if (Lp->n > 0)
+    { bb.nbox = Lp->n;  bb.m = bm;  bb.n = bn;  bb.aoff = baoff;  bb.boff = bboff;  bb.bases = bases;  bb.nbases = nbase;
+      if (damar_align_boxes(&bb, bdiffs, soff, &script))
+        return 1;
+      st->boxes += Lp->n;
+    }
+
+  /* settle */
+  for (i = 0; i < b->nrec; i++)
+    { Plan   *p = plan + i;
+      uint16 *v = tr + troff[i] + p->t0;
+      int     flags = b->flags[i], diffs = rdiffs[i];
+      if (p->fate == FATE_GONE)
+        flags |= OVL_DISCARD_FLAG | OVL_TRIM_FLAG;
+      else if (p->fate == FATE_CUT)
+        { int stop_a, dl, dr;
+          st->ntrim_bases += p->known;
+          if (p->lbox >= 0)
+            { const Seg *s = Lp->seg + p->lbox;
+              walk_script(bases + baoff[p->lbox], bm[p->lbox], bases + bboff[p->lbox], script + soff[p->lbox],
+                          (int) (soff[p->lbox + 1] - soff[p->lbox]), s->stop - s->bb, &stop_a, &dl, &dr);
+              stop_a += s->ab;
+              v[0] = (uint16) dr;
+              if (s->ae == stop_a)                         /* the cut would leave an empty first segment */
+                stop_a -= 1;
+              st->ntrim_bases += stop_a - p->a_lo;
+              p->abpos = stop_a;
+            }
+          if (p->rbox >= 0)
+            { const Seg *s = Lp->seg + p->rbox;
+              walk_script(bases + baoff[p->rbox], bm[p->rbox], bases + bboff[p->rbox], script + soff[p->rbox],
+                          (int) (soff[p->rbox + 1] - soff[p->rbox]), s->stop - s->bb, &stop_a, &dl, &dr);
+              stop_a += s->ab;
+              v[p->tlen - 2] = (uint16) dl;
+              st->ntrim_bases += p->a_hi - stop_a;
+              p->aepos = stop_a;
+            }
+          /* what is left may cover next to nothing of either read (trim.c:442) */
+          if (p->abpos >= p->aepos || p->bepos < p->keep_lo || p->bbpos > p->keep_hi)
+            flags |= OVL_DISCARD_FLAG | OVL_TRIM_FLAG;
+          else
+            { int j;
+              diffs = 0;
+              for (j = 0; j < p->tlen; j += 2)
+                diffs += v[j];
+            }
+        }
+      tm->o[0][i] = (p->fate == FATE_CUT) ? p->abpos : b->abpos[i];  tm->o[1][i] = (p->fate == FATE_CUT) ? p->aepos : b->aepos[i];
+      tm->o[2][i] = (p->fate == FATE_CUT) ? p->bbpos : b->bbpos[i];  tm->o[3][i] = (p->fate == FATE_CUT) ? p->bepos : b->bepos[i];
+      tm->o[4][i] = flags;  tm->o[5][i] = diffs;  tm->o[6][i] = p->tlen;
+      tm->otoff[i] = troff[i] + p->t0;
+    }
+  free(script);
+  res->abpos = tm->o[0];  res->aepos = tm->o[1];  res->bbpos = tm->o[2];  res->bepos = tm->o[3];
+  res->flags = tm->o[4];  res->diffs = tm->o[5];  res->tlen = tm->o[6];
+  res->toff = tm->otoff;  res->trace = tr;
+  return 0;
+}
+
+/* one record as it lies in the file: the ten words, then its trace values at tbytes bytes each.  *obuf / *ocap: the
+   caller's buffer, grown here.  0, or 1 (no message) when the write fails, 2 after the reference's message when a value
+   does not fit a byte. */
+int damar_write_record(FILE *fo, const int *rec, const uint16 *v, int tbytes, const char *tool, unsigned char **obuf, int64 *ocap)
+{ const int tlen = rec[0];
+  const int64 need = 40 + (int64) tbytes * tlen;
+  int k;
+  if (need > *ocap)
+    { *ocap = need + need / 4 + 1024;
+      *obuf = (unsigned char *) tmalloc(*obuf, (size_t) *ocap);
+    }
+  if (tbytes == 1)
+    for (k = 0; k < tlen; k++)
+      { if (v[k] > 255)
+          { fprintf(stderr, "%s: Compression of trace to bytes fails, value too big\n", tool);
+            return 2;
+          }
+        (*obuf)[40 + k] = (unsigned char) v[k];
+      }
+  else
+    memcpy(*obuf + 40, v, sizeof(uint16) * (size_t) tlen);
+  memcpy(*obuf, rec, 40);
+  return fwrite(*obuf, 1, (size_t) need, fo) != (size_t) need;
+}
+
+int damar_trim_las(const char *dbname, const char *las, const char *out, const char *track, int purge, damar_trim_stats *st)
+{ damar_dbinfo db;
+  damar_trimmer *tm = NULL;
+  damar_pile_reader *r = NULL;
+  damar_trace_batch  t;
+  damar_trimmed      res;
+  FILE   *fo = NULL;
   unsigned char *obuf = NULL;
-  int64   trcap = 0, rcap = 0, bcap = 0, basecap = 0, ocap = 0, written = 0, i;
-  int     got, rc = 1, have_db = 0, have_blk = 0, tw, tbytes;
+  int64   ocap = 0, written = 0, i;
+  int     got, rc = 1, have_db = 0, tw, no_track;
 
   memset(st, 0, sizeof(*st));
-  memset(&tt, 0, sizeof(tt));
-  memset(&L, 0, sizeof(L));
-  memset(&abuf, 0, sizeof(abuf));
   if (damar_dbinfo_open(dbname, &db))
     return 1;
   have_db = 1;
-  if (damar_track_read_a2(db.path, track, db.nreads, &tt.anno, &tt.data, &tt.ndata) && read_anno_data(&db, track, &tt))
-    { /* the loader's line first, as the reference prints it: it never sets its program name */
-      fprintf(stderr, "(null): Track '%s' does not exist\n", track);
-      fprintf(stderr, "could not open trim track '%s'\n", track);
+  if ((tm = damar_trimmer_open(dbname, &db, track, &no_track)) == NULL)
+    { if (no_track)
+        { /* the loader's line first, as the reference prints it: it never sets its program name */
+          fprintf(stderr, "(null): Track '%s' does not exist\n", track);
+          fprintf(stderr, "could not open trim track '%s'\n", track);
+        }
       goto done;
     }
-  if (damar_read_block(dbname, &blk))
-    goto done;
-  have_blk = 1;
   if ((r = damar_piles_open_traces(las, 0, 0)) == NULL)
     goto done;
   if ((fo = fopen(out, "w")) == NULL)
@@ -341,11 +597,6 @@ int damar_trim_las(const char *dbname, const char *las, const char *out, const c
       goto done;
     }
   tw = damar_piles_tspace(r);
-  tbytes = (tw <= TRACE_XOVR) ? 1 : 2;
-  abuf.room = db.maxlen + (tw > 0 ? tw : 0) + 8;
-  abuf.base = (char *) tmalloc(NULL, (size_t) abuf.room);
-  memset(abuf.base, 0, (size_t) abuf.room);
-  abuf.holds = -1;
   { const int64 zero = 0;
     if (fwrite(&zero, sizeof(int64), 1, fo) != 1 || fwrite(&tw, sizeof(int), 1, fo) != 1)
       goto wfail;
@@ -354,182 +605,29 @@ int damar_trim_las(const char *dbname, const char *las, const char *out, const c
   while ((got = damar_piles_next_traces(r, &t)) > 0)
     { const damar_pile_batch *b = &t.p;
       const int *rdiffs, *rlast;
-      int64 nval = 0, pi, nbase = 0, k;
-      damar_box_batch bb;
 
       damar_piles_rest(r, &rdiffs, &rlast);
-      for (i = 0; i < b->nrec; i++) nval += t.tlen[i];
-      if (nval > trcap)
-        { trcap = nval + nval / 4 + 1024;
-          tr = (uint16 *) tmalloc(tr, sizeof(uint16) * (size_t) trcap);
-        }
-      if (b->nrec > rcap)
-        { rcap = b->nrec + b->nrec / 4 + 1024;
-          troff = (int64 *) tmalloc(troff, sizeof(int64) * (size_t) rcap);
-          plan = (Plan *) tmalloc(plan, sizeof(Plan) * (size_t) rcap);
-          arec = (int *) tmalloc(arec, sizeof(int) * (size_t) rcap);
-        }
-      for (i = 0, nval = 0; i < b->nrec; i++)
-        { const unsigned char *src = t.trace + t.trace_off[i];
-          troff[i] = nval;
-          if (tbytes == 1)
-            for (k = 0; k < t.tlen[i]; k++) tr[nval + k] = src[k];
-          else
-            memcpy(tr + nval, src, sizeof(uint16) * (size_t) t.tlen[i]);
-          nval += t.tlen[i];
-        }
-
-      /* plan */
-      L.n = 0;
-      for (pi = 0; pi < b->npiles; pi++)
-        { const int a = b->pile_aread[pi];
-          int a_lo, a_hi;
-          if (a < 0 || a >= db.nreads)
-            { fprintf(stderr, "damar: %s holds reads the database does not have\n", las);
-              goto done;
-            }
-          trim_of(&tt, a, &a_lo, &a_hi);
-          for (i = b->pile_off[pi]; i < b->pile_off[pi + 1]; i++)
-            { Plan *p = plan + i;
-              const int br = b->bread[i];
-              int b_lo, b_hi;
-              arec[i] = a;
-              if (br < 0 || br >= db.nreads || t.tlen[i] < 2 || (t.tlen[i] & 1))
-                { fprintf(stderr, "damar: %s: record %lld is malformed\n", las, (long long) (st->novl + i));
-                  goto done;
-                }
-              p->abpos = b->abpos[i];  p->aepos = b->aepos[i];  p->bbpos = b->bbpos[i];  p->bepos = b->bepos[i];
-              st->novl_bases += (p->aepos - p->abpos) + (p->bepos - p->bbpos);
-              trim_of(&tt, br, &b_lo, &b_hi);
-              if (a_lo >= a_hi || b_lo >= b_hi)
-                { p->fate = FATE_GONE;
-                  p->t0 = 0;  p->tlen = t.tlen[i];
-                  p->lbox = p->rbox = -1;
-                  continue;
-                }
-              if (b->flags[i] & OVL_COMP_FLAG)
-                { const int blen = db.read_len[br], q = b_lo;
-                  b_lo = blen - b_hi;
-                  b_hi = blen - q;
-                }
-              plan_record(p, tr + troff[i], t.tlen[i], tw, a_lo, a_hi, b_lo, b_hi, i, &L, st);
-            }
-        }
-      st->novl += b->nrec;
-
-      /* align */
-      if (L.n > bcap)
-        { bcap = L.n + L.n / 4 + 1024;
-          bm = (int *) tmalloc(bm, sizeof(int) * (size_t) bcap);
-          bn = (int *) tmalloc(bn, sizeof(int) * (size_t) bcap);
-          bdiffs = (int *) tmalloc(bdiffs, sizeof(int) * (size_t) bcap);
-          baoff = (int64 *) tmalloc(baoff, sizeof(int64) * (size_t) bcap);
-          bboff = (int64 *) tmalloc(bboff, sizeof(int64) * (size_t) bcap);
-          soff = (int64 *) tmalloc(soff, sizeof(int64) * ((size_t) bcap + 1));
-        }
-      for (k = 0; k < L.n; k++)
-        { bm[k] = L.seg[k].ae - L.seg[k].ab;
-          bn[k] = L.seg[k].be - L.seg[k].bb;
-          st->box_a += bm[k];
-          st->box_b += bn[k];
-          baoff[k] = nbase;
-          bboff[k] = nbase + bm[k];
-          nbase += bm[k] + bn[k];
-        }
-      if (nbase > basecap)
-        { basecap = nbase + nbase / 4 + 4096;
-          bases = (char *) tmalloc(bases, (size_t) basecap);
-        }
-      for (k = 0; k < L.n; k++)
-        { const int64 rec = L.rec[k];
-          load_a(&abuf, &blk, arec[rec]);
-          for (i = 0; i < bm[k]; i++)
-            bases[baoff[k] + i] = (L.seg[k].ab + i < abuf.room) ? abuf.base[L.seg[k].ab + i] : 4;
-          gather_b(&blk, b->bread[rec], b->flags[rec] & OVL_COMP_FLAG, L.seg[k].bb, L.seg[k].be, bases + bboff[k]);
-        }
-      script = NULL;
-      if (L.n > 0)
-        { bb.nbox = L.n;  bb.m = bm;  bb.n = bn;  bb.aoff = baoff;  bb.boff = bboff;  bb.bases = bases;  bb.nbases = nbase;
-          if (damar_align_boxes(&bb, bdiffs, soff, &script))
-            goto done;
-          st->boxes += L.n;
-        }
-
-      /* settle, and the records as they go to the file */
+      if (damar_trimmer_batch(tm, &t, rdiffs, las, st->novl, st, &res))
+        goto done;
+      /* the records as they go to the file */
       for (i = 0; i < b->nrec; i++)
-        { Plan   *p = plan + i;
-          uint16 *v = tr + troff[i] + p->t0;
-          int     flags = b->flags[i], diffs = rdiffs[i], rec[10];
-          int64   need;
-          if (p->fate == FATE_GONE)
-            flags |= OVL_DISCARD_FLAG | OVL_TRIM_FLAG;
-          else if (p->fate == FATE_CUT)
-            { int stop_a, dl, dr;
-              st->ntrim_bases += p->known;
-              if (p->lbox >= 0)
-                { const Seg *s = L.seg + p->lbox;
-                  walk_script(bases + baoff[p->lbox], bm[p->lbox], bases + bboff[p->lbox], script + soff[p->lbox],
-                              (int) (soff[p->lbox + 1] - soff[p->lbox]), s->stop - s->bb, &stop_a, &dl, &dr);
-                  stop_a += s->ab;
-                  v[0] = (uint16) dr;
-                  if (s->ae == stop_a)                         /* the cut would leave an empty first segment */
-                    stop_a -= 1;
-                  st->ntrim_bases += stop_a - p->a_lo;
-                  p->abpos = stop_a;
-                }
-              if (p->rbox >= 0)
-                { const Seg *s = L.seg + p->rbox;
-                  walk_script(bases + baoff[p->rbox], bm[p->rbox], bases + bboff[p->rbox], script + soff[p->rbox],
-                              (int) (soff[p->rbox + 1] - soff[p->rbox]), s->stop - s->bb, &stop_a, &dl, &dr);
-                  stop_a += s->ab;
-                  v[p->tlen - 2] = (uint16) dl;
-                  st->ntrim_bases += p->a_hi - stop_a;
-                  p->aepos = stop_a;
-                }
-              /* what is left may cover next to nothing of either read (trim.c:442) */
-              if (p->abpos >= p->aepos || p->bepos < p->keep_lo || p->bbpos > p->keep_hi)
-                flags |= OVL_DISCARD_FLAG | OVL_TRIM_FLAG;
-              else
-                { int j;
-                  diffs = 0;
-                  for (j = 0; j < p->tlen; j += 2)
-                    diffs += v[j];
-                }
-            }
-          if (flags & OVL_DISCARD_FLAG)
+        { int rec[10], w;
+          if (res.flags[i] & OVL_DISCARD_FLAG)
             { st->discarded += 1;
               if (purge)
                 continue;
             }
-          rec[0] = p->tlen;  rec[1] = diffs;
-          rec[2] = (p->fate == FATE_CUT) ? p->abpos : b->abpos[i];  rec[3] = (p->fate == FATE_CUT) ? p->bbpos : b->bbpos[i];
-          rec[4] = (p->fate == FATE_CUT) ? p->aepos : b->aepos[i];  rec[5] = (p->fate == FATE_CUT) ? p->bepos : b->bepos[i];
-          rec[6] = flags & ~OVL_TEMP_FLAG;
-          rec[7] = arec[i];  rec[8] = b->bread[i];  rec[9] = rlast[i];
-          need = 40 + (int64) tbytes * p->tlen;
-          if (need > ocap)
-            { ocap = need + need / 4 + 1024;
-              obuf = (unsigned char *) tmalloc(obuf, (size_t) ocap);
-            }
-          if (tbytes == 1)
-            for (k = 0; k < p->tlen; k++)
-              { if (v[k] > 255)
-                  { fprintf(stderr, "LAtrim: Compression of trace to bytes fails, value too big\n");
-                    free(script);
-                    goto done;
-                  }
-                obuf[40 + k] = (unsigned char) v[k];
-              }
-          else
-            memcpy(obuf + 40, v, sizeof(uint16) * (size_t) p->tlen);
-          memcpy(obuf, rec, 40);
-          if (fwrite(obuf, 1, (size_t) need, fo) != (size_t) need)
-            { free(script);
-              goto wfail;
-            }
+          rec[0] = res.tlen[i];  rec[1] = res.diffs[i];
+          rec[2] = res.abpos[i];  rec[3] = res.bbpos[i];
+          rec[4] = res.aepos[i];  rec[5] = res.bepos[i];
+          rec[6] = res.flags[i] & ~OVL_TEMP_FLAG;
+          rec[7] = damar_trimmer_aread(tm, i);  rec[8] = b->bread[i];  rec[9] = rlast[i];
+          if ((w = damar_write_record(fo, rec, res.trace + res.toff[i], t.tbytes, "LAtrim", &obuf, &ocap)) == 2)
+            goto done;
+          if (w)
+            goto wfail;
           written += 1;
         }
-      free(script);
     }
   if (got < 0)
     goto done;
@@ -547,10 +645,11 @@ done:
       rc = 1;
     }
   damar_piles_close(r);
-  if (have_blk) damar_close_block(&blk);
+  damar_trimmer_close(tm);
   if (have_db) damar_dbinfo_close(&db);
-  free(tt.anno);  free(tt.data);
-  free(tr);  free(troff);  free(plan);  free(arec);  free(L.seg);  free(L.rec);
-  free(abuf.base);  free(bases);  free(bm);  free(bn);  free(bdiffs);  free(baoff);  free(bboff);  free(soff);  free(obuf);
+  free(obuf);
   return rc;
 }
+
+int damar_trimmer_aread(const damar_trimmer *tm, int64 rec)
+{ return tm->arec[rec]; }

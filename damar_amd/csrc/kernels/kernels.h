@@ -417,6 +417,27 @@ void damar_launch_hom_seed(const HomArgs *a, hipStream_t st);
 void damar_launch_hom_count(const HomArgs *a, hipStream_t st);
 void damar_launch_hom_emit(const HomArgs *a, hipStream_t st);
 
+/* pile_gaps.hip: LAgap's containments, gaps and breaks, one wavefront per pile (include/damar_hip.h damar_pile_gaps; the
+   DAMAR_GAP_* bounds and kinds are defined there).  A pile with status 1 afterwards is the host's: a read of more than
+   maxbins bins, skip[pile] set, or more than maxev events. */
+typedef struct
+{ u32 npiles;
+  int maxbins, maxev, stitch;
+  const long long *pile_off;          /* [npiles + 1] */
+  const int *pile_aread;              /* [npiles] */
+  const int *abpos, *aepos, *bbpos, *bepos, *bread, *flags;       /* [nrec] */
+  const int *read_len;                /* [nreads] */
+  const u64 *ex_anno;                 /* [nreads + 1] byte offsets into ex_data, NULL: no exclude track */
+  const int *ex_data;
+  const u8  *skip;                    /* [npiles] */
+  int *flags_out;                     /* [nrec] */
+  int *status, *nev;                  /* [npiles] */
+  int *ev;                            /* [npiles * DAMAR_GAP_MAXEVENTS * DAMAR_GAP_EVENT_INTS] */
+  int *cnt;                           /* [npiles * 3]: contained, breaks, records dropped */
+} GapArgs;
+
+void damar_launch_pile_gaps(const GapArgs *a, hipStream_t st);
+
 /* box_align.hip: exact alignment of a batch of boxes with their edit scripts (align.c:4734 DIFF_ALIGN).  A box with
    max(m, n) <= maxlen <= DAMAR_BOX_MAXLEN is done and leaves its differences, the length of its script (-1: it hit a bound of
    the kernel and is the host's after all) and the script at script + coff[box], max(m, n) values of room; the others are

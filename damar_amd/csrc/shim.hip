@@ -5195,3 +5195,161 @@ extern "C" int damar_trace_boxes(const damar_tbox_batch *b, int *diffs, int64 *t
   TB_ms[3] = now_ms() - w0;
   return 0;
 }
+
+/***** LAgap's containments, gaps and breaks per pile: scrub/LAgap.c (kernels/pile_gaps.hip) ******************************/
+
+static DBuf GP_off, GP_aread, GP_col[6], GP_rlen, GP_xanno, GP_xdata, GP_skip, GP_flags, GP_status, GP_nev, GP_ev, GP_cnt;
+static double GP_ms[4];        /* of the last call: upload, kernel, download (HIP events), whole call (wall) */
+static int64  GP_cnt3[3];      /* piles, piles the host routine did beside the kernel, break events */
+static hipEvent_t GP_evt[4];
+static int    GP_ev_made;
+
+extern "C" void damar_gap_release(void)
+{ DBuf *all[] = { &GP_off, &GP_aread, &GP_col[0], &GP_col[1], &GP_col[2], &GP_col[3], &GP_col[4], &GP_col[5], &GP_rlen, &GP_xanno, &GP_xdata,
+                  &GP_skip, &GP_flags, &GP_status, &GP_nev, &GP_ev, &GP_cnt };
+  for (DBuf *b : all) b->drop();
+  if (GP_ev_made)
+    for (int i = 0; i < 4; i++) (void) hipEventDestroy(GP_evt[i]);
+  GP_ev_made = 0;
+}
+
+extern "C" void damar_gap_limits(int *bins, int *events)
+{ *bins = DAMAR_GAP_MAXBINS;
+  *events = DAMAR_GAP_MAXEVENTS;
+}
+
+extern "C" void damar_gap_last(double *ms, int64 *cnt)
+{ for (int i = 0; i < 4; i++) ms[i] = GP_ms[i];
+  for (int i = 0; i < 3; i++) cnt[i] = GP_cnt3[i];
+}
+
+extern "C" int damar_pile_gaps(const damar_pile_batch *b, const damar_gap_params *p, int *flags_out, damar_gap_events *ev)
+{ const double w0 = now_ms();
+  if (ev == NULL || !damar_gap_inputs_valid(b, p) || (b->nrec > 0 && flags_out == NULL) || (b->npiles > 0 && ev->count == NULL))
+    return 1;
+  const size_t np = (size_t) b->npiles, nrec = (size_t) b->nrec;
+  const bool host = damar_piles_on_host() != 0;
+  damar_gap_list L = { NULL, 0, 0 };
+  int64 cnt[3] = { 0, 0, 0 }, fallback = 0;
+  for (int i = 0; i < 4; i++) GP_ms[i] = 0;
+
+  std::vector<u8>  skip(np + 1, 0);
+  std::vector<int> status(np + 1, 1), nev(np + 1, 0), evs, pcnt;
+  if (!host && np > 0)
+    { const char *lower = getenv("DAMAR_TEST_GAP_BINS");
+      const int maxbins = (lower != NULL && atoi(lower) < DAMAR_GAP_MAXBINS) ? atoi(lower) : DAMAR_GAP_MAXBINS;
+      /* the kernel takes the records of one B read for a run.  The reference's containment loop skips a discarded record
+         before it looks at its B read, so where the B reads do not ascend it can pair records across another read's:
+         such a pile is the host routine's */
+      for (size_t q = 0; q < np; q++)
+        for (int64 i = b->pile_off[q] + 1; i < b->pile_off[q + 1]; i++)
+          if (b->bread[i] < b->bread[i - 1])
+            { skip[q] = 1;
+              break;
+            }
+      ensure_init();
+      late_streams();                /* a tool built on this call is through soon after the library comes up: see damar_align_boxes */
+      if (!GP_ev_made)
+        { for (int i = 0; i < 4; i++) HIP_CHECK(hipEventCreate(&GP_evt[i]));
+          GP_ev_made = 1;
+        }
+      GapArgs a;
+      memset(&a, 0, sizeof(a));
+      a.npiles = (u32) np;
+      a.maxbins = maxbins;  a.maxev = DAMAR_GAP_MAXEVENTS;  a.stitch = p->stitch;
+      const size_t evints = np * DAMAR_GAP_MAXEVENTS * DAMAR_GAP_EVENT_INTS;
+      long long *d_off = (long long *) GP_off.need(sizeof(long long) * (np + 1));
+      int *d_aread = (int *) GP_aread.need(sizeof(int) * np + 16);
+      const int *src[6] = { b->abpos, b->aepos, b->bbpos, b->bepos, b->bread, b->flags };
+      int *d_col[6];
+      for (int i = 0; i < 6; i++) d_col[i] = (int *) GP_col[i].need(sizeof(int) * nrec + 16);
+      int *d_rlen = (int *) GP_rlen.need(sizeof(int) * (size_t) b->nreads);
+      u8  *d_skip = (u8 *) GP_skip.need(np + 16);
+      int *d_flags = (int *) GP_flags.need(sizeof(int) * nrec + 16);
+      int *d_status = (int *) GP_status.need(sizeof(int) * np + 16), *d_nev = (int *) GP_nev.need(sizeof(int) * np + 16);
+      int *d_ev = (int *) GP_ev.need(sizeof(int) * evints + 16), *d_cnt = (int *) GP_cnt.need(sizeof(int) * 3 * np + 16);
+      u64 *d_xanno = NULL;
+      int *d_xdata = NULL;
+      HIP_CHECK(hipEventRecord(GP_evt[0], G_st));
+      if (p->ex_anno != NULL)
+        { d_xanno = (u64 *) GP_xanno.need(sizeof(u64) * ((size_t) b->nreads + 1));
+          d_xdata = (int *) GP_xdata.need(sizeof(int) * (size_t) p->ex_ndata + 16);
+          HIP_CHECK(hipMemcpyAsync(d_xanno, p->ex_anno, sizeof(u64) * ((size_t) b->nreads + 1), hipMemcpyHostToDevice, G_st));
+          if (p->ex_ndata > 0)
+            HIP_CHECK(hipMemcpyAsync(d_xdata, p->ex_data, sizeof(int) * (size_t) p->ex_ndata, hipMemcpyHostToDevice, G_st));
+        }
+      HIP_CHECK(hipMemcpyAsync(d_off, b->pile_off, sizeof(long long) * (np + 1), hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_aread, b->pile_aread, sizeof(int) * np, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_skip, skip.data(), np, hipMemcpyHostToDevice, G_st));
+      if (nrec > 0)
+        for (int i = 0; i < 6; i++)
+          HIP_CHECK(hipMemcpyAsync(d_col[i], src[i], sizeof(int) * nrec, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_rlen, b->read_len, sizeof(int) * (size_t) b->nreads, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemsetAsync(d_nev, 0, sizeof(int) * np, G_st));
+      HIP_CHECK(hipEventRecord(GP_evt[1], G_st));
+      a.pile_off = d_off;  a.pile_aread = d_aread;
+      a.abpos = d_col[0];  a.aepos = d_col[1];  a.bbpos = d_col[2];  a.bepos = d_col[3];  a.bread = d_col[4];  a.flags = d_col[5];
+      a.read_len = d_rlen;  a.ex_anno = d_xanno;  a.ex_data = d_xdata;  a.skip = d_skip;
+      a.flags_out = d_flags;  a.status = d_status;  a.nev = d_nev;  a.ev = d_ev;  a.cnt = d_cnt;
+      damar_launch_pile_gaps(&a, G_st);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipEventRecord(GP_evt[2], G_st));
+      evs.resize(evints + 1);
+      pcnt.resize(3 * np + 1);
+      if (nrec > 0)
+        HIP_CHECK(hipMemcpyAsync(flags_out, d_flags, sizeof(int) * nrec, hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipMemcpyAsync(status.data(), d_status, sizeof(int) * np, hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipMemcpyAsync(nev.data(), d_nev, sizeof(int) * np, hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipMemcpyAsync(evs.data(), d_ev, sizeof(int) * evints, hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipMemcpyAsync(pcnt.data(), d_cnt, sizeof(int) * 3 * np, hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipEventRecord(GP_evt[3], G_st));
+      HIP_CHECK(hipStreamSynchronize(G_st));
+      for (int i = 0; i < 3; i++)
+        { float ms = 0;
+          HIP_CHECK(hipEventElapsedTime(&ms, GP_evt[i], GP_evt[i + 1]));
+          GP_ms[i] = ms;
+        }
+    }
+  /* the events in pile order; what the kernel left (all piles with DAMAR_PILES=host) is the plain routine's */
+  for (size_t q = 0; q < np; q++)
+    { const int64 before = L.n;
+      if (status[q] != 0)
+        { damar_host_gap_pile(b, (int64) q, p, flags_out, &L, cnt);
+          fallback += host ? 0 : 1;
+        }
+      else
+        { if (nev[q] < 0 || nev[q] > DAMAR_GAP_MAXEVENTS)
+            { fprintf(stderr, "damar: gaps: pile %zu came back with %d events\n", q, nev[q]);
+              free(L.ev);
+              return 1;
+            }
+          if (L.n + nev[q] > L.cap)
+            { const int64 cap = L.n + nev[q] + L.cap / 4 + 256;
+              int *grown = (int *) realloc(L.ev, sizeof(int) * DAMAR_GAP_EVENT_INTS * (size_t) cap);
+              if (grown == NULL)
+                { fprintf(stderr, "damar: out of memory (gaps)\n");
+                  free(L.ev);
+                  return 1;
+                }
+              L.ev = grown;
+              L.cap = cap;
+            }
+          if (nev[q] > 0)
+            memcpy(L.ev + DAMAR_GAP_EVENT_INTS * L.n, evs.data() + q * DAMAR_GAP_MAXEVENTS * DAMAR_GAP_EVENT_INTS,
+                   sizeof(int) * DAMAR_GAP_EVENT_INTS * (size_t) nev[q]);
+          L.n += nev[q];
+          for (int i = 0; i < 3; i++) cnt[i] += pcnt[3 * q + i];
+        }
+      ev->count[q] = (int) (L.n - before);
+    }
+  if (L.ev == NULL && (L.ev = (int *) malloc(sizeof(int) * DAMAR_GAP_EVENT_INTS)) == NULL)       /* no event: still the caller's to free */
+    { fprintf(stderr, "damar: out of memory (gaps)\n");
+      return 1;
+    }
+  ev->ev = L.ev;
+  ev->nev = L.n;
+  ev->contained = cnt[0];  ev->breaks = cnt[1];  ev->dropped = cnt[2];
+  GP_cnt3[0] = b->npiles;  GP_cnt3[1] = fallback;  GP_cnt3[2] = L.n;
+  GP_ms[3] = now_ms() - w0;
+  return 0;
+}

@@ -367,6 +367,45 @@ void damar_homog_close(damar_homog *h);
  * on the host path); cnt[3] = records seen by add, ranges set in the mask (seed and add), intervals read out */
 void damar_homog_last(double *ms, int64 *cnt);
 
+/* Containments, gaps and breaks of piles (scrub/LAgap.c drop_containments and handle_gaps_and_breaks): per pile, inside every
+ * run of one B read the contained record of a pair is discarded (OVL_DISCARD | OVL_CONT) and the shorter of two records that
+ * intersect on A marked OVL_TEMP; the remaining records are counted over bins of 100 bases, and every run of bins covered at
+ * most once is a break: left alone when an interval of the exclude track strictly contains it or (stitch > 0) a pair of
+ * records of one B read bridges it within `stitch` bases, else the records on the far side of the pile's longest record are
+ * discarded (OVL_DISCARD | OVL_GAP).  A run still open at the pile's last bin is always dropped.  flags_out[nrec] receives
+ * every record's flags word, OVL_TEMP included.  ev->count[npiles] (the caller's) receives the events per pile, ev->ev
+ * (malloc'ed, the caller's to free) DAMAR_GAP_EVENT_INTS ints per event, the piles' back to back in the order the reference
+ * meets them: {first bin, bin after the run, kind, v0, v1, records dropped}; kind is one of DAMAR_GAP_MASKED (v0, v1: the
+ * interval), _STITCHABLE (v0: pairs), _DROP_L, _DROP_R, _DROP_NONE (no record left to decide the side), with
+ * DAMAR_GAP_TRAILING or'ed in for the open run.  Runs kernels/pile_gaps.hip, one wavefront per pile; a pile on a read of more
+ * than DAMAR_GAP_MAXBINS bins (DAMAR_TEST_GAP_BINS lowers that, for tests), one with more than DAMAR_GAP_MAXEVENTS events,
+ * and one whose B reads do not ascend is done by the routine of host/gap.c.  With DAMAR_PILES=host that routine does all
+ * piles and no GPU is touched.  0 on success, 1 after a message. */
+#define DAMAR_GAP_MAXBINS    4096          /* bins of 100 bases the kernel keeps in LDS: reads up to 409 500 bases */
+#define DAMAR_GAP_MAXEVENTS  16            /* events of a pile the kernel has room for */
+#define DAMAR_GAP_EVENT_INTS 6
+enum { DAMAR_GAP_MASKED = 0, DAMAR_GAP_STITCHABLE, DAMAR_GAP_DROP_L, DAMAR_GAP_DROP_R, DAMAR_GAP_DROP_NONE, DAMAR_GAP_TRAILING = 0x100 };
+typedef struct
+{ int           stitch;                    /* -s */
+  const uint64 *ex_anno;                   /* -e: [nreads + 1] byte offsets into ex_data, {begin, end} pairs; NULL: none */
+  const int    *ex_data;
+  int64         ex_ndata;
+  int           purge;                     /* -p, -t: looked at by damar_gap_las (host/gap.c) alone; NULL: no trimming */
+  const char   *trim_track;
+} damar_gap_params;
+typedef struct
+{ int   *count;                            /* [npiles], the caller's */
+  int   *ev;                               /* malloc'ed by the call */
+  int64  nev;
+  int64  contained, breaks, dropped;       /* the reference's three counters, of the batch */
+} damar_gap_events;
+int  damar_pile_gaps(const damar_pile_batch *b, const damar_gap_params *p, int *flags_out, damar_gap_events *ev);
+void damar_gap_release(void);              /* frees the cached device buffers of damar_pile_gaps */
+void damar_gap_limits(int *bins, int *events);     /* DAMAR_GAP_MAXBINS, DAMAR_GAP_MAXEVENTS as the library was built */
+/* of the last call: ms[4] = upload, kernel, download (HIP events; 0 on the host path), whole call (wall);
+ * cnt[3] = piles, piles the host routine did beside the kernel, break events */
+void damar_gap_last(double *ms, int64 *cnt);
+
 /* Phase timings (milliseconds, HIP events on the library's stream) of the last
  * damar_index_build / damar_match: see DAMAR_T_* below. */
 enum { DAMAR_T_TUPLES = 0, DAMAR_T_KSORT, DAMAR_T_TABLE, DAMAR_T_MERGE, DAMAR_T_SSORT,
