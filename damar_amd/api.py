@@ -921,6 +921,109 @@ def gap_las(db, las, out, stitch=0, purge=False, trim=None, exclude=None, repeat
     return res
 
 
+# ---- reads patched from their piles (LAfix) -------------------------------------------------------------------------
+
+class FixParams(C.Structure):          # include/damar_hip.h damar_fix_params
+    _fields_ = [("q_anno", C.POINTER(C.c_uint64)), ("q_data", _PI), ("q_ndata", c_int64), ("rep_anno", C.POINTER(C.c_uint64)),
+                ("rep_data", _PI), ("rep_ndata", c_int64), ("lowq", C.c_int), ("maxgap", C.c_int), ("maxspanners", C.c_int),
+                ("minsupport", C.c_int), ("twidth", C.c_int)]
+
+
+class FixGaps(C.Structure):            # include/damar_hip.h damar_fix_gaps
+    _fields_ = [("count", _PI), ("gaps", _PI), ("ngaps", c_int64)]
+
+
+class FixOpts(C.Structure):            # host/damar_host.h damar_fix_opts
+    _fields_ = [("min_len", C.c_int), ("lowq", C.c_int), ("maxgap", C.c_int), ("low_coverage", C.c_int), ("q_track", C.c_char_p),
+                ("trim_track", C.c_char_p), ("rep_track", C.c_char_p), ("convert", C.POINTER(C.c_char_p)), ("nconvert", C.c_int),
+                ("trim_out", C.c_char_p)]
+
+
+class FixStats(C.Structure):           # host/damar_host.h damar_fix_stats
+    _fields_ = [(k, c_int64) for k in ("gaps", "flips", "chimers", "bases_before", "bases_after", "reads_trimmed", "reads_fixed",
+                                       "piles", "host_piles", "repairs")]
+
+
+FIX_GAP = ("ab", "ae", "bb", "be", "diff", "b", "support", "comp")
+
+
+def fix_limits():
+    """(segments, candidates) a pile may have for kernels/pile_patch.hip to do it: DAMAR_FIX_MAXSEGS, DAMAR_FIX_MAXCAND"""
+    segs, cands = C.c_int(0), C.c_int(0)
+    L = _lib()
+    L.damar_fix_limits.argtypes = [_PI, _PI]
+    L.damar_fix_limits(C.byref(segs), C.byref(cands))
+    return segs.value, cands.value
+
+
+def pile_patches(batch, read_len, trim, q, repeats=None, low_q=28, max_gap=500, low_coverage=False):
+    """LAfix's search on a batch of whole piles with their traces (the dict pile_quality takes; trim: int32[piles, 2], the
+    interval kept of every pile's A read, begin >= end: none; q and repeats: (anno, data) of a track of the whole database,
+    byte offsets): -> per pile the list of its repairs in the order they are spliced in, each a dict of FIX_GAP.  On the
+    GPU, one wavefront per pile, unless DAMAR_PILES=host is set."""
+    import numpy as np
+    L = _lib()
+    t, keep = _trace_batch(batch, read_len)
+    u64p = C.POINTER(C.c_uint64)
+    p = FixParams()
+    keep["qa"], keep["qd"] = np.ascontiguousarray(q[0], dtype=np.uint64), np.ascontiguousarray(q[1], dtype=np.int32)
+    if len(keep["qa"]) != t.p.nreads + 1:
+        raise ValueError("the q track holds one offset per read and one more")
+    p.q_anno, p.q_data, p.q_ndata = keep["qa"].ctypes.data_as(u64p), keep["qd"].ctypes.data_as(_PI), len(keep["qd"])
+    if repeats is not None:
+        keep["ra"], keep["rd"] = np.ascontiguousarray(repeats[0], dtype=np.uint64), np.ascontiguousarray(repeats[1], dtype=np.int32)
+        if len(keep["ra"]) != t.p.nreads + 1:
+            raise ValueError("the repeat track holds one offset per read and one more")
+        p.rep_anno, p.rep_data, p.rep_ndata = keep["ra"].ctypes.data_as(u64p), keep["rd"].ctypes.data_as(_PI), len(keep["rd"])
+    p.lowq, p.maxgap = int(low_q), int(max_gap)
+    p.maxspanners, p.minsupport = (3, 2) if low_coverage else (7, 4)
+    p.twidth = t.tspace
+    tr = np.ascontiguousarray(trim, dtype=np.int32).reshape(-1)
+    if len(tr) != 2 * t.p.npiles:
+        raise ValueError("trim holds a begin and an end per pile")
+    count = np.zeros(max(t.p.npiles, 1), dtype=np.int32)
+    out = FixGaps(count.ctypes.data_as(_PI), None, 0)
+    L.damar_pile_patches.argtypes = [C.POINTER(TraceBatch), C.POINTER(FixParams), _PI, C.POINTER(FixGaps)]
+    if L.damar_pile_patches(C.byref(t), C.byref(p), tr.ctypes.data_as(_PI), C.byref(out)):
+        raise RuntimeError("damar_pile_patches failed")
+    try:
+        flat = np.ctypeslib.as_array(out.gaps, shape=(max(8 * int(out.ngaps), 1),))[:8 * int(out.ngaps)].copy().reshape(-1, 8)
+    finally:
+        C.CDLL(None).free(out.gaps)
+    at, res = 0, []
+    for n in count[:t.p.npiles]:
+        res.append([dict(zip(FIX_GAP, (int(x) for x in row))) for row in flat[at:at + n]])
+        at += int(n)
+    return res
+
+
+def fix_last():
+    """Of the last pile_patches / of the last batch of fix_las: ({upload, kernel, download, call} ms, piles, piles the host
+    routine did beside the kernel, repairs)."""
+    ms, cnt = (C.c_double * 4)(), (c_int64 * 3)()
+    L = _lib()
+    L.damar_fix_last.argtypes = [C.POINTER(C.c_double), C.POINTER(c_int64)]
+    L.damar_fix_last(ms, cnt)
+    return dict(zip(("upload", "kernel", "download", "call"), list(ms))), cnt[0], cnt[1], cnt[2]
+
+
+def fix_las(db, las, fasta, *, min_len=1000, low_q=28, max_gap=500, trim=None, q="q", repeats=None, convert=(), trim_out=None,
+            low_coverage=False):
+    """LAfix on one .las file: every read with a pile patched from the reads that overlap it and written to `fasta`; trim, q,
+    repeats and convert name tracks of the database (LAfix's -t -q -r -c), trim_out is the file of -T.  The reference's
+    lines go to stdout.  -> the counters of the run (host_piles: piles the host routine did beside the kernel)."""
+    L = _lib()
+    enc = lambda s: s.encode() if s else None
+    names = (C.c_char_p * max(len(convert), 1))(*[c.encode() for c in convert])
+    o = FixOpts(int(min_len), int(low_q), int(max_gap), 1 if low_coverage else 0, enc(q), enc(trim), enc(repeats), names,
+                len(convert), enc(trim_out))
+    st = FixStats()
+    L.damar_fix_las.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(FixOpts), C.POINTER(FixStats)]
+    if L.damar_fix_las(db.encode(), las.encode(), fasta.encode(), C.byref(o), C.byref(st)):
+        raise RuntimeError("damar_fix_las failed")
+    return {k: int(getattr(st, k)) for k, _ in FixStats._fields_}
+
+
 # ---- repeat intervals carried across overlaps onto the B reads (TKhomogenize) ---------------------------------------
 
 def _trace_batch(batch, read_len):

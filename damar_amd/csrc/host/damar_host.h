@@ -175,6 +175,29 @@ typedef struct
 void damar_gap_no_track(const char *track);      /* the reference's two lines for a track that cannot be loaded */
 int  damar_gap_las(const char *db, const char *las, const char *out, const damar_gap_params *p, damar_gap_stats *st);
 
+/* fix.c: LAfix (scrub/LAfix.c without -X and -f) -- the plain routine behind damar_pile_patches (DAMAR_PILES=host, and the
+   piles the kernel leaves), the checks both paths share, and the pass over a file. */
+typedef struct { damar_fix_gap *g; int64 n, cap; } damar_fix_list;
+int  damar_fix_inputs_valid(const damar_trace_batch *t, const damar_fix_params *p, const int *trim);       /* 0 after a message */
+/* one pile kept from trim_ab to trim_ae: its repairs appended to L in the order they are spliced in */
+void damar_host_fix_pile(const damar_trace_batch *t, int64 pile, const damar_fix_params *p, int trim_ab, int trim_ae, damar_fix_list *L);
+typedef struct
+{ int   min_len, lowq, maxgap, low_coverage;     /* -x -Q -g -l */
+  const char *q_track, *trim_track, *rep_track;  /* -q, -t and -r (NULL: none) */
+  const char **convert;                          /* -c, in the order given */
+  int   nconvert;
+  const char *trim_out;                          /* -T, NULL: none */
+} damar_fix_opts;
+typedef struct
+{ int64 gaps, flips, chimers;              /* the reference's closing counters */
+  int64 bases_before, bases_after;
+  int64 reads_trimmed, reads_fixed;        /* headers written */
+  int64 piles, host_piles, repairs;        /* summed over the batches: damar_fix_last's counts */
+} damar_fix_stats;
+/* the pass over a file: per batch of whole piles the flip step, damar_pile_patches, the splice, and the reads written to
+   `fasta`; the reference's lines on stdout.  0, or 1 after a message. */
+int  damar_fix_las(const char *db, const char *las, const char *fasta, const damar_fix_opts *o, damar_fix_stats *st);
+
 /* bridge.c: the exact alignment of one box into trace pairs (what damar_trace_boxes returns per box): A[0..M) against
    B[0..N), M, N >= 1, A's position 0 lying abpos >= 0 bases into the grid of ts; trace holds
    2 * ((abpos + M + ts - 1) / ts - abpos / ts) values, *tlen receives their number; returns the differences.  Works in the

@@ -438,6 +438,35 @@ typedef struct
 
 void damar_launch_pile_gaps(const GapArgs *a, hipStream_t st);
 
+/* pile_patch.hip: LAfix's breaks and weak segments, one wavefront per pile (include/damar_hip.h damar_pile_patches; the
+   DAMAR_FIX_* bounds and damar_fix_gap are defined there).  Pile q writes its repairs to gaps + slot_off[q], where it has
+   room for slot_off[q + 1] - slot_off[q] of them (the host's bound: candidate pairs plus bad segments, DAMAR_FIX_MAXREP at
+   the most).  A pile with status 1 afterwards is the host's: a read of more than maxsegs segments, skip[pile] set, more
+   than DAMAR_FIX_MAXCAND candidates, or more than DAMAR_FIX_MAXREP repairs. */
+typedef struct
+{ u32 npiles;
+  int maxsegs, tspace, tbytes;
+  int lowq, maxgap, maxspanners, minsupport;
+  const long long *pile_off;          /* [npiles + 1] */
+  const int *pile_aread;              /* [npiles] */
+  const int *trim;                    /* [2 * npiles] */
+  const int *abpos, *aepos, *bbpos, *bepos, *bread, *flags, *tlen;       /* [nrec] */
+  const long long *trace_off;         /* [nrec] bytes into trace */
+  const u8  *trace;
+  const int *read_len;                /* [nreads] */
+  const u64 *q_anno;                  /* [nreads + 1] byte offsets into q_data */
+  const int *q_data;
+  long long  q_ndata;
+  const u64 *rep_anno;                /* NULL: no repeat track */
+  const int *rep_data;
+  const u8  *skip;                    /* [npiles] */
+  const long long *slot_off;          /* [npiles + 1] */
+  int *gaps;                          /* the eight ints of a damar_fix_gap per repair */
+  int *status, *ngaps;               /* [npiles] */
+} FixArgs;
+
+void damar_launch_pile_patch(const FixArgs *a, hipStream_t st);
+
 /* box_align.hip: exact alignment of a batch of boxes with their edit scripts (align.c:4734 DIFF_ALIGN).  A box with
    max(m, n) <= maxlen <= DAMAR_BOX_MAXLEN is done and leaves its differences, the length of its script (-1: it hit a bound of
    the kernel and is the host's after all) and the script at script + coff[box], max(m, n) values of room; the others are

@@ -5353,3 +5353,192 @@ extern "C" int damar_pile_gaps(const damar_pile_batch *b, const damar_gap_params
   GP_ms[3] = now_ms() - w0;
   return 0;
 }
+
+/***** LAfix's breaks and weak segments per pile: scrub/LAfix.c fix_process (kernels/pile_patch.hip) **********************/
+
+static DBuf FX_off, FX_aread, FX_trim, FX_col[7], FX_toff, FX_trace, FX_rlen, FX_qanno, FX_qdata, FX_ranno, FX_rdata, FX_skip, FX_slot,
+            FX_gaps, FX_status, FX_ngaps;
+static double FX_ms[4];        /* of the last call: upload, kernel, download (HIP events), whole call (wall) */
+static int64  FX_cnt3[3];      /* piles, piles the host routine did beside the kernel, repairs */
+static hipEvent_t FX_evt[4];
+static int    FX_ev_made;
+
+extern "C" void damar_fix_release(void)
+{ DBuf *all[] = { &FX_off, &FX_aread, &FX_trim, &FX_col[0], &FX_col[1], &FX_col[2], &FX_col[3], &FX_col[4], &FX_col[5], &FX_col[6], &FX_toff,
+                  &FX_trace, &FX_rlen, &FX_qanno, &FX_qdata, &FX_ranno, &FX_rdata, &FX_skip, &FX_slot, &FX_gaps, &FX_status, &FX_ngaps };
+  for (DBuf *b : all) b->drop();
+  if (FX_ev_made)
+    for (int i = 0; i < 4; i++) (void) hipEventDestroy(FX_evt[i]);
+  FX_ev_made = 0;
+}
+
+extern "C" void damar_fix_limits(int *segs, int *cands)
+{ *segs = DAMAR_FIX_MAXSEGS;
+  *cands = DAMAR_FIX_MAXCAND;
+}
+
+extern "C" void damar_fix_last(double *ms, int64 *cnt)
+{ for (int i = 0; i < 4; i++) ms[i] = FX_ms[i];
+  for (int i = 0; i < 3; i++) cnt[i] = FX_cnt3[i];
+}
+
+extern "C" int damar_pile_patches(const damar_trace_batch *t, const damar_fix_params *p, const int *trim, damar_fix_gaps *out)
+{ const double w0 = now_ms();
+  if (out == NULL || !damar_fix_inputs_valid(t, p, trim) || (t->p.npiles > 0 && out->count == NULL))
+    return 1;
+  static_assert(sizeof(damar_fix_gap) == 8 * sizeof(int), "the kernel writes a repair as eight ints");
+  const damar_pile_batch *b = &t->p;
+  const size_t np = (size_t) b->npiles, nrec = (size_t) b->nrec;
+  const bool host = damar_piles_on_host() != 0;
+  const int tw = t->tspace;
+  damar_fix_list L = { NULL, 0, 0 };
+  int64 fallback = 0;
+  for (int i = 0; i < 4; i++) FX_ms[i] = 0;
+
+  std::vector<u8>  skip(np + 1, 0);
+  std::vector<int> status(np + 1, 1), ngaps(np + 1, 0);
+  std::vector<long long> slot(np + 1, 0);
+  std::vector<damar_fix_gap> got;
+  if (!host && np > 0)
+    { const char *lower = getenv("DAMAR_TEST_FIX_SEGS");
+      const int maxsegs = (lower != NULL && atoi(lower) < DAMAR_FIX_MAXSEGS) ? atoi(lower) : DAMAR_FIX_MAXSEGS;
+      /* per pile: whether its B reads ascend (a pile where they do not is the host routine's), and the room its repairs
+         need at the most -- a repair is a pair of neighbouring records of one B read or a bad segment inside the trim */
+      for (size_t q = 0; q < np; q++)
+        { const int aread = b->pile_aread[q], tb = trim[2 * q], te = trim[2 * q + 1];
+          long long room = 0;
+          if (tb < te)
+            { for (int64 i = b->pile_off[q] + 1; i < b->pile_off[q + 1]; i++)
+                { if (b->bread[i] < b->bread[i - 1])
+                    skip[q] = 1;
+                  if (b->bread[i] == b->bread[i - 1] && b->aepos[i - 1] < b->abpos[i])
+                    room += 1;
+                }
+              const int64 qa = (int64) (p->q_anno[aread] / 4);
+              for (int s = tb / tw; s < te / tw; s++)
+                { const int v = (qa + s < p->q_ndata) ? p->q_data[qa + s] : 0;
+                  room += (v == 0 || v >= p->lowq) ? 1 : 0;
+                }
+              if (room > DAMAR_FIX_MAXREP)
+                room = DAMAR_FIX_MAXREP;
+            }
+          slot[q + 1] = slot[q] + room;
+        }
+      const size_t nslot = (size_t) slot[np];
+      ensure_init();
+      late_streams();                /* a tool built on this call is through soon after the library comes up: see damar_align_boxes */
+      if (!FX_ev_made)
+        { for (int i = 0; i < 4; i++) HIP_CHECK(hipEventCreate(&FX_evt[i]));
+          FX_ev_made = 1;
+        }
+      FixArgs a;
+      memset(&a, 0, sizeof(a));
+      a.npiles = (u32) np;
+      a.maxsegs = maxsegs;  a.tspace = tw;  a.tbytes = t->tbytes;
+      a.lowq = p->lowq;  a.maxgap = p->maxgap;  a.maxspanners = p->maxspanners;  a.minsupport = p->minsupport;
+      a.q_ndata = p->q_ndata;
+      const size_t nreads = (size_t) b->nreads;
+      long long *d_off = (long long *) FX_off.need(sizeof(long long) * (np + 1));
+      int *d_aread = (int *) FX_aread.need(sizeof(int) * np + 16);
+      int *d_trim = (int *) FX_trim.need(sizeof(int) * 2 * np + 16);
+      const int *src[7] = { b->abpos, b->aepos, b->bbpos, b->bepos, b->bread, b->flags, t->tlen };
+      int *d_col[7];
+      for (int i = 0; i < 7; i++) d_col[i] = (int *) FX_col[i].need(sizeof(int) * nrec + 16);
+      long long *d_toff = (long long *) FX_toff.need(sizeof(long long) * nrec + 16);
+      u8  *d_trace = (u8 *) FX_trace.need((size_t) t->trace_bytes + 16);
+      int *d_rlen = (int *) FX_rlen.need(sizeof(int) * nreads);
+      u64 *d_qanno = (u64 *) FX_qanno.need(sizeof(u64) * (nreads + 1));
+      int *d_qdata = (int *) FX_qdata.need(sizeof(int) * (size_t) p->q_ndata + 16);
+      u8  *d_skip = (u8 *) FX_skip.need(np + 16);
+      long long *d_slot = (long long *) FX_slot.need(sizeof(long long) * (np + 1));
+      int *d_gaps = (int *) FX_gaps.need(sizeof(damar_fix_gap) * nslot + 16);
+      int *d_status = (int *) FX_status.need(sizeof(int) * np + 16), *d_ngaps = (int *) FX_ngaps.need(sizeof(int) * np + 16);
+      u64 *d_ranno = NULL;
+      int *d_rdata = NULL;
+      HIP_CHECK(hipEventRecord(FX_evt[0], G_st));
+      if (p->rep_anno != NULL)
+        { d_ranno = (u64 *) FX_ranno.need(sizeof(u64) * (nreads + 1));
+          d_rdata = (int *) FX_rdata.need(sizeof(int) * (size_t) p->rep_ndata + 16);
+          HIP_CHECK(hipMemcpyAsync(d_ranno, p->rep_anno, sizeof(u64) * (nreads + 1), hipMemcpyHostToDevice, G_st));
+          if (p->rep_ndata > 0)
+            HIP_CHECK(hipMemcpyAsync(d_rdata, p->rep_data, sizeof(int) * (size_t) p->rep_ndata, hipMemcpyHostToDevice, G_st));
+        }
+      HIP_CHECK(hipMemcpyAsync(d_off, b->pile_off, sizeof(long long) * (np + 1), hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_aread, b->pile_aread, sizeof(int) * np, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_trim, trim, sizeof(int) * 2 * np, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_skip, skip.data(), np, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_slot, slot.data(), sizeof(long long) * (np + 1), hipMemcpyHostToDevice, G_st));
+      if (nrec > 0)
+        { for (int i = 0; i < 7; i++)
+            HIP_CHECK(hipMemcpyAsync(d_col[i], src[i], sizeof(int) * nrec, hipMemcpyHostToDevice, G_st));
+          HIP_CHECK(hipMemcpyAsync(d_toff, t->trace_off, sizeof(long long) * nrec, hipMemcpyHostToDevice, G_st));
+        }
+      if (t->trace_bytes > 0)
+        HIP_CHECK(hipMemcpyAsync(d_trace, t->trace, (size_t) t->trace_bytes, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_rlen, b->read_len, sizeof(int) * nreads, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_qanno, p->q_anno, sizeof(u64) * (nreads + 1), hipMemcpyHostToDevice, G_st));
+      if (p->q_ndata > 0)
+        HIP_CHECK(hipMemcpyAsync(d_qdata, p->q_data, sizeof(int) * (size_t) p->q_ndata, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemsetAsync(d_ngaps, 0, sizeof(int) * np, G_st));
+      HIP_CHECK(hipEventRecord(FX_evt[1], G_st));
+      a.pile_off = d_off;  a.pile_aread = d_aread;  a.trim = d_trim;
+      a.abpos = d_col[0];  a.aepos = d_col[1];  a.bbpos = d_col[2];  a.bepos = d_col[3];  a.bread = d_col[4];  a.flags = d_col[5];
+      a.tlen = d_col[6];  a.trace_off = d_toff;  a.trace = d_trace;
+      a.read_len = d_rlen;  a.q_anno = d_qanno;  a.q_data = d_qdata;  a.rep_anno = d_ranno;  a.rep_data = d_rdata;
+      a.skip = d_skip;  a.slot_off = d_slot;  a.gaps = d_gaps;  a.status = d_status;  a.ngaps = d_ngaps;
+      damar_launch_pile_patch(&a, G_st);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipEventRecord(FX_evt[2], G_st));
+      got.resize(nslot + 1);
+      HIP_CHECK(hipMemcpyAsync(status.data(), d_status, sizeof(int) * np, hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipMemcpyAsync(ngaps.data(), d_ngaps, sizeof(int) * np, hipMemcpyDeviceToHost, G_st));
+      if (nslot > 0)
+        HIP_CHECK(hipMemcpyAsync(got.data(), d_gaps, sizeof(damar_fix_gap) * nslot, hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipEventRecord(FX_evt[3], G_st));
+      HIP_CHECK(hipStreamSynchronize(G_st));
+      for (int i = 0; i < 3; i++)
+        { float ms = 0;
+          HIP_CHECK(hipEventElapsedTime(&ms, FX_evt[i], FX_evt[i + 1]));
+          FX_ms[i] = ms;
+        }
+    }
+  /* the repairs in pile order; what the kernel left (all piles with DAMAR_PILES=host) is the plain routine's */
+  for (size_t q = 0; q < np; q++)
+    { const int64 before = L.n;
+      if (status[q] != 0)
+        { damar_host_fix_pile(t, (int64) q, p, trim[2 * q], trim[2 * q + 1], &L);
+          fallback += (host || trim[2 * q] >= trim[2 * q + 1]) ? 0 : 1;
+        }
+      else
+        { if (ngaps[q] < 0 || ngaps[q] > slot[q + 1] - slot[q])
+            { fprintf(stderr, "damar: fix: pile %zu came back with %d repairs\n", q, ngaps[q]);
+              free(L.g);
+              return 1;
+            }
+          if (L.n + ngaps[q] > L.cap)
+            { const int64 cap = L.n + ngaps[q] + L.cap / 4 + 256;
+              damar_fix_gap *grown = (damar_fix_gap *) realloc(L.g, sizeof(damar_fix_gap) * (size_t) cap);
+              if (grown == NULL)
+                { fprintf(stderr, "damar: out of memory (fix)\n");
+                  free(L.g);
+                  return 1;
+                }
+              L.g = grown;
+              L.cap = cap;
+            }
+          if (ngaps[q] > 0)
+            memcpy(L.g + L.n, got.data() + slot[q], sizeof(damar_fix_gap) * (size_t) ngaps[q]);
+          L.n += ngaps[q];
+        }
+      out->count[q] = (int) (L.n - before);
+    }
+  if (L.g == NULL && (L.g = (damar_fix_gap *) malloc(sizeof(damar_fix_gap))) == NULL)       /* no repair: still the caller's to free */
+    { fprintf(stderr, "damar: out of memory (fix)\n");
+      return 1;
+    }
+  out->gaps = L.g;
+  out->ngaps = L.n;
+  FX_cnt3[0] = b->npiles;  FX_cnt3[1] = fallback;  FX_cnt3[2] = L.n;
+  FX_ms[3] = now_ms() - w0;
+  return 0;
+}

@@ -406,6 +406,52 @@ void damar_gap_limits(int *bins, int *events);     /* DAMAR_GAP_MAXBINS, DAMAR_G
  * cnt[3] = piles, piles the host routine did beside the kernel, break events */
 void damar_gap_last(double *ms, int64 *cnt);
 
+/* Repairs of piles (scrub/LAfix.c fix_process without its chimer code): per pile of a trace batch, whose A read is kept
+ * from trim[2 * pile] to trim[2 * pile + 1] (the trim track's interval after the flip step of host/fix.c; begin >= end: the
+ * pile has no repairs),
+ *   breaks   two consecutive records of one B read in one orientation that leave a gap on A are a candidate: the A interval
+ *            on segment borders, the B stretch between the last and the first trace interval.  Candidates with a zero in B's
+ *            q, with more than `maxspanners` records across both borders, with more than one scored segment strictly inside
+ *            or with a B stretch over ten times the A interval are dropped; the rest sorted (stably) by A interval and
+ *            quality, cut at `maxgap`, merged where they agree or intersect, and kept from `minsupport` on when A has a
+ *            bad segment (q = 0 or q >= lowq) inside;
+ *   weak     every bad segment inside the trim that no kept break contains is replaced by the B stretch, found through the
+ *            trace, of the record across it (a spacing to spare on either side) with the lowest mean q, the first such
+ *            record among equals; support counts the records that begin or end inside the segment.
+ * out->count[npiles] (the caller's) receives the repairs per pile, out->gaps (malloc'ed, the caller's to free) the piles'
+ * repairs back to back in the order they are spliced in (by A interval, then quality).  B's q is indexed flat into the q
+ * track's data, as the reference does it; an index outside the data counts as q = 0.  Runs kernels/pile_patch.hip, one
+ * wavefront per pile; a pile on a read of more than DAMAR_FIX_MAXSEGS segments (DAMAR_TEST_FIX_SEGS lowers that, for
+ * tests), one with more than DAMAR_FIX_MAXCAND candidates or DAMAR_FIX_MAXREP repairs, and one whose B reads do not ascend is
+ * done by the routine of host/fix.c.  With DAMAR_PILES=host that routine does all piles and no GPU is touched.
+ * 0 on success, 1 after a message. */
+#define DAMAR_FIX_MAXSEGS 4096             /* segments of the A read the kernel keeps in LDS */
+#define DAMAR_FIX_MAXCAND 256              /* break candidates of a pile the kernel sorts and merges */
+#define DAMAR_FIX_MAXREP  1024             /* repairs (kept breaks plus weak segments) of a pile the kernel has room for */
+typedef struct
+{ const uint64 *q_anno;                    /* -q: [nreads + 1] byte offsets into q_data, one value per segment */
+  const int    *q_data;
+  int64         q_ndata;
+  const uint64 *rep_anno;                  /* -r: {begin, end} pairs; NULL: none */
+  const int    *rep_data;
+  int64         rep_ndata;
+  int           lowq, maxgap;              /* -Q -g (-1: no cut) */
+  int           maxspanners, minsupport;   /* 7 and 4, or -l's 3 and 2 */
+  int           twidth;                    /* the trace spacing of the batch */
+} damar_fix_params;
+typedef struct { int ab, ae, bb, be, diff, b, support, comp; } damar_fix_gap;     /* comp: the record's OVL_COMP bit */
+typedef struct
+{ int           *count;                    /* [npiles], the caller's */
+  damar_fix_gap *gaps;                     /* malloc'ed by the call */
+  int64          ngaps;
+} damar_fix_gaps;
+int  damar_pile_patches(const damar_trace_batch *b, const damar_fix_params *p, const int *trim, damar_fix_gaps *out);
+void damar_fix_release(void);              /* frees the cached device buffers of damar_pile_patches */
+void damar_fix_limits(int *segs, int *cands);      /* DAMAR_FIX_MAXSEGS, DAMAR_FIX_MAXCAND as the library was built */
+/* of the last call: ms[4] = upload, kernel, download (HIP events; 0 on the host path), whole call (wall);
+ * cnt[3] = piles, piles the host routine did beside the kernel, repairs */
+void damar_fix_last(double *ms, int64 *cnt);
+
 /* Phase timings (milliseconds, HIP events on the library's stream) of the last
  * damar_index_build / damar_match: see DAMAR_T_* below. */
 enum { DAMAR_T_TUPLES = 0, DAMAR_T_KSORT, DAMAR_T_TABLE, DAMAR_T_MERGE, DAMAR_T_SSORT,
