@@ -1191,3 +1191,121 @@ def daligner_binary():
 
 def lib():
     return _lib()
+
+
+# ---- overlaps filtered per pile (LAfilter) ---------------------------------------------------------------------------
+
+class FilterParams(C.Structure):       # include/damar_hip.h damar_filter_params
+    _fields_ = [("steps", C.c_int), ("downsample", C.c_int), ("seg_rate", C.c_int), ("stitch", C.c_int), ("stitch_aggr", C.c_int),
+                ("min_rlen", C.c_int), ("min_olen", C.c_int), ("max_unaligned", C.c_int), ("min_nonrep", C.c_int), ("max_diffs", C.c_float),
+                ("merge_tips", C.c_int), ("multi", C.c_int), ("lowcov", C.c_int), ("remove", C.c_int), ("include", C.c_int),
+                ("trim", _PI), ("rep_anno", C.POINTER(C.c_uint64)), ("rep_data", _PI), ("rep_ndata", c_int64),
+                ("sym_off", _PI), ("sym_len", _PI), ("sym_data", _PI), ("sym_ndata", c_int64), ("read_state", C.POINTER(C.c_ubyte))]
+
+
+class FilterOut(C.Structure):          # include/damar_hip.h damar_filter_out
+    _fields_ = [(k, _PI) for k in ("flags", "aepos", "bepos", "diffs", "tlen", "reason", "cont_by", "cnt")]
+
+
+class FilterOpts(C.Structure):         # host/damar_host.h damar_filter_opts
+    _fields_ = [("p", FilterParams), ("verbose", C.c_int), ("purge", C.c_int), ("do_trim", C.c_int), ("trim_track", C.c_char_p),
+                ("rep_track", C.c_char_p), ("exclude", C.c_char_p), ("include", C.c_char_p), ("discarded_out", C.c_char_p),
+                ("discarded_in", C.c_char_p)]
+
+
+FILTER_COUNTERS = ("diffs", "unaligned", "contained", "length", "repeat", "read_length", "low_coverage", "symmetric", "multi", "multi_bases",
+                   "stitched")
+
+
+class FilterStats(C.Structure):        # host/damar_host.h damar_filter_stats
+    _fields_ = [("novl", c_int64), ("written", c_int64), ("discarded", c_int64), ("cnt", c_int64 * len(FILTER_COUNTERS)), ("piles", c_int64),
+                ("host_piles", c_int64), ("trim", TrimStats)]
+
+
+FILTER_PRE, FILTER_MAIN = 1, 2
+
+
+def filter_limits():
+    """(group, len): the records of one B read in a row and the bases of an A read (under -z with -u) a pile may have for
+    kernels/pile_filter.hip to do it: DAMAR_FILTER_MAXGROUP, DAMAR_FILTER_MAXLEN"""
+    g, n = C.c_int(), C.c_int()
+    _lib().damar_filter_limits(C.byref(g), C.byref(n))
+    return g.value, n.value
+
+
+def filter_last():
+    """Of the last pile_filter / of the last batch of filter_las: ({upload, kernel, download, call} ms, piles, piles the host
+    routine did beside the kernel, records that left discarded)."""
+    ms, cnt = (C.c_double * 4)(), (c_int64 * 3)()
+    L = _lib()
+    L.damar_filter_last.argtypes = [C.POINTER(C.c_double), C.POINTER(c_int64)]
+    L.damar_filter_last(ms, cnt)
+    return dict(zip(("upload", "kernel", "download", "call"), list(ms))), cnt[0], cnt[1], cnt[2]
+
+
+def _filter_numbers(p, downsample=0, seg_rate=-1, stitch=-1, stitch_aggr=False, min_rlen=-1, min_olen=-1, max_unaligned=-1, min_nonrep=-1,
+                    max_diffs=-1.0, merge_tips=0, multi=False, lowcov=0, remove=0):
+    p.downsample, p.seg_rate, p.stitch, p.stitch_aggr = int(downsample), int(seg_rate), int(stitch), 1 if stitch_aggr else 0
+    p.min_rlen, p.min_olen, p.max_unaligned, p.min_nonrep = int(min_rlen), int(min_olen), int(max_unaligned), int(min_nonrep)
+    p.max_diffs, p.merge_tips, p.multi, p.lowcov, p.remove = float(max_diffs), int(merge_tips), 1 if multi else 0, int(lowcov), int(remove)
+
+
+def pile_filter(batch, read_len, steps=FILTER_PRE | FILTER_MAIN, trim=None, repeats=None, sym=None, read_state=None, include=False, **numbers):
+    """LAfilter's work on a batch of whole piles with their traces (the dict of _trace_batch, with `diffs`).  trim: get_trim
+    of every read (2 * nreads ints) or None; repeats: (anno, data) of the repeat track, needed with min_nonrep; sym: (off,
+    len, data) of the -A lists; read_state: 1 / 2 per read for -x / -I; numbers: the options of damar_filter_params by
+    name.  -> dict of the per-record arrays flags, aepos, bepos, diffs, tlen, reason, cont_by, and cnt (npiles x counters).
+    On the GPU unless DAMAR_PILES=host."""
+    import numpy as np
+    L = _lib()
+    t, keep = _trace_batch(batch, read_len)
+    p = FilterParams()
+    _filter_numbers(p, **numbers)
+    p.steps, p.include = int(steps), 1 if include else 0
+    if trim is not None:
+        keep["ftrim"] = np.ascontiguousarray(trim, dtype=np.int32)
+        p.trim = keep["ftrim"].ctypes.data_as(_PI)
+    if repeats is not None:
+        keep["ranno"], keep["rdata"] = np.ascontiguousarray(repeats[0], dtype=np.uint64), np.ascontiguousarray(repeats[1], dtype=np.int32)
+        p.rep_anno, p.rep_data, p.rep_ndata = keep["ranno"].ctypes.data_as(C.POINTER(C.c_uint64)), keep["rdata"].ctypes.data_as(_PI), len(keep["rdata"])
+    if sym is not None:
+        for k, v in zip(("soff", "slen", "sdata"), sym):
+            keep[k] = np.ascontiguousarray(v, dtype=np.int32)
+        p.sym_off, p.sym_len, p.sym_data = (keep[k].ctypes.data_as(_PI) for k in ("soff", "slen", "sdata"))
+        p.sym_ndata = len(keep["sdata"])
+    if read_state is not None:
+        keep["state"] = np.ascontiguousarray(read_state, dtype=np.uint8)
+        p.read_state = keep["state"].ctypes.data_as(C.POINTER(C.c_ubyte))
+    diffs = np.ascontiguousarray(batch["diffs"], dtype=np.int32)
+    nrec, npiles = int(t.p.nrec), int(t.p.npiles)
+    names = ("flags", "aepos", "bepos", "diffs", "tlen", "reason", "cont_by")
+    res = {k: np.zeros(max(nrec, 1), dtype=np.int32) for k in names}
+    res["cnt"] = np.zeros(max(npiles, 1) * len(FILTER_COUNTERS), dtype=np.int32)
+    out = FilterOut(*[res[k].ctypes.data_as(_PI) for k in names + ("cnt",)])
+    L.damar_pile_filter.argtypes = [C.POINTER(TraceBatch), _PI, C.POINTER(FilterParams), C.POINTER(FilterOut)]
+    if L.damar_pile_filter(C.byref(t), diffs.ctypes.data_as(_PI), C.byref(p), C.byref(out)):
+        raise RuntimeError("damar_pile_filter failed")
+    res = {k: v[:nrec] for k, v in res.items() if k != "cnt"} | {"cnt": res["cnt"][:npiles * len(FILTER_COUNTERS)].reshape(npiles, -1)}
+    return res
+
+
+def filter_las(db, las, out, *, verbose=False, purge=False, do_trim=False, trim="trim", repeats="repeats", exclude=None, include=None,
+               discarded_out=None, discarded_in=None, **numbers):
+    """LAfilter on one .las file, written to `out` (purge: without the discarded records).  trim / repeats: track names (-t
+    -r), do_trim: -T, exclude / include: files of read ids (-x -I), discarded_out / discarded_in: the -a and -A files;
+    numbers: the options of damar_filter_params by name (max_diffs as a fraction).  The reference's lines go to stdout.
+    -> the counters of the run (host_piles: piles the host routine did beside the kernel)."""
+    L = _lib()
+    enc = lambda s: s.encode() if s is not None else None
+    o = FilterOpts()
+    _filter_numbers(o.p, **numbers)
+    o.verbose, o.purge, o.do_trim = 1 if verbose else 0, 1 if purge else 0, 1 if do_trim else 0
+    o.trim_track, o.rep_track, o.exclude, o.include = enc(trim), enc(repeats), enc(exclude), enc(include)
+    o.discarded_out, o.discarded_in = enc(discarded_out), enc(discarded_in)
+    st = FilterStats()
+    L.damar_filter_las.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(FilterOpts), C.POINTER(FilterStats)]
+    if L.damar_filter_las(db.encode(), las.encode(), out.encode(), C.byref(o), C.byref(st)):
+        raise RuntimeError("damar_filter_las failed")
+    res = {k: int(getattr(st, k)) for k in ("novl", "written", "discarded", "piles", "host_piles")}
+    res.update(zip(FILTER_COUNTERS, (int(x) for x in st.cnt)))
+    return res

@@ -198,6 +198,29 @@ typedef struct
    `fasta`; the reference's lines on stdout.  0, or 1 after a message. */
 int  damar_fix_las(const char *db, const char *las, const char *fasta, const damar_fix_opts *o, damar_fix_stats *st);
 
+/* filter.c: LAfilter (scrub/LAfilter.c without its experimental branches) -- the plain routine behind damar_pile_filter
+   (DAMAR_PILES=host, and the piles the kernel leaves), the checks both paths share, and the pass over a file. */
+int  damar_filter_inputs_valid(const damar_trace_batch *t, const int *diffs, const damar_filter_params *p, const damar_filter_out *out);     /* 0 after a message */
+/* one pile: every array of out at the pile's records, and its DAMAR_FC_COUNT counters */
+void damar_host_filter_pile(const damar_trace_batch *t, const int *diffs, int64 pile, const damar_filter_params *p, damar_filter_out *out);
+typedef struct
+{ damar_filter_params p;                   /* the numeric options; its pointers and `steps` are damar_filter_las's to fill */
+  int   verbose, purge, do_trim;           /* -v -p -T */
+  const char *trim_track, *rep_track;      /* -t -r */
+  const char *exclude, *include;           /* -x -I (NULL: none) */
+  const char *discarded_out, *discarded_in;        /* -a -A (NULL: none) */
+} damar_filter_opts;
+typedef struct
+{ int64 novl, written, discarded;
+  int64 cnt[DAMAR_FC_COUNT];               /* the reference's closing counters */
+  int64 piles, host_piles;                 /* summed over the batches: damar_filter_last's counts */
+  damar_trim_stats trim;                   /* -T */
+} damar_filter_stats;
+void damar_filter_no_track(const char *track);   /* the reference's two lines for a track that cannot be loaded */
+/* the reference's main from its first fopen on: the tracks and lists loaded, then per batch of whole piles -f and -b, the
+   trim (-T), damar_pile_filter, the reference's lines on stdout, the records written.  0, or 1 after a message. */
+int  damar_filter_las(const char *db, const char *las, const char *out, const damar_filter_opts *o, damar_filter_stats *st);
+
 /* bridge.c: the exact alignment of one box into trace pairs (what damar_trace_boxes returns per box): A[0..M) against
    B[0..N), M, N >= 1, A's position 0 lying abpos >= 0 bases into the grid of ts; trace holds
    2 * ((abpos + M + ts - 1) / ts - abpos / ts) values, *tlen receives their number; returns the differences.  Works in the

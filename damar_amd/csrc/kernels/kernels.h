@@ -438,6 +438,33 @@ typedef struct
 
 void damar_launch_pile_gaps(const GapArgs *a, hipStream_t st);
 
+/* pile_filter.hip: LAfilter's screens, one wavefront per pile (include/damar_hip.h damar_pile_filter; the DAMAR_FILTER_*
+   bounds, the DAMAR_FR_* reason bits and the DAMAR_FC_* counters are defined there).  A pile with status 1 afterwards is the
+   host's: a run of more than maxgroup records of one B read, or under -z with -u a read of more than maxlen bases. */
+typedef struct
+{ u32 npiles;
+  int steps, maxgroup, maxlen, mask_words;    /* mask_words: u32 words of dynamic LDS, 0 without -z -u */
+  int downsample, max_rid, seg_rate, stitch, stitch_aggr, min_rlen, min_olen, max_unaligned, min_nonrep;
+  float max_diffs;
+  int merge_tips, multi, lowcov, remove, include, tbytes;
+  const long long *pile_off;          /* [npiles + 1] */
+  const int *pile_aread;              /* [npiles] */
+  const int *abpos, *aepos, *bbpos, *bepos, *bread, *flags, *diffs, *tlen;
+  const long long *trace_off;         /* [nrec], bytes */
+  const u8  *trace;
+  const int *read_len;
+  const int *trim;                    /* [2 * nreads] or NULL */
+  const u64 *rep_anno;                /* byte offsets; NULL without -n */
+  const int *rep_data;
+  const int *sym_off, *sym_len, *sym_data;      /* NULL without -A */
+  const u8  *read_state;              /* NULL without -x / -I */
+  int *o_flags, *o_ae, *o_be, *o_df, *o_tl, *o_why, *o_by;      /* [nrec] */
+  int *status;                        /* [npiles] */
+  int *cnt;                           /* [npiles * DAMAR_FC_COUNT] */
+} FilterArgs;
+
+void damar_launch_pile_filter(const FilterArgs *a, hipStream_t st);
+
 /* pile_patch.hip: LAfix's breaks and weak segments, one wavefront per pile (include/damar_hip.h damar_pile_patches; the
    DAMAR_FIX_* bounds and damar_fix_gap are defined there).  Pile q writes its repairs to gaps + slot_off[q], where it has
    room for slot_off[q + 1] - slot_off[q] of them (the host's bound: candidate pairs plus bad segments, DAMAR_FIX_MAXREP at

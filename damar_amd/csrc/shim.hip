@@ -5354,6 +5354,162 @@ extern "C" int damar_pile_gaps(const damar_pile_batch *b, const damar_gap_params
   return 0;
 }
 
+/***** LAfilter's screens per pile: scrub/LAfilter.c filter_handler (kernels/pile_filter.hip) *****************************/
+
+static DBuf FL_off, FL_aread, FL_col[8], FL_toff, FL_trace, FL_rlen, FL_trim, FL_ranno, FL_rdata, FL_soff, FL_slen, FL_sdata, FL_state,
+            FL_out[7], FL_status, FL_cnt;
+static double FL_ms[4];        /* of the last call: upload, kernel, download (HIP events), whole call (wall) */
+static int64  FL_cnt3[3];      /* piles, piles the host routine did beside the kernel, records that left discarded */
+static hipEvent_t FL_evt[4];
+static int    FL_ev_made;
+
+extern "C" void damar_filter_release(void)
+{ DBuf *all[] = { &FL_off, &FL_aread, &FL_toff, &FL_trace, &FL_rlen, &FL_trim, &FL_ranno, &FL_rdata, &FL_soff, &FL_slen, &FL_sdata, &FL_state,
+                  &FL_status, &FL_cnt };
+  for (DBuf *b : all) b->drop();
+  for (int i = 0; i < 8; i++) FL_col[i].drop();
+  for (int i = 0; i < 7; i++) FL_out[i].drop();
+  if (FL_ev_made)
+    for (int i = 0; i < 4; i++) (void) hipEventDestroy(FL_evt[i]);
+  FL_ev_made = 0;
+}
+
+static int filter_limit(const char *name, int built)
+{ const char *lower = getenv(name);
+  return (lower != NULL && atoi(lower) > 0 && atoi(lower) < built) ? atoi(lower) : built;
+}
+
+extern "C" void damar_filter_limits(int *group, int *len)
+{ *group = DAMAR_FILTER_MAXGROUP;
+  *len = DAMAR_FILTER_MAXLEN;
+}
+
+extern "C" void damar_filter_last(double *ms, int64 *cnt)
+{ for (int i = 0; i < 4; i++) ms[i] = FL_ms[i];
+  for (int i = 0; i < 3; i++) cnt[i] = FL_cnt3[i];
+}
+
+extern "C" int damar_pile_filter(const damar_trace_batch *t, const int *diffs, const damar_filter_params *p, damar_filter_out *out)
+{ const double w0 = now_ms();
+  if (!damar_filter_inputs_valid(t, diffs, p, out))
+    return 1;
+  const damar_pile_batch *b = &t->p;
+  const size_t np = (size_t) b->npiles, nrec = (size_t) b->nrec, nreads = (size_t) b->nreads;
+  const bool host = damar_piles_on_host() != 0;
+  int64 fallback = 0, gone = 0;
+  for (int i = 0; i < 4; i++) FL_ms[i] = 0;
+
+  std::vector<int> status(np + 1, 1);
+  if (!host && np > 0)
+    { ensure_init();
+      late_streams();                /* a tool built on this call is through soon after the library comes up: see damar_align_boxes */
+      if (!FL_ev_made)
+        { for (int i = 0; i < 4; i++) HIP_CHECK(hipEventCreate(&FL_evt[i]));
+          FL_ev_made = 1;
+        }
+      FilterArgs a;
+      memset(&a, 0, sizeof(a));
+      a.npiles = (u32) np;
+      a.steps = p->steps;
+      a.maxgroup = filter_limit("DAMAR_TEST_FILTER_GROUP", DAMAR_FILTER_MAXGROUP);
+      a.maxlen = filter_limit("DAMAR_TEST_FILTER_LEN", DAMAR_FILTER_MAXLEN);
+      if ((p->steps & DAMAR_FILTER_MAIN) && p->lowcov && p->max_unaligned != -1)
+        { int longest = 0;           /* the coverage bits: room for the longest A read of the batch that the kernel takes */
+          for (size_t q = 0; q < np; q++)
+            { const int alen = b->read_len[b->pile_aread[q]];
+              if (alen <= a.maxlen && alen > longest) longest = alen;
+            }
+          a.mask_words = (longest + 31) / 32 + 2;
+        }
+      a.downsample = p->downsample;  a.max_rid = (int) (p->downsample * b->nreads / 100.0);  a.seg_rate = p->seg_rate;
+      a.stitch = p->stitch;  a.stitch_aggr = p->stitch_aggr;  a.min_rlen = p->min_rlen;  a.min_olen = p->min_olen;
+      a.max_unaligned = p->max_unaligned;  a.min_nonrep = p->min_nonrep;  a.max_diffs = p->max_diffs;  a.merge_tips = p->merge_tips;
+      a.multi = p->multi;  a.lowcov = p->lowcov;  a.remove = p->remove;  a.include = p->include;  a.tbytes = t->tbytes;
+      long long *d_off = (long long *) FL_off.need(sizeof(long long) * (np + 1));
+      int *d_aread = (int *) FL_aread.need(sizeof(int) * np + 16);
+      const int *src[8] = { b->abpos, b->aepos, b->bbpos, b->bepos, b->bread, b->flags, diffs, t->tlen };
+      int *d_col[8], *d_out[7];
+      for (int i = 0; i < 8; i++) d_col[i] = (int *) FL_col[i].need(sizeof(int) * nrec + 16);
+      for (int i = 0; i < 7; i++) d_out[i] = (int *) FL_out[i].need(sizeof(int) * nrec + 16);
+      long long *d_toff = (long long *) FL_toff.need(sizeof(long long) * nrec + 16);
+      u8  *d_trace = (u8 *) FL_trace.need((size_t) t->trace_bytes + 16);
+      int *d_rlen = (int *) FL_rlen.need(sizeof(int) * nreads);
+      int *d_status = (int *) FL_status.need(sizeof(int) * np + 16);
+      int *d_cnt = (int *) FL_cnt.need(sizeof(int) * DAMAR_FC_COUNT * np + 16);
+      HIP_CHECK(hipEventRecord(FL_evt[0], G_st));
+      if (p->trim != NULL)
+        { int *d = (int *) FL_trim.need(sizeof(int) * 2 * nreads);
+          HIP_CHECK(hipMemcpyAsync(d, p->trim, sizeof(int) * 2 * nreads, hipMemcpyHostToDevice, G_st));
+          a.trim = d;
+        }
+      if (p->min_nonrep != -1)
+        { u64 *d_anno = (u64 *) FL_ranno.need(sizeof(u64) * (nreads + 1));
+          int *d_data = (int *) FL_rdata.need(sizeof(int) * (size_t) p->rep_ndata + 16);
+          HIP_CHECK(hipMemcpyAsync(d_anno, p->rep_anno, sizeof(u64) * (nreads + 1), hipMemcpyHostToDevice, G_st));
+          if (p->rep_ndata > 0)
+            HIP_CHECK(hipMemcpyAsync(d_data, p->rep_data, sizeof(int) * (size_t) p->rep_ndata, hipMemcpyHostToDevice, G_st));
+          a.rep_anno = d_anno;  a.rep_data = d_data;
+        }
+      if (p->sym_off != NULL)
+        { int *d_so = (int *) FL_soff.need(sizeof(int) * (nreads + 1)), *d_sl = (int *) FL_slen.need(sizeof(int) * (nreads + 1));
+          int *d_sd = (int *) FL_sdata.need(sizeof(int) * (size_t) p->sym_ndata + 16);
+          HIP_CHECK(hipMemcpyAsync(d_so, p->sym_off, sizeof(int) * (nreads + 1), hipMemcpyHostToDevice, G_st));
+          HIP_CHECK(hipMemcpyAsync(d_sl, p->sym_len, sizeof(int) * (nreads + 1), hipMemcpyHostToDevice, G_st));
+          if (p->sym_ndata > 0)
+            HIP_CHECK(hipMemcpyAsync(d_sd, p->sym_data, sizeof(int) * (size_t) p->sym_ndata, hipMemcpyHostToDevice, G_st));
+          a.sym_off = d_so;  a.sym_len = d_sl;  a.sym_data = d_sd;
+        }
+      if (p->read_state != NULL)
+        { u8 *d = (u8 *) FL_state.need(nreads + 16);
+          HIP_CHECK(hipMemcpyAsync(d, p->read_state, nreads, hipMemcpyHostToDevice, G_st));
+          a.read_state = d;
+        }
+      HIP_CHECK(hipMemcpyAsync(d_off, b->pile_off, sizeof(long long) * (np + 1), hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_aread, b->pile_aread, sizeof(int) * np, hipMemcpyHostToDevice, G_st));
+      if (nrec > 0)
+        { for (int i = 0; i < 8; i++)
+            HIP_CHECK(hipMemcpyAsync(d_col[i], src[i], sizeof(int) * nrec, hipMemcpyHostToDevice, G_st));
+          HIP_CHECK(hipMemcpyAsync(d_toff, t->trace_off, sizeof(long long) * nrec, hipMemcpyHostToDevice, G_st));
+        }
+      if (t->trace_bytes > 0)
+        HIP_CHECK(hipMemcpyAsync(d_trace, t->trace, (size_t) t->trace_bytes, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipMemcpyAsync(d_rlen, b->read_len, sizeof(int) * nreads, hipMemcpyHostToDevice, G_st));
+      HIP_CHECK(hipEventRecord(FL_evt[1], G_st));
+      a.pile_off = d_off;  a.pile_aread = d_aread;
+      a.abpos = d_col[0];  a.aepos = d_col[1];  a.bbpos = d_col[2];  a.bepos = d_col[3];  a.bread = d_col[4];  a.flags = d_col[5];
+      a.diffs = d_col[6];  a.tlen = d_col[7];  a.trace_off = d_toff;  a.trace = d_trace;  a.read_len = d_rlen;
+      a.o_flags = d_out[0];  a.o_ae = d_out[1];  a.o_be = d_out[2];  a.o_df = d_out[3];  a.o_tl = d_out[4];  a.o_why = d_out[5];  a.o_by = d_out[6];
+      a.status = d_status;  a.cnt = d_cnt;
+      damar_launch_pile_filter(&a, G_st);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipEventRecord(FL_evt[2], G_st));
+      int *dst[7] = { out->flags, out->aepos, out->bepos, out->diffs, out->tlen, out->reason, out->cont_by };
+      if (nrec > 0)
+        for (int i = 0; i < 7; i++)
+          HIP_CHECK(hipMemcpyAsync(dst[i], d_out[i], sizeof(int) * nrec, hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipMemcpyAsync(status.data(), d_status, sizeof(int) * np, hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipMemcpyAsync(out->cnt, d_cnt, sizeof(int) * DAMAR_FC_COUNT * np, hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipEventRecord(FL_evt[3], G_st));
+      HIP_CHECK(hipStreamSynchronize(G_st));
+      for (int i = 0; i < 3; i++)
+        { float ms = 0;
+          HIP_CHECK(hipEventElapsedTime(&ms, FL_evt[i], FL_evt[i + 1]));
+          FL_ms[i] = ms;
+        }
+    }
+  /* what the kernel left (all piles with DAMAR_PILES=host) is the plain routine's */
+  for (size_t q = 0; q < np; q++)
+    if (status[q] != 0)
+      { damar_host_filter_pile(t, diffs, (int64) q, p, out);
+        fallback += host ? 0 : 1;
+      }
+  for (size_t i = 0; i < nrec; i++)
+    gone += (out->flags[i] & 0x2) != 0;
+  FL_cnt3[0] = b->npiles;  FL_cnt3[1] = fallback;  FL_cnt3[2] = gone;
+  FL_ms[3] = now_ms() - w0;
+  return 0;
+}
+
 /***** LAfix's breaks and weak segments per pile: scrub/LAfix.c fix_process (kernels/pile_patch.hip) **********************/
 
 static DBuf FX_off, FX_aread, FX_trim, FX_col[7], FX_toff, FX_trace, FX_rlen, FX_qanno, FX_qdata, FX_ranno, FX_rdata, FX_skip, FX_slot,

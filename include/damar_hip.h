@@ -452,6 +452,60 @@ void damar_fix_limits(int *segs, int *cands);      /* DAMAR_FIX_MAXSEGS, DAMAR_F
  * cnt[3] = piles, piles the host routine did beside the kernel, repairs */
 void damar_fix_last(double *ms, int64 *cnt);
 
+/* Overlaps filtered per pile (scrub/LAfilter.c filter_handler without its experimental branches).  Per pile of a trace
+ * batch, in the reference's order; `steps` says which half of it runs, since LAfilter's -T cuts the records between the two:
+ *   DAMAR_FILTER_PRE    -f (reads above downsample * nreads / 100.0 discarded) and -b (OVL_DISCARD | OVL_DIFF on the first
+ *                       trace segment but the last whose diffs * 100.0 / blen exceeds seg_rate), on the trace as it is;
+ *   DAMAR_FILTER_MAIN   -s / -S per run of consecutive records of one B read (the head chained to the longest later record
+ *                       of its orientation within the fuzz; its end and diffs updated, its trace dropped, OVL_DISCARD and
+ *                       OVL_LOCAL taken off it, the joined record OVL_DISCARD | OVL_STITCH); filter() per record (-A -l -o
+ *                       -u -d -n with -Y, and under -R 2 the trace points summed against bepos); -w per run; -z per pile;
+ *                       -R 0 .. 6; the -x / -I read states.
+ * `diffs` is the records' differences word.  Every array of `out` is the caller's and holds one value per record (cnt: per
+ * pile); the records' abpos and bbpos do not change.  reason has one bit per site that prints a line in the reference
+ * (DAMAR_FR_*), set whether or not the flag it stands for was set before; cont_by is the index within the pile of the record
+ * that -R 6 found a record contained in, or -1.  Runs kernels/pile_filter.hip, one wavefront per pile; a pile with a run of
+ * more than DAMAR_FILTER_MAXGROUP records of one B read, and under -z with -u a pile on a read of more than
+ * DAMAR_FILTER_MAXLEN bases, is done by the routine of host/filter.c (DAMAR_TEST_FILTER_GROUP and DAMAR_TEST_FILTER_LEN lower
+ * the two, for tests).  With DAMAR_PILES=host that routine does all piles and no GPU is touched.  0, or 1 after a message. */
+#define DAMAR_FILTER_MAXGROUP 64           /* records of one B read in a row that one lane takes */
+#define DAMAR_FILTER_MAXLEN   400000       /* bases of the A read whose coverage bits the kernel keeps in LDS */
+enum { DAMAR_FILTER_PRE = 1, DAMAR_FILTER_MAIN = 2 };
+enum { DAMAR_FR_SYM = 0x1, DAMAR_FR_OLEN = 0x2, DAMAR_FR_LOCAL = 0x4, DAMAR_FR_DIFF = 0x8, DAMAR_FR_REPA_TIPS = 0x10,
+       DAMAR_FR_REPA_LEN = 0x20, DAMAR_FR_REPA = 0x40, DAMAR_FR_REPB_LEN = 0x80, DAMAR_FR_REPB = 0x100, DAMAR_FR_TP = 0x200,
+       DAMAR_FR_MULTI = 0x400, DAMAR_FR_SELF = 0x800, DAMAR_FR_CONT = 0x1000,
+       DAMAR_FR_HEAD = 0x2000 };             /* no line: the record is the head of a stitch, its trace is gone */
+enum { DAMAR_FC_DIFFS = 0, DAMAR_FC_UNALIGNED, DAMAR_FC_CONTAINED, DAMAR_FC_LENGTH, DAMAR_FC_REPEAT, DAMAR_FC_READLEN,
+       DAMAR_FC_LOWCOV, DAMAR_FC_SYM, DAMAR_FC_MULTI, DAMAR_FC_MULTI_BASES, DAMAR_FC_STITCHED, DAMAR_FC_COUNT };
+typedef struct
+{ int           steps;                     /* DAMAR_FILTER_PRE | DAMAR_FILTER_MAIN */
+  int           downsample, seg_rate;      /* -f (0: none) -b (outside 0 .. 100: none) */
+  int           stitch, stitch_aggr;       /* -s / -S (-1: none), -S */
+  int           min_rlen, min_olen, max_unaligned, min_nonrep;      /* -l -o -u -n (-1: none) */
+  float         max_diffs;                 /* -d / 100 (<= 0: none) */
+  int           merge_tips, multi, lowcov; /* -Y -w -z */
+  int           remove;                    /* -R: bit k for -R k */
+  int           include;                   /* -I given */
+  const int    *trim;                      /* -t: get_trim of every read, [2 * nreads]; NULL: no trim track */
+  const uint64 *rep_anno;                  /* -r: [nreads + 1] byte offsets into rep_data, {begin, end} pairs; needed with -n */
+  const int    *rep_data;
+  int64         rep_ndata;
+  const int    *sym_off, *sym_len;         /* -A: read r's list is sym_data[sym_off[r] .. + sym_len[r]) ([nreads + 1] each); NULL: none */
+  const int    *sym_data;
+  int64         sym_ndata;
+  const unsigned char *read_state;         /* -x / -I: 1 discard, 2 keep, per read; NULL: none */
+} damar_filter_params;
+typedef struct
+{ int   *flags, *aepos, *bepos, *diffs, *tlen, *reason, *cont_by;      /* [nrec] */
+  int   *cnt;                              /* [npiles * DAMAR_FC_COUNT] */
+} damar_filter_out;
+int  damar_pile_filter(const damar_trace_batch *b, const int *diffs, const damar_filter_params *p, damar_filter_out *out);
+void damar_filter_release(void);           /* frees the cached device buffers of damar_pile_filter */
+void damar_filter_limits(int *group, int *len);    /* DAMAR_FILTER_MAXGROUP, DAMAR_FILTER_MAXLEN as the library was built */
+/* of the last call: ms[4] = upload, kernel, download (HIP events; 0 on the host path), whole call (wall);
+ * cnt[3] = piles, piles the host routine did beside the kernel, records that leave the call discarded */
+void damar_filter_last(double *ms, int64 *cnt);
+
 /* Phase timings (milliseconds, HIP events on the library's stream) of the last
  * damar_index_build / damar_match: see DAMAR_T_* below. */
 enum { DAMAR_T_TUPLES = 0, DAMAR_T_KSORT, DAMAR_T_TABLE, DAMAR_T_MERGE, DAMAR_T_SSORT,
