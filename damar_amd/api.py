@@ -1309,3 +1309,82 @@ def filter_las(db, las, out, *, verbose=False, purge=False, do_trim=False, trim=
     res = {k: int(getattr(st, k)) for k in ("novl", "written", "discarded", "piles", "host_piles")}
     res.update(zip(FILTER_COUNTERS, (int(x) for x in st.cnt)))
     return res
+
+
+# ---- reads corrected from the consensus of their tiles (LAcorrect) ----------------------------------------------------
+
+class TileBatch(C.Structure):          # include/damar_hip.h damar_tile_batch
+    _fields_ = [("ntiles", c_int64), ("ent_off", C.POINTER(c_int64)), ("seq_off", C.POINTER(c_int64)), ("seq_len", _PI),
+                ("bases", C.POINTER(C.c_ubyte)), ("nbases", c_int64), ("weight", _PI)]
+
+
+class CorrectOpts(C.Structure):        # host/damar_host.h damar_correct_opts
+    _fields_ = [("verbose", C.c_int), ("nthreads", C.c_int), ("block", C.c_int), ("q_track", C.c_char_p), ("read_ids", C.c_char_p)]
+
+
+class CorrectStats(C.Structure):       # host/damar_host.h damar_correct_stats
+    _fields_ = [(k, c_int64) for k in ("reads", "copies", "tiles", "host_tiles", "bases")] + \
+               [(k, C.c_double) for k in ("ms_consensus", "ms_kernel", "ms_postrace", "ms_postrace_wait", "ms_total")]
+
+
+def correct_limits():
+    """(seg, cols, cells): the bases of one sequence, the profile columns and the wave cells a tile may need for
+    kernels/tile_consensus.hip to do it: DAMAR_CORRECT_MAXSEG, DAMAR_CORRECT_MAXCOLS, DAMAR_CORRECT_CELLS"""
+    v = [C.c_int() for _ in range(3)]
+    _lib().damar_correct_limits(*[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def correct_last():
+    """Of the last tile_consensus / of the last batch of correct_las: ({upload, kernel, download, call} ms, tiles, tiles the
+    host routine did beside the kernel, bases called)."""
+    ms, cnt = (C.c_double * 4)(), (c_int64 * 3)()
+    L = _lib()
+    L.damar_correct_last.argtypes = [C.POINTER(C.c_double), C.POINTER(c_int64)]
+    L.damar_correct_last(ms, cnt)
+    return dict(zip(("upload", "kernel", "download", "call"), list(ms))), cnt[0], cnt[1], cnt[2]
+
+
+def tile_consensus(tiles, weight=None):
+    """The consensus of a batch of tiles: `tiles` is a list of tiles, a tile a list of at most 20 sequences (arrays of bases
+    0..3; a complemented read's already turned), added in order as LAcorrect's single_tile_consensus adds them.
+    -> (list of the tiles' called bases as uint8 arrays, array of the sequences each tile took).  On the GPU unless
+    DAMAR_PILES=host."""
+    import numpy as np
+    L = _lib()
+    seqs = [np.ascontiguousarray(s, dtype=np.uint8) for t in tiles for s in t]
+    ent_off = np.zeros(len(tiles) + 1, dtype=np.int64)
+    ent_off[1:] = np.cumsum([len(t) for t in tiles])
+    seq_len = np.array([len(s) for s in seqs] + [0], dtype=np.int32)
+    seq_off = np.zeros(len(seqs) + 1, dtype=np.int64)
+    seq_off[1:] = np.cumsum(seq_len[:len(seqs)])
+    bases = np.concatenate(seqs + [np.zeros(1, dtype=np.uint8)])
+    b = TileBatch(len(tiles), ent_off.ctypes.data_as(C.POINTER(c_int64)), seq_off.ctypes.data_as(C.POINTER(c_int64)),
+                  seq_len.ctypes.data_as(_PI), bases.ctypes.data_as(C.POINTER(C.c_ubyte)), int(seq_off[len(seqs)]), None)
+    if weight is not None:
+        w = np.ascontiguousarray(weight, dtype=np.int32)
+        b.weight = w.ctypes.data_as(_PI)
+    cons_off = np.zeros(len(tiles) + 1, dtype=np.int64)
+    added = np.zeros(max(len(tiles), 1), dtype=np.int32)
+    cons = C.POINTER(C.c_ubyte)()
+    L.damar_tile_consensus.argtypes = [C.POINTER(TileBatch), C.POINTER(c_int64), C.POINTER(C.POINTER(C.c_ubyte)), _PI]
+    if L.damar_tile_consensus(C.byref(b), cons_off.ctypes.data_as(C.POINTER(c_int64)), C.byref(cons), added.ctypes.data_as(_PI)):
+        raise RuntimeError("damar_tile_consensus failed")
+    flat = np.ctypeslib.as_array(cons, shape=(max(int(cons_off[-1]), 1),))[:int(cons_off[-1])].copy()
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    libc.free(C.cast(cons, C.c_void_p))
+    return [flat[cons_off[i]:cons_off[i + 1]] for i in range(len(tiles))], added[:len(tiles)]
+
+
+def correct_las(db, las, out, *, verbose=False, parts=1, block=-1, q="q", read_ids=None):
+    """LAcorrect on one .las file: the corrected reads written to <out>.NN.fasta, one file per part (-j).  q: the quality
+    track's name (-q), read_ids: a file of read numbers (-r), block: -b.  The reference's lines go to stdout.
+    -> the counters and timings of the run (host_tiles: tiles the host routine did beside the kernel)."""
+    L = _lib()
+    o = CorrectOpts(1 if verbose else 0, int(parts), int(block), q.encode(), read_ids.encode() if read_ids is not None else None)
+    st = CorrectStats()
+    L.damar_correct_las.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(CorrectOpts), C.POINTER(CorrectStats)]
+    if L.damar_correct_las(db.encode(), las.encode(), out.encode(), C.byref(o), C.byref(st)):
+        raise RuntimeError("damar_correct_las failed")
+    return {k: getattr(st, k) for k, _ in CorrectStats._fields_}

@@ -221,6 +221,27 @@ void damar_filter_no_track(const char *track);   /* the reference's two lines fo
    trim (-T), damar_pile_filter, the reference's lines on stdout, the records written.  0, or 1 after a message. */
 int  damar_filter_las(const char *db, const char *las, const char *out, const damar_filter_opts *o, damar_filter_stats *st);
 
+/* correct.c: LAcorrect (corrector/LAcorrect.c) -- the plain routine behind damar_tile_consensus (DAMAR_PILES=host, and the
+   tiles the kernel leaves), the check both paths share, and the pass over a file. */
+int  damar_tile_batch_valid(const damar_tile_batch *b);                                      /* 0 after a message */
+/* one tile: *out (room for *cap values, grown here) receives the called bases; their number, or -1 after a message */
+int  damar_host_tile(const damar_tile_batch *b, int64 tile, unsigned char **out, int64 *cap);
+void damar_host_tile_release(void);
+typedef struct
+{ int   verbose, nthreads, block;          /* -v -j -b (block <= 0: all reads) */
+  const char *q_track, *read_ids;          /* -q, -r (NULL: all reads) */
+} damar_correct_opts;
+typedef struct
+{ int64  reads, copies;                    /* headers written */
+  int64  tiles, host_tiles, bases;         /* summed over the batches: damar_correct_last's counts */
+  double ms_consensus, ms_kernel;          /* the damar_tile_consensus calls (wall), their kernels (HIP events) */
+  double ms_postrace, ms_postrace_wait;    /* the whole-read alignments summed over the worker threads; what the pass waited for them */
+  double ms_total;
+} damar_correct_stats;
+/* the pass over a file: the reads written to <out>.NN.fasta, one file per part of -j; the reference's lines on stdout.
+   The postrace alignments run in DAMAR_CORRECT_THREADS (8) worker threads.  0, or 1 after a message. */
+int  damar_correct_las(const char *db, const char *las, const char *out, const damar_correct_opts *o, damar_correct_stats *st);
+
 /* bridge.c: the exact alignment of one box into trace pairs (what damar_trace_boxes returns per box): A[0..M) against
    B[0..N), M, N >= 1, A's position 0 lying abpos >= 0 bases into the grid of ts; trace holds
    2 * ((abpos + M + ts - 1) / ts - abpos / ts) values, *tlen receives their number; returns the differences.  Works in the

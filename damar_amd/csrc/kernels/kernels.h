@@ -494,6 +494,27 @@ typedef struct
 
 void damar_launch_pile_patch(const FixArgs *a, hipStream_t st);
 
+/* tile_consensus.hip: the consensus of tiles, one lane per tile.  Task i is tile order[i] of the batch (the host sorts by
+   weight and leaves out the empty tiles and those with a sequence over its limit); its sequences are [ent_off[t],
+   ent_off[t + 1]).  Lane l of the grid works in work + l * stripe: 5 * maxcols count bytes, maxcols match codes,
+   maxscript int16 script values, cells int16 furthest points, cells int8 codes (maxcols even, so that all are aligned).
+   status[i] = 0: len[i] called bases at out + i * maxcols; else the task is the host's (TC_ROOM: a limit was met). */
+typedef struct
+{ u32 ntasks, blocks;
+  int maxcols, maxscript, cells;
+  size_t stripe;
+  const u32 *order;                   /* [ntasks] */
+  const long long *ent_off;           /* [ntiles + 1] */
+  const long long *seq_off;           /* [nent] */
+  const int *seq_len;
+  const u8  *bases;
+  u8  *work;
+  u8  *out;
+  int *status, *len;                  /* [ntasks] */
+} TileArgs;
+
+void damar_launch_tile_consensus(const TileArgs *a, hipStream_t st);
+
 /* box_align.hip: exact alignment of a batch of boxes with their edit scripts (align.c:4734 DIFF_ALIGN).  A box with
    max(m, n) <= maxlen <= DAMAR_BOX_MAXLEN is done and leaves its differences, the length of its script (-1: it hit a bound of
    the kernel and is the host's after all) and the script at script + coff[box], max(m, n) values of room; the others are

@@ -506,6 +506,38 @@ void damar_filter_limits(int *group, int *len);    /* DAMAR_FILTER_MAXGROUP, DAM
  * cnt[3] = piles, piles the host routine did beside the kernel, records that leave the call discarded */
 void damar_filter_last(double *ms, int64 *cnt);
 
+/* Consensus of tiles (corrector/consensus.c as corrector/LAcorrect.c drives it): tile t of a batch is the sequences
+ * [ent_off[t], ent_off[t + 1]) -- MAX_COVERAGE = 20 at the most, none: an empty tile -- sequence e the seq_len[e] >= 1 bases
+ * from bases + seq_off[e], one base per byte (0 .. 3), a complemented read's already turned.  The first sequence founds a
+ * profile of five counts per column; every later one is aligned to it by v3_align_onp (the O(NP) waves, all kept; the
+ * path reversed with the reference's fix-ups) and folded in from right to left; the tile's call is
+ * consensus_sequence(c, 0).  cons_off[ntiles + 1] (the caller's) receives where each tile's called bases (0 .. 3) lie in
+ * *cons (malloc'ed, the caller's to free), added[ntiles] the sequences each tile took.  weight[ntiles], if given, orders
+ * the tiles so that the lanes of a wavefront have about the same work (LAcorrect: the sum of the segments' differences).
+ * Runs kernels/tile_consensus.hip, one lane per tile; a tile with a sequence over DAMAR_CORRECT_MAXSEG bases, one whose
+ * profile outgrows DAMAR_CORRECT_MAXCOLS columns (DAMAR_TEST_CORRECT_COLS lowers that, for tests) and one whose waves
+ * outgrow DAMAR_CORRECT_CELLS cells is done by the routine of host/correct.c and counted.  With DAMAR_PILES=host that
+ * routine does all tiles and no GPU is touched.  0 on success, 1 after a message. */
+#define DAMAR_CORRECT_MAXCOV  20           /* sequences of a tile: MAX_COVERAGE, LAcorrect.c:35 */
+#define DAMAR_CORRECT_MAXSEG  320          /* bases of one sequence the kernel takes */
+#define DAMAR_CORRECT_MAXCOLS 384          /* profile columns a lane has room for */
+#define DAMAR_CORRECT_CELLS   8192         /* wave cells (an int16 and an int8 each) a lane has room for */
+typedef struct
+{ int64        ntiles;
+  const int64 *ent_off;                    /* [ntiles + 1] */
+  const int64 *seq_off;                    /* [ent_off[ntiles]] */
+  const int   *seq_len;
+  const unsigned char *bases;              /* [nbases] */
+  int64        nbases;
+  const int   *weight;                     /* [ntiles], or NULL: sequences times bases */
+} damar_tile_batch;
+int  damar_tile_consensus(const damar_tile_batch *b, int64 *cons_off, unsigned char **cons, int *added);
+void damar_correct_release(void);          /* frees the cached device buffers of damar_tile_consensus */
+void damar_correct_limits(int *seg, int *cols, int *cells);      /* the three limits as the library was built */
+/* of the last call: ms[4] = upload, kernel, download (HIP events; 0 on the host path), whole call (wall);
+ * cnt[3] = tiles, tiles the host routine did beside the kernel, bases called */
+void damar_correct_last(double *ms, int64 *cnt);
+
 /* Phase timings (milliseconds, HIP events on the library's stream) of the last
  * damar_index_build / damar_match: see DAMAR_T_* below. */
 enum { DAMAR_T_TUPLES = 0, DAMAR_T_KSORT, DAMAR_T_TABLE, DAMAR_T_MERGE, DAMAR_T_SSORT,
