@@ -485,11 +485,32 @@ def pile_tandem(piles, read_len, read_flags, min_len=0):
     return _take_track(L, t, count[:b.npiles])
 
 
+_PHASES = ("upload", "kernel", "download", "call")
+_STAGES = ("trace", "pile", "q", "box", "tbox", "gap", "fix", "filter", "correct")
+
+
+def _last(stage, ncnt, names=_PHASES):
+    """damar_<stage>_last -> ({names: ms}, the ncnt counters...)."""
+    ms, cnt = (C.c_double * 4)(), (c_int64 * ncnt)()
+    f = getattr(_lib(), "damar_%s_last" % stage)
+    f.argtypes, f.restype = [C.POINTER(C.c_double), C.POINTER(c_int64)], None
+    f(ms, cnt)
+    return (dict(zip(names, list(ms))),) + tuple(cnt)
+
+
+def release(stage):
+    """Frees the device buffers and events a call family keeps between calls: damar_<stage>_release, stage one of
+    trace, pile, q, box, tbox, gap, fix, filter, correct (a homogenize session is released by closing it)."""
+    if stage not in _STAGES:
+        raise ValueError("no stage %r" % (stage,))
+    f = getattr(_lib(), "damar_%s_release" % stage)
+    f.argtypes, f.restype = [], None
+    f()
+
+
 def pile_last():
     """Of the last device call: ({upload, sort, sweep, download} ms, events sorted, regions written)."""
-    ms, cnt = (C.c_double * 4)(), (c_int64 * 2)()
-    _lib().damar_pile_last(ms, cnt)
-    return dict(zip(("upload", "sort", "sweep", "download"), list(ms))), cnt[0], cnt[1]
+    return _last("pile", 2, ("upload", "sort", "sweep", "download"))
 
 
 def db_info(db):
@@ -655,9 +676,7 @@ def pile_quality(batch, read_len, segmin=1, segmax=20, ccs=False):
 
 def q_last():
     """Of the last device call of pile_quality / q_track: ({upload, count, select, download} ms, segments counted, tiles)."""
-    ms, cnt = (C.c_double * 4)(), (c_int64 * 2)()
-    _lib().damar_q_last(ms, cnt)
-    return dict(zip(("upload", "count", "select", "download"), list(ms))), cnt[0], cnt[1]
+    return _last("q", 2, ("upload", "count", "select", "download"))
 
 
 def _take_q(res, nreads, with_q):
@@ -747,9 +766,7 @@ def align_boxes(a_seqs, b_seqs):
 def box_last():
     """Of the last align_boxes / of the last batch of trim_las: ({upload, kernel, download, call} ms, boxes, boxes the host
     routine did beside the kernel, script values)."""
-    ms, cnt = (C.c_double * 4)(), (c_int64 * 3)()
-    _lib().damar_box_last(ms, cnt)
-    return dict(zip(("upload", "kernel", "download", "call"), list(ms))), cnt[0], cnt[1], cnt[2]
+    return _last("box", 3)
 
 
 def trim_las(db, las, out, track="trim", purge=False):
@@ -803,9 +820,7 @@ def trace_boxes(a_seqs, b_seqs, a_starts, tspace):
 def tbox_last():
     """Of the last trace_boxes / of the last round of stitch_las: ({upload, kernel, download, call} ms, boxes, boxes the host
     routine did beside the kernel, trace values)."""
-    ms, cnt = (C.c_double * 4)(), (c_int64 * 3)()
-    _lib().damar_tbox_last(ms, cnt)
-    return dict(zip(("upload", "kernel", "download", "call"), list(ms))), cnt[0], cnt[1], cnt[2]
+    return _last("tbox", 3)
 
 
 def stitch_las(db, las, out, fuzz=40, purge=False, track=None, repeats=None, anchor=500, merge=10, min_len=500, min_merge=200,
@@ -880,9 +895,7 @@ def pile_gaps(piles, read_len, stitch=0, exclude=None):
 def gap_last():
     """Of the last pile_gaps / of the last batch of gap_las: ({upload, kernel, download, call} ms, piles, piles the host
     routine did beside the kernel, break events)."""
-    ms, cnt = (C.c_double * 4)(), (c_int64 * 3)()
-    _lib().damar_gap_last(ms, cnt)
-    return dict(zip(("upload", "kernel", "download", "call"), list(ms))), cnt[0], cnt[1], cnt[2]
+    return _last("gap", 3)
 
 
 def gap_las(db, las, out, stitch=0, purge=False, trim=None, exclude=None, repeats=None):
@@ -1000,11 +1013,7 @@ def pile_patches(batch, read_len, trim, q, repeats=None, low_q=28, max_gap=500, 
 def fix_last():
     """Of the last pile_patches / of the last batch of fix_las: ({upload, kernel, download, call} ms, piles, piles the host
     routine did beside the kernel, repairs)."""
-    ms, cnt = (C.c_double * 4)(), (c_int64 * 3)()
-    L = _lib()
-    L.damar_fix_last.argtypes = [C.POINTER(C.c_double), C.POINTER(c_int64)]
-    L.damar_fix_last(ms, cnt)
-    return dict(zip(("upload", "kernel", "download", "call"), list(ms))), cnt[0], cnt[1], cnt[2]
+    return _last("fix", 3)
 
 
 def fix_las(db, las, fasta, *, min_len=1000, low_q=28, max_gap=500, trim=None, q="q", repeats=None, convert=(), trim_out=None,
@@ -1108,9 +1117,7 @@ def pile_homogenize(batches, read_len, rep_anno, rep_data, merge=False, ends=-1,
 def homog_last():
     """Of the last session of pile_homogenize / homogenize_track, summed over its calls: ({upload, mark, readout, download}
     ms, records seen, ranges set in the mask, intervals read out)."""
-    ms, cnt = (C.c_double * 4)(), (c_int64 * 3)()
-    _lib().damar_homog_last(ms, cnt)
-    return dict(zip(("upload", "mark", "readout", "download"), list(ms))), cnt[0], cnt[1], cnt[2]
+    return _last("homog", 3, ("upload", "mark", "readout", "download"))
 
 
 def _load_a2(L, d, name):
@@ -1236,11 +1243,7 @@ def filter_limits():
 def filter_last():
     """Of the last pile_filter / of the last batch of filter_las: ({upload, kernel, download, call} ms, piles, piles the host
     routine did beside the kernel, records that left discarded)."""
-    ms, cnt = (C.c_double * 4)(), (c_int64 * 3)()
-    L = _lib()
-    L.damar_filter_last.argtypes = [C.POINTER(C.c_double), C.POINTER(c_int64)]
-    L.damar_filter_last(ms, cnt)
-    return dict(zip(("upload", "kernel", "download", "call"), list(ms))), cnt[0], cnt[1], cnt[2]
+    return _last("filter", 3)
 
 
 def _filter_numbers(p, downsample=0, seg_rate=-1, stitch=-1, stitch_aggr=False, min_rlen=-1, min_olen=-1, max_unaligned=-1, min_nonrep=-1,
@@ -1338,11 +1341,7 @@ def correct_limits():
 def correct_last():
     """Of the last tile_consensus / of the last batch of correct_las: ({upload, kernel, download, call} ms, tiles, tiles the
     host routine did beside the kernel, bases called)."""
-    ms, cnt = (C.c_double * 4)(), (c_int64 * 3)()
-    L = _lib()
-    L.damar_correct_last.argtypes = [C.POINTER(C.c_double), C.POINTER(c_int64)]
-    L.damar_correct_last(ms, cnt)
-    return dict(zip(("upload", "kernel", "download", "call"), list(ms))), cnt[0], cnt[1], cnt[2]
+    return _last("correct", 3)
 
 
 def tile_consensus(tiles, weight=None):

@@ -21,6 +21,7 @@
 #include <functional>
 #include <string.h>
 #include <unistd.h>
+#include <limits.h>
 
 #include "kernels/dev_common.h"
 #include <ctype.h>
@@ -3938,9 +3939,14 @@ extern "C" Path *Local_Alignment(Alignment *align, Work_Data *work, Align_Spec *
 
 /***** (f)4: trace-point expansion, align.c:5577-5692 Compute_Trace_PTS for batches of records *********/
 
-struct DBuf
+struct DevStage;
+
+struct DBuf                        /* a device buffer kept between calls, grown when a call needs more */
 { void  *p = nullptr;
   size_t cap = 0;
+  DBuf  *next;                     /* of the stage's buffers */
+  DBuf(DevStage &s);              /* a buffer is made with the stage it belongs to, so DevStage::release() needs no list */
+  DBuf(const DBuf &) = delete;
   void *need(size_t n)
   { if (n > cap)
       { if (p) HIP_CHECK(hipFree(p));
@@ -3952,20 +3958,136 @@ struct DBuf
   void drop() { if (p) HIP_CHECK(hipFree(p));  p = nullptr;  cap = 0; }
 };
 
-static DBuf T_recs, T_pts, T_segs, T_count, T_dist, T_segoff, T_stage, T_vf, T_hf, T_over, T_ctr, T_tlen,
-            T_diffs, T_script, T_scan, T_bvf, T_bhf, T_mid, T_segs2, T_key, T_val, T_key1, T_val1, T_sortw;
-static double T_ms[4];        /* of the last damar_trace_pts: trace_waves kernel, layout..pack on the device, whole call, inside the batches (wall) */
-static int64  T_cnt[4];       /* records, segments, deferred segments, script values */
+/* What one call family keeps between its calls: the device buffers, the events that time a call's phases on G_st, and the
+   figures of the last call for its damar_*_last.  A family is a static of a struct derived from this one whose members are
+   its buffers by name; damar_homog holds one per handle. */
+struct DevStage
+{ DBuf      *bufs = nullptr;
+  hipEvent_t ev[5] = { NULL, NULL, NULL, NULL, NULL };       /* made on first use, kept like the buffers */
+  double     ms[4] = { 0, 0, 0, 0 };
+  int64      cnt[4] = { 0, 0, 0, 0 };
 
-extern "C" void damar_trace_release(void)
-{ DBuf *all[] = { &T_recs, &T_pts, &T_segs, &T_count, &T_dist, &T_segoff, &T_stage, &T_vf, &T_hf, &T_over, &T_ctr,
-                  &T_tlen, &T_diffs, &T_script, &T_scan, &T_bvf, &T_bhf, &T_mid, &T_segs2, &T_key, &T_val, &T_key1, &T_val1, &T_sortw };
-  for (DBuf *b : all) b->drop();
+  void mark(int i)                 /* event i, here on G_st */
+  { if (ev[0] == NULL)
+      for (hipEvent_t &e : ev) HIP_CHECK(hipEventCreate(&e));
+    HIP_CHECK(hipEventRecord(ev[i], G_st));
+  }
+  void laps_add(int first, int n)  /* after the caller's synchronise: the time from event i to event i + 1 added to ms[i], n of them */
+  { for (int i = first; i < first + n; i++)
+      { float t = 0;
+        HIP_CHECK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
+        ms[i] += t;
+      }
+  }
+  void laps(int first, int n)      /* the same, written over ms[i] */
+  { for (int i = first; i < first + n; i++) ms[i] = 0;
+    laps_add(first, n);
+  }
+  void last(double *m, int64 *c, int ncnt) const
+  { for (int i = 0; i < 4; i++) m[i] = ms[i];
+    for (int i = 0; i < ncnt; i++) c[i] = cnt[i];
+  }
+  void release()                   /* the buffers and the events; the figures stay */
+  { for (DBuf *b = bufs; b != NULL; b = b->next) b->drop();
+    if (ev[0] != NULL)
+      for (hipEvent_t &e : ev)
+        { (void) hipEventDestroy(e);
+          e = NULL;
+        }
+  }
+};
+
+inline DBuf::DBuf(DevStage &s) : next(s.bufs) { s.bufs = this; }
+
+/* src[0 .. n) into b on G_st: room for it and 16 bytes more (the kernels' wide loads may reach past the last value), the
+   copy where there is something to copy */
+template <typename T>
+static T *up(DBuf &b, const T *src, size_t n)
+{ T *d = (T *) b.need(sizeof(T) * n + 16);
+  if (n > 0)
+    HIP_CHECK(hipMemcpyAsync(d, src, sizeof(T) * n, hipMemcpyHostToDevice, G_st));
+  return d;
 }
 
-extern "C" void damar_trace_last(double *ms, int64 *cnt)
-{ for (int i = 0; i < 4; i++) { ms[i] = T_ms[i];  cnt[i] = T_cnt[i]; }
+/* a track of the database: anno[nreads + 1] byte offsets into data[ndata] */
+struct DevTrack { const u64 *anno;  const int *data; };
+
+static DevTrack up_track(DBuf &anno, DBuf &data, const uint64 *a, size_t nreads, const int *d, int64 ndata)
+{ DevTrack k;
+  k.anno = (const u64 *) up(anno, a, nreads + 1);
+  k.data = up(data, d, (size_t) ndata);
+  return k;
 }
+
+/* A stage whose calls take a damar_pile_batch or a damar_trace_batch, and the batch as pile_up() leaves it on the device:
+   col[i] is the i-th of the record columns the caller named, toff and trace are there for a trace batch */
+struct PileStage : DevStage
+{ DBuf off{*this}, aread{*this}, col[8] = { *this, *this, *this, *this, *this, *this, *this, *this }, toff{*this}, trace{*this};
+};
+
+struct PileDev
+{ const long long *off, *toff;
+  const int *aread, *col[8];
+  const u8  *trace;
+};
+
+static PileDev pile_up(PileStage &S, const damar_pile_batch *b, const damar_trace_batch *t, std::initializer_list<const int *> cols)
+{ const size_t np = (size_t) b->npiles, nrec = (size_t) b->nrec;
+  PileDev d;
+  memset(&d, 0, sizeof(d));
+  d.off = (const long long *) up(S.off, b->pile_off, np + 1);
+  d.aread = up(S.aread, b->pile_aread, np);
+  int i = 0;
+  for (const int *c : cols)
+    { d.col[i] = up(S.col[i], c, nrec);
+      i += 1;
+    }
+  if (t != NULL)
+    { d.toff = (const long long *) up(S.toff, t->trace_off, nrec);
+      d.trace = up(S.trace, t->trace, (size_t) t->trace_bytes);
+    }
+  return d;
+}
+
+/* a limit the library was built with, lowered by a test through the environment: a value below `floor` or not below the
+   limit leaves it as it is */
+static int test_limit(const char *name, int built, int floor)
+{ const char *e = getenv(name);
+  const int v = (e != NULL) ? atoi(e) : built;
+  return (v >= floor && v < built) ? v : built;
+}
+
+/* k more items of `per` values each at the end of a list that grows by realloc (a pile's results behind those of the piles
+   before it); 1 after a message, the list freed */
+template <typename T>
+static int list_append(T **list, int64 *n, int64 *cap, size_t per, const T *src, int64 k, const char *what)
+{ if (*n + k > *cap)
+    { const int64 c = *n + k + *cap / 4 + 256;
+      T *grown = (T *) realloc(*list, sizeof(T) * per * (size_t) c);
+      if (grown == NULL)
+        { fprintf(stderr, "damar: out of memory (%s)\n", what);
+          free(*list);
+          return 1;
+        }
+      *list = grown;
+      *cap = c;
+    }
+  if (k > 0)
+    memcpy(*list + per * (size_t) *n, src, sizeof(T) * per * (size_t) k);
+  *n += k;
+  return 0;
+}
+
+static struct : DevStage         /* ms of the last damar_trace_pts: trace_waves kernel, layout..pack on the device, whole call, inside the
+                                    batches (wall); cnt: records, segments, deferred segments, script values */
+{ DBuf recs{*this}, pts{*this}, segs{*this}, count{*this}, dist{*this}, segoff{*this}, stage{*this}, vf{*this}, hf{*this}, over{*this},
+       ctr{*this}, tlen{*this}, diffs{*this}, script{*this}, scan{*this}, bvf{*this}, bhf{*this}, mid{*this}, segs2{*this}, key{*this},
+       val{*this}, key1{*this}, val1{*this}, sortw{*this};
+} TR;
+
+extern "C" void damar_trace_release(void) { TR.release(); }
+
+extern "C" void damar_trace_last(double *ms, int64 *cnt) { TR.last(ms, cnt, 4); }
 
 /* staging slots one record needs = sum over its segments of dmax + |M - N| (the script of a segment has at
    most D + |del| <= dmax + |del| values); also dmax and the segment count */
@@ -4003,14 +4125,14 @@ static u32 trace_wave_phase(TraceArgs t, int mode, int kind, u32 nwork, u32 rows
     }
   const u32 *order = NULL;
   if (ordered)
-    { u32 *k1 = (u32 *) T_key1.need(sizeof(u32) * (size_t) nwork), *v1 = (u32 *) T_val1.need(sizeof(u32) * (size_t) nwork);
-      void *sw = T_sortw.need(damar_sort_workspace_bytes(nwork));
+    { u32 *k1 = (u32 *) TR.key1.need(sizeof(u32) * (size_t) nwork), *v1 = (u32 *) TR.val1.need(sizeof(u32) * (size_t) nwork);
+      void *sw = TR.sortw.need(damar_sort_workspace_bytes(nwork));
       order = damar_radix_sort_u32(d_key, d_val, k1, v1, nwork, 8, sw, G_st) ? v1 : d_val;
       sort_check(sw);
     }
   const size_t area = damar_trace_slot_area_cells();
-  t.vf = (short *) T_vf.need((size_t) nblocks * damar_trace_slot_vf_bytes(mode, kind));
-  t.hf = (signed char *) T_hf.need((size_t) nblocks * area);
+  t.vf = (short *) TR.vf.need((size_t) nblocks * damar_trace_slot_vf_bytes(mode, kind));
+  t.hf = (signed char *) TR.hf.need((size_t) nblocks * area);
   t.cap = rows;
   t.list = order;  t.nwork = nwork;
   t.next = d_ctr + 4;
@@ -4024,7 +4146,7 @@ static u32 trace_wave_phase(TraceArgs t, int mode, int kind, u32 nwork, u32 rows
   HIP_CHECK(hipStreamSynchronize(G_st));
   float wms = 0;
   HIP_CHECK(hipEventElapsedTime(&wms, e1, e2));
-  T_ms[0] += wms;
+  TR.ms[0] += wms;
   if (ctr[0] > 0 && !(ctr[2] & DAMAR_TRACE_ERR_POINTS))
     { /* segments the slot kernel does not take: one lane each on stripes that hold dmax + 3 rows */
       const u32 need = ctr[1];
@@ -4036,8 +4158,8 @@ static u32 trace_wave_phase(TraceArgs t, int mode, int kind, u32 nwork, u32 rows
         { fprintf(stderr, "damar: trace expansion: a segment needs %u wave cells, more than this build provides\n", need);
           return ~0u;
         }
-      t.vf = (short *) T_bvf.need(sizeof(short) * bthreads * need);
-      t.hf = (signed char *) T_bhf.need(bthreads * need);
+      t.vf = (short *) TR.bvf.need(sizeof(short) * bthreads * need);
+      t.hf = (signed char *) TR.bhf.need(bthreads * need);
       t.cap = need;
       t.list = t.over;  t.nwork = ctr[0];
       HIP_CHECK(hipMemsetAsync(d_ctr, 0, 8, G_st));
@@ -4048,8 +4170,8 @@ static u32 trace_wave_phase(TraceArgs t, int mode, int kind, u32 nwork, u32 rows
       HIP_CHECK(hipMemcpyAsync(c2, d_ctr, sizeof(c2), hipMemcpyDeviceToHost, G_st));
       HIP_CHECK(hipStreamSynchronize(G_st));
       HIP_CHECK(hipEventElapsedTime(&wms, e1, e2));
-      T_ms[0] += wms;
-      T_cnt[2] += ctr[0];
+      TR.ms[0] += wms;
+      TR.cnt[2] += ctr[0];
       if (c2[0] != 0)
         { fprintf(stderr, "damar: trace expansion: internal error, %u segments deferred twice\n", c2[0]);
           return ~0u;
@@ -4089,20 +4211,20 @@ static int trace_batch(const DevBlock *ad, const DevBlock *bd, int64 r0, int64 r
     }
   const double h0 = now_ms();
   const u32 nwork = nsegs + (kind ? nrecs : 0u);             /* segments of the script phase */
-  TraceRecIn *d_recs = (TraceRecIn *) T_recs.need(sizeof(TraceRecIn) * (size_t) nrecs);
-  void       *d_pts  = T_pts.need(pts.size() + 64);
-  TraceSeg   *d_segs = (TraceSeg *) T_segs.need(sizeof(TraceSeg) * (size_t) nsegs);
-  u32 *d_count  = (u32 *) T_count.need(sizeof(u32) * (size_t) nwork);
-  int *d_dist   = (int *) T_dist.need(sizeof(int) * (size_t) nwork);
-  u32 *d_segoff = (u32 *) T_segoff.need(sizeof(u32) * (size_t) nwork);
-  int *d_stage  = (int *) T_stage.need(sizeof(int) * (size_t) (nslots + 16));
-  u32 *d_over   = (u32 *) T_over.need(sizeof(u32) * (size_t) nwork);
-  u32 *d_ctr    = (u32 *) T_ctr.need(256);                    /* [0] deferred, [1] cells needed, [2] error flags; u64 total at +64 */
-  u32 *d_tlen   = (u32 *) T_tlen.need(sizeof(u32) * (size_t) (nrecs + 1));
-  int *d_diffs  = (int *) T_diffs.need(sizeof(int) * (size_t) nrecs);
-  void *d_scan  = T_scan.need(damar_scan_workspace_bytes(nrecs));
-  u32 *d_key    = (u32 *) T_key.need(sizeof(u32) * (size_t) nwork);
-  u32 *d_val    = (u32 *) T_val.need(sizeof(u32) * (size_t) nwork);
+  TraceRecIn *d_recs = (TraceRecIn *) TR.recs.need(sizeof(TraceRecIn) * (size_t) nrecs);
+  void       *d_pts  = TR.pts.need(pts.size() + 64);
+  TraceSeg   *d_segs = (TraceSeg *) TR.segs.need(sizeof(TraceSeg) * (size_t) nsegs);
+  u32 *d_count  = (u32 *) TR.count.need(sizeof(u32) * (size_t) nwork);
+  int *d_dist   = (int *) TR.dist.need(sizeof(int) * (size_t) nwork);
+  u32 *d_segoff = (u32 *) TR.segoff.need(sizeof(u32) * (size_t) nwork);
+  int *d_stage  = (int *) TR.stage.need(sizeof(int) * (size_t) (nslots + 16));
+  u32 *d_over   = (u32 *) TR.over.need(sizeof(u32) * (size_t) nwork);
+  u32 *d_ctr    = (u32 *) TR.ctr.need(256);                    /* [0] deferred, [1] cells needed, [2] error flags; u64 total at +64 */
+  u32 *d_tlen   = (u32 *) TR.tlen.need(sizeof(u32) * (size_t) (nrecs + 1));
+  int *d_diffs  = (int *) TR.diffs.need(sizeof(int) * (size_t) nrecs);
+  void *d_scan  = TR.scan.need(damar_scan_workspace_bytes(nrecs));
+  u32 *d_key    = (u32 *) TR.key.need(sizeof(u32) * (size_t) nwork);
+  u32 *d_val    = (u32 *) TR.val.need(sizeof(u32) * (size_t) nwork);
 
   struct Events            /* destroyed on every return path */
   { hipEvent_t e[4];
@@ -4124,10 +4246,10 @@ static int trace_batch(const DevBlock *ad, const DevBlock *bd, int64 r0, int64 r
   t.stage = d_stage;  t.count = d_count;  t.dist = d_dist;
   t.over = d_over;  t.over_cap = nwork;  t.nover = d_ctr;  t.need = d_ctr + 1;  t.err = d_ctr + 2;
   if (kind)
-    { t.mid = (int *) T_mid.need(sizeof(int) * 2 * (size_t) nsegs);
+    { t.mid = (int *) TR.mid.need(sizeof(int) * 2 * (size_t) nsegs);
       if (trace_wave_phase(t, mode, 1, nsegs, rows, maxblocks, d_ctr, d_key, d_val, e1, e2) == ~0u)
         return 1;
-      TraceSeg *d_segs2 = (TraceSeg *) T_segs2.need(sizeof(TraceSeg) * (size_t) nwork);
+      TraceSeg *d_segs2 = (TraceSeg *) TR.segs2.need(sizeof(TraceSeg) * (size_t) nwork);
       damar_launch_trace_mid_layout(d_recs, nrecs, d_segs, t.mid, ad, bd, d_segs2, d_key, d_val, d_ctr + 2, G_st);
       t.segs = d_segs = d_segs2;
     }
@@ -4143,7 +4265,7 @@ static int trace_batch(const DevBlock *ad, const DevBlock *bd, int64 r0, int64 r
     { fprintf(stderr, "damar: trace expansion: batch script exceeds 32-bit offsets\n");
       return 1;
     }
-  int *d_script = (int *) T_script.need(sizeof(int) * (size_t) (total + 16));
+  int *d_script = (int *) TR.script.need(sizeof(int) * (size_t) (total + 16));
   damar_launch_trace_pack(d_segs, nwork, d_count, d_segoff, d_tlen, d_stage, d_script, G_st);
   HIP_CHECK(hipEventRecord(e3, G_st));
   std::vector<u32> hoff(nrecs);
@@ -4163,12 +4285,12 @@ static int trace_batch(const DevBlock *ad, const DevBlock *bd, int64 r0, int64 r
   HIP_CHECK(hipStreamSynchronize(G_st));
   float dms = 0;
   HIP_CHECK(hipEventElapsedTime(&dms, e0, e3));
-  T_ms[1] += dms;
+  TR.ms[1] += dms;
   for (u32 i = 0; i < nrecs; i++)
     soff[r0 + i] = (int64) base + hoff[i];
   soff[r1] = (int64) base + (int64) total;
-  T_ms[3] += now_ms() - h0;
-  T_cnt[0] += nrecs;  T_cnt[1] += nwork;  T_cnt[3] += (int64) total;
+  TR.ms[3] += now_ms() - h0;
+  TR.cnt[0] += nrecs;  TR.cnt[1] += nwork;  TR.cnt[3] += (int64) total;
   return 0;
 }
 
@@ -4181,7 +4303,7 @@ static int trace_expand(damar_dev_block *ablk, int afirst, damar_dev_block *bblk
                         int64 *soff, int *diffs, int **script_out)
 { ensure_init();
   const double t0 = now_ms();
-  for (int i = 0; i < 4; i++) { T_ms[i] = 0;  T_cnt[i] = 0; }
+  for (int i = 0; i < 4; i++) { TR.ms[i] = 0;  TR.cnt[i] = 0; }
   int  *script = NULL;
   int64 nscript = 0;
   *script_out = NULL;
@@ -4249,7 +4371,7 @@ static int trace_expand(damar_dev_block *ablk, int afirst, damar_dev_block *bblk
   if (script == NULL)
     script = (int *) malloc(sizeof(int));
   *script_out = script;
-  T_ms[2] = now_ms() - t0;
+  TR.ms[2] = now_ms() - t0;
   return 0;
 }
 
@@ -4321,31 +4443,20 @@ extern "C" int Compute_Trace_MID(Alignment *align, Work_Data *work, int trace_sp
 
 /***** mask tracks from piles of overlaps: scrub/LArepeat.c and scrub/TANmask.c (kernels/pile_sweep.hip) **********/
 
-static DBuf P_off, P_aread, P_col[6], P_rlen, P_rflags, P_k0, P_k1, P_kept, P_koff, P_scan, P_sortw, P_bases, P_active,
-            P_rb, P_re, P_rc, P_out, P_count, P_doff, P_dst, P_misc;
-static double P_ms[4];        /* of the last call: upload, sort, sweep, download */
-static int64  P_cnt[2];       /* events sorted, regions (TANDEM: intervals) written */
-static hipEvent_t P_ev[5];    /* made once, kept like the buffers */
-static int    P_ev_made;
-static std::vector<u64> P_hsum;       /* COVER's per-pile results on the host: grown, kept */
-static std::vector<int> P_hact;
+static struct : PileStage       /* ms of the last call: upload, sort, sweep, download; cnt: events sorted, regions (TANDEM: intervals) written */
+{ DBuf rlen{*this}, rflags{*this}, k0{*this}, k1{*this}, kept{*this}, koff{*this}, scan{*this}, sortw{*this}, bases{*this}, active{*this},
+       rb{*this}, re{*this}, rc{*this}, out{*this}, count{*this}, doff{*this}, dst{*this}, misc{*this};
+  std::vector<u64> hsum;         /* COVER's per-pile results on the host: grown, kept */
+  std::vector<int> hact;
+} PL;
 
 extern "C" void damar_pile_release(void)
-{ DBuf *all[] = { &P_off, &P_aread, &P_col[0], &P_col[1], &P_col[2], &P_col[3], &P_col[4], &P_col[5], &P_rlen, &P_rflags, &P_k0,
-                  &P_k1, &P_kept, &P_koff, &P_scan, &P_sortw, &P_bases, &P_active, &P_rb, &P_re, &P_rc, &P_out, &P_count,
-                  &P_doff, &P_dst, &P_misc };
-  for (DBuf *b : all) b->drop();
-  if (P_ev_made)
-    for (int i = 0; i < 5; i++) (void) hipEventDestroy(P_ev[i]);
-  P_ev_made = 0;
-  std::vector<u64>().swap(P_hsum);
-  std::vector<int>().swap(P_hact);
+{ PL.release();
+  std::vector<u64>().swap(PL.hsum);
+  std::vector<int>().swap(PL.hact);
 }
 
-extern "C" void damar_pile_last(double *ms, int64 *cnt)
-{ for (int i = 0; i < 4; i++) ms[i] = P_ms[i];
-  cnt[0] = P_cnt[0];  cnt[1] = P_cnt[1];
-}
+extern "C" void damar_pile_last(double *ms, int64 *cnt) { PL.last(ms, cnt, 2); }
 
 static int bits_for(u64 v)      /* bits that hold the value v */
 { int b = 1;
@@ -4384,12 +4495,6 @@ static int pile_device(int mode, const damar_pile_batch *b, const damar_repeat_p
     }
   const int hibit = pbits + 1 + bits_for(np);
 
-  if (!P_ev_made)
-    { for (int i = 0; i < 5; i++) HIP_CHECK(hipEventCreate(&P_ev[i]));
-      P_ev_made = 1;
-    }
-  struct { hipEvent_t *e; } ev = { P_ev };
-
   PileArgs a;
   memset(&a, 0, sizeof(a));
   a.npiles = np;  a.mode = mode;  a.pbits = pbits;
@@ -4399,39 +4504,28 @@ static int pile_device(int mode, const damar_pile_batch *b, const damar_repeat_p
       a.enter = (int) (p->cov * p->xcov_enter);  a.leave = (int) (p->cov * p->xcov_leave);     /* LArepeat.c:328-329 */
       a.merge_dist = p->merge_dist;
     }
-  long long *d_off = (long long *) P_off.need(sizeof(long long) * ((size_t) np + 1));
-  int *d_aread = (int *) P_aread.need(sizeof(int) * (size_t) np);
-  const int *src[6] = { b->abpos, b->aepos, b->bbpos, b->bepos, b->bread, b->flags };
-  int *d_col[6];
-  for (int i = 0; i < 6; i++) d_col[i] = (int *) P_col[i].need(sizeof(int) * (size_t) nrec + 16);
-  int *d_rlen = (int *) P_rlen.need(sizeof(int) * (size_t) b->nreads);
-  int *d_rflags = (int *) P_rflags.need(sizeof(int) * (size_t) b->nreads);
-  u64 *k0 = (u64 *) P_k0.need(sizeof(u64) * (size_t) nkeys + 64), *k1 = (u64 *) P_k1.need(sizeof(u64) * (size_t) nkeys + 64);
-  u32 *d_kept = (u32 *) P_kept.need(sizeof(u32) * (size_t) np), *d_koff = (u32 *) P_koff.need(sizeof(u32) * (size_t) np);
-  u32 *d_count = (u32 *) P_count.need(sizeof(u32) * (size_t) np), *d_doff = (u32 *) P_doff.need(sizeof(u32) * (size_t) np);
-  void *d_scan = P_scan.need(damar_scan_workspace_bytes(np));
-  void *d_sortw = P_sortw.need(damar_sort_workspace_bytes(nkeys));
-  u64 *d_misc = (u64 *) P_misc.need(256);          /* [0] total kept, [1] total data, [2..3] stats, [4] error word */
+  u64 *k0 = (u64 *) PL.k0.need(sizeof(u64) * (size_t) nkeys + 64), *k1 = (u64 *) PL.k1.need(sizeof(u64) * (size_t) nkeys + 64);
+  u32 *d_kept = (u32 *) PL.kept.need(sizeof(u32) * (size_t) np), *d_koff = (u32 *) PL.koff.need(sizeof(u32) * (size_t) np);
+  u32 *d_count = (u32 *) PL.count.need(sizeof(u32) * (size_t) np), *d_doff = (u32 *) PL.doff.need(sizeof(u32) * (size_t) np);
+  void *d_scan = PL.scan.need(damar_scan_workspace_bytes(np));
+  void *d_sortw = PL.sortw.need(damar_sort_workspace_bytes(nkeys));
+  u64 *d_misc = (u64 *) PL.misc.need(256);          /* [0] total kept, [1] total data, [2..3] stats, [4] error word */
 
-  HIP_CHECK(hipEventRecord(ev.e[0], G_st));
-  HIP_CHECK(hipMemcpyAsync(d_off, b->pile_off, sizeof(long long) * ((size_t) np + 1), hipMemcpyHostToDevice, G_st));
-  HIP_CHECK(hipMemcpyAsync(d_aread, b->pile_aread, sizeof(int) * (size_t) np, hipMemcpyHostToDevice, G_st));
-  for (int i = 0; i < 6; i++)
-    HIP_CHECK(hipMemcpyAsync(d_col[i], src[i], sizeof(int) * (size_t) nrec, hipMemcpyHostToDevice, G_st));
-  HIP_CHECK(hipMemcpyAsync(d_rlen, b->read_len, sizeof(int) * (size_t) b->nreads, hipMemcpyHostToDevice, G_st));
-  HIP_CHECK(hipMemcpyAsync(d_rflags, b->read_flags, sizeof(int) * (size_t) b->nreads, hipMemcpyHostToDevice, G_st));
+  PL.mark(0);
+  const PileDev d = pile_up(PL, b, NULL, { b->abpos, b->aepos, b->bbpos, b->bepos, b->bread, b->flags });
+  a.read_len = up(PL.rlen, b->read_len, (size_t) b->nreads);
+  a.read_flags = up(PL.rflags, b->read_flags, (size_t) b->nreads);
   HIP_CHECK(hipMemsetAsync(d_misc, 0, 256, G_st));
-  HIP_CHECK(hipEventRecord(ev.e[1], G_st));
+  PL.mark(1);
 
-  a.pile_off = d_off;  a.pile_aread = d_aread;
-  a.abpos = d_col[0];  a.aepos = d_col[1];  a.bbpos = d_col[2];  a.bepos = d_col[3];  a.bread = d_col[4];  a.flags = d_col[5];
-  a.read_len = d_rlen;  a.read_flags = d_rflags;
+  a.pile_off = d.off;  a.pile_aread = d.aread;
+  a.abpos = d.col[0];  a.aepos = d.col[1];  a.bbpos = d.col[2];  a.bepos = d.col[3];  a.bread = d.col[4];  a.flags = d.col[5];
   a.keys = k0;  a.kept = d_kept;  a.koff = d_koff;
   a.stats = d_misc + 2;  a.err = (u32 *) (d_misc + 4);
   a.count = d_count;
   if (mode == DAMAR_PILE_COVER)
-    { a.bases = (u64 *) P_bases.need(sizeof(u64) * (size_t) np);
-      a.active = (int *) P_active.need(sizeof(int) * (size_t) np);
+    { a.bases = (u64 *) PL.bases.need(sizeof(u64) * (size_t) np);
+      a.active = (int *) PL.active.need(sizeof(int) * (size_t) np);
     }
   damar_launch_pile_events(&a, G_st);
   damar_exclusive_scan_u32(d_kept, d_koff, np, d_scan, d_misc, G_st);
@@ -4441,7 +4535,7 @@ static int pile_device(int mode, const damar_pile_batch *b, const damar_repeat_p
   u32 h_serr = 0;
   HIP_CHECK(hipMemcpyAsync(h_misc, d_misc, sizeof(h_misc), hipMemcpyDeviceToHost, G_st));
   HIP_CHECK(hipMemcpyAsync(&h_serr, damar_sort_error_word(d_sortw), sizeof(u32), hipMemcpyDeviceToHost, G_st));
-  HIP_CHECK(hipEventRecord(ev.e[2], G_st));
+  PL.mark(2);
   HIP_CHECK(hipStreamSynchronize(G_st));
   if (h_serr != 0)
     { fprintf(stderr, "damar: piles: the radix sort's look-back timed out\n");
@@ -4452,29 +4546,29 @@ static int pile_device(int mode, const damar_pile_batch *b, const damar_repeat_p
       return 1;
     }
   const u64 nkept = h_misc[0];
-  P_cnt[0] = (int64) (2 * nkept);
+  PL.cnt[0] = (int64) (2 * nkept);
   if (mode == DAMAR_PILE_REPEAT)
-    { a.rb = (int *) P_rb.need(sizeof(int) * (size_t) nkept + 16);
-      a.re = (int *) P_re.need(sizeof(int) * (size_t) nkept + 16);
-      a.rc = (int *) P_rc.need(sizeof(int) * (size_t) nkept + 16);
+    { a.rb = (int *) PL.rb.need(sizeof(int) * (size_t) nkept + 16);
+      a.re = (int *) PL.re.need(sizeof(int) * (size_t) nkept + 16);
+      a.rc = (int *) PL.rc.need(sizeof(int) * (size_t) nkept + 16);
     }
   if (mode != DAMAR_PILE_COVER)
-    a.out = (int *) P_out.need(sizeof(int) * 3 * (size_t) nkept + 16);
+    a.out = (int *) PL.out.need(sizeof(int) * 3 * (size_t) nkept + 16);
   damar_launch_pile_sweep(&a, G_st);
   if (mode == DAMAR_PILE_COVER)
-    { HIP_CHECK(hipEventRecord(ev.e[3], G_st));
+    { PL.mark(3);
       HIP_CHECK(hipMemcpyAsync(bases_out, a.bases, sizeof(u64) * (size_t) np, hipMemcpyDeviceToHost, G_st));
       HIP_CHECK(hipMemcpyAsync(active_out, a.active, sizeof(int) * (size_t) np, hipMemcpyDeviceToHost, G_st));
-      P_cnt[1] = 0;
+      PL.cnt[1] = 0;
     }
   else
     { damar_exclusive_scan_u32(d_count, d_doff, np, d_scan, d_misc + 1, G_st);
       HIP_CHECK(hipMemcpyAsync(h_misc, d_misc, sizeof(h_misc), hipMemcpyDeviceToHost, G_st));
       HIP_CHECK(hipStreamSynchronize(G_st));
       const u64 ndata = h_misc[1];
-      int *d_dst = (int *) P_dst.need(sizeof(int) * (size_t) ndata + 16);
+      int *d_dst = (int *) PL.dst.need(sizeof(int) * (size_t) ndata + 16);
       damar_launch_pile_gather(a.out, d_koff, d_count, d_doff, np, d_dst, G_st);
-      HIP_CHECK(hipEventRecord(ev.e[3], G_st));
+      PL.mark(3);
       out->data = (int *) malloc(sizeof(int) * (size_t) ndata + 8);
       if (out->data == NULL)
         { fprintf(stderr, "damar: out of memory (piles)\n");
@@ -4487,20 +4581,16 @@ static int pile_device(int mode, const damar_pile_batch *b, const damar_repeat_p
         HIP_CHECK(hipMemcpyAsync(out->data, d_dst, sizeof(int) * (size_t) ndata, hipMemcpyDeviceToHost, G_st));
       HIP_CHECK(hipMemcpyAsync(out->count, d_count, sizeof(int) * (size_t) np, hipMemcpyDeviceToHost, G_st));
     }
-  HIP_CHECK(hipEventRecord(ev.e[4], G_st));
+  PL.mark(4);
   HIP_CHECK(hipStreamSynchronize(G_st));
   if (mode != DAMAR_PILE_COVER)
     { const int width = (mode == DAMAR_PILE_REPEAT && a.inccov) ? 3 : 2;       /* a region left open holds its begin alone */
       int64 regions = 0;
       for (u32 i = 0; i < np; i++)
         regions += (out->count[i] + width - 1) / width;
-      P_cnt[1] = regions;
+      PL.cnt[1] = regions;
     }
-  for (int i = 0; i < 4; i++)
-    { float ms = 0;
-      HIP_CHECK(hipEventElapsedTime(&ms, ev.e[i], ev.e[i + 1]));
-      P_ms[i] = ms;
-    }
+  PL.laps(0, 4);
   return 0;
 }
 
@@ -4518,8 +4608,8 @@ extern "C" int damar_pile_coverage(const damar_pile_batch *b, const damar_repeat
     return damar_host_pile_coverage(b, p, histo, bases, inactive);
   if (b->npiles == 0)
     return 0;
-  std::vector<u64> &sum = P_hsum;
-  std::vector<int> &act = P_hact;
+  std::vector<u64> &sum = PL.hsum;
+  std::vector<int> &act = PL.hact;
   sum.assign((size_t) b->npiles, 0);
   act.assign((size_t) b->npiles, 0);
   if (b->nrec > 0)
@@ -4575,29 +4665,19 @@ extern "C" int damar_pile_tandem(const damar_pile_batch *b, int min_len, damar_p
 
 /***** LAq's per-tile quality from the traces of piles: scrub/LAq.c handler_annotate (kernels/pile_quality.hip) **********/
 
-static DBuf LQ_off, LQ_aread, LQ_alen, LQ_tile0, LQ_col[4], LQ_toff, LQ_trace, LQ_depth, LQ_run, LQ_vals, LQ_q, LQ_scan, LQ_misc;
-static double LQ_ms[4];        /* of the last device call: upload, count + scan, scatter + select, download */
-static int64  LQ_cnt[2];       /* segments counted, tiles */
-static hipEvent_t LQ_ev[5];
-static int    LQ_ev_made;
-static std::vector<int> LQ_halen;       /* per pile: the read's length and where its tiles begin (host arithmetic, kept) */
-static std::vector<u32> LQ_htile0;
+static struct : PileStage       /* ms of the last device call: upload, count + scan, scatter + select, download; cnt: segments counted, tiles */
+{ DBuf alen{*this}, tile0{*this}, depth{*this}, run{*this}, vals{*this}, q{*this}, scan{*this}, misc{*this};
+  std::vector<int> halen;        /* per pile: the read's length and where its tiles begin (host arithmetic, kept) */
+  std::vector<u32> htile0;
+} LQ;
 
 extern "C" void damar_q_release(void)
-{ DBuf *all[] = { &LQ_off, &LQ_aread, &LQ_alen, &LQ_tile0, &LQ_col[0], &LQ_col[1], &LQ_col[2], &LQ_col[3], &LQ_toff, &LQ_trace, &LQ_depth,
-                  &LQ_run, &LQ_vals, &LQ_q, &LQ_scan, &LQ_misc };
-  for (DBuf *b : all) b->drop();
-  if (LQ_ev_made)
-    for (int i = 0; i < 5; i++) (void) hipEventDestroy(LQ_ev[i]);
-  LQ_ev_made = 0;
-  std::vector<int>().swap(LQ_halen);
-  std::vector<u32>().swap(LQ_htile0);
+{ LQ.release();
+  std::vector<int>().swap(LQ.halen);
+  std::vector<u32>().swap(LQ.htile0);
 }
 
-extern "C" void damar_q_last(double *ms, int64 *cnt)
-{ for (int i = 0; i < 4; i++) ms[i] = LQ_ms[i];
-  cnt[0] = LQ_cnt[0];  cnt[1] = LQ_cnt[1];
-}
+extern "C" void damar_q_last(double *ms, int64 *cnt) { LQ.last(ms, cnt, 2); }
 
 extern "C" int damar_pile_quality(const damar_trace_batch *t, const damar_q_params *p, int *q_out, int64 *ntiles_out)
 { int64 ntiles = 0;
@@ -4619,16 +4699,12 @@ extern "C" int damar_pile_quality(const damar_trace_batch *t, const damar_q_para
   const size_t nrec = (size_t) b->nrec;
   u64 segs = 0;                                    /* what the runs hold at most: every segment of every trace */
   for (size_t i = 0; i < nrec; i++) segs += (u64) (t->tlen[i] / 2);
-  LQ_halen.resize(np);
-  LQ_htile0.resize((size_t) np + 1);
-  LQ_htile0[0] = 0;
+  LQ.halen.resize(np);
+  LQ.htile0.resize((size_t) np + 1);
+  LQ.htile0[0] = 0;
   for (u32 i = 0; i < np; i++)
-    { LQ_halen[i] = b->read_len[b->pile_aread[i]];
-      LQ_htile0[i + 1] = LQ_htile0[i] + (u32) ((LQ_halen[i] + t->tspace - 1) / t->tspace);
-    }
-  if (!LQ_ev_made)
-    { for (int i = 0; i < 5; i++) HIP_CHECK(hipEventCreate(&LQ_ev[i]));
-      LQ_ev_made = 1;
+    { LQ.halen[i] = b->read_len[b->pile_aread[i]];
+      LQ.htile0[i + 1] = LQ.htile0[i] + (u32) ((LQ.halen[i] + t->tspace - 1) / t->tspace);
     }
 
   QArgs a;
@@ -4636,58 +4712,37 @@ extern "C" int damar_pile_quality(const damar_trace_batch *t, const damar_q_para
   a.npiles = np;  a.nrec = (u32) nrec;  a.ntiles = nt;
   a.tspace = t->tspace;  a.tbytes = t->tbytes;
   a.segmin = (u32) p->segmin;  a.segmax = (u32) p->segmax;  a.ccs = p->ccs ? 1 : 0;
-  long long *d_off = (long long *) LQ_off.need(sizeof(long long) * ((size_t) np + 1));
-  int *d_aread = (int *) LQ_aread.need(sizeof(int) * (size_t) np + 16);
-  int *d_alen = (int *) LQ_alen.need(sizeof(int) * (size_t) np + 16);
-  u32 *d_tile0 = (u32 *) LQ_tile0.need(sizeof(u32) * ((size_t) np + 1));
-  const int *src[4] = { b->abpos, b->aepos, b->bread, t->tlen };
-  int *d_col[4];
-  for (int i = 0; i < 4; i++) d_col[i] = (int *) LQ_col[i].need(sizeof(int) * nrec + 16);
-  long long *d_toff = (long long *) LQ_toff.need(sizeof(long long) * nrec + 16);
-  u8  *d_trace = (u8 *) LQ_trace.need((size_t) t->trace_bytes + 16);
-  u32 *d_depth = (u32 *) LQ_depth.need(sizeof(u32) * ((size_t) nt + 1));
-  u32 *d_run = (u32 *) LQ_run.need(sizeof(u32) * ((size_t) nt + 1));
-  u16 *d_vals = (u16 *) LQ_vals.need(sizeof(u16) * (size_t) segs + 16);
-  int *d_q = (int *) LQ_q.need(sizeof(int) * (size_t) nt);
-  void *d_scan = LQ_scan.need(damar_scan_workspace_bytes((u64) nt + 1));
-  u64 *d_misc = (u64 *) LQ_misc.need(64);
+  u32 *d_depth = (u32 *) LQ.depth.need(sizeof(u32) * ((size_t) nt + 1));
+  u32 *d_run = (u32 *) LQ.run.need(sizeof(u32) * ((size_t) nt + 1));
+  u16 *d_vals = (u16 *) LQ.vals.need(sizeof(u16) * (size_t) segs + 16);
+  int *d_q = (int *) LQ.q.need(sizeof(int) * (size_t) nt);
+  void *d_scan = LQ.scan.need(damar_scan_workspace_bytes((u64) nt + 1));
+  u64 *d_misc = (u64 *) LQ.misc.need(64);
 
-  HIP_CHECK(hipEventRecord(LQ_ev[0], G_st));
-  HIP_CHECK(hipMemcpyAsync(d_off, b->pile_off, sizeof(long long) * ((size_t) np + 1), hipMemcpyHostToDevice, G_st));
-  HIP_CHECK(hipMemcpyAsync(d_aread, b->pile_aread, sizeof(int) * (size_t) np, hipMemcpyHostToDevice, G_st));
-  HIP_CHECK(hipMemcpyAsync(d_alen, LQ_halen.data(), sizeof(int) * (size_t) np, hipMemcpyHostToDevice, G_st));
-  HIP_CHECK(hipMemcpyAsync(d_tile0, LQ_htile0.data(), sizeof(u32) * ((size_t) np + 1), hipMemcpyHostToDevice, G_st));
-  if (nrec > 0)
-    { for (int i = 0; i < 4; i++)
-        HIP_CHECK(hipMemcpyAsync(d_col[i], src[i], sizeof(int) * nrec, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_toff, t->trace_off, sizeof(long long) * nrec, hipMemcpyHostToDevice, G_st));
-    }
-  if (t->trace_bytes > 0)
-    HIP_CHECK(hipMemcpyAsync(d_trace, t->trace, (size_t) t->trace_bytes, hipMemcpyHostToDevice, G_st));
+  LQ.mark(0);
+  a.pile_alen = up(LQ.alen, LQ.halen.data(), (size_t) np);
+  a.pile_tile0 = up(LQ.tile0, LQ.htile0.data(), (size_t) np + 1);
+  const PileDev d = pile_up(LQ, b, t, { b->abpos, b->aepos, b->bread, t->tlen });
   HIP_CHECK(hipMemsetAsync(d_depth, 0, sizeof(u32) * ((size_t) nt + 1), G_st));
-  HIP_CHECK(hipEventRecord(LQ_ev[1], G_st));
+  LQ.mark(1);
 
-  a.pile_off = d_off;  a.pile_aread = d_aread;  a.pile_alen = d_alen;  a.pile_tile0 = d_tile0;
-  a.abpos = d_col[0];  a.aepos = d_col[1];  a.bread = d_col[2];  a.tlen = d_col[3];
-  a.trace_off = d_toff;  a.trace = d_trace;
+  a.pile_off = d.off;  a.pile_aread = d.aread;
+  a.abpos = d.col[0];  a.aepos = d.col[1];  a.bread = d.col[2];  a.tlen = d.col[3];
+  a.trace_off = d.toff;  a.trace = d.trace;
   a.depth = d_depth;  a.off = d_run;  a.vals = d_vals;  a.q = d_q;
   damar_launch_q_count(&a, G_st);
   damar_exclusive_scan_u32(d_depth, d_run, (u64) nt + 1, d_scan, d_misc, G_st);       /* d_run[nt] = d_misc[0] = segments counted */
-  HIP_CHECK(hipEventRecord(LQ_ev[2], G_st));
+  LQ.mark(2);
   damar_launch_q_scatter(&a, G_st);
   damar_launch_q_select(&a, G_st);
-  HIP_CHECK(hipEventRecord(LQ_ev[3], G_st));
+  LQ.mark(3);
   u64 h_total = 0;
   HIP_CHECK(hipMemcpyAsync(q_out, d_q, sizeof(int) * (size_t) nt, hipMemcpyDeviceToHost, G_st));
   HIP_CHECK(hipMemcpyAsync(&h_total, d_misc, sizeof(u64), hipMemcpyDeviceToHost, G_st));
-  HIP_CHECK(hipEventRecord(LQ_ev[4], G_st));
+  LQ.mark(4);
   HIP_CHECK(hipStreamSynchronize(G_st));
-  LQ_cnt[0] = (int64) h_total;  LQ_cnt[1] = ntiles;
-  for (int i = 0; i < 4; i++)
-    { float ms = 0;
-      HIP_CHECK(hipEventElapsedTime(&ms, LQ_ev[i], LQ_ev[i + 1]));
-      LQ_ms[i] = ms;
-    }
+  LQ.cnt[0] = (int64) h_total;  LQ.cnt[1] = ntiles;
+  LQ.laps(0, 4);
   return 0;
 }
 
@@ -4701,16 +4756,14 @@ struct damar_homog
   u64  *d_woff, *d_cnt;          /* [nreads + 1] word offsets; [0] ranges set */
   int  *d_rlen;
   u64   nwords;
-  DBuf  off, aread, col[7], toff, trace, ianno, idata, trim, count, doff, scan, out;
-  hipEvent_t ev[3];
+  struct : PileStage             /* the handle's buffers; the events and the figures are HM's */
+  { DBuf ianno{*this}, idata{*this}, trim{*this}, count{*this}, doff{*this}, scan{*this}, out{*this};
+  } S;
 };
-static double HM_ms[4];          /* of the last session so far: upload, mark, read-out, download */
-static int64  HM_cnt[3];         /* records seen by add, ranges set, intervals read out */
+static DevStage HM;              /* the figures outlive the handle.  ms of the last session so far: upload, mark, read-out, download;
+                                    cnt: records seen by add, ranges set, intervals read out */
 
-extern "C" void damar_homog_last(double *ms, int64 *cnt)
-{ for (int i = 0; i < 4; i++) ms[i] = HM_ms[i];
-  for (int i = 0; i < 3; i++) cnt[i] = HM_cnt[i];
-}
+extern "C" void damar_homog_last(double *ms, int64 *cnt) { HM.last(ms, cnt, 3); }
 
 extern "C" void damar_homog_close(damar_homog *h)
 { if (h == NULL)
@@ -4718,14 +4771,11 @@ extern "C" void damar_homog_close(damar_homog *h)
   if (h->hs != NULL)
     damar_host_homog_close(h->hs);
   else
-    { DBuf *all[] = { &h->off, &h->aread, &h->col[0], &h->col[1], &h->col[2], &h->col[3], &h->col[4], &h->col[5], &h->col[6], &h->toff,
-                      &h->trace, &h->ianno, &h->idata, &h->trim, &h->count, &h->doff, &h->scan, &h->out };
-      for (DBuf *b : all) b->drop();
+    { h->S.release();
+      HM.release();
       void *own[] = { h->d_words, h->d_woff, h->d_cnt, h->d_rlen };
       for (void *p : own)
         if (p != NULL) HIP_CHECK(hipFree(p));
-      for (int i = 0; i < 3; i++)
-        if (h->ev[i] != NULL) (void) hipEventDestroy(h->ev[i]);
     }
   delete h;
 }
@@ -4743,9 +4793,8 @@ extern "C" damar_homog *damar_homog_open(const int *read_len, int nreads, int re
   damar_homog *h = new damar_homog();
   h->nreads = nreads;  h->res = res;  h->hs = NULL;
   h->d_words = NULL;  h->d_woff = NULL;  h->d_cnt = NULL;  h->d_rlen = NULL;
-  for (int i = 0; i < 3; i++) h->ev[i] = NULL;
-  for (int i = 0; i < 4; i++) HM_ms[i] = 0;
-  for (int i = 0; i < 3; i++) HM_cnt[i] = 0;
+  for (int i = 0; i < 4; i++) HM.ms[i] = 0;
+  for (int i = 0; i < 3; i++) HM.cnt[i] = 0;
   h->rlen.assign(read_len, read_len + nreads);
   if (damar_piles_on_host())
     { if ((h->hs = damar_host_homog_open(read_len, nreads, res)) == NULL)
@@ -4775,30 +4824,23 @@ extern "C" damar_homog *damar_homog_open(const int *read_len, int nreads, int re
   HIP_CHECK(hipMalloc((void **) &h->d_woff, sizeof(u64) * ((size_t) nreads + 1)));
   HIP_CHECK(hipMalloc((void **) &h->d_rlen, sizeof(int) * (size_t) nreads));
   HIP_CHECK(hipMalloc((void **) &h->d_cnt, 64));
-  for (int i = 0; i < 3; i++) HIP_CHECK(hipEventCreate(&h->ev[i]));
-  HIP_CHECK(hipEventRecord(h->ev[0], G_st));
+  HM.mark(0);
   HIP_CHECK(hipMemsetAsync(h->d_words, 0, sizeof(u32) * (size_t) h->nwords + 64, G_st));
   HIP_CHECK(hipMemsetAsync(h->d_cnt, 0, 64, G_st));
   HIP_CHECK(hipMemcpyAsync(h->d_woff, woff.data(), sizeof(u64) * ((size_t) nreads + 1), hipMemcpyHostToDevice, G_st));
   HIP_CHECK(hipMemcpyAsync(h->d_rlen, read_len, sizeof(int) * (size_t) nreads, hipMemcpyHostToDevice, G_st));
-  HIP_CHECK(hipEventRecord(h->ev[1], G_st));
+  HM.mark(1);
   HIP_CHECK(hipStreamSynchronize(G_st));
-  float ms = 0;
-  HIP_CHECK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-  HM_ms[0] += ms;
+  HM.laps_add(0, 1);
   return h;
 }
 
 /* the interval track goes up with every call: a few ints per read, next to a batch's trace bytes it does not count */
 static void homog_track_up(damar_homog *h, HomArgs *a, const uint64 *anno, const int *data, int64 ndata)
-{ u64 *d_anno = (u64 *) h->ianno.need(sizeof(u64) * ((size_t) h->nreads + 1));
-  int *d_data = (int *) h->idata.need(sizeof(int) * (size_t) ndata + 16);
-  HIP_CHECK(hipMemcpyAsync(d_anno, anno, sizeof(u64) * ((size_t) h->nreads + 1), hipMemcpyHostToDevice, G_st));
-  if (ndata > 0)
-    HIP_CHECK(hipMemcpyAsync(d_data, data, sizeof(int) * (size_t) ndata, hipMemcpyHostToDevice, G_st));
+{ const DevTrack iv = up_track(h->S.ianno, h->S.idata, anno, (size_t) h->nreads, data, ndata);
   memset(a, 0, sizeof(*a));
   a->nreads = (u32) h->nreads;  a->res = h->res;  a->ends = -1;
-  a->iv_anno = d_anno;  a->iv_data = d_data;
+  a->iv_anno = iv.anno;  a->iv_data = iv.data;
   a->read_len = h->d_rlen;  a->woff = h->d_woff;  a->words = h->d_words;  a->nranges = h->d_cnt;
 }
 
@@ -4806,12 +4848,8 @@ static void homog_marked(damar_homog *h)           /* after the kernel: its time
 { u64 ranges = 0;
   HIP_CHECK(hipMemcpyAsync(&ranges, h->d_cnt, sizeof(u64), hipMemcpyDeviceToHost, G_st));
   HIP_CHECK(hipStreamSynchronize(G_st));
-  HM_cnt[1] = (int64) ranges;
-  for (int i = 0; i < 2; i++)
-    { float ms = 0;
-      HIP_CHECK(hipEventElapsedTime(&ms, h->ev[i], h->ev[i + 1]));
-      HM_ms[i] += ms;
-    }
+  HM.cnt[1] = (int64) ranges;
+  HM.laps_add(0, 2);
 }
 
 extern "C" int damar_homog_seed(damar_homog *h, const uint64 *anno, const int *data, int64 ndata)
@@ -4822,15 +4860,15 @@ extern "C" int damar_homog_seed(damar_homog *h, const uint64 *anno, const int *d
   if (h->hs != NULL)
     { if (damar_host_homog_seed(h->hs, anno, data))
         return 1;
-      damar_host_homog_counts(h->hs, HM_cnt);
+      damar_host_homog_counts(h->hs, HM.cnt);
       return 0;
     }
   HomArgs a;
-  HIP_CHECK(hipEventRecord(h->ev[0], G_st));
+  HM.mark(0);
   homog_track_up(h, &a, anno, data, ndata);
-  HIP_CHECK(hipEventRecord(h->ev[1], G_st));
+  HM.mark(1);
   damar_launch_hom_seed(&a, G_st);
-  HIP_CHECK(hipEventRecord(h->ev[2], G_st));
+  HM.mark(2);
   homog_marked(h);
   return 0;
 }
@@ -4844,44 +4882,26 @@ extern "C" int damar_homog_add(damar_homog *h, const damar_trace_batch *t, const
   if (h->hs != NULL)
     { if (damar_host_homog_add(h->hs, t, anno, data, ends, trim))
         return 1;
-      damar_host_homog_counts(h->hs, HM_cnt);
+      damar_host_homog_counts(h->hs, HM.cnt);
       return 0;
     }
   const damar_pile_batch *b = &t->p;
-  HM_cnt[0] += b->nrec;
+  HM.cnt[0] += b->nrec;
   if (b->nrec == 0)
     return 0;
-  const u32 np = (u32) b->npiles;
-  const size_t nrec = (size_t) b->nrec;
   HomArgs a;
-  HIP_CHECK(hipEventRecord(h->ev[0], G_st));
+  HM.mark(0);
   homog_track_up(h, &a, anno, data, ndata);
-  a.npiles = np;  a.nrec = (u32) nrec;  a.tspace = t->tspace;  a.tbytes = t->tbytes;  a.ends = ends;
-  long long *d_off = (long long *) h->off.need(sizeof(long long) * ((size_t) np + 1));
-  int *d_aread = (int *) h->aread.need(sizeof(int) * (size_t) np + 16);
-  const int *src[7] = { b->abpos, b->aepos, b->bbpos, b->bepos, b->bread, b->flags, t->tlen };
-  int *d_col[7];
-  for (int i = 0; i < 7; i++) d_col[i] = (int *) h->col[i].need(sizeof(int) * nrec + 16);
-  long long *d_toff = (long long *) h->toff.need(sizeof(long long) * nrec + 16);
-  u8 *d_trace = (u8 *) h->trace.need((size_t) t->trace_bytes + 16);
-  HIP_CHECK(hipMemcpyAsync(d_off, b->pile_off, sizeof(long long) * ((size_t) np + 1), hipMemcpyHostToDevice, G_st));
-  HIP_CHECK(hipMemcpyAsync(d_aread, b->pile_aread, sizeof(int) * (size_t) np, hipMemcpyHostToDevice, G_st));
-  for (int i = 0; i < 7; i++)
-    HIP_CHECK(hipMemcpyAsync(d_col[i], src[i], sizeof(int) * nrec, hipMemcpyHostToDevice, G_st));
-  HIP_CHECK(hipMemcpyAsync(d_toff, t->trace_off, sizeof(long long) * nrec, hipMemcpyHostToDevice, G_st));
-  if (t->trace_bytes > 0)
-    HIP_CHECK(hipMemcpyAsync(d_trace, t->trace, (size_t) t->trace_bytes, hipMemcpyHostToDevice, G_st));
+  a.npiles = (u32) b->npiles;  a.nrec = (u32) b->nrec;  a.tspace = t->tspace;  a.tbytes = t->tbytes;  a.ends = ends;
+  const PileDev d = pile_up(h->S, b, t, { b->abpos, b->aepos, b->bbpos, b->bepos, b->bread, b->flags, t->tlen });
   if (ends != -1)
-    { int *d_trim = (int *) h->trim.need(sizeof(int) * 2 * (size_t) h->nreads);
-      HIP_CHECK(hipMemcpyAsync(d_trim, trim, sizeof(int) * 2 * (size_t) h->nreads, hipMemcpyHostToDevice, G_st));
-      a.trim = d_trim;
-    }
-  HIP_CHECK(hipEventRecord(h->ev[1], G_st));
-  a.pile_off = d_off;  a.pile_aread = d_aread;
-  a.abpos = d_col[0];  a.aepos = d_col[1];  a.bbpos = d_col[2];  a.bepos = d_col[3];  a.bread = d_col[4];  a.flags = d_col[5];
-  a.tlen = d_col[6];  a.trace_off = d_toff;  a.trace = d_trace;
+    a.trim = up(h->S.trim, trim, 2 * (size_t) h->nreads);
+  HM.mark(1);
+  a.pile_off = d.off;  a.pile_aread = d.aread;
+  a.abpos = d.col[0];  a.aepos = d.col[1];  a.bbpos = d.col[2];  a.bepos = d.col[3];  a.bread = d.col[4];  a.flags = d.col[5];
+  a.tlen = d.col[6];  a.trace_off = d.toff;  a.trace = d.trace;
   damar_launch_hom_mark(&a, G_st);
-  HIP_CHECK(hipEventRecord(h->ev[2], G_st));
+  HM.mark(2);
   homog_marked(h);
   return 0;
 }
@@ -4892,7 +4912,7 @@ extern "C" int damar_homog_finish(damar_homog *h, uint64 *anno, int **data, int6
   if (h->hs != NULL)
     { if (damar_host_homog_finish(h->hs, anno, data, ndata, tagged))
         return 1;
-      damar_host_homog_counts(h->hs, HM_cnt);
+      damar_host_homog_counts(h->hs, HM.cnt);
       return 0;
     }
   const size_t nr = (size_t) h->nreads;
@@ -4900,10 +4920,10 @@ extern "C" int damar_homog_finish(damar_homog *h, uint64 *anno, int **data, int6
   memset(&a, 0, sizeof(a));
   a.nreads = (u32) h->nreads;  a.res = h->res;
   a.read_len = h->d_rlen;  a.woff = h->d_woff;  a.words = h->d_words;
-  u32 *d_count = (u32 *) h->count.need(sizeof(u32) * nr), *d_doff = (u32 *) h->doff.need(sizeof(u32) * nr);
-  void *d_scan = h->scan.need(damar_scan_workspace_bytes(nr));
+  u32 *d_count = (u32 *) h->S.count.need(sizeof(u32) * nr), *d_doff = (u32 *) h->S.doff.need(sizeof(u32) * nr);
+  void *d_scan = h->S.scan.need(damar_scan_workspace_bytes(nr));
   a.count = d_count;  a.off = d_doff;
-  HIP_CHECK(hipEventRecord(h->ev[0], G_st));
+  HM.mark(2);
   damar_launch_hom_count(&a, G_st);
   damar_exclusive_scan_u32(d_count, d_doff, nr, d_scan, h->d_cnt + 1, G_st);
   u64 total = 0;
@@ -4913,9 +4933,9 @@ extern "C" int damar_homog_finish(damar_homog *h, uint64 *anno, int **data, int6
     { fprintf(stderr, "damar: homogenize: %llu intervals, 2^30 - 1 is the most a track of ints holds here\n", (unsigned long long) total);
       return 1;
     }
-  a.out = (int *) h->out.need(sizeof(int) * 2 * (size_t) total + 16);
+  a.out = (int *) h->S.out.need(sizeof(int) * 2 * (size_t) total + 16);
   damar_launch_hom_emit(&a, G_st);
-  HIP_CHECK(hipEventRecord(h->ev[1], G_st));
+  HM.mark(3);
   std::vector<u32> cnt(nr);
   int *out = (int *) malloc(sizeof(int) * 2 * (size_t) total + 8);
   if (out == NULL)
@@ -4925,7 +4945,7 @@ extern "C" int damar_homog_finish(damar_homog *h, uint64 *anno, int **data, int6
   HIP_CHECK(hipMemcpyAsync(cnt.data(), d_count, sizeof(u32) * nr, hipMemcpyDeviceToHost, G_st));
   if (total > 0)
     HIP_CHECK(hipMemcpyAsync(out, a.out, sizeof(int) * 2 * (size_t) total, hipMemcpyDeviceToHost, G_st));
-  HIP_CHECK(hipEventRecord(h->ev[2], G_st));
+  HM.mark(4);
   HIP_CHECK(hipStreamSynchronize(G_st));
   uint64 off = 0;
   for (size_t r = 0; r < nr; r++)
@@ -4937,37 +4957,23 @@ extern "C" int damar_homog_finish(damar_homog *h, uint64 *anno, int **data, int6
   for (u64 k = 0; k < total; k++)
     sum += out[2 * k + 1] - out[2 * k];
   *data = out;  *ndata = (int64) (2 * total);  *tagged = sum;
-  HM_cnt[2] = (int64) total;
-  for (int i = 0; i < 2; i++)
-    { float ms = 0;
-      HIP_CHECK(hipEventElapsedTime(&ms, h->ev[i], h->ev[i + 1]));
-      HM_ms[2 + i] += ms;
-    }
+  HM.cnt[2] = (int64) total;
+  HM.laps_add(2, 2);
   return 0;
 }
 
 /***** exact alignment of a batch of boxes with their edit scripts: Compute_Alignment(DIFF_ALIGN) (kernels/box_align.hip) ******/
 
-static DBuf BX_m, BX_n, BX_aoff, BX_boff, BX_coff, BX_bases, BX_diffs, BX_slen, BX_script;
-static double BX_ms[4];        /* of the last call: upload, kernel, download (HIP events), whole call (wall) */
-static int64  BX_cnt[3];       /* boxes, boxes the host routine did beside the kernel, script values */
-static hipEvent_t BX_ev[4];
-static int    BX_ev_made;
+static struct : DevStage        /* ms of the last call: upload, kernel, download (HIP events), whole call (wall);
+                                   cnt: boxes, boxes the host routine did beside the kernel, script values */
+{ DBuf m{*this}, n{*this}, aoff{*this}, boff{*this}, coff{*this}, bases{*this}, diffs{*this}, slen{*this}, script{*this};
+} BX;
 
-extern "C" void damar_box_release(void)
-{ DBuf *all[] = { &BX_m, &BX_n, &BX_aoff, &BX_boff, &BX_coff, &BX_bases, &BX_diffs, &BX_slen, &BX_script };
-  for (DBuf *b : all) b->drop();
-  if (BX_ev_made)
-    for (int i = 0; i < 4; i++) (void) hipEventDestroy(BX_ev[i]);
-  BX_ev_made = 0;
-}
+extern "C" void damar_box_release(void) { BX.release(); }
 
 extern "C" unsigned int damar_box_grid(void) { return damar_box_align_grid(); }
 
-extern "C" void damar_box_last(double *ms, int64 *cnt)
-{ for (int i = 0; i < 4; i++) ms[i] = BX_ms[i];
-  for (int i = 0; i < 3; i++) cnt[i] = BX_cnt[i];
-}
+extern "C" void damar_box_last(double *ms, int64 *cnt) { BX.last(ms, cnt, 3); }
 
 extern "C" int damar_align_boxes(const damar_box_batch *b, int *diffs, int64 *soff, int **script)
 { const double w0 = now_ms();
@@ -4991,57 +4997,41 @@ extern "C" int damar_align_boxes(const damar_box_batch *b, int *diffs, int64 *so
   for (size_t i = 0; i < nb; i++)
     room[i + 1] = room[i] + std::max(b->m[i], b->n[i]);
   std::vector<int> wide((size_t) room[nb] + 1), slen(nb, -1);
-  for (int i = 0; i < 4; i++) BX_ms[i] = 0;
+  for (int i = 0; i < 4; i++) BX.ms[i] = 0;
   int64 fallback = 0;
 
   const bool host = damar_trim_on_host();
-  int maxlen = DAMAR_BOX_MAXLEN;
-  if (getenv("DAMAR_TEST_BOX_LIMIT") && atoi(getenv("DAMAR_TEST_BOX_LIMIT")) < maxlen)
-    maxlen = atoi(getenv("DAMAR_TEST_BOX_LIMIT"));
   if (!host && nb > 0)
     { ensure_init();
       /* a tool built on this call is through a few milliseconds after the library comes up: its launch, its copies and
          the frees of damar_box_release would all run beside the start-up thread, which is inside HIP calls of its own for
          longer than that.  The process cannot end before that thread does (helpers_join), so waiting here costs nothing. */
       late_streams();
-      if (!BX_ev_made)
-        { for (int i = 0; i < 4; i++) HIP_CHECK(hipEventCreate(&BX_ev[i]));
-          BX_ev_made = 1;
-        }
       BoxArgs a;
       memset(&a, 0, sizeof(a));
       a.nbox = (u32) nb;
-      a.maxlen = maxlen;
-      int *d_m = (int *) BX_m.need(sizeof(int) * nb), *d_n = (int *) BX_n.need(sizeof(int) * nb);
-      long long *d_aoff = (long long *) BX_aoff.need(sizeof(long long) * nb), *d_boff = (long long *) BX_boff.need(sizeof(long long) * nb);
-      long long *d_coff = (long long *) BX_coff.need(sizeof(long long) * (nb + 1));
-      u8  *d_bases = (u8 *) BX_bases.need((size_t) b->nbases + 16);
-      int *d_diffs = (int *) BX_diffs.need(sizeof(int) * nb), *d_slen = (int *) BX_slen.need(sizeof(int) * nb);
-      int *d_script = (int *) BX_script.need(sizeof(int) * ((size_t) room[nb] + 1));
-      HIP_CHECK(hipEventRecord(BX_ev[0], G_st));
-      HIP_CHECK(hipMemcpyAsync(d_m, b->m, sizeof(int) * nb, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_n, b->n, sizeof(int) * nb, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_aoff, b->aoff, sizeof(long long) * nb, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_boff, b->boff, sizeof(long long) * nb, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_coff, room.data(), sizeof(long long) * (nb + 1), hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_bases, b->bases, (size_t) b->nbases, hipMemcpyHostToDevice, G_st));
+      a.maxlen = test_limit("DAMAR_TEST_BOX_LIMIT", DAMAR_BOX_MAXLEN, INT_MIN);
+      int *d_diffs = (int *) BX.diffs.need(sizeof(int) * nb), *d_slen = (int *) BX.slen.need(sizeof(int) * nb);
+      int *d_script = (int *) BX.script.need(sizeof(int) * ((size_t) room[nb] + 1));
+      BX.mark(0);
+      a.m = up(BX.m, b->m, nb);
+      a.n = up(BX.n, b->n, nb);
+      a.aoff = (const long long *) up(BX.aoff, b->aoff, nb);
+      a.boff = (const long long *) up(BX.boff, b->boff, nb);
+      a.coff = up(BX.coff, room.data(), nb + 1);
+      a.bases = (const u8 *) up(BX.bases, b->bases, (size_t) b->nbases);
       HIP_CHECK(hipMemsetAsync(d_slen, 0xff, sizeof(int) * nb, G_st));
-      HIP_CHECK(hipEventRecord(BX_ev[1], G_st));
-      a.m = d_m;  a.n = d_n;  a.aoff = d_aoff;  a.boff = d_boff;  a.coff = d_coff;  a.bases = d_bases;
+      BX.mark(1);
       a.diffs = d_diffs;  a.slen = d_slen;  a.script = d_script;
       damar_launch_box_align(&a, G_st);
-      HIP_CHECK(hipEventRecord(BX_ev[2], G_st));
+      BX.mark(2);
       HIP_CHECK(hipMemcpyAsync(diffs, d_diffs, sizeof(int) * nb, hipMemcpyDeviceToHost, G_st));
       HIP_CHECK(hipMemcpyAsync(slen.data(), d_slen, sizeof(int) * nb, hipMemcpyDeviceToHost, G_st));
       if (room[nb] > 0)
         HIP_CHECK(hipMemcpyAsync(wide.data(), d_script, sizeof(int) * (size_t) room[nb], hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipEventRecord(BX_ev[3], G_st));
+      BX.mark(3);
       HIP_CHECK(hipStreamSynchronize(G_st));
-      for (int i = 0; i < 3; i++)
-        { float ms = 0;
-          HIP_CHECK(hipEventElapsedTime(&ms, BX_ev[i], BX_ev[i + 1]));
-          BX_ms[i] = ms;
-        }
+      BX.laps(0, 3);
     }
   /* what the kernel left: boxes beyond its LDS budget (and all of them with DAMAR_TRIM=host) */
   for (size_t i = 0; i < nb; i++)
@@ -5060,33 +5050,24 @@ extern "C" int damar_align_boxes(const damar_box_batch *b, int *diffs, int64 *so
   for (size_t i = 0; i < nb; i++)
     if (slen[i] > 0)
       memcpy(*script + soff[i], wide.data() + room[i], sizeof(int) * (size_t) slen[i]);
-  BX_cnt[0] = b->nbox;  BX_cnt[1] = fallback;  BX_cnt[2] = soff[nb];
-  BX_ms[3] = now_ms() - w0;
+  BX.cnt[0] = b->nbox;  BX.cnt[1] = fallback;  BX.cnt[2] = soff[nb];
+  BX.ms[3] = now_ms() - w0;
   return 0;
 }
 
 /***** exact alignment of a batch of boxes into trace pairs: Compute_Alignment(DIFF_TRACE) (kernels/box_trace.hip) ******/
 
-static DBuf TB_large, TB_m, TB_n, TB_abpos, TB_aoff, TB_boff, TB_toff, TB_bases, TB_diffs, TB_tlen, TB_trace;
-static double TB_ms[4];        /* of the last call: upload, kernel, download (HIP events), whole call (wall) */
-static int64  TB_cnt[3];       /* boxes, boxes the host routine did beside the kernel, trace values */
-static hipEvent_t TB_ev[4];
-static int    TB_ev_made;
+static struct : DevStage        /* ms of the last call: upload, kernel, download (HIP events), whole call (wall);
+                                   cnt: boxes, boxes the host routine did beside the kernel, trace values */
+{ DBuf large{*this}, m{*this}, n{*this}, abpos{*this}, aoff{*this}, boff{*this}, toff{*this}, bases{*this}, diffs{*this}, tlen{*this},
+       trace{*this};
+} TB;
 
-extern "C" void damar_tbox_release(void)
-{ DBuf *all[] = { &TB_large, &TB_m, &TB_n, &TB_abpos, &TB_aoff, &TB_boff, &TB_toff, &TB_bases, &TB_diffs, &TB_tlen, &TB_trace };
-  for (DBuf *b : all) b->drop();
-  if (TB_ev_made)
-    for (int i = 0; i < 4; i++) (void) hipEventDestroy(TB_ev[i]);
-  TB_ev_made = 0;
-}
+extern "C" void damar_tbox_release(void) { TB.release(); }
 
 extern "C" unsigned int damar_tbox_grid(void) { return damar_box_trace_grid(); }
 
-extern "C" void damar_tbox_last(double *ms, int64 *cnt)
-{ for (int i = 0; i < 4; i++) ms[i] = TB_ms[i];
-  for (int i = 0; i < 3; i++) cnt[i] = TB_cnt[i];
-}
+extern "C" void damar_tbox_last(double *ms, int64 *cnt) { TB.last(ms, cnt, 3); }
 
 extern "C" int damar_trace_boxes(const damar_tbox_batch *b, int *diffs, int64 *toff, uint16 **trace)
 { const double w0 = now_ms();
@@ -5117,66 +5098,46 @@ extern "C" int damar_trace_boxes(const damar_tbox_batch *b, int *diffs, int64 *t
       return 1;
     }
   std::vector<int> tlen(nb, -1);
-  for (int i = 0; i < 4; i++) TB_ms[i] = 0;
+  for (int i = 0; i < 4; i++) TB.ms[i] = 0;
   int64 fallback = 0;
 
   const bool host = damar_stitch_on_host();
-  int maxlen = DAMAR_TBOX_MAXLEN;
-  if (getenv("DAMAR_TEST_BOX_LIMIT") && atoi(getenv("DAMAR_TEST_BOX_LIMIT")) < maxlen)
-    maxlen = atoi(getenv("DAMAR_TEST_BOX_LIMIT"));
   if (!host && nb > 0)
     { ensure_init();
       late_streams();              /* a tool built on this call is through soon after the library comes up: see damar_align_boxes */
-      if (!TB_ev_made)
-        { for (int i = 0; i < 4; i++) HIP_CHECK(hipEventCreate(&TB_ev[i]));
-          TB_ev_made = 1;
-        }
       TBoxArgs a;
       memset(&a, 0, sizeof(a));
       a.nbox = (u32) nb;
-      a.maxlen = maxlen;
+      a.maxlen = test_limit("DAMAR_TEST_BOX_LIMIT", DAMAR_TBOX_MAXLEN, INT_MIN);
       a.tspace = ts;
       std::vector<u32> large;
       for (size_t i = 0; i < nb; i++)
         if ((u32) std::max(b->m[i], b->n[i]) > damar_box_trace_small())
           large.push_back((u32) i);
       a.nlarge = (u32) large.size();
-      u32 *d_large = (u32 *) TB_large.need(sizeof(u32) * (large.size() + 1));
-      int *d_m = (int *) TB_m.need(sizeof(int) * nb), *d_n = (int *) TB_n.need(sizeof(int) * nb);
-      int *d_abpos = (int *) TB_abpos.need(sizeof(int) * nb);
-      long long *d_aoff = (long long *) TB_aoff.need(sizeof(long long) * nb), *d_boff = (long long *) TB_boff.need(sizeof(long long) * nb);
-      long long *d_toff = (long long *) TB_toff.need(sizeof(long long) * (nb + 1));
-      u8  *d_bases = (u8 *) TB_bases.need((size_t) b->nbases + 16);
-      int *d_diffs = (int *) TB_diffs.need(sizeof(int) * nb), *d_tlen = (int *) TB_tlen.need(sizeof(int) * nb);
-      u16 *d_trace = (u16 *) TB_trace.need(sizeof(u16) * ((size_t) toff[nb] + 4));
-      HIP_CHECK(hipEventRecord(TB_ev[0], G_st));
-      HIP_CHECK(hipMemcpyAsync(d_m, b->m, sizeof(int) * nb, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_n, b->n, sizeof(int) * nb, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_abpos, b->abpos, sizeof(int) * nb, hipMemcpyHostToDevice, G_st));
-      if (a.nlarge > 0)
-        HIP_CHECK(hipMemcpyAsync(d_large, large.data(), sizeof(u32) * large.size(), hipMemcpyHostToDevice, G_st));
-      a.large = d_large;
-      HIP_CHECK(hipMemcpyAsync(d_aoff, b->aoff, sizeof(long long) * nb, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_boff, b->boff, sizeof(long long) * nb, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_toff, toff, sizeof(long long) * (nb + 1), hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_bases, b->bases, (size_t) b->nbases, hipMemcpyHostToDevice, G_st));
+      int *d_diffs = (int *) TB.diffs.need(sizeof(int) * nb), *d_tlen = (int *) TB.tlen.need(sizeof(int) * nb);
+      u16 *d_trace = (u16 *) TB.trace.need(sizeof(u16) * ((size_t) toff[nb] + 4));
+      TB.mark(0);
+      a.m = up(TB.m, b->m, nb);
+      a.n = up(TB.n, b->n, nb);
+      a.abpos = up(TB.abpos, b->abpos, nb);
+      a.large = up(TB.large, large.data(), large.size());
+      a.aoff = (const long long *) up(TB.aoff, b->aoff, nb);
+      a.boff = (const long long *) up(TB.boff, b->boff, nb);
+      a.toff = (const long long *) up(TB.toff, toff, nb + 1);
+      a.bases = (const u8 *) up(TB.bases, b->bases, (size_t) b->nbases);
       HIP_CHECK(hipMemsetAsync(d_tlen, 0xff, sizeof(int) * nb, G_st));
-      HIP_CHECK(hipEventRecord(TB_ev[1], G_st));
-      a.m = d_m;  a.n = d_n;  a.abpos = d_abpos;  a.aoff = d_aoff;  a.boff = d_boff;  a.toff = d_toff;  a.bases = d_bases;
+      TB.mark(1);
       a.diffs = d_diffs;  a.tlen = d_tlen;  a.trace = d_trace;
       damar_launch_box_trace(&a, G_st);
-      HIP_CHECK(hipEventRecord(TB_ev[2], G_st));
+      TB.mark(2);
       HIP_CHECK(hipMemcpyAsync(diffs, d_diffs, sizeof(int) * nb, hipMemcpyDeviceToHost, G_st));
       HIP_CHECK(hipMemcpyAsync(tlen.data(), d_tlen, sizeof(int) * nb, hipMemcpyDeviceToHost, G_st));
       if (toff[nb] > 0)
         HIP_CHECK(hipMemcpyAsync(*trace, d_trace, sizeof(u16) * (size_t) toff[nb], hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipEventRecord(TB_ev[3], G_st));
+      TB.mark(3);
       HIP_CHECK(hipStreamSynchronize(G_st));
-      for (int i = 0; i < 3; i++)
-        { float ms = 0;
-          HIP_CHECK(hipEventElapsedTime(&ms, TB_ev[i], TB_ev[i + 1]));
-          TB_ms[i] = ms;
-        }
+      TB.laps(0, 3);
     }
   /* what the kernel left: boxes beyond its LDS budget (and all of them with DAMAR_STITCH=host) */
   for (size_t i = 0; i < nb; i++)
@@ -5191,37 +5152,26 @@ extern "C" int damar_trace_boxes(const damar_tbox_batch *b, int *diffs, int64 *t
         *trace = NULL;
         return 1;
       }
-  TB_cnt[0] = b->nbox;  TB_cnt[1] = fallback;  TB_cnt[2] = toff[nb];
-  TB_ms[3] = now_ms() - w0;
+  TB.cnt[0] = b->nbox;  TB.cnt[1] = fallback;  TB.cnt[2] = toff[nb];
+  TB.ms[3] = now_ms() - w0;
   return 0;
 }
 
 /***** LAgap's containments, gaps and breaks per pile: scrub/LAgap.c (kernels/pile_gaps.hip) ******************************/
 
-static DBuf GP_off, GP_aread, GP_col[6], GP_rlen, GP_xanno, GP_xdata, GP_skip, GP_flags, GP_status, GP_nev, GP_ev, GP_cnt;
-static double GP_ms[4];        /* of the last call: upload, kernel, download (HIP events), whole call (wall) */
-static int64  GP_cnt3[3];      /* piles, piles the host routine did beside the kernel, break events */
-static hipEvent_t GP_evt[4];
-static int    GP_ev_made;
+static struct : PileStage       /* ms of the last call: upload, kernel, download (HIP events), whole call (wall);
+                                   cnt: piles, piles the host routine did beside the kernel, break events */
+{ DBuf rlen{*this}, xanno{*this}, xdata{*this}, skip{*this}, flags{*this}, status{*this}, nev{*this}, evs{*this}, pcnt{*this};
+} GP;
 
-extern "C" void damar_gap_release(void)
-{ DBuf *all[] = { &GP_off, &GP_aread, &GP_col[0], &GP_col[1], &GP_col[2], &GP_col[3], &GP_col[4], &GP_col[5], &GP_rlen, &GP_xanno, &GP_xdata,
-                  &GP_skip, &GP_flags, &GP_status, &GP_nev, &GP_ev, &GP_cnt };
-  for (DBuf *b : all) b->drop();
-  if (GP_ev_made)
-    for (int i = 0; i < 4; i++) (void) hipEventDestroy(GP_evt[i]);
-  GP_ev_made = 0;
-}
+extern "C" void damar_gap_release(void) { GP.release(); }
 
 extern "C" void damar_gap_limits(int *bins, int *events)
 { *bins = DAMAR_GAP_MAXBINS;
   *events = DAMAR_GAP_MAXEVENTS;
 }
 
-extern "C" void damar_gap_last(double *ms, int64 *cnt)
-{ for (int i = 0; i < 4; i++) ms[i] = GP_ms[i];
-  for (int i = 0; i < 3; i++) cnt[i] = GP_cnt3[i];
-}
+extern "C" void damar_gap_last(double *ms, int64 *cnt) { GP.last(ms, cnt, 3); }
 
 extern "C" int damar_pile_gaps(const damar_pile_batch *b, const damar_gap_params *p, int *flags_out, damar_gap_events *ev)
 { const double w0 = now_ms();
@@ -5231,14 +5181,12 @@ extern "C" int damar_pile_gaps(const damar_pile_batch *b, const damar_gap_params
   const bool host = damar_piles_on_host() != 0;
   damar_gap_list L = { NULL, 0, 0 };
   int64 cnt[3] = { 0, 0, 0 }, fallback = 0;
-  for (int i = 0; i < 4; i++) GP_ms[i] = 0;
+  for (int i = 0; i < 4; i++) GP.ms[i] = 0;
 
   std::vector<u8>  skip(np + 1, 0);
   std::vector<int> status(np + 1, 1), nev(np + 1, 0), evs, pcnt;
   if (!host && np > 0)
-    { const char *lower = getenv("DAMAR_TEST_GAP_BINS");
-      const int maxbins = (lower != NULL && atoi(lower) < DAMAR_GAP_MAXBINS) ? atoi(lower) : DAMAR_GAP_MAXBINS;
-      /* the kernel takes the records of one B read for a run.  The reference's containment loop skips a discarded record
+    { /* the kernel takes the records of one B read for a run.  The reference's containment loop skips a discarded record
          before it looks at its B read, so where the B reads do not ascend it can pair records across another read's:
          such a pile is the host routine's */
       for (size_t q = 0; q < np; q++)
@@ -5249,51 +5197,31 @@ extern "C" int damar_pile_gaps(const damar_pile_batch *b, const damar_gap_params
             }
       ensure_init();
       late_streams();                /* a tool built on this call is through soon after the library comes up: see damar_align_boxes */
-      if (!GP_ev_made)
-        { for (int i = 0; i < 4; i++) HIP_CHECK(hipEventCreate(&GP_evt[i]));
-          GP_ev_made = 1;
-        }
       GapArgs a;
       memset(&a, 0, sizeof(a));
       a.npiles = (u32) np;
-      a.maxbins = maxbins;  a.maxev = DAMAR_GAP_MAXEVENTS;  a.stitch = p->stitch;
+      a.maxbins = test_limit("DAMAR_TEST_GAP_BINS", DAMAR_GAP_MAXBINS, INT_MIN);
+      a.maxev = DAMAR_GAP_MAXEVENTS;  a.stitch = p->stitch;
       const size_t evints = np * DAMAR_GAP_MAXEVENTS * DAMAR_GAP_EVENT_INTS;
-      long long *d_off = (long long *) GP_off.need(sizeof(long long) * (np + 1));
-      int *d_aread = (int *) GP_aread.need(sizeof(int) * np + 16);
-      const int *src[6] = { b->abpos, b->aepos, b->bbpos, b->bepos, b->bread, b->flags };
-      int *d_col[6];
-      for (int i = 0; i < 6; i++) d_col[i] = (int *) GP_col[i].need(sizeof(int) * nrec + 16);
-      int *d_rlen = (int *) GP_rlen.need(sizeof(int) * (size_t) b->nreads);
-      u8  *d_skip = (u8 *) GP_skip.need(np + 16);
-      int *d_flags = (int *) GP_flags.need(sizeof(int) * nrec + 16);
-      int *d_status = (int *) GP_status.need(sizeof(int) * np + 16), *d_nev = (int *) GP_nev.need(sizeof(int) * np + 16);
-      int *d_ev = (int *) GP_ev.need(sizeof(int) * evints + 16), *d_cnt = (int *) GP_cnt.need(sizeof(int) * 3 * np + 16);
-      u64 *d_xanno = NULL;
-      int *d_xdata = NULL;
-      HIP_CHECK(hipEventRecord(GP_evt[0], G_st));
+      int *d_flags = (int *) GP.flags.need(sizeof(int) * nrec + 16);
+      int *d_status = (int *) GP.status.need(sizeof(int) * np + 16), *d_nev = (int *) GP.nev.need(sizeof(int) * np + 16);
+      int *d_ev = (int *) GP.evs.need(sizeof(int) * evints + 16), *d_cnt = (int *) GP.pcnt.need(sizeof(int) * 3 * np + 16);
+      GP.mark(0);
       if (p->ex_anno != NULL)
-        { d_xanno = (u64 *) GP_xanno.need(sizeof(u64) * ((size_t) b->nreads + 1));
-          d_xdata = (int *) GP_xdata.need(sizeof(int) * (size_t) p->ex_ndata + 16);
-          HIP_CHECK(hipMemcpyAsync(d_xanno, p->ex_anno, sizeof(u64) * ((size_t) b->nreads + 1), hipMemcpyHostToDevice, G_st));
-          if (p->ex_ndata > 0)
-            HIP_CHECK(hipMemcpyAsync(d_xdata, p->ex_data, sizeof(int) * (size_t) p->ex_ndata, hipMemcpyHostToDevice, G_st));
+        { const DevTrack ex = up_track(GP.xanno, GP.xdata, p->ex_anno, (size_t) b->nreads, p->ex_data, p->ex_ndata);
+          a.ex_anno = ex.anno;  a.ex_data = ex.data;
         }
-      HIP_CHECK(hipMemcpyAsync(d_off, b->pile_off, sizeof(long long) * (np + 1), hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_aread, b->pile_aread, sizeof(int) * np, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_skip, skip.data(), np, hipMemcpyHostToDevice, G_st));
-      if (nrec > 0)
-        for (int i = 0; i < 6; i++)
-          HIP_CHECK(hipMemcpyAsync(d_col[i], src[i], sizeof(int) * nrec, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_rlen, b->read_len, sizeof(int) * (size_t) b->nreads, hipMemcpyHostToDevice, G_st));
+      a.skip = up(GP.skip, skip.data(), np);
+      const PileDev d = pile_up(GP, b, NULL, { b->abpos, b->aepos, b->bbpos, b->bepos, b->bread, b->flags });
+      a.read_len = up(GP.rlen, b->read_len, (size_t) b->nreads);
       HIP_CHECK(hipMemsetAsync(d_nev, 0, sizeof(int) * np, G_st));
-      HIP_CHECK(hipEventRecord(GP_evt[1], G_st));
-      a.pile_off = d_off;  a.pile_aread = d_aread;
-      a.abpos = d_col[0];  a.aepos = d_col[1];  a.bbpos = d_col[2];  a.bepos = d_col[3];  a.bread = d_col[4];  a.flags = d_col[5];
-      a.read_len = d_rlen;  a.ex_anno = d_xanno;  a.ex_data = d_xdata;  a.skip = d_skip;
+      GP.mark(1);
+      a.pile_off = d.off;  a.pile_aread = d.aread;
+      a.abpos = d.col[0];  a.aepos = d.col[1];  a.bbpos = d.col[2];  a.bepos = d.col[3];  a.bread = d.col[4];  a.flags = d.col[5];
       a.flags_out = d_flags;  a.status = d_status;  a.nev = d_nev;  a.ev = d_ev;  a.cnt = d_cnt;
       damar_launch_pile_gaps(&a, G_st);
       HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipEventRecord(GP_evt[2], G_st));
+      GP.mark(2);
       evs.resize(evints + 1);
       pcnt.resize(3 * np + 1);
       if (nrec > 0)
@@ -5302,13 +5230,9 @@ extern "C" int damar_pile_gaps(const damar_pile_batch *b, const damar_gap_params
       HIP_CHECK(hipMemcpyAsync(nev.data(), d_nev, sizeof(int) * np, hipMemcpyDeviceToHost, G_st));
       HIP_CHECK(hipMemcpyAsync(evs.data(), d_ev, sizeof(int) * evints, hipMemcpyDeviceToHost, G_st));
       HIP_CHECK(hipMemcpyAsync(pcnt.data(), d_cnt, sizeof(int) * 3 * np, hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipEventRecord(GP_evt[3], G_st));
+      GP.mark(3);
       HIP_CHECK(hipStreamSynchronize(G_st));
-      for (int i = 0; i < 3; i++)
-        { float ms = 0;
-          HIP_CHECK(hipEventElapsedTime(&ms, GP_evt[i], GP_evt[i + 1]));
-          GP_ms[i] = ms;
-        }
+      GP.laps(0, 3);
     }
   /* the events in pile order; what the kernel left (all piles with DAMAR_PILES=host) is the plain routine's */
   for (size_t q = 0; q < np; q++)
@@ -5323,21 +5247,8 @@ extern "C" int damar_pile_gaps(const damar_pile_batch *b, const damar_gap_params
               free(L.ev);
               return 1;
             }
-          if (L.n + nev[q] > L.cap)
-            { const int64 cap = L.n + nev[q] + L.cap / 4 + 256;
-              int *grown = (int *) realloc(L.ev, sizeof(int) * DAMAR_GAP_EVENT_INTS * (size_t) cap);
-              if (grown == NULL)
-                { fprintf(stderr, "damar: out of memory (gaps)\n");
-                  free(L.ev);
-                  return 1;
-                }
-              L.ev = grown;
-              L.cap = cap;
-            }
-          if (nev[q] > 0)
-            memcpy(L.ev + DAMAR_GAP_EVENT_INTS * L.n, evs.data() + q * DAMAR_GAP_MAXEVENTS * DAMAR_GAP_EVENT_INTS,
-                   sizeof(int) * DAMAR_GAP_EVENT_INTS * (size_t) nev[q]);
-          L.n += nev[q];
+          if (list_append(&L.ev, &L.n, &L.cap, DAMAR_GAP_EVENT_INTS, evs.data() + q * DAMAR_GAP_MAXEVENTS * DAMAR_GAP_EVENT_INTS, nev[q], "gaps"))
+            return 1;
           for (int i = 0; i < 3; i++) cnt[i] += pcnt[3 * q + i];
         }
       ev->count[q] = (int) (L.n - before);
@@ -5349,45 +5260,27 @@ extern "C" int damar_pile_gaps(const damar_pile_batch *b, const damar_gap_params
   ev->ev = L.ev;
   ev->nev = L.n;
   ev->contained = cnt[0];  ev->breaks = cnt[1];  ev->dropped = cnt[2];
-  GP_cnt3[0] = b->npiles;  GP_cnt3[1] = fallback;  GP_cnt3[2] = L.n;
-  GP_ms[3] = now_ms() - w0;
+  GP.cnt[0] = b->npiles;  GP.cnt[1] = fallback;  GP.cnt[2] = L.n;
+  GP.ms[3] = now_ms() - w0;
   return 0;
 }
 
 /***** LAfilter's screens per pile: scrub/LAfilter.c filter_handler (kernels/pile_filter.hip) *****************************/
 
-static DBuf FL_off, FL_aread, FL_col[8], FL_toff, FL_trace, FL_rlen, FL_trim, FL_ranno, FL_rdata, FL_soff, FL_slen, FL_sdata, FL_state,
-            FL_out[7], FL_status, FL_cnt;
-static double FL_ms[4];        /* of the last call: upload, kernel, download (HIP events), whole call (wall) */
-static int64  FL_cnt3[3];      /* piles, piles the host routine did beside the kernel, records that left discarded */
-static hipEvent_t FL_evt[4];
-static int    FL_ev_made;
+static struct : PileStage       /* ms of the last call: upload, kernel, download (HIP events), whole call (wall);
+                                   cnt: piles, piles the host routine did beside the kernel, records that left discarded */
+{ DBuf rlen{*this}, trim{*this}, ranno{*this}, rdata{*this}, soff{*this}, slen{*this}, sdata{*this}, state{*this},
+       out[7] = { *this, *this, *this, *this, *this, *this, *this }, status{*this}, pcnt{*this};
+} FL;
 
-extern "C" void damar_filter_release(void)
-{ DBuf *all[] = { &FL_off, &FL_aread, &FL_toff, &FL_trace, &FL_rlen, &FL_trim, &FL_ranno, &FL_rdata, &FL_soff, &FL_slen, &FL_sdata, &FL_state,
-                  &FL_status, &FL_cnt };
-  for (DBuf *b : all) b->drop();
-  for (int i = 0; i < 8; i++) FL_col[i].drop();
-  for (int i = 0; i < 7; i++) FL_out[i].drop();
-  if (FL_ev_made)
-    for (int i = 0; i < 4; i++) (void) hipEventDestroy(FL_evt[i]);
-  FL_ev_made = 0;
-}
-
-static int filter_limit(const char *name, int built)
-{ const char *lower = getenv(name);
-  return (lower != NULL && atoi(lower) > 0 && atoi(lower) < built) ? atoi(lower) : built;
-}
+extern "C" void damar_filter_release(void) { FL.release(); }
 
 extern "C" void damar_filter_limits(int *group, int *len)
 { *group = DAMAR_FILTER_MAXGROUP;
   *len = DAMAR_FILTER_MAXLEN;
 }
 
-extern "C" void damar_filter_last(double *ms, int64 *cnt)
-{ for (int i = 0; i < 4; i++) ms[i] = FL_ms[i];
-  for (int i = 0; i < 3; i++) cnt[i] = FL_cnt3[i];
-}
+extern "C" void damar_filter_last(double *ms, int64 *cnt) { FL.last(ms, cnt, 3); }
 
 extern "C" int damar_pile_filter(const damar_trace_batch *t, const int *diffs, const damar_filter_params *p, damar_filter_out *out)
 { const double w0 = now_ms();
@@ -5397,22 +5290,18 @@ extern "C" int damar_pile_filter(const damar_trace_batch *t, const int *diffs, c
   const size_t np = (size_t) b->npiles, nrec = (size_t) b->nrec, nreads = (size_t) b->nreads;
   const bool host = damar_piles_on_host() != 0;
   int64 fallback = 0, gone = 0;
-  for (int i = 0; i < 4; i++) FL_ms[i] = 0;
+  for (int i = 0; i < 4; i++) FL.ms[i] = 0;
 
   std::vector<int> status(np + 1, 1);
   if (!host && np > 0)
     { ensure_init();
       late_streams();                /* a tool built on this call is through soon after the library comes up: see damar_align_boxes */
-      if (!FL_ev_made)
-        { for (int i = 0; i < 4; i++) HIP_CHECK(hipEventCreate(&FL_evt[i]));
-          FL_ev_made = 1;
-        }
       FilterArgs a;
       memset(&a, 0, sizeof(a));
       a.npiles = (u32) np;
       a.steps = p->steps;
-      a.maxgroup = filter_limit("DAMAR_TEST_FILTER_GROUP", DAMAR_FILTER_MAXGROUP);
-      a.maxlen = filter_limit("DAMAR_TEST_FILTER_LEN", DAMAR_FILTER_MAXLEN);
+      a.maxgroup = test_limit("DAMAR_TEST_FILTER_GROUP", DAMAR_FILTER_MAXGROUP, 1);
+      a.maxlen = test_limit("DAMAR_TEST_FILTER_LEN", DAMAR_FILTER_MAXLEN, 1);
       if ((p->steps & DAMAR_FILTER_MAIN) && p->lowcov && p->max_unaligned != -1)
         { int longest = 0;           /* the coverage bits: room for the longest A read of the batch that the kernel takes */
           for (size_t q = 0; q < np; q++)
@@ -5425,77 +5314,44 @@ extern "C" int damar_pile_filter(const damar_trace_batch *t, const int *diffs, c
       a.stitch = p->stitch;  a.stitch_aggr = p->stitch_aggr;  a.min_rlen = p->min_rlen;  a.min_olen = p->min_olen;
       a.max_unaligned = p->max_unaligned;  a.min_nonrep = p->min_nonrep;  a.max_diffs = p->max_diffs;  a.merge_tips = p->merge_tips;
       a.multi = p->multi;  a.lowcov = p->lowcov;  a.remove = p->remove;  a.include = p->include;  a.tbytes = t->tbytes;
-      long long *d_off = (long long *) FL_off.need(sizeof(long long) * (np + 1));
-      int *d_aread = (int *) FL_aread.need(sizeof(int) * np + 16);
-      const int *src[8] = { b->abpos, b->aepos, b->bbpos, b->bepos, b->bread, b->flags, diffs, t->tlen };
-      int *d_col[8], *d_out[7];
-      for (int i = 0; i < 8; i++) d_col[i] = (int *) FL_col[i].need(sizeof(int) * nrec + 16);
-      for (int i = 0; i < 7; i++) d_out[i] = (int *) FL_out[i].need(sizeof(int) * nrec + 16);
-      long long *d_toff = (long long *) FL_toff.need(sizeof(long long) * nrec + 16);
-      u8  *d_trace = (u8 *) FL_trace.need((size_t) t->trace_bytes + 16);
-      int *d_rlen = (int *) FL_rlen.need(sizeof(int) * nreads);
-      int *d_status = (int *) FL_status.need(sizeof(int) * np + 16);
-      int *d_cnt = (int *) FL_cnt.need(sizeof(int) * DAMAR_FC_COUNT * np + 16);
-      HIP_CHECK(hipEventRecord(FL_evt[0], G_st));
+      int *d_out[7];
+      for (int i = 0; i < 7; i++) d_out[i] = (int *) FL.out[i].need(sizeof(int) * nrec + 16);
+      int *d_status = (int *) FL.status.need(sizeof(int) * np + 16);
+      int *d_cnt = (int *) FL.pcnt.need(sizeof(int) * DAMAR_FC_COUNT * np + 16);
+      FL.mark(0);
       if (p->trim != NULL)
-        { int *d = (int *) FL_trim.need(sizeof(int) * 2 * nreads);
-          HIP_CHECK(hipMemcpyAsync(d, p->trim, sizeof(int) * 2 * nreads, hipMemcpyHostToDevice, G_st));
-          a.trim = d;
-        }
+        a.trim = up(FL.trim, p->trim, 2 * nreads);
       if (p->min_nonrep != -1)
-        { u64 *d_anno = (u64 *) FL_ranno.need(sizeof(u64) * (nreads + 1));
-          int *d_data = (int *) FL_rdata.need(sizeof(int) * (size_t) p->rep_ndata + 16);
-          HIP_CHECK(hipMemcpyAsync(d_anno, p->rep_anno, sizeof(u64) * (nreads + 1), hipMemcpyHostToDevice, G_st));
-          if (p->rep_ndata > 0)
-            HIP_CHECK(hipMemcpyAsync(d_data, p->rep_data, sizeof(int) * (size_t) p->rep_ndata, hipMemcpyHostToDevice, G_st));
-          a.rep_anno = d_anno;  a.rep_data = d_data;
+        { const DevTrack rep = up_track(FL.ranno, FL.rdata, p->rep_anno, nreads, p->rep_data, p->rep_ndata);
+          a.rep_anno = rep.anno;  a.rep_data = rep.data;
         }
       if (p->sym_off != NULL)
-        { int *d_so = (int *) FL_soff.need(sizeof(int) * (nreads + 1)), *d_sl = (int *) FL_slen.need(sizeof(int) * (nreads + 1));
-          int *d_sd = (int *) FL_sdata.need(sizeof(int) * (size_t) p->sym_ndata + 16);
-          HIP_CHECK(hipMemcpyAsync(d_so, p->sym_off, sizeof(int) * (nreads + 1), hipMemcpyHostToDevice, G_st));
-          HIP_CHECK(hipMemcpyAsync(d_sl, p->sym_len, sizeof(int) * (nreads + 1), hipMemcpyHostToDevice, G_st));
-          if (p->sym_ndata > 0)
-            HIP_CHECK(hipMemcpyAsync(d_sd, p->sym_data, sizeof(int) * (size_t) p->sym_ndata, hipMemcpyHostToDevice, G_st));
-          a.sym_off = d_so;  a.sym_len = d_sl;  a.sym_data = d_sd;
+        { a.sym_off = up(FL.soff, p->sym_off, nreads + 1);
+          a.sym_len = up(FL.slen, p->sym_len, nreads + 1);
+          a.sym_data = up(FL.sdata, p->sym_data, (size_t) p->sym_ndata);
         }
       if (p->read_state != NULL)
-        { u8 *d = (u8 *) FL_state.need(nreads + 16);
-          HIP_CHECK(hipMemcpyAsync(d, p->read_state, nreads, hipMemcpyHostToDevice, G_st));
-          a.read_state = d;
-        }
-      HIP_CHECK(hipMemcpyAsync(d_off, b->pile_off, sizeof(long long) * (np + 1), hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_aread, b->pile_aread, sizeof(int) * np, hipMemcpyHostToDevice, G_st));
-      if (nrec > 0)
-        { for (int i = 0; i < 8; i++)
-            HIP_CHECK(hipMemcpyAsync(d_col[i], src[i], sizeof(int) * nrec, hipMemcpyHostToDevice, G_st));
-          HIP_CHECK(hipMemcpyAsync(d_toff, t->trace_off, sizeof(long long) * nrec, hipMemcpyHostToDevice, G_st));
-        }
-      if (t->trace_bytes > 0)
-        HIP_CHECK(hipMemcpyAsync(d_trace, t->trace, (size_t) t->trace_bytes, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_rlen, b->read_len, sizeof(int) * nreads, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipEventRecord(FL_evt[1], G_st));
-      a.pile_off = d_off;  a.pile_aread = d_aread;
-      a.abpos = d_col[0];  a.aepos = d_col[1];  a.bbpos = d_col[2];  a.bepos = d_col[3];  a.bread = d_col[4];  a.flags = d_col[5];
-      a.diffs = d_col[6];  a.tlen = d_col[7];  a.trace_off = d_toff;  a.trace = d_trace;  a.read_len = d_rlen;
+        a.read_state = up(FL.state, p->read_state, nreads);
+      const PileDev d = pile_up(FL, b, t, { b->abpos, b->aepos, b->bbpos, b->bepos, b->bread, b->flags, diffs, t->tlen });
+      a.read_len = up(FL.rlen, b->read_len, nreads);
+      FL.mark(1);
+      a.pile_off = d.off;  a.pile_aread = d.aread;
+      a.abpos = d.col[0];  a.aepos = d.col[1];  a.bbpos = d.col[2];  a.bepos = d.col[3];  a.bread = d.col[4];  a.flags = d.col[5];
+      a.diffs = d.col[6];  a.tlen = d.col[7];  a.trace_off = d.toff;  a.trace = d.trace;
       a.o_flags = d_out[0];  a.o_ae = d_out[1];  a.o_be = d_out[2];  a.o_df = d_out[3];  a.o_tl = d_out[4];  a.o_why = d_out[5];  a.o_by = d_out[6];
       a.status = d_status;  a.cnt = d_cnt;
       damar_launch_pile_filter(&a, G_st);
       HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipEventRecord(FL_evt[2], G_st));
+      FL.mark(2);
       int *dst[7] = { out->flags, out->aepos, out->bepos, out->diffs, out->tlen, out->reason, out->cont_by };
       if (nrec > 0)
         for (int i = 0; i < 7; i++)
           HIP_CHECK(hipMemcpyAsync(dst[i], d_out[i], sizeof(int) * nrec, hipMemcpyDeviceToHost, G_st));
       HIP_CHECK(hipMemcpyAsync(status.data(), d_status, sizeof(int) * np, hipMemcpyDeviceToHost, G_st));
       HIP_CHECK(hipMemcpyAsync(out->cnt, d_cnt, sizeof(int) * DAMAR_FC_COUNT * np, hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipEventRecord(FL_evt[3], G_st));
+      FL.mark(3);
       HIP_CHECK(hipStreamSynchronize(G_st));
-      for (int i = 0; i < 3; i++)
-        { float ms = 0;
-          HIP_CHECK(hipEventElapsedTime(&ms, FL_evt[i], FL_evt[i + 1]));
-          FL_ms[i] = ms;
-        }
+      FL.laps(0, 3);
     }
   /* what the kernel left (all piles with DAMAR_PILES=host) is the plain routine's */
   for (size_t q = 0; q < np; q++)
@@ -5505,38 +5361,27 @@ extern "C" int damar_pile_filter(const damar_trace_batch *t, const int *diffs, c
       }
   for (size_t i = 0; i < nrec; i++)
     gone += (out->flags[i] & 0x2) != 0;
-  FL_cnt3[0] = b->npiles;  FL_cnt3[1] = fallback;  FL_cnt3[2] = gone;
-  FL_ms[3] = now_ms() - w0;
+  FL.cnt[0] = b->npiles;  FL.cnt[1] = fallback;  FL.cnt[2] = gone;
+  FL.ms[3] = now_ms() - w0;
   return 0;
 }
 
 /***** LAfix's breaks and weak segments per pile: scrub/LAfix.c fix_process (kernels/pile_patch.hip) **********************/
 
-static DBuf FX_off, FX_aread, FX_trim, FX_col[7], FX_toff, FX_trace, FX_rlen, FX_qanno, FX_qdata, FX_ranno, FX_rdata, FX_skip, FX_slot,
-            FX_gaps, FX_status, FX_ngaps;
-static double FX_ms[4];        /* of the last call: upload, kernel, download (HIP events), whole call (wall) */
-static int64  FX_cnt3[3];      /* piles, piles the host routine did beside the kernel, repairs */
-static hipEvent_t FX_evt[4];
-static int    FX_ev_made;
+static struct : PileStage       /* ms of the last call: upload, kernel, download (HIP events), whole call (wall);
+                                   cnt: piles, piles the host routine did beside the kernel, repairs */
+{ DBuf trim{*this}, rlen{*this}, qanno{*this}, qdata{*this}, ranno{*this}, rdata{*this}, skip{*this}, slot{*this}, gaps{*this}, status{*this},
+       ngaps{*this};
+} FX;
 
-extern "C" void damar_fix_release(void)
-{ DBuf *all[] = { &FX_off, &FX_aread, &FX_trim, &FX_col[0], &FX_col[1], &FX_col[2], &FX_col[3], &FX_col[4], &FX_col[5], &FX_col[6], &FX_toff,
-                  &FX_trace, &FX_rlen, &FX_qanno, &FX_qdata, &FX_ranno, &FX_rdata, &FX_skip, &FX_slot, &FX_gaps, &FX_status, &FX_ngaps };
-  for (DBuf *b : all) b->drop();
-  if (FX_ev_made)
-    for (int i = 0; i < 4; i++) (void) hipEventDestroy(FX_evt[i]);
-  FX_ev_made = 0;
-}
+extern "C" void damar_fix_release(void) { FX.release(); }
 
 extern "C" void damar_fix_limits(int *segs, int *cands)
 { *segs = DAMAR_FIX_MAXSEGS;
   *cands = DAMAR_FIX_MAXCAND;
 }
 
-extern "C" void damar_fix_last(double *ms, int64 *cnt)
-{ for (int i = 0; i < 4; i++) ms[i] = FX_ms[i];
-  for (int i = 0; i < 3; i++) cnt[i] = FX_cnt3[i];
-}
+extern "C" void damar_fix_last(double *ms, int64 *cnt) { FX.last(ms, cnt, 3); }
 
 extern "C" int damar_pile_patches(const damar_trace_batch *t, const damar_fix_params *p, const int *trim, damar_fix_gaps *out)
 { const double w0 = now_ms();
@@ -5549,16 +5394,14 @@ extern "C" int damar_pile_patches(const damar_trace_batch *t, const damar_fix_pa
   const int tw = t->tspace;
   damar_fix_list L = { NULL, 0, 0 };
   int64 fallback = 0;
-  for (int i = 0; i < 4; i++) FX_ms[i] = 0;
+  for (int i = 0; i < 4; i++) FX.ms[i] = 0;
 
   std::vector<u8>  skip(np + 1, 0);
   std::vector<int> status(np + 1, 1), ngaps(np + 1, 0);
   std::vector<long long> slot(np + 1, 0);
   std::vector<damar_fix_gap> got;
   if (!host && np > 0)
-    { const char *lower = getenv("DAMAR_TEST_FIX_SEGS");
-      const int maxsegs = (lower != NULL && atoi(lower) < DAMAR_FIX_MAXSEGS) ? atoi(lower) : DAMAR_FIX_MAXSEGS;
-      /* per pile: whether its B reads ascend (a pile where they do not is the host routine's), and the room its repairs
+    { /* per pile: whether its B reads ascend (a pile where they do not is the host routine's), and the room its repairs
          need at the most -- a repair is a pair of neighbouring records of one B read or a bad segment inside the trim */
       for (size_t q = 0; q < np; q++)
         { const int aread = b->pile_aread[q], tb = trim[2 * q], te = trim[2 * q + 1];
@@ -5583,80 +5426,45 @@ extern "C" int damar_pile_patches(const damar_trace_batch *t, const damar_fix_pa
       const size_t nslot = (size_t) slot[np];
       ensure_init();
       late_streams();                /* a tool built on this call is through soon after the library comes up: see damar_align_boxes */
-      if (!FX_ev_made)
-        { for (int i = 0; i < 4; i++) HIP_CHECK(hipEventCreate(&FX_evt[i]));
-          FX_ev_made = 1;
-        }
       FixArgs a;
       memset(&a, 0, sizeof(a));
       a.npiles = (u32) np;
-      a.maxsegs = maxsegs;  a.tspace = tw;  a.tbytes = t->tbytes;
+      a.maxsegs = test_limit("DAMAR_TEST_FIX_SEGS", DAMAR_FIX_MAXSEGS, INT_MIN);
+      a.tspace = tw;  a.tbytes = t->tbytes;
       a.lowq = p->lowq;  a.maxgap = p->maxgap;  a.maxspanners = p->maxspanners;  a.minsupport = p->minsupport;
       a.q_ndata = p->q_ndata;
       const size_t nreads = (size_t) b->nreads;
-      long long *d_off = (long long *) FX_off.need(sizeof(long long) * (np + 1));
-      int *d_aread = (int *) FX_aread.need(sizeof(int) * np + 16);
-      int *d_trim = (int *) FX_trim.need(sizeof(int) * 2 * np + 16);
-      const int *src[7] = { b->abpos, b->aepos, b->bbpos, b->bepos, b->bread, b->flags, t->tlen };
-      int *d_col[7];
-      for (int i = 0; i < 7; i++) d_col[i] = (int *) FX_col[i].need(sizeof(int) * nrec + 16);
-      long long *d_toff = (long long *) FX_toff.need(sizeof(long long) * nrec + 16);
-      u8  *d_trace = (u8 *) FX_trace.need((size_t) t->trace_bytes + 16);
-      int *d_rlen = (int *) FX_rlen.need(sizeof(int) * nreads);
-      u64 *d_qanno = (u64 *) FX_qanno.need(sizeof(u64) * (nreads + 1));
-      int *d_qdata = (int *) FX_qdata.need(sizeof(int) * (size_t) p->q_ndata + 16);
-      u8  *d_skip = (u8 *) FX_skip.need(np + 16);
-      long long *d_slot = (long long *) FX_slot.need(sizeof(long long) * (np + 1));
-      int *d_gaps = (int *) FX_gaps.need(sizeof(damar_fix_gap) * nslot + 16);
-      int *d_status = (int *) FX_status.need(sizeof(int) * np + 16), *d_ngaps = (int *) FX_ngaps.need(sizeof(int) * np + 16);
-      u64 *d_ranno = NULL;
-      int *d_rdata = NULL;
-      HIP_CHECK(hipEventRecord(FX_evt[0], G_st));
+      int *d_gaps = (int *) FX.gaps.need(sizeof(damar_fix_gap) * nslot + 16);
+      int *d_status = (int *) FX.status.need(sizeof(int) * np + 16), *d_ngaps = (int *) FX.ngaps.need(sizeof(int) * np + 16);
+      FX.mark(0);
       if (p->rep_anno != NULL)
-        { d_ranno = (u64 *) FX_ranno.need(sizeof(u64) * (nreads + 1));
-          d_rdata = (int *) FX_rdata.need(sizeof(int) * (size_t) p->rep_ndata + 16);
-          HIP_CHECK(hipMemcpyAsync(d_ranno, p->rep_anno, sizeof(u64) * (nreads + 1), hipMemcpyHostToDevice, G_st));
-          if (p->rep_ndata > 0)
-            HIP_CHECK(hipMemcpyAsync(d_rdata, p->rep_data, sizeof(int) * (size_t) p->rep_ndata, hipMemcpyHostToDevice, G_st));
+        { const DevTrack rep = up_track(FX.ranno, FX.rdata, p->rep_anno, nreads, p->rep_data, p->rep_ndata);
+          a.rep_anno = rep.anno;  a.rep_data = rep.data;
         }
-      HIP_CHECK(hipMemcpyAsync(d_off, b->pile_off, sizeof(long long) * (np + 1), hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_aread, b->pile_aread, sizeof(int) * np, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_trim, trim, sizeof(int) * 2 * np, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_skip, skip.data(), np, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_slot, slot.data(), sizeof(long long) * (np + 1), hipMemcpyHostToDevice, G_st));
-      if (nrec > 0)
-        { for (int i = 0; i < 7; i++)
-            HIP_CHECK(hipMemcpyAsync(d_col[i], src[i], sizeof(int) * nrec, hipMemcpyHostToDevice, G_st));
-          HIP_CHECK(hipMemcpyAsync(d_toff, t->trace_off, sizeof(long long) * nrec, hipMemcpyHostToDevice, G_st));
-        }
-      if (t->trace_bytes > 0)
-        HIP_CHECK(hipMemcpyAsync(d_trace, t->trace, (size_t) t->trace_bytes, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_rlen, b->read_len, sizeof(int) * nreads, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_qanno, p->q_anno, sizeof(u64) * (nreads + 1), hipMemcpyHostToDevice, G_st));
-      if (p->q_ndata > 0)
-        HIP_CHECK(hipMemcpyAsync(d_qdata, p->q_data, sizeof(int) * (size_t) p->q_ndata, hipMemcpyHostToDevice, G_st));
+      a.trim = up(FX.trim, trim, 2 * np);
+      a.skip = up(FX.skip, skip.data(), np);
+      a.slot_off = up(FX.slot, slot.data(), np + 1);
+      const PileDev d = pile_up(FX, b, t, { b->abpos, b->aepos, b->bbpos, b->bepos, b->bread, b->flags, t->tlen });
+      a.read_len = up(FX.rlen, b->read_len, nreads);
+      const DevTrack q = up_track(FX.qanno, FX.qdata, p->q_anno, nreads, p->q_data, p->q_ndata);
       HIP_CHECK(hipMemsetAsync(d_ngaps, 0, sizeof(int) * np, G_st));
-      HIP_CHECK(hipEventRecord(FX_evt[1], G_st));
-      a.pile_off = d_off;  a.pile_aread = d_aread;  a.trim = d_trim;
-      a.abpos = d_col[0];  a.aepos = d_col[1];  a.bbpos = d_col[2];  a.bepos = d_col[3];  a.bread = d_col[4];  a.flags = d_col[5];
-      a.tlen = d_col[6];  a.trace_off = d_toff;  a.trace = d_trace;
-      a.read_len = d_rlen;  a.q_anno = d_qanno;  a.q_data = d_qdata;  a.rep_anno = d_ranno;  a.rep_data = d_rdata;
-      a.skip = d_skip;  a.slot_off = d_slot;  a.gaps = d_gaps;  a.status = d_status;  a.ngaps = d_ngaps;
+      FX.mark(1);
+      a.pile_off = d.off;  a.pile_aread = d.aread;
+      a.abpos = d.col[0];  a.aepos = d.col[1];  a.bbpos = d.col[2];  a.bepos = d.col[3];  a.bread = d.col[4];  a.flags = d.col[5];
+      a.tlen = d.col[6];  a.trace_off = d.toff;  a.trace = d.trace;
+      a.q_anno = q.anno;  a.q_data = q.data;
+      a.gaps = d_gaps;  a.status = d_status;  a.ngaps = d_ngaps;
       damar_launch_pile_patch(&a, G_st);
       HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipEventRecord(FX_evt[2], G_st));
+      FX.mark(2);
       got.resize(nslot + 1);
       HIP_CHECK(hipMemcpyAsync(status.data(), d_status, sizeof(int) * np, hipMemcpyDeviceToHost, G_st));
       HIP_CHECK(hipMemcpyAsync(ngaps.data(), d_ngaps, sizeof(int) * np, hipMemcpyDeviceToHost, G_st));
       if (nslot > 0)
         HIP_CHECK(hipMemcpyAsync(got.data(), d_gaps, sizeof(damar_fix_gap) * nslot, hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipEventRecord(FX_evt[3], G_st));
+      FX.mark(3);
       HIP_CHECK(hipStreamSynchronize(G_st));
-      for (int i = 0; i < 3; i++)
-        { float ms = 0;
-          HIP_CHECK(hipEventElapsedTime(&ms, FX_evt[i], FX_evt[i + 1]));
-          FX_ms[i] = ms;
-        }
+      FX.laps(0, 3);
     }
   /* the repairs in pile order; what the kernel left (all piles with DAMAR_PILES=host) is the plain routine's */
   for (size_t q = 0; q < np; q++)
@@ -5671,20 +5479,8 @@ extern "C" int damar_pile_patches(const damar_trace_batch *t, const damar_fix_pa
               free(L.g);
               return 1;
             }
-          if (L.n + ngaps[q] > L.cap)
-            { const int64 cap = L.n + ngaps[q] + L.cap / 4 + 256;
-              damar_fix_gap *grown = (damar_fix_gap *) realloc(L.g, sizeof(damar_fix_gap) * (size_t) cap);
-              if (grown == NULL)
-                { fprintf(stderr, "damar: out of memory (fix)\n");
-                  free(L.g);
-                  return 1;
-                }
-              L.g = grown;
-              L.cap = cap;
-            }
-          if (ngaps[q] > 0)
-            memcpy(L.g + L.n, got.data() + slot[q], sizeof(damar_fix_gap) * (size_t) ngaps[q]);
-          L.n += ngaps[q];
+          if (list_append(&L.g, &L.n, &L.cap, 1, got.data() + slot[q], ngaps[q], "fix"))
+            return 1;
         }
       out->count[q] = (int) (L.n - before);
     }
@@ -5694,8 +5490,8 @@ extern "C" int damar_pile_patches(const damar_trace_batch *t, const damar_fix_pa
     }
   out->gaps = L.g;
   out->ngaps = L.n;
-  FX_cnt3[0] = b->npiles;  FX_cnt3[1] = fallback;  FX_cnt3[2] = L.n;
-  FX_ms[3] = now_ms() - w0;
+  FX.cnt[0] = b->npiles;  FX.cnt[1] = fallback;  FX.cnt[2] = L.n;
+  FX.ms[3] = now_ms() - w0;
   return 0;
 }
 
@@ -5704,19 +5500,12 @@ extern "C" int damar_pile_patches(const damar_trace_batch *t, const damar_fix_pa
 #define TCN_MAXLANES 32768u    /* stripes of the work area: 512 wavefronts */
 #define TCN_CHUNK    131072u   /* tasks per launch: bounds the staging of the called bases */
 
-static DBuf TCN_order, TCN_eoff, TCN_soff, TCN_slen, TCN_bases, TCN_work, TCN_out, TCN_status, TCN_len;
-static double TCN_ms[4];       /* of the last call: upload, kernel, download (HIP events), whole call (wall) */
-static int64  TCN_cnt3[3];     /* tiles, tiles the host routine did beside the kernel, bases called */
-static hipEvent_t TCN_evt[4];
-static int    TCN_ev_made;
+static struct : DevStage        /* ms of the last call: upload, kernel, download (HIP events), whole call (wall);
+                                   cnt: tiles, tiles the host routine did beside the kernel, bases called */
+{ DBuf order{*this}, eoff{*this}, soff{*this}, slen{*this}, bases{*this}, work{*this}, out{*this}, status{*this}, len{*this};
+} TCN;
 
-extern "C" void damar_correct_release(void)
-{ DBuf *all[] = { &TCN_order, &TCN_eoff, &TCN_soff, &TCN_slen, &TCN_bases, &TCN_work, &TCN_out, &TCN_status, &TCN_len };
-  for (DBuf *b : all) b->drop();
-  if (TCN_ev_made)
-    for (int i = 0; i < 4; i++) (void) hipEventDestroy(TCN_evt[i]);
-  TCN_ev_made = 0;
-}
+extern "C" void damar_correct_release(void) { TCN.release(); }
 
 extern "C" void damar_correct_limits(int *seg, int *cols, int *cells)
 { *seg = DAMAR_CORRECT_MAXSEG;
@@ -5724,10 +5513,7 @@ extern "C" void damar_correct_limits(int *seg, int *cols, int *cells)
   *cells = DAMAR_CORRECT_CELLS;
 }
 
-extern "C" void damar_correct_last(double *ms, int64 *cnt)
-{ for (int i = 0; i < 4; i++) ms[i] = TCN_ms[i];
-  for (int i = 0; i < 3; i++) cnt[i] = TCN_cnt3[i];
-}
+extern "C" void damar_correct_last(double *ms, int64 *cnt) { TCN.last(ms, cnt, 3); }
 
 extern "C" int damar_tile_consensus(const damar_tile_batch *b, int64 *cons_off, unsigned char **cons, int *added)
 { const double w0 = now_ms();
@@ -5737,8 +5523,8 @@ extern "C" int damar_tile_consensus(const damar_tile_batch *b, int64 *cons_off, 
   const size_t nt = (size_t) b->ntiles;
   const bool host = damar_piles_on_host() != 0;
   int64 fallback = 0;
-  for (int i = 0; i < 4; i++) TCN_ms[i] = 0;
-  for (int i = 0; i < 3; i++) TCN_cnt3[i] = 0;       /* a call that fails leaves zeros, not a mixture */
+  for (int i = 0; i < 4; i++) TCN.ms[i] = 0;
+  for (int i = 0; i < 3; i++) TCN.cnt[i] = 0;       /* a call that fails leaves zeros, not a mixture */
   if (nt >= ((size_t) 1 << 31))
     { fprintf(stderr, "damar: correct: %zu tiles in one call (below 2^31 are taken)\n", nt);
       return 1;
@@ -5764,8 +5550,7 @@ extern "C" int damar_tile_consensus(const damar_tile_batch *b, int64 *cons_off, 
         order.push_back((u32) t);
     }
   if (!order.empty())
-    { const char *lower = getenv("DAMAR_TEST_CORRECT_COLS");
-      const int maxcols = ((lower != NULL && atoi(lower) >= 2 && atoi(lower) < DAMAR_CORRECT_MAXCOLS) ? atoi(lower) : DAMAR_CORRECT_MAXCOLS) & ~1;
+    { const int maxcols = test_limit("DAMAR_TEST_CORRECT_COLS", DAMAR_CORRECT_MAXCOLS, 2) & ~1;
       auto weight = [&](u32 t) -> long long
         { if (b->weight != NULL) return b->weight[t];
           const int64 e0 = b->ent_off[t], e1 = b->ent_off[t + 1];
@@ -5775,10 +5560,6 @@ extern "C" int damar_tile_consensus(const damar_tile_batch *b, int64 *cons_off, 
       const size_t ntask = order.size(), nent = (size_t) b->ent_off[nt];
       ensure_init();
       late_streams();
-      if (!TCN_ev_made)
-        { for (int i = 0; i < 4; i++) HIP_CHECK(hipEventCreate(&TCN_evt[i]));
-          TCN_ev_made = 1;
-        }
       TileArgs a;
       memset(&a, 0, sizeof(a));
       a.maxcols = maxcols;
@@ -5787,28 +5568,19 @@ extern "C" int damar_tile_consensus(const damar_tile_batch *b, int64 *cons_off, 
       a.stripe = ((size_t) 6 * maxcols + 2 * (size_t) a.maxscript + 3 * (size_t) a.cells + 15) & ~(size_t) 15;
       const u32 lanes = (u32) std::min<size_t>((ntask + 63) / 64 * 64, TCN_MAXLANES);
       a.blocks = lanes / 64;
-      long long *d_eoff = (long long *) TCN_eoff.need(sizeof(long long) * (nt + 1));
-      long long *d_soff = (long long *) TCN_soff.need(sizeof(long long) * nent + 16);
-      int *d_slen = (int *) TCN_slen.need(sizeof(int) * nent + 16);
-      u8  *d_bases = (u8 *) TCN_bases.need((size_t) b->nbases + 16);
-      u32 *d_order = (u32 *) TCN_order.need(sizeof(u32) * ntask);
       const size_t chunk = std::min<size_t>(ntask, TCN_CHUNK);
-      u8  *d_out = (u8 *) TCN_out.need(chunk * (size_t) maxcols);
-      int *d_status = (int *) TCN_status.need(sizeof(int) * chunk), *d_len = (int *) TCN_len.need(sizeof(int) * chunk);
-      a.work = (u8 *) TCN_work.need((size_t) lanes * a.stripe);
-      HIP_CHECK(hipEventRecord(TCN_evt[0], G_st));
-      HIP_CHECK(hipMemcpyAsync(d_eoff, b->ent_off, sizeof(long long) * (nt + 1), hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_soff, b->seq_off, sizeof(long long) * nent, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_slen, b->seq_len, sizeof(int) * nent, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_bases, b->bases, (size_t) b->nbases, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipMemcpyAsync(d_order, order.data(), sizeof(u32) * ntask, hipMemcpyHostToDevice, G_st));
-      HIP_CHECK(hipEventRecord(TCN_evt[1], G_st));
+      u8  *d_out = (u8 *) TCN.out.need(chunk * (size_t) maxcols);
+      int *d_status = (int *) TCN.status.need(sizeof(int) * chunk), *d_len = (int *) TCN.len.need(sizeof(int) * chunk);
+      a.work = (u8 *) TCN.work.need((size_t) lanes * a.stripe);
+      TCN.mark(0);
+      a.ent_off = (const long long *) up(TCN.eoff, b->ent_off, nt + 1);
+      a.seq_off = (const long long *) up(TCN.soff, b->seq_off, nent);
+      a.seq_len = up(TCN.slen, b->seq_len, nent);
+      a.bases = up(TCN.bases, b->bases, (size_t) b->nbases);
+      const u32 *d_order = up(TCN.order, order.data(), ntask);
+      TCN.mark(1);
       HIP_CHECK(hipStreamSynchronize(G_st));
-      { float ms = 0;
-        HIP_CHECK(hipEventElapsedTime(&ms, TCN_evt[0], TCN_evt[1]));
-        TCN_ms[0] = ms;
-      }
-      a.ent_off = d_eoff;  a.seq_off = d_soff;  a.seq_len = d_slen;  a.bases = d_bases;
+      TCN.laps(0, 1);
       a.out = d_out;  a.status = d_status;  a.len = d_len;
       std::vector<int> status(chunk), len(chunk);
       std::vector<u8>  got(chunk * (size_t) maxcols);
@@ -5817,20 +5589,16 @@ extern "C" int damar_tile_consensus(const damar_tile_batch *b, int64 *cons_off, 
         { const size_t n = std::min(chunk, ntask - c0);
           a.ntasks = (u32) n;
           a.order = d_order + c0;
-          HIP_CHECK(hipEventRecord(TCN_evt[1], G_st));
+          TCN.mark(1);
           damar_launch_tile_consensus(&a, G_st);
           HIP_CHECK(hipGetLastError());
-          HIP_CHECK(hipEventRecord(TCN_evt[2], G_st));
+          TCN.mark(2);
           HIP_CHECK(hipMemcpyAsync(status.data(), d_status, sizeof(int) * n, hipMemcpyDeviceToHost, G_st));
           HIP_CHECK(hipMemcpyAsync(len.data(), d_len, sizeof(int) * n, hipMemcpyDeviceToHost, G_st));
           HIP_CHECK(hipMemcpyAsync(got.data(), d_out, n * (size_t) maxcols, hipMemcpyDeviceToHost, G_st));
-          HIP_CHECK(hipEventRecord(TCN_evt[3], G_st));
+          TCN.mark(3);
           HIP_CHECK(hipStreamSynchronize(G_st));
-          for (int i = 1; i < 3; i++)
-            { float ms = 0;
-              HIP_CHECK(hipEventElapsedTime(&ms, TCN_evt[i], TCN_evt[i + 1]));
-              TCN_ms[i] += ms;
-            }
+          TCN.laps_add(1, 2);
           for (size_t i = 0; i < n; i++)
             { const size_t it = c0 + i;
               comp_off[it + 1] = comp_off[it];
@@ -5838,7 +5606,7 @@ extern "C" int damar_tile_consensus(const damar_tile_batch *b, int64 *cons_off, 
                 continue;
               if (len[i] < 0 || len[i] > maxcols)
                 { fprintf(stderr, "damar: correct: tile %u came back with %d bases\n", order[it], len[i]);
-                  for (int k = 0; k < 4; k++) TCN_ms[k] = 0;
+                  for (int k = 0; k < 4; k++) TCN.ms[k] = 0;
                   return 1;
                 }
               task_of[order[it]] = (long long) it;
@@ -5890,7 +5658,7 @@ extern "C" int damar_tile_consensus(const damar_tile_batch *b, int64 *cons_off, 
       return 1;
     }
   *cons = all;
-  TCN_cnt3[0] = b->ntiles;  TCN_cnt3[1] = fallback;  TCN_cnt3[2] = n;
-  TCN_ms[3] = now_ms() - w0;
+  TCN.cnt[0] = b->ntiles;  TCN.cnt[1] = fallback;  TCN.cnt[2] = n;
+  TCN.ms[3] = now_ms() - w0;
   return 0;
 }
