@@ -465,6 +465,8 @@ static int   set_ev(int oset, int k) { return 16 + 4 * oset + k; }
 extern "C" void damar_last_timings(double *ms)  { memcpy(ms, G_ms, sizeof(G_ms)); }
 extern "C" void damar_last_counters(int64 *c)   { memcpy(c, G_cnt, sizeof(G_cnt)); }
 extern "C" int  damar_last_limit(void)          { return G_limit; }
+static int G_merge_flagged = -1;         /* tiles of the last COUNT sweep that the general kernel did; -1: not looked at */
+extern "C" int  damar_last_merge_flagged(void)  { return G_merge_flagged; }
 
 /***** blocks ************************************************************************************/
 
@@ -2140,6 +2142,19 @@ static bool front_setup(SeedStage &s, damar_match_job *job, int slot, Front *f, 
   return true;
 }
 
+/* For the tests (only while damar_last_seeds keeps the seed list: a blocking copy): how many tiles of the COUNT sweep
+   just completed were left to the general kernel -- those merge_fast did not mark as done (MergeTile.pad[2]). */
+static void front_note_flagged(SeedStage &s)
+{ G_merge_flagged = -1;
+  if (!G_keep_seeds)
+    return;
+  std::vector<MergeTile> tl(s.mtiles);
+  HIP_CHECK(hipMemcpy(tl.data(), s.mw, sizeof(MergeTile) * (size_t) s.mtiles, hipMemcpyDeviceToHost));
+  G_merge_flagged = 0;
+  for (const MergeTile &t : tl)
+    G_merge_flagged += (t.pad[2] == 0);
+}
+
 /* The merge's COUNT sweep over s.m (for a slab: with merge_range behind it) and the scan of the tile totals.  Starts
    the stage's clock (the host-profile lines, tick(0)), takes the merge workspace from G_work and leaves mw / tcount /
    tot / mscw and s.total.  One host wait: stream_wait for the total. */
@@ -2163,6 +2178,7 @@ static void front_count(SeedStage &s)
   stage("merge_scan");
   HIP_CHECK(hipMemcpyAsync(&s.total, s.tot, sizeof(u64), hipMemcpyDeviceToHost, G_st));
   stream_wait(G_st);
+  front_note_flagged(s);
 }
 
 /* The reference's words for too little memory (filter.c:2634-2699), behind `lead`. */
@@ -2224,6 +2240,7 @@ static void front_adapt_limit(SeedStage &s)
       damar_exclusive_scan_u32(s.tcount, s.tcount, s.mtiles, s.mscw, s.tot, G_st);
       HIP_CHECK(hipMemcpyAsync(&s.total, s.tot, sizeof(u64), hipMemcpyDeviceToHost, G_st));
       HIP_CHECK(hipStreamSynchronize(G_st));
+      front_note_flagged(s);
     }
   G_limit = limit;
   if (VERBOSE)
@@ -3297,6 +3314,8 @@ extern "C" void damar_match_batch(damar_match_job *jobs, int njobs)
           if (AC.n >= hard || AC.bytes > budget || (AC.n >= soft && (!defer || AC.nwork >= (u64) report_opts().batch_work)))
             flush_accum();
         };
+      if (G_keep_seeds)                        /* (a comparison without seed pairs downloads nothing: not the list of an earlier one) */
+        { G_seed_keys.clear();  G_seed_vals.clear(); }
       const int got = match_front(&jobs[i], slot, &AC.c[AC.n].fr, -1);
       if (got != FRONT_SPLIT)
         { H_ms[1] += now_ms() - f0;

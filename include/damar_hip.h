@@ -180,6 +180,11 @@ int  damar_slab_cut(const uint64_t *hits, int nreads, uint64_t cap, int *b_lo /*
  * 10000 unless the host memory limit forces it lower; INT32_MAX when MEM_LIMIT is 0). */
 int damar_last_limit(void);
 
+/* For the tests: the tiles of the A index that the merge's last COUNT sweep left to its general kernel (all of them
+ * under DAMAR_MERGE_GENERAL; otherwise those whose B piece exceeds the stage or in which a cap might apply).  Looked at
+ * only while damar_last_seeds keeps the seed list; -1 otherwise. */
+int damar_last_merge_flagged(void);
+
 /* -b: the reference derives its log base weights from the first block a PROCESS sorts and keeps
  * them (filter.c:774-789).  A caller that runs several jobs in one process calls this between
  * them to get what separate daligner processes would compute. */

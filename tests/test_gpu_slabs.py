@@ -49,13 +49,15 @@ def greedy(h, cap):
 class Pair:
     """One comparison through the C ABI: blocks and indexes resident, damar_match as often as wanted."""
 
-    def __init__(self, L, an, bn, comp, k=14, j=4, identity=0, h=35):
+    def __init__(self, L, an, bn, comp, k=14, j=4, identity=0, h=35, blocks=None):
+        """blocks: (A block, B block, cross) made in memory, the B block not yet complemented, instead of blocks read from
+        an and bn"""
         from damar_amd import api
-        self.L, self.comp, self.cross, self.k, self.h = L, comp, int(an != bn), k, h
+        self.L, self.comp, self.cross, self.k, self.h = L, comp, int(an != bn) if blocks is None else int(blocks[2]), k, h
         L.Set_Filter_Params(k, 6, 0, h, j)
         L.damar_set_async(0)
         api.set_globals(identity=identity)
-        self.adb, self.bdb = api.read_block(an), api.read_block(bn)
+        self.adb, self.bdb = (api.read_block(an), api.read_block(bn)) if blocks is None else blocks[:2]
         if comp:
             L.damar_complement_block(C.byref(self.bdb), 1)
         n = C.c_int(0)
