@@ -240,6 +240,8 @@ def _lib():
         L.damar_q_result_free.argtypes = [C.POINTER(QResult)]
         L.damar_align_boxes.argtypes = [C.POINTER(BoxBatch), _PI, C.POINTER(c_int64), C.POINTER(_PI)]
         L.damar_box_grid.restype = C.c_uint
+        L.damar_align_reads.argtypes = [C.POINTER(BoxBatch), _PI, C.POINTER(c_int64), C.POINTER(_PI)]
+        L.damar_read_grid.restype = C.c_uint
         L.damar_box_last.argtypes = [C.POINTER(C.c_double), C.POINTER(c_int64)]
         L.damar_trace_boxes.argtypes = [C.POINTER(TBoxBatch), _PI, C.POINTER(c_int64), C.POINTER(C.POINTER(C.c_uint16))]
         L.damar_tbox_grid.restype = C.c_uint
@@ -486,7 +488,7 @@ def pile_tandem(piles, read_len, read_flags, min_len=0):
 
 
 _PHASES = ("upload", "kernel", "download", "call")
-_STAGES = ("trace", "pile", "q", "box", "tbox", "gap", "fix", "filter", "correct")
+_STAGES = ("trace", "pile", "q", "box", "tbox", "gap", "fix", "filter", "correct", "read")
 
 
 def _last(stage, ncnt, names=_PHASES):
@@ -500,7 +502,7 @@ def _last(stage, ncnt, names=_PHASES):
 
 def release(stage):
     """Frees the device buffers and events a call family keeps between calls: damar_<stage>_release, stage one of
-    trace, pile, q, box, tbox, gap, fix, filter, correct (a homogenize session is released by closing it)."""
+    trace, pile, q, box, tbox, gap, fix, filter, correct, read (a homogenize session is released by closing it)."""
     if stage not in _STAGES:
         raise ValueError("no stage %r" % (stage,))
     f = getattr(_lib(), "damar_%s_release" % stage)
@@ -737,8 +739,11 @@ def align_boxes(a_seqs, b_seqs):
     as the reference's Compute_Alignment(DIFF_ALIGN) does it: -> (diffs int32[boxes], scripts: a list of int32 arrays, the
     indels in path order, -(a + 1) for a base of B alone in front of A position a, b + 1 for a base of A alone in front of
     B position b).  On the GPU, one wavefront per box, unless DAMAR_TRIM=host is set."""
+    return _align(_lib().damar_align_boxes, "damar_align_boxes", a_seqs, b_seqs)
+
+
+def _align(call, name, a_seqs, b_seqs):
     import numpy as np
-    L = _lib()
     if len(a_seqs) != len(b_seqs):
         raise ValueError("one B sequence per A sequence")
     nb = len(a_seqs)
@@ -753,8 +758,8 @@ def align_boxes(a_seqs, b_seqs):
     bb = BoxBatch(nb, m.ctypes.data_as(_PI), n.ctypes.data_as(_PI), aoff.ctypes.data_as(C.POINTER(c_int64)),
                   boff.ctypes.data_as(C.POINTER(c_int64)), bases.ctypes.data, int(offs[-1]))
     diffs, soff, script = np.zeros(max(nb, 1), dtype=np.int32), np.zeros(nb + 1, dtype=np.int64), _PI()
-    if L.damar_align_boxes(C.byref(bb), diffs.ctypes.data_as(_PI), soff.ctypes.data_as(C.POINTER(c_int64)), C.byref(script)):
-        raise RuntimeError("damar_align_boxes failed")
+    if call(C.byref(bb), diffs.ctypes.data_as(_PI), soff.ctypes.data_as(C.POINTER(c_int64)), C.byref(script)):
+        raise RuntimeError(name + " failed")
     try:
         total = int(soff[nb])
         flat = np.ctypeslib.as_array(script, shape=(max(total, 1),))[:total].copy()
@@ -767,6 +772,19 @@ def box_last():
     """Of the last align_boxes / of the last batch of trim_las: ({upload, kernel, download, call} ms, boxes, boxes the host
     routine did beside the kernel, script values)."""
     return _last("box", 3)
+
+
+def align_reads(a_seqs, b_seqs):
+    """align_boxes for boxes of read length (a read against its correction, LAcorrect's postrace): the same arguments and
+    the same result.  On the GPU, one workgroup of eight wavefronts per box and the boxes dealt longest first, unless
+    DAMAR_POSTRACE=host is set; what bounds a box there is its differences (8000), not its length."""
+    return _align(_lib().damar_align_reads, "damar_align_reads", a_seqs, b_seqs)
+
+
+def read_last():
+    """Of the last align_reads / of the last batch of correct_las: ({upload, kernel, download, call} ms, boxes, boxes the
+    host routine did beside the kernel, script values)."""
+    return _last("read", 3)
 
 
 def trim_las(db, las, out, track="trim", purge=False):
@@ -1327,7 +1345,9 @@ class CorrectOpts(C.Structure):        # host/damar_host.h damar_correct_opts
 
 class CorrectStats(C.Structure):       # host/damar_host.h damar_correct_stats
     _fields_ = [(k, c_int64) for k in ("reads", "copies", "tiles", "host_tiles", "bases")] + \
-               [(k, C.c_double) for k in ("ms_consensus", "ms_kernel", "ms_postrace", "ms_postrace_wait", "ms_total")]
+               [(k, C.c_double) for k in ("ms_consensus", "ms_kernel", "ms_postrace", "ms_postrace_wait", "ms_total")] + \
+               [(k, c_int64) for k in ("postrace_boxes", "postrace_host")] + \
+               [(k, C.c_double) for k in ("ms_postrace_kernel", "ms_postrace_call")]
 
 
 def correct_limits():

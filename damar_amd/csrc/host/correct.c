@@ -6,7 +6,8 @@
  *   - the plain routine for one tile, damar_host_tile, the code of kernels/tile_core.h on storage that grows: what
  *     DAMAR_PILES=host runs, and what does the tiles beyond the kernel's limits;
  *   - the pass over a file, damar_correct_las: per batch of whole piles the layout, one damar_tile_consensus call, the reads
- *     put together; the whole-read alignment behind " postrace=" (break_read, :1055-1096) is damar_exact_box of
+ *     put together; the whole-read alignments behind " postrace=" (break_read, :1055-1096) are one damar_align_reads
+ *     call per batch (kernels/read_align.hip), or, with DAMAR_POSTRACE=host or DAMAR_PILES=host, damar_exact_box of
  *     host/bridge.c in worker threads, which run while the next batch is laid out and called.
  * Deviations from the reference, both where it reads what it never wrote: a pile whose first record has no trace is used
  * without that record; a -j for which partition_overlaps writes past its offsets is refused with a message. */
@@ -350,6 +351,63 @@ static void wave_start(Wave *w)
     postrace_worker(w);
 }
 
+/* the same alignments in one damar_align_reads call (kernels/read_align.hip): no thread is started, and wave_finish finds
+   the scripts where the workers would have left them.  0; 1 after a message. */
+static int wave_device(Wave *w, damar_correct_stats *st)
+{ damar_box_batch bb;
+  int64  *off, *soff, nbases = 0, at = 0, c3[3];
+  int    *mn, *diffs, *script = NULL, i, nb = 0, k = 0;
+  char   *bases;
+  double  ms[4];
+  w->next = w->n;
+  w->running = 0;
+  for (i = 0; i < w->n; i++)
+    if (w->job[i].len > 0)
+      { nb += 1;
+        nbases += w->blk->reads[w->job[i].aread].rlen + w->job[i].len;
+      }
+  if (nb == 0)
+    return 0;
+  mn = (int *) grow(NULL, sizeof(int) * 3 * (size_t) nb);
+  off = (int64 *) grow(NULL, sizeof(int64) * (3 * (size_t) nb + 1));
+  bases = (char *) grow(NULL, (size_t) nbases + 8);
+  diffs = mn + 2 * nb;
+  soff = off + 2 * nb;
+  for (i = 0; i < w->n; i++)
+    { const Job *j = w->job + i;
+      const HITS_READ *rd = w->blk->reads + j->aread;
+      if (j->len == 0)
+        continue;
+      mn[k] = rd->rlen;  mn[nb + k] = j->len;
+      off[k] = at;
+      memcpy(bases + at, (const char *) w->blk->bases + rd->boff, (size_t) rd->rlen);
+      at += rd->rlen;
+      off[nb + k] = at;
+      memcpy(bases + at, j->cons, (size_t) j->len);
+      at += j->len;
+      k += 1;
+    }
+  bb.nbox = nb;  bb.m = mn;  bb.n = mn + nb;  bb.aoff = off;  bb.boff = off + nb;  bb.bases = bases;  bb.nbases = nbases;
+  if (damar_align_reads(&bb, diffs, soff, &script))
+    { free(mn);  free(off);  free(bases);
+      return 1;
+    }
+  for (i = 0, k = 0; i < w->n; i++)
+    { Job *j = w->job + i;
+      if (j->len == 0)
+        continue;
+      j->slen = (int) (soff[k + 1] - soff[k]);
+      j->script = (int *) grow(NULL, sizeof(int) * ((size_t) j->slen + 1));
+      memcpy(j->script, script + soff[k], sizeof(int) * (size_t) j->slen);
+      k += 1;
+    }
+  damar_read_last(ms, c3);
+  st->postrace_boxes += c3[0];  st->postrace_host += c3[1];
+  st->ms_postrace_kernel += ms[1];  st->ms_postrace_call += ms[3];
+  free(script);  free(mn);  free(off);  free(bases);
+  return 0;
+}
+
 /* the reads of a wave written in file order: break_read, LAcorrect.c:1012 */
 static void wave_finish(Wave *w, FILE **fo, int tw, const int *read_len, damar_correct_stats *st)
 { int i, k;
@@ -469,6 +527,7 @@ int damar_correct_las(const char *dbname, const char *las, const char *out, cons
   int     got, rc = 1, have_db = 0, have_blk = 0, i, part = 0, fresh = 1, tw;
   const char *e = getenv("DAMAR_CORRECT_THREADS");
   const double w0 = now_ms();
+  const int on_device = !damar_piles_on_host() && !damar_postrace_on_host();      /* the postrace alignments */
 
   memset(st, 0, sizeof(*st));
   memset(&L, 0, sizeof(L));  memset(&T, 0, sizeof(T));  memset(W, 0, sizeof(W));
@@ -681,8 +740,11 @@ int damar_correct_las(const char *dbname, const char *las, const char *out, cons
       if (prev != NULL)
         wave_finish(prev, fo, tw, db.read_len, st);
       loose = NULL;
-      wave_start(cur);
       prev = cur;
+      if (!on_device)
+        wave_start(cur);
+      else if (wave_device(cur, st))
+        goto done;
       wi ^= 1;
     }
   if (prev != NULL)

@@ -237,9 +237,12 @@ typedef struct
   double ms_consensus, ms_kernel;          /* the damar_tile_consensus calls (wall), their kernels (HIP events) */
   double ms_postrace, ms_postrace_wait;    /* the whole-read alignments summed over the worker threads; what the pass waited for them */
   double ms_total;
+  int64  postrace_boxes, postrace_host;    /* summed over the damar_align_reads calls: boxes, boxes the host routine did beside the kernel */
+  double ms_postrace_kernel, ms_postrace_call;     /* their kernels (HIP events), the calls (wall) */
 } damar_correct_stats;
 /* the pass over a file: the reads written to <out>.NN.fasta, one file per part of -j; the reference's lines on stdout.
-   The postrace alignments run in DAMAR_CORRECT_THREADS (8) worker threads.  0, or 1 after a message. */
+   The postrace alignments of a batch go through one damar_align_reads call; with DAMAR_POSTRACE=host or DAMAR_PILES=host
+   they run in DAMAR_CORRECT_THREADS (8) worker threads.  0, or 1 after a message. */
 int  damar_correct_las(const char *db, const char *las, const char *out, const damar_correct_opts *o, damar_correct_stats *st);
 
 /* bridge.c: the exact alignment of one box into trace pairs (what damar_trace_boxes returns per box): A[0..M) against

@@ -1,7 +1,8 @@
 /* LAcorrect -- every read rewritten as the consensus of the tiles its pile lays over it, written as FASTA: the command of
  * corrector/LAcorrect.c (option letters, usage text, messages and exit codes of its main, :1567-1794) around
  * damar_correct_las (correct.c).  The consensus per tile runs on the GPU (kernels/tile_consensus.hip) unless
- * DAMAR_PILES=host is set; the whole-read alignment behind " postrace=" runs on the host in either case.
+ * DAMAR_PILES=host is set, and so does the whole-read alignment behind " postrace=" (kernels/read_align.hip) unless that or
+ * DAMAR_POSTRACE=host is set.
  * -j <n> writes n files, as the reference's n threads do; here it says nothing about threads.  -x stands in the usage text
  * and is not an option, as in the reference. */
 #include <stdio.h>
@@ -59,5 +60,6 @@ int main(int argc, char *argv[])
   fclose(f);
   rc = damar_correct_las(argv[optind], argv[optind + 1], argv[optind + 2], &o, &st);
   damar_correct_release();
+  damar_read_release();
   return rc ? 1 : 0;
 }

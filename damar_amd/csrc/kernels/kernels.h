@@ -534,6 +534,27 @@ typedef struct
 void damar_launch_box_align(const BoxArgs *a, hipStream_t st);
 u32  damar_box_align_grid(void);      /* workgroups of the largest launch: beyond that many boxes a workgroup does several */
 
+/* read_align.hip: the same alignment for boxes of read length, one workgroup of several wavefronts per box, the bases left
+   in global memory and the frontiers sized by the differences.  Box order[i] is the i-th longest.  A box with max(m, n) <=
+   DAMAR_READ_MAXLEN and at most maxdiff <= DAMAR_READ_MAXDIFF differences is done and leaves what box_align leaves; a box
+   beyond either bound, or one that hits a loop bound, has length -1 and is the host's. */
+#define DAMAR_READ_MAXDIFF 8000
+#define DAMAR_READ_MAXLEN  (1 << 20)
+typedef struct
+{ u32 nbox;
+  int maxdiff;
+  const u32 *order;                   /* [nbox] */
+  const int *m, *n;                   /* [nbox] */
+  const long long *aoff, *boff;       /* [nbox] bytes into bases */
+  const long long *coff;              /* [nbox] values into script */
+  const u8  *bases;
+  int *diffs, *slen;                  /* [nbox] */
+  int *script;
+} ReadArgs;
+
+void damar_launch_read_align(const ReadArgs *a, u32 grid, hipStream_t st);
+u32  damar_read_align_grid(void);     /* workgroups of the largest launch: beyond that many boxes a workgroup does several */
+
 /* box_trace.hip: exact alignment of a batch of boxes into trace pairs (align.c:4734 DIFF_TRACE).  Box i is m[i] bases of A
    against n[i] of B, its A side beginning abpos[i] bases into A's grid of tspace.  A box with max(m, n) <= maxlen <=
    DAMAR_TBOX_MAXLEN and no more intervals than the kernel's ledger holds is done and leaves its differences, the number

@@ -5074,6 +5074,108 @@ extern "C" int damar_align_boxes(const damar_box_batch *b, int *diffs, int64 *so
   return 0;
 }
 
+/***** the same for boxes of read length, LAcorrect's postrace (kernels/read_align.hip) ******/
+
+static struct : DevStage        /* ms and cnt as in BX */
+{ DBuf order{*this}, m{*this}, n{*this}, aoff{*this}, boff{*this}, coff{*this}, bases{*this}, diffs{*this}, slen{*this}, script{*this};
+} RD;
+
+extern "C" void damar_read_release(void) { RD.release(); }
+
+extern "C" unsigned int damar_read_grid(void) { return damar_read_align_grid(); }
+
+extern "C" void damar_read_last(double *ms, int64 *cnt) { RD.last(ms, cnt, 3); }
+
+extern "C" int damar_postrace_on_host(void)
+{ const char *e = getenv("DAMAR_POSTRACE");
+  return e != NULL && strcmp(e, "host") == 0;
+}
+
+extern "C" int damar_align_reads(const damar_box_batch *b, int *diffs, int64 *soff, int **script)
+{ const double w0 = now_ms();
+  if (b == NULL || soff == NULL || script == NULL || b->nbox < 0 || (b->nbox > 0 && diffs == NULL))
+    { fprintf(stderr, "damar: reads: malformed batch\n");
+      return 1;
+    }
+  const size_t nb = (size_t) b->nbox;
+  if (b->nbox >= ((int64) 1 << 31))
+    { fprintf(stderr, "damar: reads: a batch holds fewer than 2^31 boxes\n");
+      return 1;
+    }
+  for (size_t i = 0; i < nb; i++)
+    if (b->m[i] < 1 || b->n[i] < 1 || b->aoff[i] < 0 || b->boff[i] < 0 || b->aoff[i] + b->m[i] > b->nbases || b->boff[i] + b->n[i] > b->nbases)
+      { fprintf(stderr, "damar: reads: box %zu (%d x %d) does not lie inside the %lld bases\n", i, b->m[i], b->n[i], (long long) b->nbases);
+        return 1;
+      }
+  /* every box gets max(m, n) values of room; the scripts are moved together at the end */
+  std::vector<long long> room(nb + 1);
+  room[0] = 0;
+  for (size_t i = 0; i < nb; i++)
+    room[i + 1] = room[i] + std::max(b->m[i], b->n[i]);
+  std::vector<int> wide((size_t) room[nb] + 1), slen(nb, -1);
+  for (int i = 0; i < 4; i++) RD.ms[i] = 0;
+  int64 fallback = 0;
+
+  const bool host = damar_postrace_on_host();
+  if (!host && nb > 0)
+    { ensure_init();
+      late_streams();               /* see damar_align_boxes */
+      /* longest first: the workgroups take the boxes in this order, and the longest box is the launch's critical path */
+      std::vector<u32> order(nb);
+      for (size_t i = 0; i < nb; i++) order[i] = (u32) i;
+      std::stable_sort(order.begin(), order.end(),
+                       [&](u32 x, u32 y) { return std::max(b->m[x], b->n[x]) > std::max(b->m[y], b->n[y]); });
+      ReadArgs a;
+      memset(&a, 0, sizeof(a));
+      a.nbox = (u32) nb;
+      a.maxdiff = test_limit("DAMAR_TEST_READ_DIFFS", DAMAR_READ_MAXDIFF, 0);
+      const u32 grid = (u32) test_limit("DAMAR_TEST_READ_GRID", (int) damar_read_align_grid(), 1);
+      int *d_diffs = (int *) RD.diffs.need(sizeof(int) * nb), *d_slen = (int *) RD.slen.need(sizeof(int) * nb);
+      int *d_script = (int *) RD.script.need(sizeof(int) * ((size_t) room[nb] + 1));
+      RD.mark(0);
+      a.order = up(RD.order, order.data(), nb);
+      a.m = up(RD.m, b->m, nb);
+      a.n = up(RD.n, b->n, nb);
+      a.aoff = (const long long *) up(RD.aoff, b->aoff, nb);
+      a.boff = (const long long *) up(RD.boff, b->boff, nb);
+      a.coff = up(RD.coff, room.data(), nb + 1);
+      a.bases = (const u8 *) up(RD.bases, b->bases, (size_t) b->nbases);
+      HIP_CHECK(hipMemsetAsync(d_slen, 0xff, sizeof(int) * nb, G_st));
+      RD.mark(1);
+      a.diffs = d_diffs;  a.slen = d_slen;  a.script = d_script;
+      damar_launch_read_align(&a, grid, G_st);
+      HIP_CHECK(hipGetLastError());
+      RD.mark(2);
+      HIP_CHECK(hipMemcpyAsync(diffs, d_diffs, sizeof(int) * nb, hipMemcpyDeviceToHost, G_st));
+      HIP_CHECK(hipMemcpyAsync(slen.data(), d_slen, sizeof(int) * nb, hipMemcpyDeviceToHost, G_st));
+      if (room[nb] > 0)
+        HIP_CHECK(hipMemcpyAsync(wide.data(), d_script, sizeof(int) * (size_t) room[nb], hipMemcpyDeviceToHost, G_st));
+      RD.mark(3);
+      HIP_CHECK(hipStreamSynchronize(G_st));
+      RD.laps(0, 3);
+    }
+  /* what the kernel left: boxes beyond its bounds (and all of them with DAMAR_POSTRACE=host) */
+  for (size_t i = 0; i < nb; i++)
+    if (slen[i] < 0)
+      { diffs[i] = damar_exact_box(b->bases + b->aoff[i], b->m[i], b->bases + b->boff[i], b->n[i], wide.data() + room[i], &slen[i]);
+        fallback += host ? 0 : 1;
+      }
+  soff[0] = 0;
+  for (size_t i = 0; i < nb; i++)
+    soff[i + 1] = soff[i] + slen[i];
+  *script = (int *) malloc(sizeof(int) * (size_t) soff[nb] + 8);
+  if (*script == NULL)
+    { fprintf(stderr, "damar: out of memory (reads)\n");
+      return 1;
+    }
+  for (size_t i = 0; i < nb; i++)
+    if (slen[i] > 0)
+      memcpy(*script + soff[i], wide.data() + room[i], sizeof(int) * (size_t) slen[i]);
+  RD.cnt[0] = b->nbox;  RD.cnt[1] = fallback;  RD.cnt[2] = soff[nb];
+  RD.ms[3] = now_ms() - w0;
+  return 0;
+}
+
 /***** exact alignment of a batch of boxes into trace pairs: Compute_Alignment(DIFF_TRACE) (kernels/box_trace.hip) ******/
 
 static struct : DevStage        /* ms of the last call: upload, kernel, download (HIP events), whole call (wall);

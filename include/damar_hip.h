@@ -321,6 +321,20 @@ void damar_box_release(void);              /* frees the cached device buffers of
 void damar_box_last(double *ms, int64 *cnt);
 unsigned int damar_box_grid(void);         /* workgroups of the kernel's largest launch: a batch of more boxes gives a workgroup several */
 
+/* The same alignment for boxes of read length -- a read against its correction, what LAcorrect writes behind " postrace=":
+ * the batch, diffs, soff and *script are those of damar_align_boxes.  Runs kernels/read_align.hip, one workgroup of eight
+ * wavefronts per box, the boxes dealt longest first; what bounds a box there is its differences, not its length: a box of
+ * more than DAMAR_READ_MAXDIFF (8000) differences, or with max(m, n) above DAMAR_READ_MAXLEN (2^20), goes to the host
+ * routine of host/bridge.c (DAMAR_TEST_READ_DIFFS lowers the first bound and DAMAR_TEST_READ_GRID the workgroups of a
+ * launch, for tests).  With DAMAR_POSTRACE=host the host routine does all boxes and no GPU is touched.  0 on success. */
+int  damar_align_reads(const damar_box_batch *b, int *diffs, int64 *soff, int **script);
+void damar_read_release(void);             /* frees the cached device buffers of damar_align_reads */
+/* of the last call: ms[4] = upload, kernel, download (HIP events; 0 on the host path), whole call (wall);
+ * cnt[3] = boxes, boxes the host routine did beside the kernel, script values */
+void damar_read_last(double *ms, int64 *cnt);
+unsigned int damar_read_grid(void);        /* workgroups of the kernel's largest launch: a batch of more boxes gives a workgroup several */
+int  damar_postrace_on_host(void);         /* DAMAR_POSTRACE=host */
+
 /* Exact alignment of a batch of boxes into trace pairs (Compute_Alignment(DIFF_TRACE), align.c:4734 through trace_nd and
  * split_nd): box i is A = bases + aoff[i], m[i] >= 1 bases, against B = bases + boff[i], n[i] >= 1 bases, one base per
  * byte, B already complemented where that is wanted.  abpos[i] >= 0 is where the box begins in A (or that position modulo
