@@ -742,10 +742,10 @@ def align_boxes(a_seqs, b_seqs):
     return _align(_lib().damar_align_boxes, "damar_align_boxes", a_seqs, b_seqs)
 
 
-def _align(call, name, a_seqs, b_seqs):
+def _box_columns(a_seqs, b_seqs):
+    """The sequences of a batch of boxes as the arrays behind a BoxBatch or TBoxBatch, to be kept alive while the batch is
+    in use: -> (m, n, aoff, boff, bases, nbases), the bases of all boxes in one array, A before B."""
     import numpy as np
-    if len(a_seqs) != len(b_seqs):
-        raise ValueError("one B sequence per A sequence")
     nb = len(a_seqs)
     seqs = [np.ascontiguousarray(x, dtype=np.uint8) for pair in zip(a_seqs, b_seqs) for x in pair]
     if any(len(x) == 0 for x in seqs):
@@ -754,9 +754,17 @@ def _align(call, name, a_seqs, b_seqs):
     offs = np.concatenate([[0], np.cumsum(lens.reshape(-1))]).astype(np.int64)
     bases = np.concatenate(seqs) if nb else np.zeros(1, dtype=np.uint8)
     m, n = (np.ascontiguousarray(lens[:, k], dtype=np.int32) for k in (0, 1))
-    aoff, boff = np.ascontiguousarray(offs[:-1:2]), np.ascontiguousarray(offs[1::2])
+    return m, n, np.ascontiguousarray(offs[:-1:2]), np.ascontiguousarray(offs[1::2]), bases, int(offs[-1])
+
+
+def _align(call, name, a_seqs, b_seqs):
+    import numpy as np
+    if len(a_seqs) != len(b_seqs):
+        raise ValueError("one B sequence per A sequence")
+    nb = len(a_seqs)
+    m, n, aoff, boff, bases, nbases = _box_columns(a_seqs, b_seqs)
     bb = BoxBatch(nb, m.ctypes.data_as(_PI), n.ctypes.data_as(_PI), aoff.ctypes.data_as(C.POINTER(c_int64)),
-                  boff.ctypes.data_as(C.POINTER(c_int64)), bases.ctypes.data, int(offs[-1]))
+                  boff.ctypes.data_as(C.POINTER(c_int64)), bases.ctypes.data, nbases)
     diffs, soff, script = np.zeros(max(nb, 1), dtype=np.int32), np.zeros(nb + 1, dtype=np.int64), _PI()
     if call(C.byref(bb), diffs.ctypes.data_as(_PI), soff.ctypes.data_as(C.POINTER(c_int64)), C.byref(script)):
         raise RuntimeError(name + " failed")
@@ -810,20 +818,13 @@ def trace_boxes(a_seqs, b_seqs, a_starts, tspace):
     if int(tspace) < 1:
         raise ValueError("the trace spacing is at least 1")
     nb = len(a_seqs)
-    seqs = [np.ascontiguousarray(x, dtype=np.uint8) for pair in zip(a_seqs, b_seqs) for x in pair]
-    if any(len(x) == 0 for x in seqs):
-        raise ValueError("a box has at least one base on either side")
-    lens = np.array([len(x) for x in seqs], dtype=np.int64).reshape(nb, 2)
-    offs = np.concatenate([[0], np.cumsum(lens.reshape(-1))]).astype(np.int64)
-    bases = np.concatenate(seqs) if nb else np.zeros(1, dtype=np.uint8)
-    m, n = (np.ascontiguousarray(lens[:, k], dtype=np.int32) for k in (0, 1))
+    m, n, aoff, boff, bases, nbases = _box_columns(a_seqs, b_seqs)
     ab = np.ascontiguousarray(a_starts, dtype=np.int32).reshape(nb)
     if nb and ab.min() < 0:
         raise ValueError("a box begins at or behind position 0 of A")
-    aoff, boff = np.ascontiguousarray(offs[:-1:2]), np.ascontiguousarray(offs[1::2])
     i64p = C.POINTER(c_int64)
     tb = TBoxBatch(nb, m.ctypes.data_as(_PI), n.ctypes.data_as(_PI), ab.ctypes.data_as(_PI), aoff.ctypes.data_as(i64p),
-                   boff.ctypes.data_as(i64p), bases.ctypes.data, int(offs[-1]), int(tspace))
+                   boff.ctypes.data_as(i64p), bases.ctypes.data, nbases, int(tspace))
     diffs, toff, trace = np.zeros(max(nb, 1), dtype=np.int32), np.zeros(nb + 1, dtype=np.int64), C.POINTER(C.c_uint16)()
     if L.damar_trace_boxes(C.byref(tb), diffs.ctypes.data_as(_PI), toff.ctypes.data_as(i64p), C.byref(trace)):
         raise RuntimeError("damar_trace_boxes failed")

@@ -518,11 +518,15 @@ void damar_launch_tile_consensus(const TileArgs *a, hipStream_t st);
 /* box_align.hip: exact alignment of a batch of boxes with their edit scripts (align.c:4734 DIFF_ALIGN).  A box with
    max(m, n) <= maxlen <= DAMAR_BOX_MAXLEN is done and leaves its differences, the length of its script (-1: it hit a bound of
    the kernel and is the host's after all) and the script at script + coff[box], max(m, n) values of room; the others are
-   not touched. */
+   not touched.  read_align.hip takes the same record: maxdiff and order are its own, and box_align reads neither. */
 #define DAMAR_BOX_MAXLEN 1000
 typedef struct
 { u32 nbox;
-  int maxlen;
+  union
+  { int maxlen;                       /* the kernel's bound: box_align's on max(m, n), */
+    int maxdiff;                      /* read_align's on the differences of a box */
+  };
+  const u32 *order;                   /* read_align's: [nbox], the order its workgroups take the boxes in */
   const int *m, *n;                   /* [nbox] */
   const long long *aoff, *boff;       /* [nbox] bytes into bases */
   const long long *coff;              /* [nbox] values into script */
@@ -540,19 +544,8 @@ u32  damar_box_align_grid(void);      /* workgroups of the largest launch: beyon
    beyond either bound, or one that hits a loop bound, has length -1 and is the host's. */
 #define DAMAR_READ_MAXDIFF 8000
 #define DAMAR_READ_MAXLEN  (1 << 20)
-typedef struct
-{ u32 nbox;
-  int maxdiff;
-  const u32 *order;                   /* [nbox] */
-  const int *m, *n;                   /* [nbox] */
-  const long long *aoff, *boff;       /* [nbox] bytes into bases */
-  const long long *coff;              /* [nbox] values into script */
-  const u8  *bases;
-  int *diffs, *slen;                  /* [nbox] */
-  int *script;
-} ReadArgs;
 
-void damar_launch_read_align(const ReadArgs *a, u32 grid, hipStream_t st);
+void damar_launch_read_align(const BoxArgs *a, u32 grid, hipStream_t st);
 u32  damar_read_align_grid(void);     /* workgroups of the largest launch: beyond that many boxes a workgroup does several */
 
 /* box_trace.hip: exact alignment of a batch of boxes into trace pairs (align.c:4734 DIFF_TRACE).  Box i is m[i] bases of A

@@ -32,7 +32,7 @@
 static_assert((DAMAR_READ_MAXDIFF + 1) / 2 <= RA_HALF - 3, "the frontiers of a box of the most differences fit their buffers");
 
 __global__ __launch_bounds__(RA_THREADS)
-void read_align(ReadArgs a)
+void read_align(BoxArgs a)
 { __shared__ int s_f[2][RA_SPAN], s_g[2][RA_SPAN];
   __shared__ int s_todo[RA_STACK][4];     /* boxes still to do: a0, m, b0, n inside the top box */
   __shared__ int s_red[2][RA_THREADS / WAVE];
@@ -118,7 +118,7 @@ void read_align(ReadArgs a)
     }
 }
 
-void damar_launch_read_align(const ReadArgs *a, u32 grid, hipStream_t st)
+void damar_launch_read_align(const BoxArgs *a, u32 grid, hipStream_t st)
 { if (grid < 1 || grid > RA_GRID)
     grid = RA_GRID;
   if (a->nbox > 0)

@@ -11,7 +11,8 @@ import q_common
 
 pytestmark = pytest.mark.gpu
 DROP = ("DAMAR_PILES", "DAMAR_TRIM", "DAMAR_STITCH", "DAMAR_PILE_BATCH", "DAMAR_TEST_GAP_BINS", "DAMAR_TEST_FIX_SEGS",
-        "DAMAR_TEST_FILTER_LEN", "DAMAR_TEST_FILTER_GROUP", "DAMAR_TEST_CORRECT_COLS", "DAMAR_TEST_BOX_LIMIT")
+        "DAMAR_TEST_FILTER_LEN", "DAMAR_TEST_FILTER_GROUP", "DAMAR_TEST_CORRECT_COLS", "DAMAR_TEST_BOX_LIMIT", "DAMAR_POSTRACE",
+        "DAMAR_TEST_READ_DIFFS", "DAMAR_TEST_READ_GRID")
 RECORD_COLS = ("abpos", "aepos", "bbpos", "bepos", "bread", "flags", "diffs", "tlen", "trace_off")
 PHASES = ("upload", "kernel", "download")
 
@@ -146,8 +147,17 @@ def correct_stage():
     return lambda part: api.tile_consensus(parts[part]), api.correct_last, "correct", "DAMAR_PILES", PHASES
 
 
+def read_stage():
+    import read_align_common as rc
+    from damar_amd import api
+    bx = rc.boxes()
+    a, b = rc.box_seqs(bx, rc.family_rows(bx, "many"))                       # forty short boxes
+    parts = dict(head=(a[:2], b[:2]), whole=(a, b))
+    return lambda part: api.align_reads(*parts[part]), api.read_last, "read", "DAMAR_POSTRACE", PHASES
+
+
 STAGES = dict(pile=pile_stage, q=q_stage, homog=homog_stage, box=box_stage, tbox=tbox_stage, gap=gap_stage, fix=fix_stage,
-              filter=filter_stage, correct=correct_stage)
+              filter=filter_stage, correct=correct_stage, read=read_stage)
 
 
 @pytest.mark.parametrize("stage", sorted(STAGES))
