@@ -436,7 +436,8 @@ typedef struct
   int *cnt;                           /* [npiles * 3]: contained, breaks, records dropped */
 } GapArgs;
 
-void damar_launch_pile_gaps(const GapArgs *a, hipStream_t st);
+void damar_launch_pile_gaps(const GapArgs *a, u32 grid, hipStream_t st);      /* min(npiles, grid) workgroups */
+u32  damar_pile_gaps_grid(void);      /* workgroups of the largest launch: beyond that many piles a workgroup does several */
 
 /* pile_filter.hip: LAfilter's screens, one wavefront per pile (include/damar_hip.h damar_pile_filter; the DAMAR_FILTER_*
    bounds, the DAMAR_FR_* reason bits and the DAMAR_FC_* counters are defined there).  A pile with status 1 afterwards is the

@@ -284,9 +284,13 @@ void pile_gaps(GapArgs a)
     }
 }
 
-void damar_launch_pile_gaps(const GapArgs *a, hipStream_t st)
+void damar_launch_pile_gaps(const GapArgs *a, u32 grid, hipStream_t st)
 { if (a->npiles == 0)
     return;
-  const u32 blocks = a->npiles < PG_MAX_BLOCKS ? a->npiles : PG_MAX_BLOCKS;
+  if (grid < 1 || grid > PG_MAX_BLOCKS)
+    grid = PG_MAX_BLOCKS;
+  const u32 blocks = a->npiles < grid ? a->npiles : grid;
   hipLaunchKernelGGL(pile_gaps, dim3(blocks), dim3(PG_THREADS), 0, st, *a);
 }
+
+u32 damar_pile_gaps_grid(void) { return PG_MAX_BLOCKS; }

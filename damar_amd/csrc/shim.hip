@@ -5323,7 +5323,7 @@ extern "C" int damar_pile_gaps(const damar_pile_batch *b, const damar_gap_params
       a.pile_off = d.off;  a.pile_aread = d.aread;
       a.abpos = d.col[0];  a.aepos = d.col[1];  a.bbpos = d.col[2];  a.bepos = d.col[3];  a.bread = d.col[4];  a.flags = d.col[5];
       a.flags_out = d_flags;  a.status = d_status;  a.nev = d_nev;  a.ev = d_ev;  a.cnt = d_cnt;
-      damar_launch_pile_gaps(&a, G_st);
+      damar_launch_pile_gaps(&a, (u32) test_limit("DAMAR_TEST_GAP_GRID", (int) damar_pile_gaps_grid(), 1), G_st);
       HIP_CHECK(hipGetLastError());
       GP.mark(2);
       evs.resize(evints + 1);

@@ -398,8 +398,9 @@ void damar_homog_last(double *ms, int64 *cnt);
  * interval), _STITCHABLE (v0: pairs), _DROP_L, _DROP_R, _DROP_NONE (no record left to decide the side), with
  * DAMAR_GAP_TRAILING or'ed in for the open run.  Runs kernels/pile_gaps.hip, one wavefront per pile; a pile on a read of more
  * than DAMAR_GAP_MAXBINS bins (DAMAR_TEST_GAP_BINS lowers that, for tests), one with more than DAMAR_GAP_MAXEVENTS events,
- * and one whose B reads do not ascend is done by the routine of host/gap.c.  With DAMAR_PILES=host that routine does all
- * piles and no GPU is touched.  0 on success, 1 after a message. */
+ * and one whose B reads do not ascend is done by the routine of host/gap.c.  DAMAR_TEST_GAP_GRID lowers the number of
+ * workgroups, for tests: each then takes several piles, as in a batch of more piles than the largest launch has workgroups.
+ * With DAMAR_PILES=host that routine does all piles and no GPU is touched.  0 on success, 1 after a message. */
 #define DAMAR_GAP_MAXBINS    4096          /* bins of 100 bases the kernel keeps in LDS: reads up to 409 500 bases */
 #define DAMAR_GAP_MAXEVENTS  16            /* events of a pile the kernel has room for */
 #define DAMAR_GAP_EVENT_INTS 6

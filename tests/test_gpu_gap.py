@@ -10,7 +10,7 @@ import q_common
 
 pytestmark = pytest.mark.gpu
 CASES = gc.load_cases()
-DROP = ("DAMAR_PILES", "DAMAR_TRIM", "DAMAR_TEST_GAP_BINS", "DAMAR_TEST_BOX_LIMIT", "DAMAR_PILE_BATCH")
+DROP = ("DAMAR_PILES", "DAMAR_TRIM", "DAMAR_TEST_GAP_BINS", "DAMAR_TEST_GAP_GRID", "DAMAR_TEST_BOX_LIMIT", "DAMAR_PILE_BATCH")
 
 
 @pytest.fixture(autouse=True)
@@ -55,6 +55,15 @@ def test_planted_piles_match_the_host_routine(planted, kw, monkeypatch):
     assert [int(piles["pile_aread"][i]) for i in over] == [many]
     assert (npiles, host_piles, nev) == (len(events), 1, sum(len(e) for e in events))
     assert ms["kernel"] > 0
+
+
+@pytest.mark.parametrize("kw", [dict(), dict(stitch=300), dict(exclude=True), dict(stitch=300, exclude=True)], ids=["def", "s300", "e", "es"])
+def test_random_piles_match_the_host_routine(kw, monkeypatch):
+    import gap_shapes
+    piles, rl, ex = gap_shapes.random_piles()
+    kw = dict(kw, exclude=ex) if kw.get("exclude") else kw
+    host, (ms, npiles, host_piles, nev) = both_paths(piles, rl, monkeypatch, **kw)
+    assert (npiles, nev) == (len(host[1]), sum(len(e) for e in host[1]))
 
 
 def test_bin_limit_leaves_only_the_longest_read(planted, monkeypatch):
