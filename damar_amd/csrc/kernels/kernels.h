@@ -464,7 +464,8 @@ typedef struct
   int *cnt;                           /* [npiles * DAMAR_FC_COUNT] */
 } FilterArgs;
 
-void damar_launch_pile_filter(const FilterArgs *a, hipStream_t st);
+void damar_launch_pile_filter(const FilterArgs *a, u32 grid, hipStream_t st);      /* min(npiles, grid) workgroups */
+u32  damar_pile_filter_grid(void);    /* workgroups of the largest launch: beyond that many piles a workgroup does several */
 
 /* pile_patch.hip: LAfix's breaks and weak segments, one wavefront per pile (include/damar_hip.h damar_pile_patches; the
    DAMAR_FIX_* bounds and damar_fix_gap are defined there).  Pile q writes its repairs to gaps + slot_off[q], where it has

@@ -561,9 +561,13 @@ void pile_filter(FilterArgs a)
     }
 }
 
-void damar_launch_pile_filter(const FilterArgs *a, hipStream_t st)
+void damar_launch_pile_filter(const FilterArgs *a, u32 grid, hipStream_t st)
 { if (a->npiles == 0)
     return;
-  const u32 blocks = a->npiles < FL_MAX_BLOCKS ? a->npiles : FL_MAX_BLOCKS;
+  if (grid < 1 || grid > FL_MAX_BLOCKS)
+    grid = FL_MAX_BLOCKS;
+  const u32 blocks = a->npiles < grid ? a->npiles : grid;
   hipLaunchKernelGGL(pile_filter, dim3(blocks), dim3(FL_THREADS), sizeof(u32) * (size_t) a->mask_words, st, *a);
 }
+
+u32 damar_pile_filter_grid(void) { return FL_MAX_BLOCKS; }

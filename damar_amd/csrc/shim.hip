@@ -5444,7 +5444,7 @@ extern "C" int damar_pile_filter(const damar_trace_batch *t, const int *diffs, c
       a.diffs = d.col[6];  a.tlen = d.col[7];  a.trace_off = d.toff;  a.trace = d.trace;
       a.o_flags = d_out[0];  a.o_ae = d_out[1];  a.o_be = d_out[2];  a.o_df = d_out[3];  a.o_tl = d_out[4];  a.o_why = d_out[5];  a.o_by = d_out[6];
       a.status = d_status;  a.cnt = d_cnt;
-      damar_launch_pile_filter(&a, G_st);
+      damar_launch_pile_filter(&a, (u32) test_limit("DAMAR_TEST_FILTER_GRID", (int) damar_pile_filter_grid(), 1), G_st);
       HIP_CHECK(hipGetLastError());
       FL.mark(2);
       int *dst[7] = { out->flags, out->aepos, out->bepos, out->diffs, out->tlen, out->reason, out->cont_by };

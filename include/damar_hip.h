@@ -487,7 +487,9 @@ void damar_fix_last(double *ms, int64 *cnt);
  * that -R 6 found a record contained in, or -1.  Runs kernels/pile_filter.hip, one wavefront per pile; a pile with a run of
  * more than DAMAR_FILTER_MAXGROUP records of one B read, and under -z with -u a pile on a read of more than
  * DAMAR_FILTER_MAXLEN bases, is done by the routine of host/filter.c (DAMAR_TEST_FILTER_GROUP and DAMAR_TEST_FILTER_LEN lower
- * the two, for tests).  With DAMAR_PILES=host that routine does all piles and no GPU is touched.  0, or 1 after a message. */
+ * the two, for tests).  DAMAR_TEST_FILTER_GRID lowers the number of workgroups, for tests: each then takes several piles, as
+ * in a batch of more piles than the largest launch has workgroups.  With DAMAR_PILES=host that routine does all piles and no
+ * GPU is touched.  0, or 1 after a message. */
 #define DAMAR_FILTER_MAXGROUP 64           /* records of one B read in a row that one lane takes */
 #define DAMAR_FILTER_MAXLEN   400000       /* bases of the A read whose coverage bits the kernel keeps in LDS */
 enum { DAMAR_FILTER_PRE = 1, DAMAR_FILTER_MAIN = 2 };

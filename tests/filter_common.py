@@ -190,9 +190,10 @@ def sym_lists(text, nreads):
     return np.array(off, dtype=np.int32), np.array(ln, dtype=np.int32), np.array(data, dtype=np.int32)
 
 
-def opts_to_params(opts, inp, files):
-    """the options of a case as api.pile_filter takes them (without -T, -p, -a, -L, -v, which the pile call does not see)"""
-    ta, td, ra, rd = tracks(inp)
+def opts_to_params(opts, inp, files, own=None):
+    """the options of a case as api.pile_filter takes them (without -T, -p, -a, -L, -v, which the pile call does not see);
+    own: (trim anno, trim data, repeat anno, repeat data) in place of the input's tracks"""
+    ta, td, ra, rd = own or tracks(inp)
     nreads = len(ta) - 1
     kw = dict(trim=trim_pairs(ta, td), remove=0)
     ints = {"-f": "downsample", "-b": "seg_rate", "-l": "min_rlen", "-o": "min_olen", "-u": "max_unaligned", "-n": "min_nonrep", "-Y": "merge_tips",

@@ -4,6 +4,9 @@ field for field.  The names of the options are those api.pile_filter takes."""
 
 COMP, DISCARD, REPEAT, LOCAL, DIFF, STITCH, SYM, OLEN, RLEN = 0x1, 0x2, 0x8, 0x10, 0x20, 0x80, 0x100, 0x200, 0x400
 CONT, GAP, TRIM, MODULE = 0x8000, 0x10000, 0x20000, 0x40000
+# the method got wrong in one place each: what filter_pile and run_batch take as `mutant`
+MUTANTS = ("r4_single_count", "stitch_first", "z_enter_lt", "z_leave_gt", "z_bases_lt", "z_uncovered_ge", "cover_end_bit", "cover_outside_trim",
+           "w_skips_last", "cont_by_first", "b_last_segment", "one_byte_trace")
 # reason bits and counters, as include/damar_hip.h numbers them
 R_SYM, R_OLEN, R_LOCAL, R_DIFF, R_TIPS, R_ALEN, R_AREP, R_BLEN, R_BREP, R_TP, R_MULTI, R_SELF, R_CONT, R_HEAD = (1 << k for k in range(14))
 C_DIFFS, C_UNAL, C_CONT, C_LEN, C_REP, C_RLEN, C_LOWCOV, C_SYM, C_MULTI, C_MBASES, C_STITCHED = range(11)
@@ -77,10 +80,11 @@ def repeat_site(o, aread, rl, tab, tae, rep, need, tips):
 
 def filter_pile(aread, recs, rl, pre=True, main=True, downsample=0, seg_rate=-1, stitch=-1, stitch_aggr=False, min_rlen=-1, min_olen=-1,
                 max_unaligned=-1, min_nonrep=-1, max_diffs=-1.0, merge_tips=0, multi=False, lowcov=0, remove=0, trim=None, rep=None,
-                sym=None, read_state=None, include=False):
+                sym=None, read_state=None, include=False, mutant=None):
     """recs: dicts of b, ab, ae, bb, be, flags, diffs and trace (the values as they lie: diffs at even, B lengths at odd
     places; None once dropped).  trim(r) -> (b, e) or None without a track; rep(r) -> list of intervals; sym(r) -> the list
-    a read's pairs are looked up in.  Changes the records in place, adds `why` and `by`; -> the counters."""
+    a read's pairs are looked up in.  Changes the records in place, adds `why` and `by`; -> the counters.  mutant: one of
+    MUTANTS, the method got wrong in one place, for the tests that hold the shapes of tests/filter_shapes.py to their names."""
     import numpy as np
     cnt = [0] * 11
     for o in recs:
@@ -94,7 +98,7 @@ def filter_pile(aread, recs, rl, pre=True, main=True, downsample=0, seg_rate=-1,
         if 0 <= seg_rate <= 100:
             for o in recs:
                 t = o["trace"]
-                for k in range(0, len(t) - 2, 2):
+                for k in range(0, len(t) - (0 if mutant == "b_last_segment" else 2), 2):
                     with np.errstate(divide="ignore", invalid="ignore"):
                         bad = np.float64(t[k]) * 100.0 / np.float64(t[k + 1]) > seg_rate
                     if bad:
@@ -123,6 +127,8 @@ def filter_pile(aread, recs, rl, pre=True, main=True, downsample=0, seg_rate=-1,
                         if da < stitch and db < stitch and (stitch_aggr or abs(da - db) < 40):
                             if o["ae"] - o["ab"] > (recs[best]["ae"] - recs[best]["ab"] if best is not None else 0):
                                 best = k
+                                if mutant == "stitch_first":
+                                    break
                     if best is None:
                         break
                     o = recs[best]
@@ -181,7 +187,7 @@ def filter_pile(aread, recs, rl, pre=True, main=True, downsample=0, seg_rate=-1,
 
     if multi:
         for run in runs(recs):
-            live = [k for k in run if not recs[k]["flags"] & (STITCH | DISCARD)]
+            live = [k for k in (run[:-1] if mutant == "w_skips_last" else run) if not recs[k]["flags"] & (STITCH | DISCARD)]
             hit = any(inside(x["ab"], x["ae"], y["ab"], y["ae"]) or inside(y["ab"], y["ae"], x["ab"], x["ae"]) or
                       inside(x["bb"], x["be"], y["bb"], y["be"]) or inside(y["bb"], y["be"], x["bb"], x["be"])
                       for p, i in enumerate(live) for j in live[p + 1:] for x, y in [(recs[i], recs[j])])
@@ -194,15 +200,18 @@ def filter_pile(aread, recs, rl, pre=True, main=True, downsample=0, seg_rate=-1,
 
     if lowcov and tae - tab:
         live = [o for o in recs if not o["flags"] & DISCARD]
-        enter = sum(o["ab"] <= tab for o in live)
-        leave = sum(o["ae"] >= tae for o in live)
+        enter = sum(o["ab"] < tab if mutant == "z_enter_lt" else o["ab"] <= tab for o in live)
+        leave = sum(o["ae"] > tae if mutant == "z_leave_gt" else o["ae"] >= tae for o in live)
         bases = sum(o["ae"] - o["ab"] for o in live)
-        drop = int(bases / (tae - tab)) <= lowcov or enter < lowcov or leave < lowcov
+        mean = int(bases / (tae - tab))
+        drop = (mean < lowcov if mutant == "z_bases_lt" else mean <= lowcov) or enter < lowcov or leave < lowcov
         if max_unaligned != -1:
             cov = np.zeros(alen + 1, dtype=bool)
             for o in live:
-                cov[max(o["ab"], 0):min(o["ae"], alen)] = True
-            drop = drop or (tae - tab) - int(cov[tab:tae].sum()) > max_unaligned
+                cov[max(o["ab"], 0):min(o["ae"], alen) - (1 if mutant == "cover_end_bit" else 0)] = True
+            lo, hi = (0, alen) if mutant == "cover_outside_trim" else (tab, tae)
+            bare = (hi - lo) - int(cov[lo:hi].sum())
+            drop = drop or (bare >= max_unaligned if mutant == "z_uncovered_ge" else bare > max_unaligned)
         if drop:
             for o in live:
                 o["flags"] |= DISCARD
@@ -225,7 +234,8 @@ def filter_pile(aread, recs, rl, pre=True, main=True, downsample=0, seg_rate=-1,
         if remove & 16:
             for run in runs(recs):
                 # the reference counts the first record of every run but the pile's first twice
-                n = sum(is_proper(recs[k]) for k in run) + (1 if run[0] > 0 and is_proper(recs[run[0]]) else 0)
+                twice = run[0] > 0 and mutant != "r4_single_count"
+                n = sum(is_proper(recs[k]) for k in run) + (1 if twice and is_proper(recs[run[0]]) else 0)
                 if n == 1 and len(run) > 1:
                     for k in run:
                         if not is_proper(recs[k]):
@@ -252,7 +262,7 @@ def filter_pile(aread, recs, rl, pre=True, main=True, downsample=0, seg_rate=-1,
                         if gone:
                             y["flags"] |= DISCARD | CONT
                             y["why"] |= R_CONT
-                            y["by"] = i
+                            y["by"] = run[0] if mutant == "cont_by_first" else i
                             cnt[C_CONT] += 1
 
     if read_state is not None:
@@ -267,7 +277,7 @@ def run_batch(batch, rl, **kw):
     """the model over a batch of the tests' trace_batch form with api.pile_filter's keywords: -> the same dict of arrays"""
     import numpy as np
     trim_arr, reps, sym = kw.pop("trim", None), kw.pop("repeats", None), kw.pop("sym", None)
-    steps = kw.pop("steps", 3)
+    steps, mutant = kw.pop("steps", 3), kw.get("mutant")
     trim = None if trim_arr is None else (lambda r: (int(trim_arr[2 * r]), int(trim_arr[2 * r + 1])))
     rep = None
     if reps is not None:
@@ -286,7 +296,7 @@ def run_batch(batch, rl, **kw):
         recs = []
         for i in range(lo, hi):
             raw = batch["trace"][int(batch["trace_off"][i]):int(batch["trace_off"][i]) + tb * int(batch["tlen"][i])]
-            vals = raw if tb == 1 else raw.view("<u2")
+            vals = raw if tb == 1 else raw[0::2] if mutant == "one_byte_trace" else raw.view("<u2")
             recs.append(dict(b=int(batch["bread"][i]), ab=int(batch["abpos"][i]), ae=int(batch["aepos"][i]), bb=int(batch["bbpos"][i]),
                              be=int(batch["bepos"][i]), flags=int(batch["flags"][i]), diffs=int(batch["diffs"][i]), trace=[int(x) for x in vals]))
         cnts.append(filter_pile(int(aread), recs, [int(x) for x in rl], pre=bool(steps & 1), main=bool(steps & 2), trim=trim, rep=rep, sym=symf, **kw))

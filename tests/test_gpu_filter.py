@@ -11,7 +11,8 @@ import q_common
 
 pytestmark = pytest.mark.gpu
 CASES = fc.load_cases()
-DROP = ("DAMAR_PILES", "DAMAR_TRIM", "DAMAR_TEST_FILTER_LEN", "DAMAR_TEST_FILTER_GROUP", "DAMAR_TEST_BOX_LIMIT", "DAMAR_PILE_BATCH")
+DROP = ("DAMAR_PILES", "DAMAR_TRIM", "DAMAR_TEST_FILTER_LEN", "DAMAR_TEST_FILTER_GROUP", "DAMAR_TEST_FILTER_GRID", "DAMAR_TEST_BOX_LIMIT",
+        "DAMAR_PILE_BATCH")
 NAMES = ("flags", "aepos", "bepos", "diffs", "tlen", "reason", "cont_by", "cnt")
 # the option sets of the pile call: what the cases run on the planted file, without the options only the file pass sees
 SETS = {c["name"][:-6]: [o for o in c["opts"] if o not in ("-v", "-p", "-T", "-L")] for c in CASES if c["input"] == "fsynth"}

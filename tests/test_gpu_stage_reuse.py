@@ -12,7 +12,7 @@ import q_common
 pytestmark = pytest.mark.gpu
 DROP = ("DAMAR_PILES", "DAMAR_TRIM", "DAMAR_STITCH", "DAMAR_PILE_BATCH", "DAMAR_TEST_GAP_BINS", "DAMAR_TEST_FIX_SEGS",
         "DAMAR_TEST_FILTER_LEN", "DAMAR_TEST_FILTER_GROUP", "DAMAR_TEST_CORRECT_COLS", "DAMAR_TEST_BOX_LIMIT", "DAMAR_POSTRACE",
-        "DAMAR_TEST_READ_DIFFS", "DAMAR_TEST_READ_GRID")
+        "DAMAR_TEST_READ_DIFFS", "DAMAR_TEST_READ_GRID", "DAMAR_TEST_FILTER_GRID")
 RECORD_COLS = ("abpos", "aepos", "bbpos", "bepos", "bread", "flags", "diffs", "tlen", "trace_off")
 PHASES = ("upload", "kernel", "download")
 
