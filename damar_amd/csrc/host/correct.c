@@ -23,8 +23,6 @@
 #define MIN_TWIDTH   20                   /* LAcorrect.c:33-36 */
 #define MAX_COVERAGE DAMAR_CORRECT_MAXCOV
 #define MAX_TILES    40
-#define OVL_COMP     0x1                  /* lib/oflags.h */
-#define OVL_DISCARD  0x2
 #define REC_BYTES    40                   /* a record's header in the file */
 #define LINE_WIDTH   100
 
@@ -37,15 +35,6 @@ static double now_ms(void)
 { struct timeval tv;
   gettimeofday(&tv, NULL);
   return tv.tv_sec * 1e3 + tv.tv_usec * 1e-3;
-}
-
-static void *grow(void *p, size_t n)
-{ void *q = realloc(p, n ? n : 1);
-  if (q == NULL)
-    { fprintf(stderr, "damar: out of memory (%zu bytes, correct)\n", n);
-      exit(1);
-    }
-  return q;
 }
 
 /***** the plain routine for one tile ************************************************************/
@@ -100,21 +89,18 @@ int damar_host_tile(const damar_tile_batch *b, int64 tile, unsigned char **out, 
     }
   if (cols > g_cols)
     { g_cols = cols + cols / 4 + 1024;
-      g_w.cnt = (unsigned char *) grow(g_w.cnt, 5 * (size_t) g_cols);
-      g_w.pc = (unsigned char *) grow(g_w.pc, (size_t) g_cols);
+      g_w.cnt = (unsigned char *) damar_grow(g_w.cnt, 5 * (size_t) g_cols, "correct");
+      g_w.pc = (unsigned char *) damar_grow(g_w.pc, (size_t) g_cols, "correct");
     }
   if (cols + longest > g_script)
     { g_script = cols + longest + 1024;
-      g_w.script = (int *) grow(g_w.script, sizeof(int) * (size_t) g_script);
+      g_w.script = (int *) damar_grow(g_w.script, sizeof(int) * (size_t) g_script, "correct");
     }
-  if (cols > *cap)
-    { *cap = cols + cols / 4 + 1024;
-      *out = (unsigned char *) grow(*out, (size_t) *cap);
-    }
+  *out = (unsigned char *) damar_reserve(*out, cap, cols, 1, 1024, "correct");
   if (g_cells == 0)
     { g_cells = 1 << 16;
-      g_w.vf = (int *) grow(g_w.vf, sizeof(int) * (size_t) g_cells);
-      g_w.hf = (signed char *) grow(g_w.hf, (size_t) g_cells);
+      g_w.vf = (int *) damar_grow(g_w.vf, sizeof(int) * (size_t) g_cells, "correct");
+      g_w.hf = (signed char *) damar_grow(g_w.hf, (size_t) g_cells, "correct");
     }
   g_w.maxcols = (int) cols;
   g_w.maxscript = (int) (cols + longest);
@@ -128,8 +114,8 @@ int damar_host_tile(const damar_tile_batch *b, int64 tile, unsigned char **out, 
           return -1;
         }
       g_cells *= 2;
-      g_w.vf = (int *) grow(g_w.vf, sizeof(int) * (size_t) g_cells);
-      g_w.hf = (signed char *) grow(g_w.hf, (size_t) g_cells);
+      g_w.vf = (int *) damar_grow(g_w.vf, sizeof(int) * (size_t) g_cells, "correct");
+      g_w.hf = (signed char *) damar_grow(g_w.hf, (size_t) g_cells, "correct");
     }
   if (st != 0)
     { fprintf(stderr, "damar: correct: the path of tile %lld left its waves\n", (long long) tile);
@@ -149,20 +135,15 @@ typedef struct
   int64 ntoff, ntovl, norder;
 } Layout;
 
-static int trace_at(const damar_trace_batch *t, int64 rec, int k)
-{ const unsigned char *p = t->trace + t->trace_off[rec];
-  return t->tbytes == 1 ? p[k] : (p[2 * k] | (p[2 * k + 1] << 8));
-}
-
 static int valid_pt_points(const damar_trace_batch *t, int64 rec)        /* has_valid_pt_points, LAcorrect.c:173 */
 { const int bbpos = t->p.bbpos[rec], bepos = t->p.bepos[rec], tlen = t->tlen[rec];
-  int bb, be = bbpos + trace_at(t, rec, 1), k;
+  int bb, be = bbpos + damar_trace_value(t, rec, 1), k;
   for (k = 2; k < tlen; k += 2)
     { bb = be;
       if (k == tlen - 1)
         be = bepos + 1;
       else
-        be += trace_at(t, rec, k + 1);
+        be += damar_trace_value(t, rec, k + 1);
       if (bb > be || bb < bbpos || bb > bepos || be < bbpos || be > bepos + 1)
         return 0;
     }
@@ -206,8 +187,8 @@ static int layout_pile(Layout *L, const damar_trace_batch *t, const int *rec, in
   int i, k, p = 0, tile;
   if ((int64) ntiles + 2 > L->ntoff)
     { L->ntoff = ntiles + ntiles / 4 + 64;
-      L->toff = (int *) grow(L->toff, sizeof(int) * (size_t) L->ntoff);
-      L->cur = (int *) grow(L->cur, sizeof(int) * (size_t) L->ntoff);
+      L->toff = (int *) damar_grow(L->toff, sizeof(int) * (size_t) L->ntoff, "correct");
+      L->cur = (int *) damar_grow(L->cur, sizeof(int) * (size_t) L->ntoff, "correct");
     }
   memset(L->toff, 0, sizeof(int) * (size_t) (ntiles + 1));
   memset(L->cur, 0, sizeof(int) * (size_t) ntiles);
@@ -220,7 +201,7 @@ static int layout_pile(Layout *L, const damar_trace_batch *t, const int *rec, in
           return 1;
         }
       for (k = 1; k < t->tlen[r]; k += 2)
-        be += trace_at(t, r, k);
+        be += damar_trace_value(t, r, k);
       if (be > read_len[b])
         { fprintf(stderr, "damar: correct: the trace of a record of read %d runs past read %d\n", aread, b);
           return 1;
@@ -236,8 +217,8 @@ static int layout_pile(Layout *L, const damar_trace_batch *t, const int *rec, in
     L->toff[i] += L->toff[i - 1];
   if ((int64) L->toff[ntiles] + 1 > L->ntovl)
     { L->ntovl = L->toff[ntiles] + L->toff[ntiles] / 4 + 1024;
-      L->tovl = (Tile *) grow(L->tovl, sizeof(Tile) * (size_t) L->ntovl);
-      L->tmp = (Tile *) grow(L->tmp, sizeof(Tile) * (size_t) L->ntovl);
+      L->tovl = (Tile *) damar_grow(L->tovl, sizeof(Tile) * (size_t) L->ntovl, "correct");
+      L->tmp = (Tile *) damar_grow(L->tmp, sizeof(Tile) * (size_t) L->ntovl, "correct");
     }
   for (i = 0; i < ntiles; i++)
     { Tile *x;
@@ -251,26 +232,26 @@ static int layout_pile(Layout *L, const damar_trace_batch *t, const int *rec, in
   for (i = 0; i < n; i++)
     { const int64 r = lo + rec[i];
       const int comp = t->p.flags[r] & OVL_COMP, b = t->p.bread[r], abpos = t->p.abpos[r], aepos = t->p.aepos[r];
-      int be = t->p.bbpos[r] + trace_at(t, r, 1), bb;
+      int be = t->p.bbpos[r] + damar_trace_value(t, r, 1), bb;
       tile = abpos / tw;
       if (L->cur[tile] < MAX_TILES)
         { Tile *x;
           p = L->toff[tile] + L->cur[tile];
           L->cur[tile] += 1;
           x = L->tovl + p;
-          x->b = b;  x->comp = comp;  x->bb = t->p.bbpos[r];  x->be = be;  x->qv = trace_at(t, r, 0);
+          x->b = b;  x->comp = comp;  x->bb = t->p.bbpos[r];  x->be = be;  x->qv = damar_trace_value(t, r, 0);
           x->apos = (abpos % tw) ? abpos : 0;
         }
       for (k = 2; k < t->tlen[r]; k += 2)
         { tile += 1;
           bb = be;
-          be += trace_at(t, r, k + 1);
+          be += damar_trace_value(t, r, k + 1);
           if (L->cur[tile] < MAX_TILES)
             { Tile *x;
               p = L->toff[tile] + L->cur[tile];
               L->cur[tile] += 1;
               x = L->tovl + p;
-              x->b = b;  x->comp = comp;  x->bb = bb;  x->be = be;  x->qv = trace_at(t, r, k);  x->apos = 0;
+              x->b = b;  x->comp = comp;  x->bb = bb;  x->be = be;  x->qv = damar_trace_value(t, r, k);  x->apos = 0;
             }
           else
             p = -1;
@@ -323,7 +304,7 @@ static void *postrace_worker(void *arg)
       t0 = now_ms();
       { const HITS_READ *rd = w->blk->reads + j->aread;
         const char *A = (const char *) w->blk->bases + rd->boff;
-        j->script = (int *) grow(NULL, sizeof(int) * ((size_t) rd->rlen + (size_t) j->len + 8));
+        j->script = (int *) damar_grow(NULL, sizeof(int) * ((size_t) rd->rlen + (size_t) j->len + 8), "correct");
         damar_exact_box(A, rd->rlen, j->cons, j->len, j->script, &j->slen);
       }
       j->ms = now_ms() - t0;
@@ -368,9 +349,9 @@ static int wave_device(Wave *w, damar_correct_stats *st)
       }
   if (nb == 0)
     return 0;
-  mn = (int *) grow(NULL, sizeof(int) * 3 * (size_t) nb);
-  off = (int64 *) grow(NULL, sizeof(int64) * (3 * (size_t) nb + 1));
-  bases = (char *) grow(NULL, (size_t) nbases + 8);
+  mn = (int *) damar_grow(NULL, sizeof(int) * 3 * (size_t) nb, "correct");
+  off = (int64 *) damar_grow(NULL, sizeof(int64) * (3 * (size_t) nb + 1), "correct");
+  bases = (char *) damar_grow(NULL, (size_t) nbases + 8, "correct");
   diffs = mn + 2 * nb;
   soff = off + 2 * nb;
   for (i = 0; i < w->n; i++)
@@ -397,7 +378,7 @@ static int wave_device(Wave *w, damar_correct_stats *st)
       if (j->len == 0)
         continue;
       j->slen = (int) (soff[k + 1] - soff[k]);
-      j->script = (int *) grow(NULL, sizeof(int) * ((size_t) j->slen + 1));
+      j->script = (int *) damar_grow(NULL, sizeof(int) * ((size_t) j->slen + 1), "correct");
       memcpy(j->script, script + soff[k], sizeof(int) * (size_t) j->slen);
       k += 1;
     }
@@ -495,11 +476,11 @@ static int64 *read_ids(const char *path, int *n)                   /* fread_inte
   *n = 0;
   if (f == NULL)
     return NULL;
-  v = (int64 *) grow(NULL, sizeof(int64));
+  v = (int64 *) damar_grow(NULL, sizeof(int64), "correct");
   while (fscanf(f, "%d\n", &x) == 1)
     { if (*n == cap)
         { cap = cap + cap / 4 + 100;
-          v = (int64 *) grow(v, sizeof(int64) * (size_t) cap);
+          v = (int64 *) damar_grow(v, sizeof(int64) * (size_t) cap, "correct");
         }
       v[(*n)++] = x;
     }
@@ -575,7 +556,7 @@ int damar_correct_las(const char *dbname, const char *las, const char *out, cons
   for (i = 0; i < parts; i++)
     { sprintf(name, "%s.%02d.fasta", out, i);
       if ((fo[i] = fopen(name, "w")) == NULL)
-        { fprintf(stderr, "damar: cannot write %s\n", name);
+        { damar_cannot_write(name);
           goto done;
         }
     }
@@ -594,7 +575,7 @@ int damar_correct_las(const char *dbname, const char *las, const char *out, cons
 
       T.ntiles = T.nent = T.nbases = 0;
       cur = &W[wi];
-      cur->job = loose = (Job *) grow(NULL, sizeof(Job) * (size_t) (b->npiles + 1));
+      cur->job = loose = (Job *) damar_grow(NULL, sizeof(Job) * (size_t) (b->npiles + 1), "correct");
       for (pi = 0; pi < b->npiles; pi++)
         { const int64 lo = b->pile_off[pi];
           const int   aread = b->pile_aread[pi], nall = (int) (b->pile_off[pi + 1] - lo);
@@ -605,18 +586,17 @@ int damar_correct_las(const char *dbname, const char *las, const char *out, cons
           for (k = lo; k < b->pile_off[pi + 1]; k++)
             pos += REC_BYTES + (int64) t.tlen[k] * t.tbytes;
           if (aread < 0 || aread >= db.nreads)
-            { fprintf(stderr, "damar: %s holds reads the database does not have\n", las);
+            { damar_reads_missing(las);
               goto done;
             }
           while (part + 1 < parts && at >= offs[part + 1])
             { part += 1;
               fresh = 1;
             }
-          if (nall > ocap)
-            { ocap = nall + nall / 4 + 1024;
-              order = (int *) grow(order, sizeof(int) * (size_t) ocap);
-              otmp = (int *) grow(otmp, sizeof(int) * (size_t) ocap);
-              key = (int *) grow(key, sizeof(int) * (size_t) ocap);
+          if (damar_room(&ocap, nall, 1024))
+            { order = (int *) damar_grow(order, sizeof(int) * (size_t) ocap, "correct");
+              otmp = (int *) damar_grow(otmp, sizeof(int) * (size_t) ocap, "correct");
+              key = (int *) damar_grow(key, sizeof(int) * (size_t) ocap, "correct");
             }
           /* the records of the pile that the reference keeps: LAcorrect.c:1444-1517.  A thread skips discarded records
              at the head of its part, over piles if need be; after that the first record of a pile is used whatever its
@@ -659,8 +639,8 @@ int damar_correct_las(const char *dbname, const char *las, const char *out, cons
           /* the sequences each tile's consensus takes: single_tile_consensus, LAcorrect.c:287 */
           if (T.ntiles + ntiles + 1 > T.ctile)
             { T.ctile = T.ntiles + ntiles + T.ctile / 4 + 4096;
-              T.ent_off = (int64 *) grow(T.ent_off, sizeof(int64) * (size_t) (T.ctile + 1));
-              T.weight = (int *) grow(T.weight, sizeof(int) * (size_t) T.ctile);
+              T.ent_off = (int64 *) damar_grow(T.ent_off, sizeof(int64) * (size_t) (T.ctile + 1), "correct");
+              T.weight = (int *) damar_grow(T.weight, sizeof(int) * (size_t) T.ctile, "correct");
             }
           for (i = 0; i < ntiles; i++)
             { int taken = 0, x, wsum = 0;
@@ -675,12 +655,12 @@ int damar_correct_las(const char *dbname, const char *las, const char *out, cons
                     continue;
                   if (T.nent + 1 > T.cent)
                     { T.cent = T.nent + T.cent / 4 + 4096;
-                      T.seq_off = (int64 *) grow(T.seq_off, sizeof(int64) * (size_t) T.cent);
-                      T.seq_len = (int *) grow(T.seq_len, sizeof(int) * (size_t) T.cent);
+                      T.seq_off = (int64 *) damar_grow(T.seq_off, sizeof(int64) * (size_t) T.cent, "correct");
+                      T.seq_len = (int *) damar_grow(T.seq_len, sizeof(int) * (size_t) T.cent, "correct");
                     }
                   if (T.nbases + len > T.cbases)
                     { T.cbases = T.nbases + len + T.cbases / 4 + (1 << 16);
-                      T.bases = (unsigned char *) grow(T.bases, (size_t) T.cbases);
+                      T.bases = (unsigned char *) damar_grow(T.bases, (size_t) T.cbases, "correct");
                     }
                   d = T.bases + T.nbases;
                   if (!tl->comp)
@@ -701,14 +681,14 @@ int damar_correct_las(const char *dbname, const char *las, const char *out, cons
             }
         }
       if (T.ent_off == NULL)          /* a batch without a tile */
-        T.ent_off = (int64 *) grow(NULL, sizeof(int64) * 2);
+        T.ent_off = (int64 *) damar_grow(NULL, sizeof(int64) * 2, "correct");
       T.ent_off[T.ntiles] = T.nent;
       tb.ntiles = T.ntiles;  tb.ent_off = T.ent_off;  tb.seq_off = T.seq_off;  tb.seq_len = T.seq_len;
       tb.bases = T.bases;  tb.nbases = T.nbases;  tb.weight = T.weight;
       if (T.ntiles + 1 > tcap)
         { tcap = T.ntiles + T.ntiles / 4 + 4096;
-          cons_off = (int64 *) grow(cons_off, sizeof(int64) * (size_t) (tcap + 1));
-          added = (int *) grow(added, sizeof(int) * (size_t) tcap);
+          cons_off = (int64 *) damar_grow(cons_off, sizeof(int64) * (size_t) (tcap + 1), "correct");
+          added = (int *) damar_grow(added, sizeof(int) * (size_t) tcap, "correct");
         }
       c0 = now_ms();
       if (damar_tile_consensus(&tb, cons_off, &cons, added))
@@ -724,13 +704,13 @@ int damar_correct_las(const char *dbname, const char *las, const char *out, cons
         { Job *j = cur->job + i;
           const int64 a0 = cons_off[j->tile0], a1 = cons_off[j->tile0 + j->ntiles];
           j->len = (int) (a1 - a0);
-          j->q = (int *) grow(NULL, sizeof(int) * 2 * (size_t) j->ntiles);
+          j->q = (int *) damar_grow(NULL, sizeof(int) * 2 * (size_t) j->ntiles, "correct");
           for (k = 0; k < j->ntiles; k++)
             { j->q[2 * k] = (int) (cons_off[j->tile0 + k + 1] - cons_off[j->tile0 + k]);
               j->q[2 * k + 1] = added[j->tile0 + k];
             }
           if (j->len > 0)
-            { j->cons = (char *) grow(NULL, (size_t) j->len + 1);
+            { j->cons = (char *) damar_grow(NULL, (size_t) j->len + 1, "correct");
               memcpy(j->cons, cons + a0, (size_t) j->len);
               j->serial = serial[j->part]++;
             }
@@ -766,7 +746,7 @@ int damar_correct_las(const char *dbname, const char *las, const char *out, cons
       if (want[i] && !done[i])
         { const int len = blk.reads[i].rlen;
           const char *s = (const char *) blk.bases + blk.reads[i].boff;
-          char *buf = (char *) grow(NULL, (size_t) len + 1);
+          char *buf = (char *) damar_grow(NULL, (size_t) len + 1, "correct");
           int k;
           for (k = 0; k < len; k++)
             buf[k] = "acgt"[(int) s[k] & 3];
@@ -784,8 +764,8 @@ done:
   if (fo != NULL)
     for (i = 0; i < parts; i++)
       if (fo[i] != NULL && fclose(fo[i]) != 0 && rc == 0)
-        { fprintf(stderr, "damar: cannot write %s.%02d.fasta\n", out, i);
-          rc = 1;
+        { sprintf(name, "%s.%02d.fasta", out, i);
+          rc = damar_cannot_write(name);
         }
   fflush(stdout);
   damar_piles_close(r);

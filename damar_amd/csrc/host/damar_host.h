@@ -80,6 +80,107 @@ typedef struct
 int  damar_dbinfo_open(const char *name, damar_dbinfo *db);     /* stub + .idx, no bases */
 void damar_dbinfo_close(damar_dbinfo *db);
 
+/* What the host passes share in small: the flag bits of a record, the colours of the reference's PASS lines, and the
+   routines every pass had a copy of. */
+#define OVL_COMP       0x1                /* lib/oflags.h */
+#define OVL_DISCARD    0x2
+#define OVL_REPEAT     0x8
+#define OVL_LOCAL      0x10
+#define OVL_DIFF       0x20
+#define OVL_STITCH     0x80
+#define OVL_SYMDISCARD 0x100
+#define OVL_OLEN       0x200
+#define OVL_RLEN       0x400
+#define OVL_TEMP       0x800
+#define OVL_CONT       0x8000
+#define OVL_GAP        0x10000
+#define OVL_TRIM       0x20000
+#define OVL_MODULE     0x40000
+
+#define GREEN "\x1b[32m"                  /* lib/colors.h */
+#define RESET "\x1b[0m"
+
+/* value k of a trace of tbytes bytes a value, and of record rec of a batch */
+static inline int damar_trace_at(const void *trace, int tbytes, int64 k)
+{ const unsigned char *q = (const unsigned char *) trace + tbytes * k;
+  return tbytes == 1 ? q[0] : (q[0] | (q[1] << 8));
+}
+
+static inline int damar_trace_value(const damar_trace_batch *t, int64 rec, int k)
+{ return damar_trace_at(t->trace + t->trace_off[rec], t->tbytes, k);
+}
+
+/* LAgap.c:255: 1 when [ab, ae) lies within [bb, be), 2 when it is the other way round, else 0.  LAfilter.c:252 asks for
+   the first alone: == 1 */
+static inline int damar_contained(int ab, int ae, int bb, int be)
+{ if (ab >= bb && ae <= be)
+    return 1;
+  if (bb >= ab && be <= ae)
+    return 2;
+  return 0;
+}
+
+static inline int damar_intersect(int ab, int ae, int bb, int be)      /* lib/utils.c:250 */
+{ const int b = ab > bb ? ab : bb, e = ae < be ? ae : be;
+  return b < e ? e - b : 0;
+}
+
+/* anno[0 .. nreads]: a track's byte counts per read into its offsets */
+static inline void damar_counts_to_offsets(uint64 *anno, int nreads)
+{ uint64 off = 0, c;
+  int    j;
+  for (j = 0; j <= nreads; j++)
+    { c = anno[j];
+      anno[j] = off;
+      off += c;
+    }
+}
+
+/* B read r's bases [from, to) as an alignment sees them: the read itself, or its complement; 4 beyond its ends */
+static inline void damar_gather_b(const HITS_DB *blk, int r, int comp, int from, int to, char *dst)
+{ const char *s = (const char *) blk->bases + blk->reads[r].boff;
+  const int   len = blk->reads[r].rlen;
+  int i;
+  for (i = from; i < to; i++)
+    if (i < 0 || i >= len)
+      *dst++ = 4;
+    else
+      *dst++ = comp ? (char) (3 - s[len - 1 - i]) : s[i];
+}
+
+/* laspass.c: what a pass over a .las file needs.  Plain C, nothing of the GPU runtime. */
+void *damar_grow(void *p, size_t n, const char *who);         /* realloc or, after a message, exit(1) */
+/* 1 and *cap raised to need + need / 4 + slack when need is above *cap (the caller grows its arrays to *cap), else 0 */
+static inline int damar_room(int64 *cap, int64 need, int64 slack)
+{ if (need <= *cap)
+    return 0;
+  *cap = need + need / 4 + slack;
+  return 1;
+}
+/* p with room for `need` elements of `size` bytes by that rule */
+void *damar_reserve(void *p, int64 *cap, int64 need, size_t size, int64 slack, const char *who);
+
+/* A batch takes the database's read table; which of its reads are looked up in it: none, the A read of every pile, or the
+   B read of every record as well.  0, or 1 after "damar: <las> holds reads the database does not have". */
+enum { DAMAR_BIND_ONLY = 0, DAMAR_BIND_A, DAMAR_BIND_AB };
+int  damar_batch_bind(damar_pile_batch *b, const damar_dbinfo *db, const char *las, int reads);
+int  damar_reads_missing(const char *las);                     /* that line alone, for a pass that looks per pile; 1 */
+
+/* The records of a pass written to a .las file in file order.  open: the fopen alone (NULL: it failed, nothing is said);
+   begin: the header; put: the ten words of rec (rec[0]: the number of trace values) and the trace -- vals, narrowed to
+   tbytes bytes a value, or when vals is NULL the tbytes-wide values at bytes.  OVL_TEMP is taken off the flags word, a
+   record flagged OVL_DISCARD is counted and, with purge, not written.  0; 1 (no message) when the write fails; 2 after
+   "<tool>: Compression of trace to bytes fails, value too big".  close: with ok (the pass came to its end) the count goes
+   into the header and *written receives it; "damar: cannot write <path>" once when a write, or with ok the close, failed.
+   0, or 1 after that line. */
+typedef struct damar_las_out damar_las_out;
+int   damar_cannot_write(const char *path);                    /* that line alone, for the files a pass writes beside; 1 */
+damar_las_out *damar_las_out_open(const char *path, int purge);
+int   damar_las_out_begin(damar_las_out *o, int tspace);
+int   damar_las_out_put(damar_las_out *o, const int *rec, const unsigned char *bytes, const uint16 *vals, int tbytes, const char *tool);
+int64 damar_las_out_written(const damar_las_out *o);
+int   damar_las_out_close(damar_las_out *o, int ok, int64 *written, int64 *discarded);
+
 typedef struct damar_pile_reader damar_pile_reader;
 damar_pile_reader *damar_piles_open(const char *las, int64 bound);     /* bound <= 0: 8 M records; DAMAR_PILE_BATCH lowers it */
 int   damar_piles_next(damar_pile_reader *r, damar_pile_batch *b);
@@ -150,11 +251,8 @@ int  damar_trimmer_batch(damar_trimmer *tm, const damar_trace_batch *t, const in
                          damar_trim_stats *st, damar_trimmed *res);
 int  damar_trimmer_aread(const damar_trimmer *tm, int64 rec);
 void damar_trimmer_close(damar_trimmer *tm);
-/* one record as it lies in a .las file: the ten words of rec (rec[0]: the number of trace values), then v at tbytes bytes a
-   value.  0; 1 (no message) when the write fails; 2 after "<tool>: Compression of trace to bytes fails, value too big" */
-int  damar_write_record(FILE *fo, const int *rec, const uint16 *v, int tbytes, const char *tool, unsigned char **obuf, int64 *ocap);
-
-/* a track of the whole database in either form, the compressed one first: as damar_track_read_a2.  0, or 1 (no message) */
+/* quality.c: a track of the whole database in either form, the compressed one first (then .anno / .data, db/DB.c
+   Load_Track): as damar_track_read_a2.  0, or 1 (no message) */
 int  damar_track_read_any(const damar_dbinfo *db, const char *track, uint64 **anno, int **data, int64 *ndata);
 
 /* gap.c: LAgap (scrub/LAgap.c) -- the plain routine behind damar_pile_gaps (DAMAR_PILES=host, and the piles the kernel

@@ -15,21 +15,6 @@
 #include "damar_hip.h"
 #include "damar_host.h"
 
-#define OVL_COMP       0x1                /* lib/oflags.h */
-#define OVL_DISCARD    0x2
-#define OVL_REPEAT     0x8
-#define OVL_LOCAL      0x10
-#define OVL_DIFF       0x20
-#define OVL_OLEN       0x200
-#define OVL_RLEN       0x400
-#define OVL_STITCH     0x80
-#define OVL_TEMP       0x800
-#define OVL_CONT       0x8000
-#define OVL_GAP        0x10000
-#define OVL_TRIM       0x20000
-#define OVL_MODULE     0x40000
-#define OVL_SYMDISCARD 0x100
-
 #define R_STITCH 0x1                      /* LAfilter.c:49-55 */
 #define R_MOD    0x2
 #define R_TP     0x4
@@ -37,18 +22,6 @@
 #define R_SPEC   0x10
 #define R_ID     0x20
 #define R_CONT   0x40
-
-#define GREEN "\x1b[32m"                  /* lib/colors.h */
-#define RESET "\x1b[0m"
-
-static void *grow(void *p, size_t n)
-{ void *q = realloc(p, n ? n : 1);
-  if (q == NULL)
-    { fprintf(stderr, "damar: out of memory (%zu bytes, filter)\n", n);
-      exit(1);
-    }
-  return q;
-}
 
 static int pairs_valid(const uint64 *anno, int64 ndata, int nreads)
 { int r;
@@ -126,20 +99,6 @@ typedef struct
 #define AB(i) (pl->b->abpos[pl->lo + (i)])
 #define BB(i) (pl->b->bbpos[pl->lo + (i)])
 #define BR(i) (pl->b->bread[pl->lo + (i)])
-
-static int trace_val(const damar_trace_batch *t, int64 rec, int k)
-{ const unsigned char *q = t->trace + t->trace_off[rec] + (int64) t->tbytes * k;
-  return t->tbytes == 1 ? q[0] : (q[0] | (q[1] << 8));
-}
-
-static int contained(int ab, int ae, int bb, int be)         /* LAfilter.c:252 */
-{ return ab >= bb && ae <= be;
-}
-
-static int intersect(int ab, int ae, int bb, int be)         /* lib/utils.c:250 */
-{ const int b = ab > bb ? ab : bb, e = ae < be ? ae : be;
-  return b < e ? e - b : 0;
-}
 
 /* LAfilter.c:492-610 on the run [j, j + n) */
 static int stitch_run(Pile *pl, int j, int n, int fuzz, int aggressive)
@@ -280,7 +239,7 @@ static int filter_record(Pile *pl, int i)
                 continue;
               if (b0 < tip_ab) b0 = tip_ab;
               if (e0 > tip_ae) e0 = tip_ae;
-              repeat += intersect(ab, ae, b0, e0);
+              repeat += damar_intersect(ab, ae, b0, e0);
             }
           if (repeat > 0 && ovllen - repeat < need)
             site = DAMAR_FR_REPA;
@@ -304,7 +263,7 @@ static int filter_record(Pile *pl, int i)
             }
           repeat = 0;
           for (k = 0; k < nb; k += 2)
-            repeat += intersect(b0, e0, rb[k], rb[k + 1]);
+            repeat += damar_intersect(b0, e0, rb[k], rb[k + 1]);
           if (repeat > 0 && ovllen - repeat < need)
             site = DAMAR_FR_REPB;
         }
@@ -317,7 +276,7 @@ static int filter_record(Pile *pl, int i)
   if (!(pl->fl[i] & OVL_DISCARD) && (p->remove & R_TP))
     { int bpos = bb, k;
       for (k = 0; k < pl->tl[i]; k += 2)
-        bpos += trace_val(pl->t, pl->lo + i, k + 1);
+        bpos += damar_trace_value(pl->t, pl->lo + i, k + 1);
       if (bpos != be)
         { ret |= OVL_DISCARD;
           pl->why[i] |= DAMAR_FR_TP;
@@ -364,7 +323,7 @@ void damar_host_filter_pile(const damar_trace_batch *t, const int *diffs, int64 
       if (p->seg_rate >= 0 && p->seg_rate <= 100)
         for (i = 0; i < P.n; i++)
           for (k = 0; k < P.tl[i] - 2; k += 2)
-            if (trace_val(t, P.lo + i, k) * 100.0 / trace_val(t, P.lo + i, k + 1) > p->seg_rate)
+            if (damar_trace_value(t, P.lo + i, k) * 100.0 / damar_trace_value(t, P.lo + i, k + 1) > p->seg_rate)
               { P.fl[i] |= OVL_DISCARD | OVL_DIFF;
                 P.cnt[DAMAR_FC_DIFFS] += 1;
                 break;
@@ -393,8 +352,7 @@ void damar_host_filter_pile(const damar_trace_batch *t, const int *diffs, int64 
             for (m = l + 1; m <= k && !found; m++)
               { if (P.fl[m] & (OVL_STITCH | OVL_DISCARD))
                   continue;
-                if (contained(AB(l), P.ae[l], AB(m), P.ae[m]) || contained(AB(m), P.ae[m], AB(l), P.ae[l]) ||
-                    contained(BB(l), P.be[l], BB(m), P.be[m]) || contained(BB(m), P.be[m], BB(l), P.be[l]))
+                if (damar_contained(AB(l), P.ae[l], AB(m), P.ae[m]) || damar_contained(BB(l), P.be[l], BB(m), P.be[m]))
                   found = 1;
               }
           }
@@ -414,7 +372,7 @@ void damar_host_filter_pile(const damar_trace_batch *t, const int *diffs, int64 
         { int enter = 0, leave = 0, bases = 0, active = 0;
           unsigned char *cov = NULL;
           if (p->max_unaligned != -1)
-            cov = (unsigned char *) memset(grow(NULL, (size_t) alen + 1), 0, (size_t) alen + 1);
+            cov = (unsigned char *) memset(damar_grow(NULL, (size_t) alen + 1, "filter"), 0, (size_t) alen + 1);
           for (i = 0; i < P.n; i++)
             { if (P.fl[i] & OVL_DISCARD)
                 continue;
@@ -496,7 +454,7 @@ void damar_host_filter_pile(const damar_trace_batch *t, const int *diffs, int64 
                     if (P.fl[m] & OVL_DISCARD)
                       continue;
                     if (P.aread != BR(j))
-                      gone = contained(AB(m), P.ae[m], AB(l), P.ae[l]) && contained(BB(m), P.be[m], BB(l), P.be[l]);
+                      gone = damar_contained(AB(m), P.ae[m], AB(l), P.ae[l]) == 1 && damar_contained(BB(m), P.be[m], BB(l), P.be[l]) == 1;
                     else                           /* identity overlaps: duplicates only */
                       gone = AB(m) == AB(l) && P.ae[m] == P.ae[l] && BB(m) == BB(l) && P.be[m] == P.be[l];
                     if (gone)
@@ -562,7 +520,7 @@ static void print_pile(const damar_trace_batch *t, int64 pile, const damar_filte
           { int bpos = bb[i];                      /* the trace as filter() saw it: none left on a stitched head */
             if (!(w & DAMAR_FR_HEAD))
               for (k = 0; k < t->tlen[lo + i]; k += 2)
-                bpos += trace_val(t, lo + i, k + 1);
+                bpos += damar_trace_value(t, lo + i, k + 1);
             printf("overlap (%d x %d): pass-through points inconsistent be = %d (expected %d)\n", a, br[i], bpos, be[i]);
           }
       }
@@ -613,7 +571,7 @@ static int *read_integers(FILE *f, int *n)
   while (fscanf(f, "%d\n", &x) == 1)
     { if (*n == cap)
         { cap = cap + cap / 4 + 100;
-          v = (int *) grow(v, sizeof(int) * (size_t) cap);
+          v = (int *) damar_grow(v, sizeof(int) * (size_t) cap, "filter");
         }
       v[(*n)++] = x;
     }
@@ -648,9 +606,9 @@ static int read_sym_list(const char *path, int nreads, int **off, int **len, int
       pb = b;
     }
   rewind(f);
-  *off = (int *) grow(NULL, sizeof(int) * ((size_t) nreads + 1));
-  *len = (int *) memset(grow(NULL, sizeof(int) * ((size_t) nreads + 1)), 0, sizeof(int) * ((size_t) nreads + 1));
-  *data = (int *) grow(NULL, sizeof(int) * ((size_t) nb + na + 10));
+  *off = (int *) damar_grow(NULL, sizeof(int) * ((size_t) nreads + 1), "filter");
+  *len = (int *) memset(damar_grow(NULL, sizeof(int) * ((size_t) nreads + 1), "filter"), 0, sizeof(int) * ((size_t) nreads + 1));
+  *data = (int *) damar_grow(NULL, sizeof(int) * ((size_t) nb + na + 10), "filter");
   for (r = 0; r <= nreads; r++)
     (*off)[r] = -1;
   pa = -2;
@@ -684,14 +642,15 @@ int damar_filter_las(const char *dbname, const char *las, const char *out, const
   damar_trimmed      res;
   damar_filter_out   fo_, pre;
   damar_filter_params P = o->p, *p0 = &P;
-  FILE   *fo = NULL, *fa = NULL, *f;
-  unsigned char *obuf = NULL, *state = NULL;
+  damar_las_out *wr = NULL;
+  FILE   *fa = NULL, *f;
+  unsigned char *state = NULL;
   uint64 *ranno = NULL, *tanno = NULL;
   int    *rdata = NULL, *tdata = NULL, *pairs = NULL, *soff = NULL, *slen = NULL, *sdata = NULL;
   int    *buf = NULL, *pbuf = NULL, *cnt = NULL, *pcnt = NULL;
   int64  *toff2 = NULL;
-  int64   ocap = 0, fcap = 0, ccap = 0, written = 0, i, pi, tot[DAMAR_FC_COUNT], tndata = 0;
-  int     got, rc = 1, have_db = 0, tw, no_track, k, pass;
+  int64   fcap = 0, ccap = 0, i, pi, tot[DAMAR_FC_COUNT], tndata = 0;
+  int     got, rc = 1, have_db = 0, no_track, k, pass;
 
   memset(st, 0, sizeof(*st));
   memset(tot, 0, sizeof(tot));
@@ -702,7 +661,7 @@ int damar_filter_las(const char *dbname, const char *las, const char *out, const
       return 1;
     }
   fclose(f);
-  if ((fo = fopen(out, "w")) == NULL)
+  if ((wr = damar_las_out_open(out, o->purge)) == NULL)
     { fprintf(stderr, "could not open %s\n", out);
       return 1;
     }
@@ -731,7 +690,7 @@ int damar_filter_las(const char *dbname, const char *las, const char *out, const
       damar_filter_no_track(o->trim_track);            /* as in the reference: said, and done without */
     }
   else
-    { pairs = (int *) grow(NULL, sizeof(int) * 2 * ((size_t) db.nreads + 1));
+    { pairs = (int *) damar_grow(NULL, sizeof(int) * 2 * ((size_t) db.nreads + 1), "filter");
       if (damar_trim_pairs(tanno, tdata, db.nreads, pairs))
         { fprintf(stderr, "LAfilter: the trim track '%s' does not hold one interval per read at most\n", o->trim_track);
           goto done;
@@ -754,7 +713,7 @@ int damar_filter_las(const char *dbname, const char *las, const char *out, const
       v = read_integers(f, &nv);
       fclose(f);
       printf("%s %d reads\n", pass == 0 ? "excluding" : "including", nv);
-      state = (unsigned char *) memset(grow(NULL, (size_t) db.nreads + 1), 0, (size_t) db.nreads + 1);
+      state = (unsigned char *) memset(damar_grow(NULL, (size_t) db.nreads + 1, "filter"), 0, (size_t) db.nreads + 1);
       for (k = 0; k < nv; k++)
         if (v[k] < 0 || v[k] >= db.nreads)
           fprintf(stderr, "[WARNING] LAfilter: %s read %d not possible! Must be in range: [0, %d]", pass == 0 ? "excluding" : "including", v[k],
@@ -778,11 +737,8 @@ int damar_filter_las(const char *dbname, const char *las, const char *out, const
     goto done;
   if ((r = damar_piles_open_traces(las, 0, 0)) == NULL)
     goto done;
-  tw = damar_piles_tspace(r);
-  { const int64 zero = 0;
-    if (fwrite(&zero, sizeof(int64), 1, fo) != 1 || fwrite(&tw, sizeof(int), 1, fo) != 1)
-      goto wfail;
-  }
+  if (damar_las_out_begin(wr, damar_piles_tspace(r)))
+    goto done;
   printf(GREEN "PASS filtering\n" RESET);
 
   while ((got = damar_piles_next_traces(r, &t)) > 0)
@@ -794,27 +750,21 @@ int damar_filter_las(const char *dbname, const char *las, const char *out, const
       const int with_pre = p0->downsample || (p0->seg_rate >= 0 && p0->seg_rate <= 100);
 
       damar_piles_rest(r, &rdiffs, &rlast);
-      for (pi = 0; pi < t.p.npiles; pi++)
-        if (t.p.pile_aread[pi] < 0 || t.p.pile_aread[pi] >= db.nreads)
-          { fprintf(stderr, "damar: %s holds reads the database does not have\n", las);
-            goto done;
-          }
-      if (t.p.nrec > fcap)
-        { fcap = t.p.nrec + t.p.nrec / 4 + 1024;
-          buf = (int *) grow(buf, sizeof(int) * 7 * (size_t) fcap);
-          pbuf = (int *) grow(pbuf, sizeof(int) * 7 * (size_t) fcap);
-          toff2 = (int64 *) grow(toff2, sizeof(int64) * (size_t) fcap);
+      if (damar_batch_bind(&m.p, &db, las, DAMAR_BIND_A))
+        goto done;
+      if (damar_room(&fcap, t.p.nrec, 1024))                   /* one capacity: the three grow together */
+        { buf = (int *) damar_grow(buf, sizeof(int) * 7 * (size_t) fcap, "filter");
+          pbuf = (int *) damar_grow(pbuf, sizeof(int) * 7 * (size_t) fcap, "filter");
+          toff2 = (int64 *) damar_grow(toff2, sizeof(int64) * (size_t) fcap, "filter");
         }
-      if (t.p.npiles > ccap)
-        { ccap = t.p.npiles + t.p.npiles / 4 + 1024;
-          cnt = (int *) grow(cnt, sizeof(int) * DAMAR_FC_COUNT * (size_t) ccap);
-          pcnt = (int *) grow(pcnt, sizeof(int) * DAMAR_FC_COUNT * (size_t) ccap);
+      if (damar_room(&ccap, t.p.npiles, 1024))
+        { cnt = (int *) damar_grow(cnt, sizeof(int) * DAMAR_FC_COUNT * (size_t) ccap, "filter");
+          pcnt = (int *) damar_grow(pcnt, sizeof(int) * DAMAR_FC_COUNT * (size_t) ccap, "filter");
         }
       fo_.flags = buf;  fo_.aepos = buf + fcap;  fo_.bepos = buf + 2 * fcap;  fo_.diffs = buf + 3 * fcap;  fo_.tlen = buf + 4 * fcap;
       fo_.reason = buf + 5 * fcap;  fo_.cont_by = buf + 6 * fcap;  fo_.cnt = cnt;
       pre.flags = pbuf;  pre.aepos = pbuf + fcap;  pre.bepos = pbuf + 2 * fcap;  pre.diffs = pbuf + 3 * fcap;  pre.tlen = pbuf + 4 * fcap;
       pre.reason = pbuf + 5 * fcap;  pre.cont_by = pbuf + 6 * fcap;  pre.cnt = pcnt;
-      m.p.read_len = db.read_len;  m.p.read_flags = db.read_flags;  m.p.nreads = db.nreads;  m.p.maxlen = db.maxlen;
       dfs = rdiffs;
       p.steps = DAMAR_FILTER_PRE | DAMAR_FILTER_MAIN;
       if (tm != NULL)
@@ -855,38 +805,21 @@ int damar_filter_las(const char *dbname, const char *las, const char *out, const
 
       for (pi = 0; pi < t.p.npiles; pi++)
         for (i = t.p.pile_off[pi]; i < t.p.pile_off[pi + 1]; i++)
-          { int rec[10], w;
-            if (fo_.flags[i] & OVL_DISCARD)
-              { st->discarded += 1;
-                if (fa != NULL)
-                  fprintf(fa, "%d %d\n", t.p.pile_aread[pi], t.p.bread[i]);
-                if (o->purge)
-                  continue;
-              }
+          { int rec[10];
+            if ((fo_.flags[i] & OVL_DISCARD) && fa != NULL)
+              fprintf(fa, "%d %d\n", t.p.pile_aread[pi], t.p.bread[i]);
             rec[0] = fo_.tlen[i];
             rec[1] = fo_.diffs[i];
             rec[2] = m.p.abpos[i];  rec[3] = m.p.bbpos[i];  rec[4] = fo_.aepos[i];  rec[5] = fo_.bepos[i];
-            rec[6] = fo_.flags[i] & ~OVL_TEMP;
+            rec[6] = fo_.flags[i];
             rec[7] = t.p.pile_aread[pi];  rec[8] = t.p.bread[i];  rec[9] = rlast[i];
-            if (tm != NULL)
-              { if ((w = damar_write_record(fo, rec, res.trace + res.toff[i], t.tbytes, "(null)", &obuf, &ocap)) == 2)
-                  goto done;
-                if (w)
-                  goto wfail;
-              }
-            else if (fwrite(rec, sizeof(int), 10, fo) != 10 ||
-                     (rec[0] > 0 && fwrite(t.trace + t.trace_off[i], (size_t) t.tbytes, (size_t) rec[0], fo) != (size_t) rec[0]))
-              goto wfail;
-            written += 1;
+            if (damar_las_out_put(wr, rec, t.trace + t.trace_off[i], tm != NULL ? res.trace + res.toff[i] : NULL, t.tbytes, "(null)"))
+              goto done;
           }
       st->novl += t.p.nrec;
     }
   if (got < 0)
     goto done;
-  st->written = written;
-  rewind(fo);
-  if (fwrite(&written, sizeof(int64), 1, fo) != 1)
-    goto wfail;
   for (k = 0; k < DAMAR_FC_COUNT; k++)
     st->cnt[k] = tot[k];
   /* filter_post, LAfilter.c:1762-1841 */
@@ -915,23 +848,16 @@ int damar_filter_las(const char *dbname, const char *las, const char *out, const
   if (tot[DAMAR_FC_SYM])
     printf("symmetrically remove discarded overlaps          %10d\n", (int) tot[DAMAR_FC_SYM]);
   rc = 0;
-  goto done;
-wfail:
-  fprintf(stderr, "damar: cannot write %s\n", out);
 done:
-  if (fo != NULL && fclose(fo) != 0 && rc == 0)
-    { fprintf(stderr, "damar: cannot write %s\n", out);
-      rc = 1;
-    }
+  if (damar_las_out_close(wr, rc == 0, &st->written, &st->discarded))
+    rc = 1;
   fflush(stdout);
   damar_piles_close(r);
   damar_trimmer_close(tm);
   if (have_db) damar_dbinfo_close(&db);
   if (fa != NULL && fclose(fa) != 0 && rc == 0)
-    { fprintf(stderr, "damar: cannot write %s\n", o->discarded_out);
-      rc = 1;
-    }
-  free(obuf);  free(buf);  free(pbuf);  free(cnt);  free(pcnt);  free(toff2);
+    rc = damar_cannot_write(o->discarded_out);
+  free(buf);  free(pbuf);  free(cnt);  free(pcnt);  free(toff2);
   free(state);  free(ranno);  free(rdata);  free(tanno);  free(tdata);  free(pairs);  free(soff);  free(slen);  free(sdata);
   return rc;
 }

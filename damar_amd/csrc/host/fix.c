@@ -19,20 +19,6 @@
 #define MIN_SPAN        400
 #define MIN_SPAN_REPEAT 800
 
-#define OVL_COMP 0x1                      /* lib/oflags.h */
-
-#define GREEN "\x1b[32m"                  /* lib/colors.h */
-#define RESET "\x1b[0m"
-
-static void *grow(void *p, size_t n)
-{ void *q = realloc(p, n ? n : 1);
-  if (q == NULL)
-    { fprintf(stderr, "damar: out of memory (%zu bytes, fix)\n", n);
-      exit(1);
-    }
-  return q;
-}
-
 static int track_shaped(const uint64 *anno, int64 ndata, int nreads)
 { int r;
   if (anno[0] % 4 || anno[nreads] > 4 * (uint64) ndata)
@@ -109,11 +95,6 @@ bad:
 
 /***** the plain routine ************************************************************************/
 
-static int trace_at(const damar_trace_batch *t, int64 rec, int k)
-{ const unsigned char *p = t->trace + t->trace_off[rec] + (int64) t->tbytes * k;
-  return t->tbytes == 1 ? p[0] : p[0] | (p[1] << 8);
-}
-
 /* the reference indexes the q track's data flat, base + k with base where a read's values begin: a value outside the data
    (B's segment at be / tw when be is the end of a read of a whole number of segments, as the last read) counts as 0 */
 static int q_at(const damar_fix_params *p, int64 base, int64 k)
@@ -149,7 +130,7 @@ typedef struct
 #define BR(i) (pl->b->bread[pl->lo + (i)])
 #define FL(i) (pl->b->flags[pl->lo + (i)])
 #define TL(i) (pl->t->tlen[pl->lo + (i)])
-#define TR(i, k) trace_at(pl->t, pl->lo + (i), (k))
+#define TR(i, k) damar_trace_value(pl->t, pl->lo + (i), (k))
 
 /* spanners_point, LAfix.c:1413: the reference stops counting beyond max, which changes nothing of the answer */
 static int point_spanned(const Pile *pl, const damar_fix_params *p, int pt)
@@ -181,7 +162,7 @@ static void sort_gaps(damar_fix_gap *g, int64 n)
 static damar_fix_gap *next_gap(damar_fix_list *L)
 { if (L->n >= L->cap)
     { L->cap = L->cap + L->cap / 4 + 256;
-      L->g = (damar_fix_gap *) grow(L->g, sizeof(damar_fix_gap) * (size_t) L->cap);
+      L->g = (damar_fix_gap *) damar_grow(L->g, sizeof(damar_fix_gap) * (size_t) L->cap, "fix");
     }
   return L->g + L->n++;
 }
@@ -379,7 +360,8 @@ typedef struct
   const int    *data;
 } Track;
 
-/* get_trim, lib/utils.c:258; 1: the read's entry is not an interval */
+/* get_trim, lib/utils.c:258; 1: the read's entry is not an interval.  (trim.c's trim_of is another rule: there such an
+   entry keeps nothing, and the track is never missing.) */
 static int trim_of(const Track *tt, int alen, int rid, int *b, int *e)
 { if (tt->anno == NULL)
     { *b = 0;
@@ -398,11 +380,6 @@ static int trim_of(const Track *tt, int alen, int rid, int *b, int *e)
       }
   }
   return 0;
-}
-
-static int overlap_of(int ab, int ae, int bb, int be)        /* intersect, lib/utils.c:250 */
-{ const int b = ab > bb ? ab : bb, e = ae < be ? ae : be;
-  return b < e ? e - b : 0;
 }
 
 /* spanners_interval, LAfix.c:1378: tb, te are the track's interval, not what the flips have made of it so far */
@@ -438,14 +415,14 @@ static int cut_flips(const Pile *pl, const damar_fix_params *p, int tb, int te, 
     return 0;
   for (i = b; i < e; i++)
     { int sab, sae, sbb, sbe;
-      if (!(FL(i) & OVL_COMP) || !overlap_of(AB(i), AE(i), alen - BE(i), alen - BB(i)))
+      if (!(FL(i) & OVL_COMP) || !damar_intersect(AB(i), AE(i), alen - BE(i), alen - BB(i)))
         continue;
       sab = AB(i);
       sae = (sab / tw + 1) * tw;
       sbb = BB(i);
       sbe = sbb + TR(i, 1);
       for (j = 2; j < TL(i) - 2; j += 2)
-        { if (overlap_of(sab, sae + 1, alen - sbe, alen - sbb - 1) && interval_spanners(pl, p, tb, te, sab, sae) <= 1)
+        { if (damar_intersect(sab, sae + 1, alen - sbe, alen - sbb - 1) && interval_spanners(pl, p, tb, te, sab, sae) <= 1)
             { printf("%8d CROSS @ %5d..%5d x %5d..%5d\n", pl->aread, sab, sae, alen - sbe, alen - sbb);
               cut = 1;
               if (*trim_b < sab && sae < *trim_e)
@@ -469,7 +446,7 @@ static int cut_flips(const Pile *pl, const damar_fix_params *p, int tb, int te, 
       ae = AB(i + 1);
       ab_c = alen - BB(i + 1);
       ae_c = alen - BE(i);
-      if (overlap_of(ab, ae, ab_c, ae_c) && interval_spanners(pl, p, tb, te, ab, ae) <= 1)
+      if (damar_intersect(ab, ae, ab_c, ae_c) && interval_spanners(pl, p, tb, te, ab, ae) <= 1)
         { const int mid = (ab + ae) / 2;
           printf("%8d GAP   @ %5d..%5d x %5d..%5d\n", pl->aread, ab, ae, ab_c, ae_c);
           cut = 1;
@@ -666,16 +643,11 @@ int damar_fix_las(const char *dbname, const char *las, const char *fasta, const 
       char   msg[256];
 
       msg[0] = 0;
-      for (pi = 0; pi < b->npiles; pi++)
-        if (b->pile_aread[pi] < 0 || b->pile_aread[pi] >= db.nreads)
-          { fprintf(stderr, "damar: %s holds reads the database does not have\n", las);
-            goto done;
-          }
-      b->read_len = db.read_len;  b->read_flags = db.read_flags;  b->nreads = db.nreads;  b->maxlen = db.maxlen;
-      if (b->npiles > tcap)
-        { tcap = b->npiles + b->npiles / 4 + 1024;
-          trim = (int *) grow(trim, sizeof(int) * 2 * (size_t) tcap);
-          count = (int *) grow(count, sizeof(int) * (size_t) tcap);
+      if (damar_batch_bind(b, &db, las, DAMAR_BIND_A))
+        goto done;
+      if (damar_room(&tcap, b->npiles, 1024))
+        { trim = (int *) damar_grow(trim, sizeof(int) * 2 * (size_t) tcap, "fix");
+          count = (int *) damar_grow(count, sizeof(int) * (size_t) tcap, "fix");
         }
       /* per pile the trim interval, the flip step, the -T line and the reference's two checks: LAfix.c:1817-1894.  A pile
          that is skipped has an empty interval from here on. */
@@ -747,10 +719,7 @@ int damar_fix_las(const char *dbname, const char *las, const char *fasta, const 
               fprintf(fo, ">trimmed_%d source=%d", aread, aread);
               tracks_trimmed(fo, cv, ncv, aread, tb, te);
               fprintf(fo, "\n");
-              if (need > scap)
-                { scap = need + need / 4;
-                  seq = (char *) grow(seq, (size_t) scap);
-                }
+              seq = (char *) damar_reserve(seq, &scap, need, 1, 0, "fix");
               a_piece(&blk, aread, tb, te, seq);
               write_wrapped(fo, seq, te - tb);
               st->reads_trimmed += 1;
@@ -758,13 +727,10 @@ int damar_fix_las(const char *dbname, const char *las, const char *fasta, const 
             }
           for (k = 0; k < n; k++)
             need += abs(g[k].be - g[k].bb) + 1;
-          if (need > scap)
-            { scap = need + need / 4;
-              seq = (char *) grow(seq, (size_t) scap);
-            }
+          seq = (char *) damar_reserve(seq, &scap, need, 1, 0, "fix");
           if (3 * ((int64) n + 1) > apcap)
             { apcap = 3 * ((int64) n + 1) + 64;
-              ap = (int *) grow(ap, sizeof(int) * (size_t) apcap);
+              ap = (int *) damar_grow(ap, sizeof(int) * (size_t) apcap, "fix");
             }
           /* the new read from pieces of A and B: LAfix.c:2440-2560 */
           for (k = 0; k < n; k++)
@@ -831,9 +797,7 @@ int damar_fix_las(const char *dbname, const char *las, const char *fasta, const 
   rc = 0;
 done:
   if (fo != NULL && fclose(fo) != 0 && rc == 0)
-    { fprintf(stderr, "damar: cannot write %s\n", fasta);
-      rc = 1;
-    }
+    rc = damar_cannot_write(fasta);
   if (ft != NULL) fclose(ft);
   fflush(stdout);
   damar_piles_close(r);

@@ -18,26 +18,6 @@
 #define BIN_SIZE 100                      /* LAgap.c:33-34 */
 #define MIN_LR   450
 
-#define OVL_COMP    0x1                   /* lib/oflags.h */
-#define OVL_DISCARD 0x2
-#define OVL_STITCH  0x80
-#define OVL_TEMP    0x800
-#define OVL_CONT    0x8000
-#define OVL_GAP     0x10000
-#define OVL_TRIM    0x20000
-
-#define GREEN "\x1b[32m"                  /* lib/colors.h */
-#define RESET "\x1b[0m"
-
-static void *grow(void *p, size_t n)
-{ void *q = realloc(p, n ? n : 1);
-  if (q == NULL)
-    { fprintf(stderr, "damar: out of memory (%zu bytes, gap)\n", n);
-      exit(1);
-    }
-  return q;
-}
-
 int damar_gap_inputs_valid(const damar_pile_batch *b, const damar_gap_params *p)
 { const char *why = "malformed batch";
   int64 i, pi;
@@ -93,14 +73,6 @@ typedef struct
 #define BE(i) (pl->b->bepos[pl->lo + (i)])
 #define BR(i) (pl->b->bread[pl->lo + (i)])
 
-static int contained(int ab, int ae, int bb, int be)         /* LAgap.c:255 */
-{ if (ab >= bb && ae <= be)
-    return 1;
-  if (bb >= ab && be <= ae)
-    return 2;
-  return 0;
-}
-
 /* LAgap.c:1782-1871 */
 static int64 drop_containments(Pile *pl)
 { int64 gone = 0;
@@ -126,8 +98,8 @@ static int64 drop_containments(Pile *pl)
             { bb2 = blen - BE(k);  be2 = blen - BB(k); }
           else
             { bb2 = BB(k);  be2 = BE(k); }
-          cont = contained(AB(i), AE(i), AB(k), AE(k));
-          if (cont && contained(bb1, be1, bb2, be2))
+          cont = damar_contained(AB(i), AE(i), AB(k), AE(k));
+          if (cont && damar_contained(bb1, be1, bb2, be2))
             { gone += 1;
               if (cont == 1)
                 { pl->flags[i] |= OVL_DISCARD | OVL_CONT;
@@ -189,7 +161,7 @@ static void add_event(damar_gap_list *L, int beg, int b, int kind, int v0, int v
 { int *e;
   if (L->n >= L->cap)
     { L->cap = L->cap + L->cap / 4 + 256;
-      L->ev = (int *) grow(L->ev, sizeof(int) * DAMAR_GAP_EVENT_INTS * (size_t) L->cap);
+      L->ev = (int *) damar_grow(L->ev, sizeof(int) * DAMAR_GAP_EVENT_INTS * (size_t) L->cap, "gap");
     }
   e = L->ev + DAMAR_GAP_EVENT_INTS * L->n++;
   e[0] = beg;  e[1] = b;  e[2] = kind;  e[3] = v0;  e[4] = v1;  e[5] = dropped;
@@ -313,11 +285,10 @@ int damar_gap_las(const char *dbname, const char *las, const char *out, const da
   damar_trace_batch  t;
   damar_trimmed      res;
   damar_gap_events   ev;
-  FILE   *fo = NULL;
-  unsigned char *obuf = NULL;
+  damar_las_out *wr = NULL;
   int    *flags = NULL, *count = NULL;
-  int64   ocap = 0, fcap = 0, ccap = 0, written = 0, i, pi;
-  int     got, rc = 1, have_db = 0, tw, no_track;
+  int64   fcap = 0, ccap = 0, i, pi;
+  int     got, rc = 1, have_db = 0, no_track;
 
   memset(st, 0, sizeof(*st));
   memset(&ev, 0, sizeof(ev));
@@ -331,15 +302,12 @@ int damar_gap_las(const char *dbname, const char *las, const char *out, const da
     }
   if ((r = damar_piles_open_traces(las, 0, 0)) == NULL)
     goto done;
-  if ((fo = fopen(out, "w")) == NULL)
+  if ((wr = damar_las_out_open(out, p->purge)) == NULL)
     { fprintf(stderr, "could not open output track '%s'\n", out);
       goto done;
     }
-  tw = damar_piles_tspace(r);
-  { const int64 zero = 0;
-    if (fwrite(&zero, sizeof(int64), 1, fo) != 1 || fwrite(&tw, sizeof(int), 1, fo) != 1)
-      goto wfail;
-  }
+  if (damar_las_out_begin(wr, damar_piles_tspace(r)))
+    goto done;
   printf(GREEN "PASS gaps" RESET "\n");
 
   while ((got = damar_piles_next_traces(r, &t)) > 0)
@@ -350,25 +318,15 @@ int damar_gap_las(const char *dbname, const char *las, const char *out, const da
       int64  c3[3];
 
       damar_piles_rest(r, &rdiffs, &rlast);
-      for (pi = 0; pi < b.npiles; pi++)
-        if (b.pile_aread[pi] < 0 || b.pile_aread[pi] >= db.nreads)
-          { fprintf(stderr, "damar: %s holds reads the database does not have\n", las);
-            goto done;
-          }
+      if (damar_batch_bind(&b, &db, las, DAMAR_BIND_A))
+        goto done;
       if (tm != NULL)
         { if (damar_trimmer_batch(tm, &t, rdiffs, las, st->novl, &st->trim, &res))
             goto done;
           b.abpos = res.abpos;  b.aepos = res.aepos;  b.bbpos = res.bbpos;  b.bepos = res.bepos;  b.flags = res.flags;
         }
-      b.read_len = db.read_len;  b.read_flags = db.read_flags;  b.nreads = db.nreads;  b.maxlen = db.maxlen;
-      if (b.nrec > fcap)
-        { fcap = b.nrec + b.nrec / 4 + 1024;
-          flags = (int *) grow(flags, sizeof(int) * (size_t) fcap);
-        }
-      if (b.npiles > ccap)
-        { ccap = b.npiles + b.npiles / 4 + 1024;
-          count = (int *) grow(count, sizeof(int) * (size_t) ccap);
-        }
+      flags = (int *) damar_reserve(flags, &fcap, b.nrec, sizeof(int), 1024, "gap");
+      count = (int *) damar_reserve(count, &ccap, b.npiles, sizeof(int), 1024, "gap");
       ev.count = count;
       ev.ev = NULL;
       if (damar_pile_gaps(&b, p, flags, &ev))
@@ -386,36 +344,19 @@ int damar_gap_las(const char *dbname, const char *las, const char *out, const da
          record it writes: it does not reach the file */
       for (pi = 0; pi < b.npiles; pi++)
         for (i = b.pile_off[pi]; i < b.pile_off[pi + 1]; i++)
-          { int rec[10], w;
-            if (flags[i] & OVL_DISCARD)
-              { st->discarded += 1;
-                if (p->purge)
-                  continue;
-              }
+          { int rec[10];
             rec[0] = tm != NULL ? res.tlen[i] : t.tlen[i];
             rec[1] = tm != NULL ? res.diffs[i] : rdiffs[i];
             rec[2] = b.abpos[i];  rec[3] = b.bbpos[i];  rec[4] = b.aepos[i];  rec[5] = b.bepos[i];
-            rec[6] = flags[i] & ~OVL_TEMP;
+            rec[6] = flags[i];
             rec[7] = b.pile_aread[pi];  rec[8] = b.bread[i];  rec[9] = rlast[i];
-            if (tm != NULL)
-              { if ((w = damar_write_record(fo, rec, res.trace + res.toff[i], t.tbytes, "(null)", &obuf, &ocap)) == 2)
-                  goto done;
-                if (w)
-                  goto wfail;
-              }
-            else if (fwrite(rec, sizeof(int), 10, fo) != 10 ||
-                     (t.tlen[i] > 0 && fwrite(t.trace + t.trace_off[i], (size_t) t.tbytes, (size_t) t.tlen[i], fo) != (size_t) t.tlen[i]))
-              goto wfail;
-            written += 1;
+            if (damar_las_out_put(wr, rec, t.trace + t.trace_off[i], tm != NULL ? res.trace + res.toff[i] : NULL, t.tbytes, "(null)"))
+              goto done;
           }
       st->novl += b.nrec;
     }
   if (got < 0)
     goto done;
-  st->written = written;
-  rewind(fo);
-  if (fwrite(&written, sizeof(int64), 1, fo) != 1)
-    goto wfail;
   /* gaps_post, LAgap.c:1906-1914 */
   if (tm != NULL)
     { printf("%13lld of %13lld overlaps trimmed\n", (long long) st->trim.ntrimmed, (long long) st->trim.novl);
@@ -424,19 +365,14 @@ int damar_gap_las(const char *dbname, const char *las, const char *out, const da
   printf("dropped %d containments\n", (int) st->contained);
   printf("dropped %d overlaps in %d break/gaps\n", (int) st->dropped, (int) st->breaks);
   rc = 0;
-  goto done;
-wfail:
-  fprintf(stderr, "damar: cannot write %s\n", out);
 done:
-  if (fo != NULL && fclose(fo) != 0 && rc == 0)
-    { fprintf(stderr, "damar: cannot write %s\n", out);
-      rc = 1;
-    }
+  if (wr != NULL && damar_las_out_close(wr, rc == 0, &st->written, &st->discarded))
+    rc = 1;
   fflush(stdout);
   free(ev.ev);
   damar_piles_close(r);
   damar_trimmer_close(tm);
   if (have_db) damar_dbinfo_close(&db);
-  free(obuf);  free(flags);  free(count);
+  free(flags);  free(count);
   return rc;
 }

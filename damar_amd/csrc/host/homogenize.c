@@ -13,17 +13,6 @@
 #include "damar_host.h"
 
 #define MIN_INT_LEN 500                   /* TKhomogenize.c:49 */
-#define OVL_COMP_FLAG 0x1                 /* lib/oflags.h */
-
-static void *grow(void *p, size_t n)
-{ void *q = realloc(p, n ? n : 1);
-  if (q == NULL)
-    { fprintf(stderr, "damar: out of memory (%zu bytes, homogenize)\n", n);
-      exit(1);
-    }
-  return q;
-}
-
 /* ba_assign_range(arr, beg, end, 1) (lib.ext/bitarr.c:263-284): bits beg .. end inclusive, the single bit beg when
    end < beg; bit j is bit j % 8 of byte j / 8.  Held to the nbits bits of the array. */
 void damar_bits_set_range(unsigned char *bits, int64 nbits, int64 beg, int64 end)
@@ -154,8 +143,8 @@ damar_host_homog *damar_host_homog_open(const int *read_len, int nreads, int res
     return NULL;
   h->nreads = nreads;
   h->res = res;
-  h->rlen = (int *) grow(NULL, sizeof(int) * (size_t) nreads);
-  h->boff = (int64 *) grow(NULL, sizeof(int64) * ((size_t) nreads + 1));
+  h->rlen = (int *) damar_grow(NULL, sizeof(int) * (size_t) nreads, "homogenize");
+  h->boff = (int64 *) damar_grow(NULL, sizeof(int64) * ((size_t) nreads + 1), "homogenize");
   h->boff[0] = 0;
   for (r = 0; r < nreads; r++)
     { h->rlen[r] = read_len[r];
@@ -202,8 +191,7 @@ int damar_host_homog_seed(damar_host_homog *h, const uint64 *anno, const int *da
 }
 
 static int trace_b(const damar_trace_batch *t, int64 rec, int seg)
-{ const unsigned char *p = t->trace + t->trace_off[rec] + (int64) t->tbytes * (2 * seg + 1);
-  return t->tbytes == 1 ? p[0] : p[0] | (p[1] << 8);
+{ return damar_trace_value(t, rec, 2 * seg + 1);
 }
 
 /* handler_homogenize (TKhomogenize.c:346-546), the walk as written */
@@ -260,7 +248,7 @@ int damar_host_homog_add(damar_host_homog *h, const damar_trace_batch *t, const 
                 }
               if (ibb == -1 || ibe == -1)
                 continue;
-              if (b->flags[i] & OVL_COMP_FLAG)
+              if (b->flags[i] & OVL_COMP)
                 { const int x = ibb;
                   ibb = blen - ibe;
                   ibe = blen - x;
@@ -286,7 +274,7 @@ int damar_host_homog_add(damar_host_homog *h, const damar_trace_batch *t, const 
 /* post_homogenize (TKhomogenize.c:230-321): anno receives byte offsets */
 int damar_host_homog_finish(damar_host_homog *h, uint64 *anno, int **data_out, int64 *ndata, int64 *tagged)
 { const int res = h->res;
-  int  *data = (int *) grow(NULL, 8);
+  int  *data = (int *) damar_grow(NULL, 8, "homogenize");
   int64 cap = 0, top = 0, k;
   uint64 off = 0;
   int   r;
@@ -302,7 +290,7 @@ int damar_host_homog_finish(damar_host_homog *h, uint64 *anno, int **data_out, i
           else if (!val && beg != -1)
             { if (top + 2 > cap)
                 { cap = cap + cap / 4 + 1024;
-                  data = (int *) grow(data, sizeof(int) * (size_t) cap);
+                  data = (int *) damar_grow(data, sizeof(int) * (size_t) cap, "homogenize");
                 }
               data[top++] = beg * res;
               if (j == alen)                                     /* the run reaches the last bit */
@@ -342,7 +330,6 @@ int damar_homogenize_track(const damar_dbinfo *db, const char *las, const damar_
   damar_trace_batch  t;
   int   *pairs = NULL;
   int    got, rc = 1;
-  int64  i;
 
   memset(res, 0, sizeof(*res));
   if (p->res < 1 || p->ends == 0 || p->ends < -1 || p->iv_anno == NULL)
@@ -350,7 +337,7 @@ int damar_homogenize_track(const damar_dbinfo *db, const char *las, const damar_
       return 1;
     }
   if (p->ends != -1)
-    { pairs = (int *) grow(NULL, sizeof(int) * 2 * ((size_t) db->nreads + 1));
+    { pairs = (int *) damar_grow(NULL, sizeof(int) * 2 * ((size_t) db->nreads + 1), "homogenize");
       if (p->trim_anno == NULL || damar_trim_pairs(p->trim_anno, p->trim_data, db->nreads, pairs))
         { fprintf(stderr, "damar: homogenize: the trim track does not hold one interval per read at most\n");
           goto done;
@@ -363,19 +350,14 @@ int damar_homogenize_track(const damar_dbinfo *db, const char *las, const damar_
   if (p->merge && damar_homog_seed(h, p->iv_anno, p->iv_data, p->iv_ndata))
     goto done;
   while ((got = damar_piles_next_traces(r, &t)) > 0)
-    { t.p.read_len = db->read_len;  t.p.read_flags = db->read_flags;
-      t.p.nreads = db->nreads;  t.p.maxlen = db->maxlen;
-      for (i = 0; i < t.p.npiles; i++)
-        if (t.p.pile_aread[i] < 0 || t.p.pile_aread[i] >= db->nreads)
-          { fprintf(stderr, "damar: %s holds reads the database does not have\n", las);
-            goto done;
-          }
+    { if (damar_batch_bind(&t.p, db, las, DAMAR_BIND_A))
+        goto done;
       if (damar_homog_add(h, &t, p->iv_anno, p->iv_data, p->iv_ndata, p->ends, pairs))
         goto done;
     }
   if (got < 0)
     goto done;
-  res->anno = (uint64 *) grow(NULL, sizeof(uint64) * ((size_t) db->nreads + 2));
+  res->anno = (uint64 *) damar_grow(NULL, sizeof(uint64) * ((size_t) db->nreads + 2), "homogenize");
   if (damar_homog_finish(h, res->anno, &res->data, &res->ndata, &res->tagged))
     goto done;
   rc = 0;

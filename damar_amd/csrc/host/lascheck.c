@@ -21,6 +21,7 @@
 #include <string.h>
 
 #include "damar_check.h"
+#include "damar_host.h"                   /* damar_trace_at alone: the checker stays a program of its own */
 
 static void say(damar_lascheck *ck, int kind, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
 
@@ -69,10 +70,6 @@ static int same_beyond_keys(const Overlap *l, const Overlap *r)
          l->path.bepos == r->path.bepos && l->path.tlen == r->path.tlen;
 }
 
-static int trace_value(const void *trace, int tbytes, int j)
-{ return tbytes == 1 ? ((const uint8 *) trace)[j] : ((const uint16 *) trace)[j];
-}
-
 static void strict_checks(damar_lascheck *ck, const Overlap *o, const void *trace, int tbytes)
 { const Path *p = &o->path;
   const long long n = (long long) ck->seen;
@@ -94,14 +91,14 @@ static void strict_checks(damar_lascheck *ck, const Overlap *o, const void *trac
     { long long diffs = 0;
       int j, wide = 0;
       for (j = 0; j + 1 < p->tlen; j += 2)
-        diffs += trace_value(trace, tbytes, j);
+        diffs += damar_trace_at(trace, tbytes, j);
       if (diffs != p->diffs)
         say(ck, DAMAR_CHECK_MESSAGE, "strict: overlap %lld (%d x %d): the trace holds %lld differences, the record %d",
             n, o->aread, o->bread, diffs, p->diffs);
       if (tbytes == 2 && ts <= TRACE_XOVR)
         { for (j = 0; j < p->tlen; j++)
-            if (trace_value(trace, 2, j) > 255)
-              wide = trace_value(trace, 2, j);
+            if (damar_trace_at(trace, 2, j) > 255)
+              wide = damar_trace_at(trace, 2, j);
           if (wide)
             say(ck, DAMAR_CHECK_MESSAGE, "strict: overlap %lld (%d x %d): trace value %d does not fit the file's one-byte traces",
                 n, o->aread, o->bread, wide);
@@ -163,7 +160,7 @@ int damar_lascheck_feed(damar_lascheck *ck, const Overlap *o, const void *trace,
       if ((opt & DAMAR_CHECK_PTP) && (trace != NULL || o->path.tlen <= 0))
         { int be = o->path.bbpos, j;
           for (j = 0; j + 1 < o->path.tlen; j += 2)
-            be += trace_value(trace, tbytes, j + 1);
+            be += damar_trace_at(trace, tbytes, j + 1);
           if (be != o->path.bepos)
             say(ck, DAMAR_CHECK_MESSAGE, "overlap %lld (%d x %d): pass-through points inconsistent be = %d (expected %d)",
                 n, o->aread, o->bread, be, o->path.bepos);

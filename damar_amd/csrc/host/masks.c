@@ -9,32 +9,6 @@
 #include "damar_hip.h"
 #include "damar_host.h"
 
-static void *grow(void *p, size_t n)
-{ void *q = realloc(p, n ? n : 1);
-  if (q == NULL)
-    { fprintf(stderr, "damar: out of memory (%zu bytes, masks)\n", n);
-      exit(1);
-    }
-  return q;
-}
-
-static void bind_db(damar_pile_batch *b, const damar_dbinfo *db)
-{ b->read_len = db->read_len;  b->read_flags = db->read_flags;
-  b->nreads = db->nreads;  b->maxlen = db->maxlen;
-}
-
-/* every record of the batch names reads of the database */
-static int batch_in_db(const damar_pile_batch *b)
-{ int64 i;
-  for (i = 0; i < b->npiles; i++)
-    if (b->pile_aread[i] < 0 || b->pile_aread[i] >= b->nreads)
-      return 0;
-  for (i = 0; i < b->nrec; i++)
-    if (b->bread[i] < 0 || b->bread[i] >= b->nreads)
-      return 0;
-  return 1;
-}
-
 void damar_repeat_result_free(damar_repeat_result *res)
 { free(res->histo);  free(res->anno);  free(res->data);
   memset(res, 0, sizeof(*res));
@@ -60,11 +34,8 @@ int damar_repeat_track(const damar_dbinfo *db, const char *las, const damar_repe
       int   j, best = 0;
       res->histo = (int64 *) calloc((size_t) p.max_cov, sizeof(int64));
       while (left > 0 && (got = damar_piles_next(r, &b)) > 0)
-        { bind_db(&b, db);
-          if (!batch_in_db(&b))
-            { fprintf(stderr, "damar: %s holds reads the database does not have\n", las);
-              goto done;
-            }
+        { if (damar_batch_bind(&b, db, las, DAMAR_BIND_AB))
+            goto done;
           if (b.npiles > left)
             { b.npiles = left;
               b.nrec = b.pile_off[left];
@@ -95,22 +66,16 @@ int damar_repeat_track(const damar_dbinfo *db, const char *las, const damar_repe
     { res->anno = (uint64 *) calloc((size_t) db->nreads + 2, sizeof(uint64));
       while ((got = damar_piles_next(r, &b)) > 0)
         { damar_pile_track t;
-          bind_db(&b, db);
-          if (!batch_in_db(&b))
-            { fprintf(stderr, "damar: %s holds reads the database does not have\n", las);
-              goto done;
-            }
-          if (b.npiles > ccap)
-            { ccap = b.npiles + b.npiles / 4 + 64;
-              count = (int *) grow(count, sizeof(int) * (size_t) ccap);
-            }
+          if (damar_batch_bind(&b, db, las, DAMAR_BIND_AB))
+            goto done;
+          count = (int *) damar_reserve(count, &ccap, b.npiles, sizeof(int), 64, "masks");
           memset(&t, 0, sizeof(t));
           t.count = count;
           if (damar_pile_repeats(&b, &p, &t))
             goto done;
           if (res->ndata + t.ndata > dcap)
             { dcap = res->ndata + t.ndata + dcap / 4 + 1024;
-              res->data = (int *) grow(res->data, sizeof(int) * (size_t) dcap);
+              res->data = (int *) damar_grow(res->data, sizeof(int) * (size_t) dcap, "masks");
             }
           if (t.ndata > 0)
             memcpy(res->data + res->ndata, t.data, sizeof(int) * (size_t) t.ndata);
@@ -125,15 +90,9 @@ int damar_repeat_track(const damar_dbinfo *db, const char *las, const damar_repe
         }
       if (got < 0)
         goto done;
-      { uint64 off = 0, c;                                   /* :256-263: counts to offsets */
-        for (i = 0; i <= db->nreads; i++)
-          { c = res->anno[i];
-            res->anno[i] = off;
-            off += c;
-          }
-      }
+      damar_counts_to_offsets(res->anno, db->nreads);       /* :256-263 */
       if (res->data == NULL)
-        res->data = (int *) grow(NULL, 8);
+        res->data = (int *) damar_grow(NULL, 8, "masks");
     }
   rc = 0;
 done:
@@ -158,7 +117,7 @@ int damar_tan_track(const damar_dbinfo *db, const char *las, int first, int last
     }
   while ((got = damar_piles_next(r, &b)) > 0)
     { damar_pile_track t;
-      bind_db(&b, db);
+      damar_batch_bind(&b, db, las, DAMAR_BIND_ONLY);
       for (i = 0; i < b.npiles; i++)                          /* TANmask.c:259-263, 318-322: ascending, inside the block */
         { if (b.pile_aread[i] < next || b.pile_aread[i] >= last)
             { rc = 2;
@@ -166,17 +125,14 @@ int damar_tan_track(const damar_dbinfo *db, const char *las, int first, int last
             }
           next = b.pile_aread[i] + 1;
         }
-      if (b.npiles > ccap)
-        { ccap = b.npiles + b.npiles / 4 + 64;
-          count = (int *) grow(count, sizeof(int) * (size_t) ccap);
-        }
+      count = (int *) damar_reserve(count, &ccap, b.npiles, sizeof(int), 64, "masks");
       memset(&t, 0, sizeof(t));
       t.count = count;
       if (damar_pile_tandem(&b, min_len, &t))
         goto done;
       if (ndata + t.ndata > dcap)
         { dcap = ndata + t.ndata + dcap / 4 + 1024;
-          data = (int *) grow(data, sizeof(int) * (size_t) dcap);
+          data = (int *) damar_grow(data, sizeof(int) * (size_t) dcap, "masks");
         }
       if (t.ndata > 0)
         memcpy(data + ndata, t.data, sizeof(int) * (size_t) t.ndata);
@@ -194,7 +150,7 @@ int damar_tan_track(const damar_dbinfo *db, const char *las, int first, int last
   for (i = 1; i <= last - first; i++)
     offs[i] += offs[i - 1];
   if (data == NULL)
-    data = (int *) grow(NULL, 8);
+    data = (int *) damar_grow(NULL, 8, "masks");
   *offs_out = offs;
   *data_out = data;
   offs = NULL;

@@ -13,28 +13,9 @@
 #include "damar_hip.h"
 #include "damar_host.h"
 
-#define OVL_DISCARD_FLAG 0x2              /* lib/oflags.h:5 */
 #define EDGE_DIST 1000                    /* LArepeat.c:38-39 */
 #define EDGE_FUZZ 200
 #define SEP_FUZZ  20                      /* TANmask.c:82 */
-
-static void *pmalloc(size_t n)
-{ void *p = malloc(n ? n : 1);
-  if (p == NULL)
-    { fprintf(stderr, "damar: out of memory (%zu bytes, piles)\n", n);
-      exit(1);
-    }
-  return p;
-}
-
-static void *prealloc(void *q, size_t n)
-{ void *p = realloc(q, n ? n : 1);
-  if (p == NULL)
-    { fprintf(stderr, "damar: out of memory (%zu bytes, piles)\n", n);
-      exit(1);
-    }
-  return p;
-}
 
 int damar_piles_on_host(void)
 { const char *e = getenv("DAMAR_PILES");
@@ -69,13 +50,13 @@ int damar_dbinfo_open(const char *name, damar_dbinfo *db)
     }
   db->nreads = head.ureads;
   db->maxlen = head.maxlen;
-  reads = (HITS_READ *) pmalloc(sizeof(HITS_READ) * (size_t) db->nreads);
+  reads = (HITS_READ *) damar_grow(NULL, sizeof(HITS_READ) * (size_t) db->nreads, "piles");
   if (fread(reads, sizeof(HITS_READ), (size_t) db->nreads, idx) != (size_t) db->nreads)
     { fprintf(stderr, "damar: index %s is truncated\n", path);
       goto fail;
     }
-  db->read_len   = (int *) pmalloc(sizeof(int) * (size_t) db->nreads);
-  db->read_flags = (int *) pmalloc(sizeof(int) * (size_t) db->nreads);
+  db->read_len   = (int *) damar_grow(NULL, sizeof(int) * (size_t) db->nreads, "piles");
+  db->read_flags = (int *) damar_grow(NULL, sizeof(int) * (size_t) db->nreads, "piles");
   for (i = 0; i < db->nreads; i++)
     { db->read_len[i]   = reads[i].rlen;
       db->read_flags[i] = reads[i].flags;
@@ -92,7 +73,7 @@ int damar_dbinfo_open(const char *name, damar_dbinfo *db)
     { long long size;
       if (fscanf(stub, "size = %9lld\n", &size) != 1)
         goto junk;
-      db->block_first = (int *) pmalloc(sizeof(int) * (size_t) (db->nblocks + 1));
+      db->block_first = (int *) damar_grow(NULL, sizeof(int) * (size_t) (db->nblocks + 1), "piles");
       for (i = 0; i <= db->nblocks; i++)
         if (fscanf(stub, " %9d\n", &db->block_first[i]) != 1)
           goto junk;
@@ -155,10 +136,7 @@ static int next_record(damar_pile_reader *r)
     { const int64 n = (int64) r->tbytes * r->rec[0];
       if ((int64) ftello(r->f) + n > r->size)
         return -1;
-      if (n > r->rtcap)
-        { r->rtcap = n + n / 4 + 1024;
-          r->rtrace = (unsigned char *) prealloc(r->rtrace, (size_t) r->rtcap);
-        }
+      r->rtrace = (unsigned char *) damar_reserve(r->rtrace, &r->rtcap, n, 1, 1024, "piles");
       if (n > 0 && fread(r->rtrace, 1, (size_t) n, r->f) != (size_t) n)
         return -1;
     }
@@ -274,17 +252,17 @@ static int piles_next(damar_pile_reader *r, damar_pile_batch *b)
         { if (n >= r->cap)
             { r->cap = r->cap + r->cap / 4 + 1024;
               for (i = 0; i < 8; i++)
-                r->col[i] = (int *) prealloc(r->col[i], sizeof(int) * (size_t) r->cap);
+                r->col[i] = (int *) damar_grow(r->col[i], sizeof(int) * (size_t) r->cap, "piles");
               if (r->traces)
-                { r->toff = (int64 *) prealloc(r->toff, sizeof(int64) * (size_t) r->cap);
-                  r->tlen = (int *) prealloc(r->tlen, sizeof(int) * (size_t) r->cap);
+                { r->toff = (int64 *) damar_grow(r->toff, sizeof(int64) * (size_t) r->cap, "piles");
+                  r->tlen = (int *) damar_grow(r->tlen, sizeof(int) * (size_t) r->cap, "piles");
                 }
             }
           if (r->traces)
             { const int64 nb = (int64) r->tbytes * r->rec[0];
               if (r->ttop + nb > r->tcap)
                 { r->tcap = r->ttop + nb + r->tcap / 4 + 4096;
-                  r->tbuf = (unsigned char *) prealloc(r->tbuf, (size_t) r->tcap);
+                  r->tbuf = (unsigned char *) damar_grow(r->tbuf, (size_t) r->tcap, "piles");
                 }
               if (nb > 0)
                 memcpy(r->tbuf + r->ttop, r->rtrace, (size_t) nb);
@@ -312,8 +290,8 @@ static int piles_next(damar_pile_reader *r, damar_pile_batch *b)
         }
       if (np + 2 >= r->pcap)
         { r->pcap = r->pcap + r->pcap / 4 + 256;
-          r->pile_off   = (int64 *) prealloc(r->pile_off, sizeof(int64) * (size_t) (r->pcap + 1));
-          r->pile_aread = (int *) prealloc(r->pile_aread, sizeof(int) * (size_t) r->pcap);
+          r->pile_off   = (int64 *) damar_grow(r->pile_off, sizeof(int64) * (size_t) (r->pcap + 1), "piles");
+          r->pile_aread = (int *) damar_grow(r->pile_aread, sizeof(int) * (size_t) r->pcap, "piles");
         }
       r->pile_off[np] = start;
       r->pile_aread[np] = a;
@@ -384,10 +362,10 @@ int damar_host_pile_coverage(const damar_pile_batch *b, const damar_repeat_param
       int   n = 0, depth = 0;
       if (2 * (hi - lo) > cap)
         { cap = 2 * (hi - lo) + 64;
-          ev = (int *) prealloc(ev, sizeof(int) * (size_t) cap);
+          ev = (int *) damar_grow(ev, sizeof(int) * (size_t) cap, "piles");
         }
       for (i = lo; i < hi; i++)
-        { if (!(b->read_flags[b->bread[i]] & DB_BEST) || (b->flags[i] & OVL_DISCARD_FLAG) || b->bread[i] == a ||
+        { if (!(b->read_flags[b->bread[i]] & DB_BEST) || (b->flags[i] & OVL_DISCARD) || b->bread[i] == a ||
               b->aepos[i] - b->abpos[i] < p->min_aln_len)
             continue;
           sum += b->aepos[i] - b->abpos[i];
@@ -414,7 +392,7 @@ int damar_host_pile_repeats(const damar_pile_batch *b, const damar_repeat_params
 { const int enter = (int) (p->cov * p->xcov_enter), leave = (int) (p->cov * p->xcov_leave);
   const int width = 2 + (p->inccov ? 1 : 0);
   int64 pi, i, j, cap = 0, dcap = 1024, top = 0;
-  int  *ev = NULL, *data = (int *) pmalloc(sizeof(int) * (size_t) dcap);
+  int  *ev = NULL, *data = (int *) damar_grow(NULL, sizeof(int) * (size_t) dcap, "piles");
   out->merged = out->repeat_bases = 0;
   for (pi = 0; pi < b->npiles; pi++)
     { const int64 lo = b->pile_off[pi], hi = b->pile_off[pi + 1], base = top;
@@ -422,10 +400,10 @@ int damar_host_pile_repeats(const damar_pile_batch *b, const damar_repeat_params
       int n = 0, k, span = 0, inside = 0, peak = 0;
       if (2 * (hi - lo) > cap)
         { cap = 2 * (hi - lo) + 64;
-          ev = (int *) prealloc(ev, sizeof(int) * (size_t) cap);
+          ev = (int *) damar_grow(ev, sizeof(int) * (size_t) cap, "piles");
         }
       for (i = lo; i < hi; i++)
-        { if ((b->flags[i] & OVL_DISCARD_FLAG) || (!p->inc_identity && b->bread[i] == a) ||
+        { if ((b->flags[i] & OVL_DISCARD) || (!p->inc_identity && b->bread[i] == a) ||
               b->aepos[i] - b->abpos[i] < p->min_aln_len)
             continue;
           ev[n++] = b->abpos[i];
@@ -435,7 +413,7 @@ int damar_host_pile_repeats(const damar_pile_batch *b, const damar_repeat_params
       qsort(ev, (size_t) n, sizeof(int), cmp_event);
       if (top + 3 * (int64) k + 8 > dcap)
         { dcap = dcap + dcap / 4 + 3 * (int64) k + 8;
-          data = (int *) prealloc(data, sizeof(int) * (size_t) dcap);
+          data = (int *) damar_grow(data, sizeof(int) * (size_t) dcap, "piles");
         }
       /* a region is open from the event that lifts the depth above `enter` to the one that drops it below `leave`; the
          value kept with -C is the highest depth a start reached strictly after the opening event (:340-352, 405) and, over
@@ -495,14 +473,14 @@ int damar_host_pile_repeats(const damar_pile_batch *b, const damar_repeat_params
 
 int damar_host_pile_tandem(const damar_pile_batch *b, int min_len, damar_pile_track *out)
 { int64 pi, i, cap = 0, dcap = 1024, top = 0;
-  int  *ev = NULL, *data = (int *) pmalloc(sizeof(int) * (size_t) dcap);
+  int  *ev = NULL, *data = (int *) damar_grow(NULL, sizeof(int) * (size_t) dcap, "piles");
   out->merged = out->repeat_bases = 0;
   for (pi = 0; pi < b->npiles; pi++)
     { const int64 lo = b->pile_off[pi], hi = b->pile_off[pi + 1], base = top;
       int n = 0, depth = 0;
       if (2 * (hi - lo) > cap)
         { cap = 2 * (hi - lo) + 64;
-          ev = (int *) prealloc(ev, sizeof(int) * (size_t) cap);
+          ev = (int *) damar_grow(ev, sizeof(int) * (size_t) cap, "piles");
         }
       for (i = lo; i < hi; i++)
         if (b->abpos[i] - b->bepos[i] <= SEP_FUZZ && b->aepos[i] - b->bbpos[i] > min_len)
@@ -512,7 +490,7 @@ int damar_host_pile_tandem(const damar_pile_batch *b, int min_len, damar_pile_tr
       qsort(ev, (size_t) n, sizeof(int), cmp_int);
       if (top + n + 8 > dcap)
         { dcap = dcap + dcap / 4 + n + 8;
-          data = (int *) prealloc(data, sizeof(int) * (size_t) dcap);
+          data = (int *) damar_grow(data, sizeof(int) * (size_t) dcap, "piles");
         }
       for (i = 0; i < n; i++)
         if (ev[i] & 1)
@@ -537,7 +515,7 @@ static int write_chunks(FILE *f, const void *buf, uint64 len, uint64 *written)
   while (len > 0)
     { const uint64 n = len < chunk ? len : chunk;
       uLongf  clen = compressBound((uLong) n);
-      unsigned char *o = (unsigned char *) pmalloc(clen);
+      unsigned char *o = (unsigned char *) damar_grow(NULL, clen, "piles");
       uint64  c64;
       if (compress(o, &clen, in, (uLong) n) != Z_OK)
         { free(o);

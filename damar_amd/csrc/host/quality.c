@@ -16,17 +16,7 @@
 #include "damar_hip.h"
 #include "damar_host.h"
 
-#define OVL_DISCARD_FLAG 0x2              /* lib/oflags.h:5 */
 #define TRIM_WINDOW 5                     /* LAq.c:36 */
-
-static void *grow(void *p, size_t n)
-{ void *q = realloc(p, n ? n : 1);
-  if (q == NULL)
-    { fprintf(stderr, "damar: out of memory (%zu bytes, quality)\n", n);
-      exit(1);
-    }
-  return q;
-}
 
 int damar_trace_batch_valid(const damar_trace_batch *t, int64 *ntiles_out)
 { const damar_pile_batch *b = &t->p;
@@ -69,11 +59,6 @@ bad:
   return 0;
 }
 
-static int trace_at(const damar_trace_batch *t, int64 rec, int k)
-{ const unsigned char *p = t->trace + t->trace_off[rec] + (int64) t->tbytes * k;
-  return t->tbytes == 1 ? p[0] : p[0] | (p[1] << 8);
-}
-
 /* handler_annotate (LAq.c:312-409).  The reference's histogram is flat, q_histo[2 * tw * tile + 2 * q + comp], so a segment
    of q >= tw differences counts in tile + q / tw at q % tw; what would land beyond the read's tiles is dropped (the reference
    writes it where it is never read).  A record of tlen < 4 makes the reference read past the trace: here the first
@@ -90,7 +75,7 @@ int damar_host_pile_quality(const damar_trace_batch *t, const damar_q_params *p,
       int64 tile;
       if (ntiles * tw > hcap)
         { hcap = ntiles * tw;
-          histo = (uint32 *) grow(histo, sizeof(uint32) * (size_t) hcap);
+          histo = (uint32 *) damar_grow(histo, sizeof(uint32) * (size_t) hcap, "quality");
         }
       memset(histo, 0, sizeof(uint32) * (size_t) (ntiles * tw));
       for (i = b->pile_off[pi]; i < b->pile_off[pi + 1]; i++)
@@ -104,7 +89,7 @@ int damar_host_pile_quality(const damar_trace_batch *t, const damar_q_params *p,
                 { if (b->abpos[i] % tw != 0) continue; }
               else if (s == nseg - 1)
                 { if (b->aepos[i] % tw != 0 && b->aepos[i] != alen) continue; }
-              q = trace_at(t, i, 2 * s);
+              q = damar_trace_value(t, i, 2 * s);
               tile = (int64) b->abpos[i] / tw + s + q / tw;
               if (tile < ntiles)
                 histo[tile * tw + q % tw] += 1;
@@ -193,31 +178,6 @@ void damar_q_result_free(damar_q_result *res)
   memset(res, 0, sizeof(*res));
 }
 
-static void counts_to_offsets(uint64 *anno, int nreads)
-{ uint64 off = 0, c;
-  int    j;
-  for (j = 0; j <= nreads; j++)
-    { c = anno[j];
-      anno[j] = off;
-      off += c;
-    }
-}
-
-static void bind_db(damar_pile_batch *b, const damar_dbinfo *db)
-{ b->read_len = db->read_len;  b->read_flags = db->read_flags;
-  b->nreads = db->nreads;  b->maxlen = db->maxlen;
-}
-
-static int piles_in_db(const damar_pile_batch *b, const char *las)
-{ int64 i;
-  for (i = 0; i < b->npiles; i++)
-    if (b->pile_aread[i] < 0 || b->pile_aread[i] >= b->nreads)
-      { fprintf(stderr, "damar: %s holds reads the database does not have\n", las);
-        return 0;
-      }
-  return 1;
-}
-
 int damar_q_track(const damar_dbinfo *db, const char *las, const damar_q_params *p, int trim_q, int min_len, damar_q_result *res)
 { damar_pile_reader *r;
   damar_trace_batch  t;
@@ -229,16 +189,15 @@ int damar_q_track(const damar_dbinfo *db, const char *las, const damar_q_params 
     return 1;
   res->q_anno = (uint64 *) calloc((size_t) db->nreads + 2, sizeof(uint64));
   res->trim_anno = (uint64 *) calloc((size_t) db->nreads + 2, sizeof(uint64));
-  res->q_data = (int *) grow(NULL, 8);
-  res->trim_data = (int *) grow(NULL, sizeof(int) * 2 * ((size_t) db->nreads + 1));
+  res->q_data = (int *) damar_grow(NULL, 8, "quality");
+  res->trim_data = (int *) damar_grow(NULL, sizeof(int) * 2 * ((size_t) db->nreads + 1), "quality");
   while ((got = damar_piles_next_traces(r, &t)) > 0)
     { int64 ntiles = 0;
-      bind_db(&t.p, db);
-      if (!piles_in_db(&t.p, las) || damar_pile_quality(&t, p, NULL, &ntiles))
+      if (damar_batch_bind(&t.p, db, las, DAMAR_BIND_A) || damar_pile_quality(&t, p, NULL, &ntiles))
         goto done;
       if (res->nq + ntiles > qcap)
         { qcap = res->nq + ntiles + qcap / 4 + 1024;
-          res->q_data = (int *) grow(res->q_data, sizeof(int) * (size_t) qcap);
+          res->q_data = (int *) damar_grow(res->q_data, sizeof(int) * (size_t) qcap, "quality");
         }
       if (damar_pile_quality(&t, p, res->q_data + res->nq, &ntiles))
         goto done;
@@ -248,7 +207,7 @@ int damar_q_track(const damar_dbinfo *db, const char *las, const damar_q_params 
     }
   if (got < 0)
     goto done;
-  counts_to_offsets(res->q_anno, db->nreads);                  /* post_annotate, calculate_trim */
+  damar_counts_to_offsets(res->q_anno, db->nreads);                  /* post_annotate, calculate_trim */
   for (a = 0; a < db->nreads; a++)
     { int tb = 0, te = 0;
       if (damar_trim_from_q(res->q_data, res->nq, (int64) (res->q_anno[a] / sizeof(int)), (int64) (res->q_anno[a + 1] / sizeof(int)),
@@ -258,7 +217,7 @@ int damar_q_track(const damar_dbinfo *db, const char *las, const damar_q_params 
           res->trim_anno[a] += 2 * sizeof(int);
         }
     }
-  counts_to_offsets(res->trim_anno, db->nreads);
+  damar_counts_to_offsets(res->trim_anno, db->nreads);
   rc = 0;
 done:
   if (rc)
@@ -280,14 +239,13 @@ int damar_trim_update(const damar_dbinfo *db, const char *las, const uint64 *q_a
     return 1;
   tw = damar_piles_tspace(r);
   res->trim_anno = (uint64 *) calloc((size_t) db->nreads + 2, sizeof(uint64));
-  res->trim_data = (int *) grow(NULL, 8);
+  res->trim_data = (int *) damar_grow(NULL, 8, "quality");
   while ((got = damar_piles_next(r, &b)) > 0)
-    { bind_db(&b, db);
-      if (!piles_in_db(&b, las))
+    { if (damar_batch_bind(&b, db, las, DAMAR_BIND_A))
         goto done;
       if (res->ntrim + 2 * b.npiles > cap)
         { cap = res->ntrim + 2 * b.npiles + cap / 4 + 1024;
-          res->trim_data = (int *) grow(res->trim_data, sizeof(int) * (size_t) cap);
+          res->trim_data = (int *) damar_grow(res->trim_data, sizeof(int) * (size_t) cap, "quality");
         }
       for (pi = 0; pi < b.npiles; pi++)
         { const int a = b.pile_aread[pi];
@@ -298,7 +256,7 @@ int damar_trim_update(const damar_dbinfo *db, const char *las, const uint64 *q_a
               goto done;
             }
           for (i = b.pile_off[pi]; i < b.pile_off[pi + 1]; i++)
-            { if ((b.flags[i] & OVL_DISCARD_FLAG) || b.bread[i] == a)
+            { if ((b.flags[i] & OVL_DISCARD) || b.bread[i] == a)
                 continue;
               if (b.abpos[i] < ab_min) ab_min = b.abpos[i];
               if (b.aepos[i] > ae_max) ae_max = b.aepos[i];
@@ -322,7 +280,7 @@ int damar_trim_update(const damar_dbinfo *db, const char *las, const uint64 *q_a
     }
   if (got < 0)
     goto done;
-  counts_to_offsets(res->trim_anno, db->nreads);
+  damar_counts_to_offsets(res->trim_anno, db->nreads);
   rc = 0;
 done:
   if (rc)
@@ -354,7 +312,7 @@ static unsigned char *slurp(const char *path, uint64 skip, uint64 len)
   unsigned char *buf;
   if (f == NULL)
     return NULL;
-  buf = (unsigned char *) grow(NULL, (size_t) len);
+  buf = (unsigned char *) damar_grow(NULL, (size_t) len, "quality");
   if (fseeko(f, (off_t) skip, SEEK_SET) != 0 || (len > 0 && fread(buf, (size_t) len, 1, f) != 1))
     { free(buf);
       buf = NULL;
@@ -378,7 +336,7 @@ int damar_track_read_a2(const char *dbpath, const char *track, int nreads, uint6
       return 1;
     }
   fclose(f);
-  anno = (uint64 *) grow(NULL, 8 * ((size_t) nreads + 1));
+  anno = (uint64 *) damar_grow(NULL, 8 * ((size_t) nreads + 1), "quality");
   if ((ca = slurp(path, sizeof(h), h.clen)) == NULL || read_chunks(ca, h.clen, (unsigned char *) anno, 8 * ((uint64) nreads + 1)))
     goto done;
   total = anno[nreads];
@@ -388,7 +346,7 @@ int damar_track_read_a2(const char *dbpath, const char *track, int nreads, uint6
   if (total % 4)
     goto done;
   snprintf(path, sizeof(path), "%s.%s.d2", dbpath, track);
-  data = (int *) grow(NULL, (size_t) total);
+  data = (int *) damar_grow(NULL, (size_t) total, "quality");
   if ((cd = slurp(path, 0, h.cdlen)) == NULL || read_chunks(cd, h.cdlen, (unsigned char *) data, total))
     goto done;
   *anno_out = anno;
@@ -400,4 +358,46 @@ int damar_track_read_a2(const char *dbpath, const char *track, int nreads, uint6
 done:
   free(ca);  free(cd);  free(anno);  free(data);
   return rc;
+}
+
+/* the uncompressed form (db/DB.c Load_Track): int len, int size, len + 1 offsets of `size` bytes; the data file */
+static int read_anno_data(const damar_dbinfo *db, const char *track, uint64 **anno_out, int **data_out, int64 *ndata_out)
+{ char    path[4500];
+  FILE   *af, *df = NULL;
+  uint64 *anno = NULL;
+  int    *data = NULL;
+  int64   ndata;
+  int     len, size, j, rc = 1;
+  snprintf(path, sizeof(path), "%s.%s.anno", db->path, track);
+  if ((af = fopen(path, "r")) == NULL)
+    return 1;
+  snprintf(path, sizeof(path), "%s.%s.data", db->path, track);
+  if (fread(&len, sizeof(int), 1, af) != 1 || fread(&size, sizeof(int), 1, af) != 1 || (size != 4 && size != 8) ||
+      len != db->nreads || (df = fopen(path, "r")) == NULL)
+    goto done;
+  anno = (uint64 *) damar_grow(NULL, sizeof(uint64) * ((size_t) db->nreads + 1), "track");
+  for (j = 0; j <= db->nreads; j++)
+    { int64 v8 = 0;
+      int   v4 = 0;
+      if (fread(size == 4 ? (void *) &v4 : (void *) &v8, (size_t) size, 1, af) != 1)
+        goto done;
+      anno[j] = (uint64) (size == 4 ? v4 : v8);
+    }
+  ndata = (int64) (anno[db->nreads] / sizeof(int));
+  data = (int *) damar_grow(NULL, sizeof(int) * (size_t) ndata, "track");
+  if (ndata > 0 && fread(data, sizeof(int), (size_t) ndata, df) != (size_t) ndata)
+    goto done;
+  *anno_out = anno;  *data_out = data;  *ndata_out = ndata;
+  anno = NULL;
+  data = NULL;
+  rc = 0;
+done:
+  fclose(af);
+  if (df) fclose(df);
+  free(anno);  free(data);
+  return rc;
+}
+
+int damar_track_read_any(const damar_dbinfo *db, const char *track, uint64 **anno, int **data, int64 *ndata)
+{ return damar_track_read_a2(db->path, track, db->nreads, anno, data, ndata) && read_anno_data(db, track, anno, data, ndata);
 }

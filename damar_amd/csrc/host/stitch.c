@@ -16,21 +16,7 @@
 #include "damar_hip.h"
 #include "damar_host.h"
 
-#define OVL_COMP_FLAG    0x1              /* lib/oflags.h */
-#define OVL_DISCARD_FLAG 0x2
-#define OVL_STITCH_FLAG  0x80
-#define OVL_TEMP_FLAG    0x800
-
 #define MAX_STITCH_ALIGN_ERROR 0.57
-
-static void *smalloc(void *q, size_t n)
-{ void *p = realloc(q, n ? n : 1);
-  if (p == NULL)
-    { fprintf(stderr, "damar: out of memory (%zu bytes, stitch)\n", n);
-      exit(1);
-    }
-  return p;
-}
 
 int damar_stitch_on_host(void)
 { const char *e = getenv("DAMAR_STITCH");
@@ -45,44 +31,9 @@ typedef struct
   int64   ndata;
 } Track;
 
-/* the uncompressed form (db/DB.c Load_Track), what the reference's loader falls back to */
-static int read_anno_data(const damar_dbinfo *db, const char *track, Track *t)
-{ char  path[4500];
-  FILE *af, *df = NULL;
-  int   len, size, j, rc = 1;
-  snprintf(path, sizeof(path), "%s.%s.anno", db->path, track);
-  if ((af = fopen(path, "r")) == NULL)
-    return 1;
-  snprintf(path, sizeof(path), "%s.%s.data", db->path, track);
-  if (fread(&len, sizeof(int), 1, af) != 1 || fread(&size, sizeof(int), 1, af) != 1 || (size != 4 && size != 8) ||
-      len != db->nreads || (df = fopen(path, "r")) == NULL)
-    goto done;
-  t->anno = (uint64 *) smalloc(NULL, sizeof(uint64) * ((size_t) db->nreads + 1));
-  for (j = 0; j <= db->nreads; j++)
-    { int64 v8 = 0;
-      int   v4 = 0;
-      if (fread(size == 4 ? (void *) &v4 : (void *) &v8, (size_t) size, 1, af) != 1)
-        goto done;
-      t->anno[j] = (uint64) (size == 4 ? v4 : v8);
-    }
-  t->ndata = (int64) (t->anno[db->nreads] / sizeof(int));
-  t->data = (int *) smalloc(NULL, sizeof(int) * (size_t) t->ndata);
-  if (t->ndata > 0 && fread(t->data, sizeof(int), (size_t) t->ndata, df) != (size_t) t->ndata)
-    goto done;
-  rc = 0;
-done:
-  fclose(af);
-  if (df) fclose(df);
-  if (rc)
-    { free(t->anno);  free(t->data);
-      memset(t, 0, sizeof(*t));
-    }
-  return rc;
-}
-
 static int load_track(const damar_dbinfo *db, const char *name, Track *t)
 { int64 j;
-  if (damar_track_read_a2(db->path, name, db->nreads, &t->anno, &t->data, &t->ndata) && read_anno_data(db, name, t))
+  if (damar_track_read_any(db, name, &t->anno, &t->data, &t->ndata))
     { fprintf(stderr, "(null): Track '%s' does not exist\n", name);     /* the loader's line: it never sets its program name */
       fprintf(stderr, "could not load track %s\n", name);
       return 1;
@@ -128,11 +79,6 @@ typedef struct
   damar_stitch_stats *st;
 } Ctx;
 
-static int intersect(int ab, int ae, int bb, int be)
-{ const int b = (ab > bb) ? ab : bb, e = (ae < be) ? ae : be;
-  return (b < e) ? e - b : 0;
-}
-
 /* LAstitch.c:310-361: the bases of [from, to) of a read outside the repeat track (-r, else -t, else all of them) */
 static int anchor_bases(const Ctx *c, int read, int from, int to)
 { const Track *t = c->rep ? c->rep : c->lc;
@@ -145,7 +91,7 @@ static int anchor_bases(const Ctx *c, int read, int from, int to)
   rb = t->anno[read] / sizeof(int);
   re = t->anno[read + 1] / sizeof(int);
   for (; rb < re; rb += 2)
-    rep += intersect(from, to, t->data[rb], t->data[rb + 1]);
+    rep += damar_intersect(from, to, t->data[rb], t->data[rb + 1]);
   return (to - from - rep > 0) ? to - from - rep : 0;
 }
 
@@ -293,7 +239,7 @@ static int splice(Ctx *c, SRec *head, const Group *g, const uint16 *box, int box
     return 1;
   if (P->top + total >= P->max)
     { P->max = (int64) (1.2 * (double) (P->top + total)) + 1000;
-      P->val = (uint16 *) smalloc(P->val, sizeof(uint16) * (size_t) P->max);
+      P->val = (uint16 *) damar_grow(P->val, sizeof(uint16) * (size_t) P->max, "stitch");
     }
   at = P->top;
   P->top += total;
@@ -321,7 +267,7 @@ static int next_candidate(const Ctx *c, Group *g)
   while (g->i < g->n)
     { const SRec *oi = ovl + g->i;
       if (g->k == 0)
-        { if (oi->flags & OVL_DISCARD_FLAG)
+        { if (oi->flags & OVL_DISCARD)
             { g->i += 1;
               continue;
             }
@@ -330,7 +276,7 @@ static int next_candidate(const Ctx *c, Group *g)
         }
       for (; g->k < g->n; g->k++)
         { const SRec *ok = ovl + g->k;
-          if ((ok->flags & OVL_DISCARD_FLAG) || (oi->flags & OVL_COMP_FLAG) != (ok->flags & OVL_COMP_FLAG))
+          if ((ok->flags & OVL_DISCARD) || (oi->flags & OVL_COMP) != (ok->flags & OVL_COMP))
             continue;
           if (g->ab1 > ok->abpos || g->ae1 > ok->aepos || g->bb1 > ok->bbpos || g->be1 > ok->bepos)
             continue;
@@ -353,18 +299,6 @@ static int next_candidate(const Ctx *c, Group *g)
   return 0;
 }
 
-/* B read r's bases [from, to) as the alignment sees them: the read itself, or its complement */
-static void gather_b(const HITS_DB *blk, int r, int comp, int from, int to, char *dst)
-{ const char *s = (const char *) blk->bases + blk->reads[r].boff;
-  const int   len = blk->reads[r].rlen;
-  int i;
-  for (i = from; i < to; i++)
-    if (i < 0 || i >= len)
-      *dst++ = 4;
-    else
-      *dst++ = comp ? (char) (3 - s[len - 1 - i]) : s[i];
-}
-
 int damar_stitch_las(const char *dbname, const char *las, const char *out, const damar_stitch_params *p, damar_stitch_stats *st)
 { damar_dbinfo db;
   HITS_DB blk;
@@ -372,14 +306,13 @@ int damar_stitch_las(const char *dbname, const char *las, const char *out, const
   Ctx     c;
   damar_pile_reader *r = NULL;
   damar_trace_batch  t;
-  FILE   *fo = NULL;
+  damar_las_out *wr = NULL;
   Group  *grp = NULL;
   int64  *act = NULL;          /* the groups of the round, one box each */
   int    *arec = NULL, *bm = NULL, *bn = NULL, *bab = NULL, *bdiffs = NULL;
   int64  *baoff = NULL, *bboff = NULL, *toff = NULL;
   char   *bases = NULL;
-  unsigned char *obuf = NULL;
-  int64   rcap = 0, gcap = 0, bcap = 0, basecap = 0, ocap = 0, written = 0, i;
+  int64   rcap = 0, gcap = 0, bcap = 0, basecap = 0, i;
   int     got, rc = 1, have_db = 0, have_blk = 0, tw, tbytes;
 
   memset(st, 0, sizeof(*st));
@@ -407,7 +340,7 @@ int damar_stitch_las(const char *dbname, const char *las, const char *out, const
   have_blk = 1;
   if ((r = damar_piles_open_traces(las, 0, 0)) == NULL)
     goto done;
-  if ((fo = fopen(out, "w")) == NULL)
+  if ((wr = damar_las_out_open(out, p->purge)) == NULL)
     { fprintf(stderr, "could not open '%s'\n", out);
       goto done;
     }
@@ -419,10 +352,8 @@ int damar_stitch_las(const char *dbname, const char *las, const char *out, const
   c.tw = tw;
   tbytes = (tw <= TRACE_XOVR) ? 1 : 2;
   st->novl = damar_piles_novl(r);
-  { const int64 zero = 0;
-    if (fwrite(&zero, sizeof(int64), 1, fo) != 1 || fwrite(&tw, sizeof(int), 1, fo) != 1)
-      goto wfail;
-  }
+  if (damar_las_out_begin(wr, tw))
+    goto done;
 
   while ((got = damar_piles_next_traces(r, &t)) > 0)
     { const damar_pile_batch *b = &t.p;
@@ -432,14 +363,13 @@ int damar_stitch_las(const char *dbname, const char *las, const char *out, const
 
       damar_piles_rest(r, &rdiffs, &rlast);
       for (i = 0; i < b->nrec; i++) nval += t.tlen[i];
-      if (b->nrec > rcap)
-        { rcap = b->nrec + b->nrec / 4 + 1024;
-          c.rec = (SRec *) smalloc(c.rec, sizeof(SRec) * (size_t) rcap);
-          arec = (int *) smalloc(arec, sizeof(int) * (size_t) rcap);
+      if (damar_room(&rcap, b->nrec, 1024))
+        { c.rec = (SRec *) damar_grow(c.rec, sizeof(SRec) * (size_t) rcap, "stitch");
+          arec = (int *) damar_grow(arec, sizeof(int) * (size_t) rcap, "stitch");
         }
       if (nval + 1 > c.pool.max)
         { c.pool.max = nval + nval / 2 + 4096;
-          c.pool.val = (uint16 *) smalloc(c.pool.val, sizeof(uint16) * (size_t) c.pool.max);
+          c.pool.val = (uint16 *) damar_grow(c.pool.val, sizeof(uint16) * (size_t) c.pool.max, "stitch");
         }
       for (i = 0, nval = 0; i < b->nrec; i++)
         { const unsigned char *src = t.trace + t.trace_off[i];
@@ -459,7 +389,7 @@ int damar_stitch_las(const char *dbname, const char *las, const char *out, const
         { const int a = b->pile_aread[pi];
           int64 lo = b->pile_off[pi], hi = b->pile_off[pi + 1], e;
           if (a < 0 || a >= db.nreads)
-            { fprintf(stderr, "damar: %s holds reads the database does not have\n", las);
+            { damar_reads_missing(las);
               goto done;
             }
           for (i = lo; i < hi; i++)
@@ -468,7 +398,7 @@ int damar_stitch_las(const char *dbname, const char *las, const char *out, const
               arec[i] = a;
               if (br < 0 || br >= db.nreads || o->tlen != 2 * nseg || o->abpos < 0 || o->aepos > db.read_len[a] || o->abpos >= o->aepos ||
                   o->bbpos < 0 || o->bepos > db.read_len[br])
-                { fprintf(stderr, "damar: %s: record %lld is malformed\n", las, (long long) (written + i));
+                { fprintf(stderr, "damar: %s: record %lld is malformed\n", las, (long long) (damar_las_out_written(wr) + i));
                   goto done;
                 }
             }
@@ -479,8 +409,8 @@ int damar_stitch_las(const char *dbname, const char *las, const char *out, const
                 continue;
               if (ngrp >= gcap)
                 { gcap = gcap + gcap / 4 + 1024;
-                  grp = (Group *) smalloc(grp, sizeof(Group) * (size_t) gcap);
-                  act = (int64 *) smalloc(act, sizeof(int64) * (size_t) gcap);
+                  grp = (Group *) damar_grow(grp, sizeof(Group) * (size_t) gcap, "stitch");
+                  act = (int64 *) damar_grow(act, sizeof(int64) * (size_t) gcap, "stitch");
                 }
               memset(grp + ngrp, 0, sizeof(Group));
               grp[ngrp].first = lo;  grp[ngrp].n = (int) (e - lo);  grp[ngrp].aread = a;  grp[ngrp].bread = b->bread[lo];
@@ -496,15 +426,14 @@ int damar_stitch_las(const char *dbname, const char *las, const char *out, const
         { damar_tbox_batch tb;
           uint16 *trace = NULL;
           int64   nbase = 0, keep = 0;
-          if (nact > bcap)
-            { bcap = nact + nact / 4 + 1024;
-              bm = (int *) smalloc(bm, sizeof(int) * (size_t) bcap);
-              bn = (int *) smalloc(bn, sizeof(int) * (size_t) bcap);
-              bab = (int *) smalloc(bab, sizeof(int) * (size_t) bcap);
-              bdiffs = (int *) smalloc(bdiffs, sizeof(int) * (size_t) bcap);
-              baoff = (int64 *) smalloc(baoff, sizeof(int64) * (size_t) bcap);
-              bboff = (int64 *) smalloc(bboff, sizeof(int64) * (size_t) bcap);
-              toff = (int64 *) smalloc(toff, sizeof(int64) * ((size_t) bcap + 1));
+          if (damar_room(&bcap, nact, 1024))
+            { bm = (int *) damar_grow(bm, sizeof(int) * (size_t) bcap, "stitch");
+              bn = (int *) damar_grow(bn, sizeof(int) * (size_t) bcap, "stitch");
+              bab = (int *) damar_grow(bab, sizeof(int) * (size_t) bcap, "stitch");
+              bdiffs = (int *) damar_grow(bdiffs, sizeof(int) * (size_t) bcap, "stitch");
+              baoff = (int64 *) damar_grow(baoff, sizeof(int64) * (size_t) bcap, "stitch");
+              bboff = (int64 *) damar_grow(bboff, sizeof(int64) * (size_t) bcap, "stitch");
+              toff = (int64 *) damar_grow(toff, sizeof(int64) * ((size_t) bcap + 1), "stitch");
             }
           for (k = 0; k < nact; k++)
             { const Group *g = grp + act[k];
@@ -522,20 +451,17 @@ int damar_stitch_las(const char *dbname, const char *las, const char *out, const
               st->box_a += bm[k];
               st->box_b += bn[k];
             }
-          if (nbase > basecap)
-            { basecap = nbase + nbase / 4 + 4096;
-              bases = (char *) smalloc(bases, (size_t) basecap);
-            }
+          bases = (char *) damar_reserve(bases, &basecap, nbase, 1, 4096, "stitch");
           for (k = 0; k < nact; k++)
             { const Group *g = grp + act[k];
-              const int comp = c.rec[g->first + g->i].flags & OVL_COMP_FLAG, blen = db.read_len[g->bread];
+              const int comp = c.rec[g->first + g->i].flags & OVL_COMP, blen = db.read_len[g->bread];
               memcpy(bases + baoff[k], (const char *) blk.bases + blk.reads[g->aread].boff + g->box_ab, (size_t) bm[k]);
               /* a complement pair is realigned as the reference realigns it: its B coordinates, which are the complement's
                  already, mapped through the read's length once more (LAstitch.c:856-862) */
               if (comp)
-                gather_b(&blk, g->bread, 1, blen - g->box_be, blen - g->box_bb, bases + bboff[k]);
+                damar_gather_b(&blk, g->bread, 1, blen - g->box_be, blen - g->box_bb, bases + bboff[k]);
               else
-                gather_b(&blk, g->bread, 0, g->box_bb, g->box_be, bases + bboff[k]);
+                damar_gather_b(&blk, g->bread, 0, g->box_bb, g->box_be, bases + bboff[k]);
             }
           tb.nbox = nact;  tb.m = bm;  tb.n = bn;  tb.abpos = bab;  tb.aoff = baoff;  tb.boff = bboff;  tb.bases = bases;
           tb.nbases = nbase;  tb.tspace = tw;
@@ -550,7 +476,7 @@ int damar_stitch_las(const char *dbname, const char *las, const char *out, const
               SRec   *oi = c.rec + g->first + g->i, *ok = c.rec + g->first + g->k;
               uint16 *bt = trace + toff[k];
               const int btlen = (int) (toff[k + 1] - toff[k]);
-              if (oi->flags & OVL_COMP_FLAG)                   /* ... and its pairs turned round (LAstitch.c:883-897) */
+              if (oi->flags & OVL_COMP)                   /* ... and its pairs turned round (LAstitch.c:883-897) */
                 { int x, y;
                   for (x = 0, y = btlen - 2; x < y; x += 2, y -= 2)
                     { const uint16 d = bt[x], l = bt[x + 1];
@@ -577,7 +503,7 @@ int damar_stitch_las(const char *dbname, const char *las, const char *out, const
                       free(trace);
                       goto done;
                     }
-                  ok->flags |= OVL_DISCARD_FLAG | OVL_STITCH_FLAG;
+                  ok->flags |= OVL_DISCARD | OVL_STITCH;
                   g->ae1 = ok->aepos;
                   g->be1 = ok->bepos;
                   if (g->lc)
@@ -600,56 +526,24 @@ int damar_stitch_las(const char *dbname, const char *las, const char *out, const
         { const SRec   *o = c.rec + i;
           const uint16 *v = c.pool.val + o->toff;
           int   rec[10];
-          int64 need;
-          if (o->flags & OVL_DISCARD_FLAG)
-            { st->discarded += 1;
-              if (p->purge)
-                continue;
-            }
           rec[0] = o->tlen;  rec[1] = o->diffs;  rec[2] = o->abpos;  rec[3] = o->bbpos;  rec[4] = o->aepos;  rec[5] = o->bepos;
-          rec[6] = o->flags & ~OVL_TEMP_FLAG;
+          rec[6] = o->flags;
           rec[7] = arec[i];  rec[8] = b->bread[i];  rec[9] = rlast[i];
-          need = 40 + (int64) tbytes * o->tlen;
-          if (need > ocap)
-            { ocap = need + need / 4 + 1024;
-              obuf = (unsigned char *) smalloc(obuf, (size_t) ocap);
-            }
-          if (tbytes == 1)
-            for (k = 0; k < o->tlen; k++)
-              { if (v[k] > 255)
-                  { fprintf(stderr, "(null): Compression of trace to bytes fails, value too big\n");
-                    goto done;
-                  }
-                obuf[40 + k] = (unsigned char) v[k];
-              }
-          else
-            memcpy(obuf + 40, v, sizeof(uint16) * (size_t) o->tlen);
-          memcpy(obuf, rec, 40);
-          if (fwrite(obuf, 1, (size_t) need, fo) != (size_t) need)
-            goto wfail;
-          written += 1;
+          if (damar_las_out_put(wr, rec, NULL, v, tbytes, "(null)"))
+            goto done;
         }
     }
   if (got < 0)
     goto done;
-  st->written = written;
-  rewind(fo);
-  if (fwrite(&written, sizeof(int64), 1, fo) != 1)
-    goto wfail;
   rc = 0;
-  goto done;
-wfail:
-  fprintf(stderr, "damar: cannot write %s\n", out);
 done:
-  if (fo != NULL && fclose(fo) != 0 && rc == 0)
-    { fprintf(stderr, "damar: cannot write %s\n", out);
-      rc = 1;
-    }
+  if (wr != NULL && damar_las_out_close(wr, rc == 0, &st->written, &st->discarded))
+    rc = 1;
   damar_piles_close(r);
   if (have_blk) damar_close_block(&blk);
   if (have_db) damar_dbinfo_close(&db);
   free(lc.anno);  free(lc.data);  free(rep.anno);  free(rep.data);
   free(c.rec);  free(c.pool.val);  free(grp);  free(act);  free(arec);
-  free(bm);  free(bn);  free(bab);  free(bdiffs);  free(baoff);  free(bboff);  free(toff);  free(bases);  free(obuf);
+  free(bm);  free(bn);  free(bab);  free(bdiffs);  free(baoff);  free(bboff);  free(toff);  free(bases);
   return rc;
 }

@@ -19,20 +19,6 @@
 #include "damar_hip.h"
 #include "damar_host.h"
 
-#define OVL_COMP_FLAG    0x1              /* lib/oflags.h */
-#define OVL_DISCARD_FLAG 0x2
-#define OVL_TEMP_FLAG    0x800
-#define OVL_TRIM_FLAG    0x20000
-
-static void *tmalloc(void *q, size_t n)
-{ void *p = realloc(q, n ? n : 1);
-  if (p == NULL)
-    { fprintf(stderr, "damar: out of memory (%zu bytes, trim)\n", n);
-      exit(1);
-    }
-  return p;
-}
-
 int damar_trim_on_host(void)
 { const char *e = getenv("DAMAR_TRIM");
   return e != NULL && strcmp(e, "host") == 0;
@@ -46,51 +32,8 @@ typedef struct
   int64   ndata;
 } TrimTrack;
 
-/* the uncompressed form (db/DB.c Load_Track): int len, int size, len + 1 offsets of `size` bytes; the data file */
-static int read_anno_data(const damar_dbinfo *db, const char *track, TrimTrack *t)
-{ char  path[4500];
-  FILE *af, *df = NULL;
-  int   len, size, j, rc = 1;
-  snprintf(path, sizeof(path), "%s.%s.anno", db->path, track);
-  if ((af = fopen(path, "r")) == NULL)
-    return 1;
-  snprintf(path, sizeof(path), "%s.%s.data", db->path, track);
-  if (fread(&len, sizeof(int), 1, af) != 1 || fread(&size, sizeof(int), 1, af) != 1 || (size != 4 && size != 8) ||
-      len != db->nreads || (df = fopen(path, "r")) == NULL)
-    goto done;
-  t->anno = (uint64 *) tmalloc(NULL, sizeof(uint64) * ((size_t) db->nreads + 1));
-  for (j = 0; j <= db->nreads; j++)
-    { int64 v8 = 0;
-      int   v4 = 0;
-      if (fread(size == 4 ? (void *) &v4 : (void *) &v8, (size_t) size, 1, af) != 1)
-        goto done;
-      t->anno[j] = (uint64) (size == 4 ? v4 : v8);
-    }
-  t->ndata = (int64) (t->anno[db->nreads] / sizeof(int));
-  t->data = (int *) tmalloc(NULL, sizeof(int) * (size_t) t->ndata);
-  if (t->ndata > 0 && fread(t->data, sizeof(int), (size_t) t->ndata, df) != (size_t) t->ndata)
-    goto done;
-  rc = 0;
-done:
-  fclose(af);
-  if (df) fclose(df);
-  if (rc)
-    { free(t->anno);  free(t->data);
-      memset(t, 0, sizeof(*t));
-    }
-  return rc;
-}
-
-int damar_track_read_any(const damar_dbinfo *db, const char *track, uint64 **anno, int **data, int64 *ndata)
-{ TrimTrack t;
-  memset(&t, 0, sizeof(t));
-  if (damar_track_read_a2(db->path, track, db->nreads, &t.anno, &t.data, &t.ndata) && read_anno_data(db, track, &t))
-    return 1;
-  *anno = t.anno;  *data = t.data;  *ndata = t.ndata;
-  return 0;
-}
-
-/* lib/utils.c:258-284: a read without an entry, or with an empty one, keeps nothing */
+/* lib/utils.c:258-284: a read without an entry, or with an empty one, keeps nothing.  (fix.c's trim_of is another rule:
+   it refuses an entry that is no interval and takes a missing track for the whole read.) */
 static void trim_of(const TrimTrack *t, int rid, int *b, int *e)
 { const uint64 ob = t->anno[rid] / sizeof(int), oe = t->anno[rid + 1] / sizeof(int);
   *b = *e = 0;
@@ -127,8 +70,8 @@ typedef struct
 static int64 add_seg(SegList *L, int64 rec, int ab, int ae, int bb, int be, int stop)
 { if (L->n >= L->cap)
     { L->cap = L->cap + L->cap / 4 + 1024;
-      L->seg = (Seg *) tmalloc(L->seg, sizeof(Seg) * (size_t) L->cap);
-      L->rec = (int64 *) tmalloc(L->rec, sizeof(int64) * (size_t) L->cap);
+      L->seg = (Seg *) damar_grow(L->seg, sizeof(Seg) * (size_t) L->cap, "trim");
+      L->rec = (int64 *) damar_grow(L->rec, sizeof(int64) * (size_t) L->cap, "trim");
     }
   L->seg[L->n].ab = ab;  L->seg[L->n].ae = ae;  L->seg[L->n].bb = bb;  L->seg[L->n].be = be;  L->seg[L->n].stop = stop;
   L->rec[L->n] = rec;
@@ -280,18 +223,6 @@ static void walk_script(const char *A, int M, const char *B, const int *script, 
 
 /***** the pass *********************************************************************************/
 
-/* B read r's bases [from, to) as the alignment sees them: the read itself, or its complement */
-static void gather_b(const HITS_DB *blk, int r, int comp, int from, int to, char *dst)
-{ const char *s = (const char *) blk->bases + blk->reads[r].boff;
-  const int   len = blk->reads[r].rlen;
-  int i;
-  for (i = from; i < to; i++)
-    if (i < 0 || i >= len)
-      *dst++ = 4;
-    else
-      *dst++ = comp ? (char) (3 - s[len - 1 - i]) : s[i];
-}
-
 /* The A side of a box ends on a segment boundary, which for a cut in a read's last segment lies beyond the read's end.  The
    reference aligns what its read buffer holds there: the end mark, then the bases of the last longer read that was loaded
    for an alignment before.  That buffer is kept here as the reference keeps it, so that such a box sees the same bases. */
@@ -350,7 +281,7 @@ damar_trimmer *damar_trimmer_open(const char *dbname, const damar_dbinfo *db, co
     return NULL;
   tm->db = db;
   tm->abuf.holds = -1;
-  if (damar_track_read_a2(db->path, track, db->nreads, &tm->tt.anno, &tm->tt.data, &tm->tt.ndata) && read_anno_data(db, track, &tm->tt))
+  if (damar_track_read_any(db, track, &tm->tt.anno, &tm->tt.data, &tm->tt.ndata))
     { *no_track = 1;
       damar_trimmer_close(tm);
       return NULL;
@@ -384,23 +315,20 @@ int damar_trimmer_batch(damar_trimmer *tm, const damar_trace_batch *tb, const in
 
   if (abuf->base == NULL || abuf->room < db->maxlen + (tw > 0 ? tw : 0) + 8)
     { abuf->room = db->maxlen + (tw > 0 ? tw : 0) + 8;
-      abuf->base = (char *) tmalloc(abuf->base, (size_t) abuf->room);
+      abuf->base = (char *) damar_grow(abuf->base, (size_t) abuf->room, "trim");
       memset(abuf->base, 0, (size_t) abuf->room);
       abuf->holds = -1;
     }
   for (i = 0; i < b->nrec; i++) nval += t.tlen[i];
-  if (nval > tm->trcap)
-    { tm->trcap = nval + nval / 4 + 1024;
-      tm->tr = (uint16 *) tmalloc(tm->tr, sizeof(uint16) * (size_t) tm->trcap);
-    }
+  tm->tr = (uint16 *) damar_reserve(tm->tr, &tm->trcap, nval, sizeof(uint16), 1024, "trim");
   if (b->nrec > tm->rcap || tm->plan == NULL)
     { tm->rcap = b->nrec + b->nrec / 4 + 1024;
-      tm->troff = (int64 *) tmalloc(tm->troff, sizeof(int64) * (size_t) tm->rcap);
-      tm->otoff = (int64 *) tmalloc(tm->otoff, sizeof(int64) * (size_t) tm->rcap);
-      tm->plan = (Plan *) tmalloc(tm->plan, sizeof(Plan) * (size_t) tm->rcap);
-      tm->arec = (int *) tmalloc(tm->arec, sizeof(int) * (size_t) tm->rcap);
+      tm->troff = (int64 *) damar_grow(tm->troff, sizeof(int64) * (size_t) tm->rcap, "trim");
+      tm->otoff = (int64 *) damar_grow(tm->otoff, sizeof(int64) * (size_t) tm->rcap, "trim");
+      tm->plan = (Plan *) damar_grow(tm->plan, sizeof(Plan) * (size_t) tm->rcap, "trim");
+      tm->arec = (int *) damar_grow(tm->arec, sizeof(int) * (size_t) tm->rcap, "trim");
       for (k = 0; k < 7; k++)
-        tm->o[k] = (int *) tmalloc(tm->o[k], sizeof(int) * (size_t) tm->rcap);
+        tm->o[k] = (int *) damar_grow(tm->o[k], sizeof(int) * (size_t) tm->rcap, "trim");
     }
   tr = tm->tr;  troff = tm->troff;  plan = tm->plan;  arec = tm->arec;
   for (i = 0, nval = 0; i < b->nrec; i++)
@@ -419,9 +347,7 @@ int damar_trimmer_batch(damar_trimmer *tm, const damar_trace_batch *tb, const in
     { const int a = b->pile_aread[pi];
       int a_lo, a_hi;
       if (a < 0 || a >= db->nreads)
-        { fprintf(stderr, "damar: %s holds reads the database does not have\n", las);
-          return 1;
-        }
+        return damar_reads_missing(las);
       trim_of(&tm->tt, a, &a_lo, &a_hi);
       for (i = b->pile_off[pi]; i < b->pile_off[pi + 1]; i++)
         { Plan *p = plan + i;
@@ -441,7 +367,7 @@ int damar_trimmer_batch(damar_trimmer *tm, const damar_trace_batch *tb, const in
               p->lbox = p->rbox = -1;
               continue;
             }
-          if (b->flags[i] & OVL_COMP_FLAG)
+          if (b->flags[i] & OVL_COMP)
             { const int blen = db->read_len[br], q = b_lo;
               b_lo = blen - b_hi;
               b_hi = blen - q;
@@ -454,12 +380,12 @@ int damar_trimmer_batch(damar_trimmer *tm, const damar_trace_batch *tb, const in
   /* align */
   if (Lp->n > tm->bcap || tm->bm == NULL)
     { tm->bcap = Lp->n + Lp->n / 4 + 1024;
-      tm->bm = (int *) tmalloc(tm->bm, sizeof(int) * (size_t) tm->bcap);
-      tm->bn = (int *) tmalloc(tm->bn, sizeof(int) * (size_t) tm->bcap);
-      tm->bdiffs = (int *) tmalloc(tm->bdiffs, sizeof(int) * (size_t) tm->bcap);
-      tm->baoff = (int64 *) tmalloc(tm->baoff, sizeof(int64) * (size_t) tm->bcap);
-      tm->bboff = (int64 *) tmalloc(tm->bboff, sizeof(int64) * (size_t) tm->bcap);
-      tm->soff = (int64 *) tmalloc(tm->soff, sizeof(int64) * ((size_t) tm->bcap + 1));
+      tm->bm = (int *) damar_grow(tm->bm, sizeof(int) * (size_t) tm->bcap, "trim");
+      tm->bn = (int *) damar_grow(tm->bn, sizeof(int) * (size_t) tm->bcap, "trim");
+      tm->bdiffs = (int *) damar_grow(tm->bdiffs, sizeof(int) * (size_t) tm->bcap, "trim");
+      tm->baoff = (int64 *) damar_grow(tm->baoff, sizeof(int64) * (size_t) tm->bcap, "trim");
+      tm->bboff = (int64 *) damar_grow(tm->bboff, sizeof(int64) * (size_t) tm->bcap, "trim");
+      tm->soff = (int64 *) damar_grow(tm->soff, sizeof(int64) * ((size_t) tm->bcap + 1), "trim");
     }
   bm = tm->bm;  bn = tm->bn;  bdiffs = tm->bdiffs;  baoff = tm->baoff;  bboff = tm->bboff;  soff = tm->soff;
   for (k = 0; k < Lp->n; k++)
@@ -473,7 +399,7 @@ int damar_trimmer_batch(damar_trimmer *tm, const damar_trace_batch *tb, const in
     }
   if (nbase > tm->basecap || tm->bases == NULL)
     { tm->basecap = nbase + nbase / 4 + 4096;
-      tm->bases = (char *) tmalloc(tm->bases, (size_t) tm->basecap);
+      tm->bases = (char *) damar_grow(tm->bases, (size_t) tm->basecap, "trim");
     }
   bases = tm->bases;
   for (k = 0; k < Lp->n; k++)
@@ -481,7 +407,7 @@ int damar_trimmer_batch(damar_trimmer *tm, const damar_trace_batch *tb, const in
       load_a(abuf, &tm->blk, arec[rec]);
       for (i = 0; i < bm[k]; i++)
         bases[baoff[k] + i] = (Lp->seg[k].ab + i < abuf->room) ? abuf->base[Lp->seg[k].ab + i] : 4;
-      gather_b(&tm->blk, b->bread[rec], b->flags[rec] & OVL_COMP_FLAG, Lp->seg[k].bb, Lp->seg[k].be, bases + bboff[k]);
+      damar_gather_b(&tm->blk, b->bread[rec], b->flags[rec] & OVL_COMP, Lp->seg[k].bb, Lp->seg[k].be, bases + bboff[k]);
     }
   if (Lp->n > 0)
     { bb.nbox = Lp->n;  bb.m = bm;  bb.n = bn;  bb.aoff = baoff;  bb.boff = bboff;  bb.bases = bases;  bb.nbases = nbase;
@@ -496,7 +422,7 @@ int damar_trimmer_batch(damar_trimmer *tm, const damar_trace_batch *tb, const in
       uint16 *v = tr + troff[i] + p->t0;
       int     flags = b->flags[i], diffs = rdiffs[i];
       if (p->fate == FATE_GONE)
-        flags |= OVL_DISCARD_FLAG | OVL_TRIM_FLAG;
+        flags |= OVL_DISCARD | OVL_TRIM;
       else if (p->fate == FATE_CUT)
         { int stop_a, dl, dr;
           st->ntrim_bases += p->known;
@@ -522,7 +448,7 @@ int damar_trimmer_batch(damar_trimmer *tm, const damar_trace_batch *tb, const in
             }
           /* what is left may cover next to nothing of either read (trim.c:442) */
           if (p->abpos >= p->aepos || p->bepos < p->keep_lo || p->bbpos > p->keep_hi)
-            flags |= OVL_DISCARD_FLAG | OVL_TRIM_FLAG;
+            flags |= OVL_DISCARD | OVL_TRIM;
           else
             { int j;
               diffs = 0;
@@ -542,41 +468,15 @@ int damar_trimmer_batch(damar_trimmer *tm, const damar_trace_batch *tb, const in
   return 0;
 }
 
-/* one record as it lies in the file: the ten words, then its trace values at tbytes bytes each.  *obuf / *ocap: the
-   caller's buffer, grown here.  0, or 1 (no message) when the write fails, 2 after the reference's message when a value
-   does not fit a byte. */
-int damar_write_record(FILE *fo, const int *rec, const uint16 *v, int tbytes, const char *tool, unsigned char **obuf, int64 *ocap)
-{ const int tlen = rec[0];
-  const int64 need = 40 + (int64) tbytes * tlen;
-  int k;
-  if (need > *ocap)
-    { *ocap = need + need / 4 + 1024;
-      *obuf = (unsigned char *) tmalloc(*obuf, (size_t) *ocap);
-    }
-  if (tbytes == 1)
-    for (k = 0; k < tlen; k++)
-      { if (v[k] > 255)
-          { fprintf(stderr, "%s: Compression of trace to bytes fails, value too big\n", tool);
-            return 2;
-          }
-        (*obuf)[40 + k] = (unsigned char) v[k];
-      }
-  else
-    memcpy(*obuf + 40, v, sizeof(uint16) * (size_t) tlen);
-  memcpy(*obuf, rec, 40);
-  return fwrite(*obuf, 1, (size_t) need, fo) != (size_t) need;
-}
-
 int damar_trim_las(const char *dbname, const char *las, const char *out, const char *track, int purge, damar_trim_stats *st)
 { damar_dbinfo db;
   damar_trimmer *tm = NULL;
   damar_pile_reader *r = NULL;
   damar_trace_batch  t;
   damar_trimmed      res;
-  FILE   *fo = NULL;
-  unsigned char *obuf = NULL;
-  int64   ocap = 0, written = 0, i;
-  int     got, rc = 1, have_db = 0, tw, no_track;
+  damar_las_out *wr = NULL;
+  int64   i;
+  int     got, rc = 1, have_db = 0, no_track;
 
   memset(st, 0, sizeof(*st));
   if (damar_dbinfo_open(dbname, &db))
@@ -592,15 +492,12 @@ int damar_trim_las(const char *dbname, const char *las, const char *out, const c
     }
   if ((r = damar_piles_open_traces(las, 0, 0)) == NULL)
     goto done;
-  if ((fo = fopen(out, "w")) == NULL)
+  if ((wr = damar_las_out_open(out, purge)) == NULL)
     { fprintf(stderr, "could not open '%s'\n", out);
       goto done;
     }
-  tw = damar_piles_tspace(r);
-  { const int64 zero = 0;
-    if (fwrite(&zero, sizeof(int64), 1, fo) != 1 || fwrite(&tw, sizeof(int), 1, fo) != 1)
-      goto wfail;
-  }
+  if (damar_las_out_begin(wr, damar_piles_tspace(r)))
+    goto done;
 
   while ((got = damar_piles_next_traces(r, &t)) > 0)
     { const damar_pile_batch *b = &t.p;
@@ -611,43 +508,25 @@ int damar_trim_las(const char *dbname, const char *las, const char *out, const c
         goto done;
       /* the records as they go to the file */
       for (i = 0; i < b->nrec; i++)
-        { int rec[10], w;
-          if (res.flags[i] & OVL_DISCARD_FLAG)
-            { st->discarded += 1;
-              if (purge)
-                continue;
-            }
+        { int rec[10];
           rec[0] = res.tlen[i];  rec[1] = res.diffs[i];
           rec[2] = res.abpos[i];  rec[3] = res.bbpos[i];
           rec[4] = res.aepos[i];  rec[5] = res.bepos[i];
-          rec[6] = res.flags[i] & ~OVL_TEMP_FLAG;
+          rec[6] = res.flags[i];
           rec[7] = damar_trimmer_aread(tm, i);  rec[8] = b->bread[i];  rec[9] = rlast[i];
-          if ((w = damar_write_record(fo, rec, res.trace + res.toff[i], t.tbytes, "LAtrim", &obuf, &ocap)) == 2)
+          if (damar_las_out_put(wr, rec, NULL, res.trace + res.toff[i], t.tbytes, "LAtrim"))
             goto done;
-          if (w)
-            goto wfail;
-          written += 1;
         }
     }
   if (got < 0)
     goto done;
-  st->written = written;
-  rewind(fo);
-  if (fwrite(&written, sizeof(int64), 1, fo) != 1)
-    goto wfail;
   rc = 0;
-  goto done;
-wfail:
-  fprintf(stderr, "damar: cannot write %s\n", out);
 done:
-  if (fo != NULL && fclose(fo) != 0 && rc == 0)
-    { fprintf(stderr, "damar: cannot write %s\n", out);
-      rc = 1;
-    }
+  if (wr != NULL && damar_las_out_close(wr, rc == 0, &st->written, &st->discarded))
+    rc = 1;
   damar_piles_close(r);
   damar_trimmer_close(tm);
   if (have_db) damar_dbinfo_close(&db);
-  free(obuf);
   return rc;
 }
 

@@ -81,3 +81,10 @@ def test_model_equals_reference_on_planted_piles():
     for tag, pl in cc.load_cases("plants").items():
         for tile, n in pl.get("added", {}).items():
             assert len(added[pl["aread"]]["tiles"][int(tile)]) == n, (tag, tile)
+
+
+def test_reads_the_database_does_not_have(tmp_path):
+    tmp = cc.workdir(str(tmp_path), "tiny2")
+    cc.tc.foreign_aread(os.path.join(tmp, cc.LAS), cc.tc.nreads_of("tiny2"))
+    r = cc.run_tool([], tmp, HOST)
+    assert (r.returncode, r.stdout, r.stderr) == (1, "", cc.tc.FOREIGN)

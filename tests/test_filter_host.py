@@ -99,3 +99,27 @@ def test_pre_step_equals_the_model(batches):
         got, want = api.pile_filter(both[which], rl, **kw), filter_model.run_batch(both[which], rl, **kw)
         for k in NAMES:
             assert np.array_equal(got[k], want[k]), (which, k)
+
+
+PASS = "\x1b[32mPASS filtering\n\x1b[0m"
+# what the one-record file leaves on stdout before the close fails: the closing lines are out by then
+CLOSE_STDOUT = {(): PASS, ("-T",): PASS + "trimmed 1 of 1 overlaps\ntrimmed 0 of 3108 bases\n"}
+
+
+@pytest.mark.parametrize("opts", [(), ("-T",)], ids=["plain", "T"])
+@pytest.mark.parametrize("small", [False, True], ids=["records", "close"])
+def test_refused_write(small, opts, tmp_path):
+    """the output on a device that refuses the data: at a record, and (one record, all of it in the stream's buffer) at the close"""
+    tmp = fc.workdir(str(tmp_path), "tiny2")
+    if small:
+        fc.tc.keep_first_record(os.path.join(tmp, fc.LAS))
+    r = fc.run_tool(opts, tmp, HOST, args=("G", fc.LAS, fc.tc.FULL))
+    assert (r.returncode, r.stdout, r.stderr) == (1, CLOSE_STDOUT[opts] if small else PASS, fc.tc.CANNOT_WRITE)
+
+
+@pytest.mark.parametrize("opts", [(), ("-T",)], ids=["plain", "T"])
+def test_reads_the_database_does_not_have(opts, tmp_path):
+    tmp = fc.workdir(str(tmp_path), "tiny2")
+    fc.tc.foreign_aread(os.path.join(tmp, fc.LAS), fc.tc.nreads_of("tiny2"))
+    r = fc.run_tool(opts, tmp, HOST)
+    assert (r.returncode, r.stdout, r.stderr) == (1, PASS, fc.tc.FOREIGN)

@@ -110,3 +110,10 @@ def test_pile_patches_on_the_planted_file():
     assert by_read[plants["comp_winner"]["aread"]][0]["comp"] == 1
     none = api.pile_patches(batch, rl, np.zeros_like(trims), tr["q"])
     assert all(g == [] for g in none)
+
+
+def test_reads_the_database_does_not_have(tmp_path):
+    tmp = fc.workdir(str(tmp_path), "tiny2")
+    fc.tc.foreign_aread(os.path.join(tmp, fc.LAS), fc.tc.nreads_of("tiny2"))
+    r = fc.run_tool(["-t", "trim"], tmp, HOST)
+    assert (r.returncode, r.stdout, r.stderr) == (1, "\x1b[32mPASS fix\x1b[0m\n", fc.tc.FOREIGN)

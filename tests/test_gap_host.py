@@ -53,3 +53,33 @@ def test_api_agrees_with_the_command(name, tmp_path, capfd):
     tail = case["stdout"].splitlines()[-2:]
     assert tail == ["dropped %d containments" % st["contained"], "dropped %d overlaps in %d break/gaps" % (st["dropped"], st["breaks"])]
     assert capfd.readouterr().out == case["stdout"]
+
+
+PASS = "\x1b[32mPASS gaps\x1b[0m\n"
+# what the one-record file leaves on stdout before the close fails: the closing lines are out by then
+CLOSE_STDOUT = {(): PASS + "DROP R @ 10400..11300\ndropped 0 containments\ndropped 1 overlaps in 1 break/gaps\n",
+                ("-t", "trim"): PASS + "            1 of             1 overlaps trimmed\n            0 of          3108 bases trimmed\n"
+                                "dropped 0 containments\ndropped 0 overlaps in 0 break/gaps\n"}
+
+
+@pytest.mark.parametrize("opts", [(), ("-t", "trim")], ids=["plain", "t"])
+@pytest.mark.parametrize("small", [False, True], ids=["records", "close"])
+def test_refused_write(small, opts, tmp_path):
+    """the output on a device that refuses the data: at a record, and (one record, all of it in the stream's buffer) at the close"""
+    tmp = gc.workdir(str(tmp_path), "tiny2")
+    if small:
+        gc.tc.keep_first_record(os.path.join(tmp, gc.LAS))
+    r = gc.run_tool(opts, tmp, HOST, args=("G", gc.LAS, gc.tc.FULL))
+    assert (r.returncode, r.stderr) == (1, gc.tc.CANNOT_WRITE)
+    if small:
+        assert r.stdout == CLOSE_STDOUT[opts]
+    else:
+        assert r.stdout.startswith(PASS) and "dropped" not in r.stdout
+
+
+@pytest.mark.parametrize("opts", [(), ("-t", "trim")], ids=["plain", "t"])
+def test_reads_the_database_does_not_have(opts, tmp_path):
+    tmp = gc.workdir(str(tmp_path), "tiny2")
+    gc.tc.foreign_aread(os.path.join(tmp, gc.LAS), gc.tc.nreads_of("tiny2"))
+    r = gc.run_tool(opts, tmp, HOST)
+    assert (r.returncode, r.stdout, r.stderr) == (1, PASS, gc.tc.FOREIGN)

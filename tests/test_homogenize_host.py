@@ -111,3 +111,12 @@ def test_calls_refuse_what_they_cannot_index():
         api.pile_homogenize([b], p.rl, ra, rd, res=0)
     with pytest.raises(ValueError):
         api.pile_homogenize([b], p.rl, ra, rd, ends=1500)
+
+
+def test_reads_the_database_does_not_have(tmp_path):
+    case = next(c for c in CASES if c["name"] == "def_tiny2")
+    tmp = hc.workdir(str(tmp_path), case, hc.expected(case["name"]))
+    hc.trim_common.foreign_aread(str(tmp_path / hc.LAS), hc.trim_common.nreads_of("tiny2"))
+    r = hc.run_tool(case["opts"], tmp, HOST)
+    assert (r.returncode, r.stderr) == (1, hc.trim_common.FOREIGN)
+    assert r.stdout.startswith("\x1b[32mPASS homogenising\n\x1b[0m")

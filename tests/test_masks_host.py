@@ -231,3 +231,13 @@ def test_calls_refuse_what_they_cannot_compute():
     case = TAN_CASES[0]
     with pytest.raises(ValueError):
         api.tan_track(os.path.join(GOLDEN, case["db"], "G"), os.path.join(GOLDEN, case["las"]), 0, 99)
+
+
+@pytest.mark.parametrize("opts", [["-c", "8"], []], ids=["repeat_pass", "estimate_pass"])
+def test_reads_the_database_does_not_have(opts, tmp_path):
+    import q_common
+    import trim_common
+    tmp = q_common.workdir(str(tmp_path), "tiny2")
+    trim_common.foreign_aread(os.path.join(tmp, q_common.LAS), trim_common.nreads_of("tiny2"))
+    r = q_common.run_tool(os.path.join(BIN, "LArepeat"), opts, tmp, env=dict(os.environ, DAMAR_PILES="host"))
+    assert (r.returncode, r.stderr) == (1, trim_common.FOREIGN)

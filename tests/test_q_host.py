@@ -161,3 +161,11 @@ def test_host_batches_equal_model():
         api.pile_quality(b, rl, segmin=0)
     with pytest.raises(RuntimeError):
         api.pile_quality(dict(b, trace=b["trace"][:-1]), rl)
+
+
+def test_reads_the_database_does_not_have(tmp_path):
+    import trim_common
+    tmp = q_common.workdir(str(tmp_path), "tiny2")
+    trim_common.foreign_aread(os.path.join(tmp, LAS), trim_common.nreads_of("tiny2"))
+    r = q_common.run_tool(os.path.join(BIN, "LAq"), [], tmp, env=dict(os.environ, DAMAR_PILES="host"))
+    assert (r.returncode, r.stdout, r.stderr) == (1, "\x1b[32mPASS quality estimate and trimming\x1b[0m\n", trim_common.FOREIGN)

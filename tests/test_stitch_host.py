@@ -137,3 +137,32 @@ def test_api_stitch_las(tmp_path):
     case = next(c for c in CASES if c["name"] == "synth_t")
     st = api.stitch_las(p("G"), p(sc.LAS), p(sc.OUT), track=sc.LC_TRACK)
     assert sc.tc.md5(p(sc.OUT)) == case["md5"] and st["stitched_lc"] == 1
+
+
+@pytest.mark.parametrize("small", [False, True], ids=["records", "close"])
+def test_refused_write(small, tmp_path):
+    """the output on a device that refuses the data: at a record, and (one record, all of it in the stream's buffer) at the close"""
+    sc.workdir(str(tmp_path), "tiny2")
+    if small:
+        sc.tc.keep_first_record(str(tmp_path / sc.LAS))
+    r = sc.run_tool([], str(tmp_path), HOST, args=("G", sc.LAS, sc.tc.FULL))
+    assert (r.returncode, r.stdout, r.stderr) == (1, "", sc.tc.CANNOT_WRITE)
+
+
+def test_reads_the_database_does_not_have(tmp_path):
+    sc.workdir(str(tmp_path), "tiny2")
+    sc.tc.foreign_aread(str(tmp_path / sc.LAS), sc.tc.nreads_of("tiny2"))
+    r = sc.run_tool([], str(tmp_path), HOST)
+    assert (r.returncode, r.stdout, r.stderr) == (1, "", sc.tc.FOREIGN)
+
+
+def test_uncompressed_track(tmp_path):
+    """-t from .anno / .data, what the loader falls back to"""
+    case = next(c for c in CASES if c["name"] == "synth_t")
+    sc.workdir(str(tmp_path), case["input"])
+    for ext in (".a2", ".d2"):
+        os.remove(str(tmp_path / (".G." + sc.LC_TRACK + ext)))
+    anno, data = sc.lc_track()
+    sc.tc.write_track_anno(str(tmp_path / (".G." + sc.LC_TRACK)), len(anno) - 1, anno, data)
+    r = sc.run_tool(case["opts"], str(tmp_path), HOST)
+    sc.check_output(case, r, str(tmp_path / sc.OUT))

@@ -107,3 +107,22 @@ def test_api_trim_las(tmp_path):
     st = api.trim_las(p("G"), p(tc.LAS), p(tc.OUT), purge=True)
     assert tc.md5(p(tc.OUT)) == case["md5"]
     assert (st["novl"], st["ntrimmed"], st["written"]) == (1746, 1500, int(exp["novl"])) and st["boxes"] > 0
+
+
+@pytest.mark.parametrize("small", [False, True], ids=["records", "close"])
+def test_refused_write(small, tmp_path):
+    """the output on a device that refuses the data: at a record, and (one record, all of it in the stream's buffer) at the close"""
+    case = next(c for c in CASES if c["name"] == "def_tiny2")
+    tc.workdir(str(tmp_path), case, tc.expected(case["name"]))
+    if small:
+        tc.keep_first_record(str(tmp_path / tc.LAS))
+    r = tc.run_tool([], str(tmp_path), HOST, args=("G", tc.LAS, tc.FULL))
+    assert (r.returncode, r.stdout, r.stderr) == (1, "", tc.CANNOT_WRITE)
+
+
+def test_reads_the_database_does_not_have(tmp_path):
+    case = next(c for c in CASES if c["name"] == "def_tiny2")
+    tc.workdir(str(tmp_path), case, tc.expected(case["name"]))
+    tc.foreign_aread(str(tmp_path / tc.LAS), tc.nreads_of("tiny2"))
+    r = tc.run_tool([], str(tmp_path), HOST)
+    assert (r.returncode, r.stdout, r.stderr) == (1, "", tc.FOREIGN)

@@ -169,3 +169,39 @@ def check_boxes(bx, diffs, scripts, idx=None):
         assert int(diffs[j]) == int(bx["diffs"][i]), "box %d (%d x %d): %d differences against %d" % (i, bx["m"][i], bx["n"][i],
                                                                                                      diffs[j], bx["diffs"][i])
         assert np.array_equal(scripts[j], want), "box %d (%d x %d): the scripts part ways" % (i, bx["m"][i], bx["n"][i])
+
+
+# ---- what the passes over a .las file share: a refused write, reads the database does not have -----------------------
+
+FULL = "/dev/full"                      # takes the open and refuses the data
+CANNOT_WRITE = "damar: cannot write %s\n" % FULL
+FOREIGN = "damar: %s holds reads the database does not have\n" % LAS
+
+
+def record_offsets(buf):
+    """where every record of a .las file begins, and where the last one ends"""
+    novl, tspace = struct.unpack_from("<qi", buf, 0)
+    tb, at, offs = (1 if tspace <= 125 else 2), 12, []
+    for _ in range(novl):
+        offs.append(at)
+        at += 40 + tb * struct.unpack_from("<i", buf, at)[0]
+    return offs, at
+
+
+def keep_first_record(path):
+    """the file cut to its first record: what a run writes of it fits the stream's buffer, the refusal comes at the close"""
+    buf = open(path, "rb").read()
+    offs, _ = record_offsets(buf)
+    open(path, "wb").write(struct.pack("<q", 1) + buf[8:offs[1]])
+
+
+def foreign_aread(path, nreads):
+    """the A read of the file's last record set to nreads: the first read the database does not have"""
+    buf = bytearray(open(path, "rb").read())
+    offs, _ = record_offsets(buf)
+    struct.pack_into("<i", buf, offs[-1] + 28, nreads)
+    open(path, "wb").write(buf)
+
+
+def nreads_of(db):
+    return len(q_common.db_read_len(db))
