@@ -488,7 +488,7 @@ def pile_tandem(piles, read_len, read_flags, min_len=0):
 
 
 _PHASES = ("upload", "kernel", "download", "call")
-_STAGES = ("trace", "pile", "q", "box", "tbox", "gap", "fix", "filter", "correct", "read")
+_STAGES = ("trace", "pile", "q", "box", "tbox", "gap", "fix", "filter", "correct", "read", "dust")
 
 
 def _last(stage, ncnt, names=_PHASES):
@@ -502,7 +502,7 @@ def _last(stage, ncnt, names=_PHASES):
 
 def release(stage):
     """Frees the device buffers and events a call family keeps between calls: damar_<stage>_release, stage one of
-    trace, pile, q, box, tbox, gap, fix, filter, correct, read (a homogenize session is released by closing it)."""
+    trace, pile, q, box, tbox, gap, fix, filter, correct, read, dust (a homogenize session is released by closing it)."""
     if stage not in _STAGES:
         raise ValueError("no stage %r" % (stage,))
     f = getattr(_lib(), "damar_%s_release" % stage)
@@ -1408,3 +1408,133 @@ def correct_las(db, las, out, *, verbose=False, parts=1, block=-1, q="q", read_i
     if L.damar_correct_las(db.encode(), las.encode(), out.encode(), C.byref(o), C.byref(st)):
         raise RuntimeError("damar_correct_las failed")
     return {k: getattr(st, k) for k, _ in CorrectStats._fields_}
+
+
+# ---- the low-complexity mask of reads (DBdust) --------------------------------------------------------------------
+
+class DustParams(C.Structure):         # include/damar_hip.h damar_dust_params
+    _fields_ = [("window", C.c_int), ("thresh", C.c_double), ("minlen", C.c_int), ("biased", C.c_int), ("freq", C.c_float * 4)]
+
+
+class DustList(C.Structure):           # host/damar_host.h damar_dust_list
+    _fields_ = [("iv", _PI), ("n", c_int64), ("cap", c_int64)]
+
+
+def _dust_params(window, thresh, minlen, biased, freq):
+    p = DustParams(int(window), float(thresh), int(minlen), 1 if biased else 0)
+    if biased:
+        if freq is None:
+            raise ValueError("biased needs the four base frequencies")
+        for i in range(4):
+            p.freq[i] = freq[i]
+    return p
+
+
+def dust_limits():
+    """(piece, halo, stripe, window): the triplet starts of a piece, the triplets run in front of it, the candidates a piece
+    may retire and the widest window of kernels/dust.hip: DAMAR_DUST_PIECE, _HALO, _STRIPE, _MAXWINDOW"""
+    v = [C.c_int() for _ in range(4)]
+    L = _lib()
+    L.damar_dust_limits.argtypes = [_PI] * 4
+    L.damar_dust_limits(*[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def dust_last():
+    """Of the last dust_reads / of the last batch of dust_track: ({upload, kernel, download, call} ms, reads, reads the host
+    routine did beside the kernel, intervals, steps taken, steps that entered the walk over the window's starts)."""
+    st = (c_int64 * 2)()
+    L = _lib()
+    L.damar_dust_steps.argtypes = [C.POINTER(c_int64)]
+    L.damar_dust_steps(st)
+    return _last("dust", 3) + (st[0], st[1])
+
+
+def dust_reads(seqs, window=64, thresh=2.0, minlen=10, biased=False, freq=None):
+    """DBdust's mask of each read of `seqs` (arrays of bases 0..3): -> a list of int32 arrays [n, 2] of [beg, end) pairs.
+    On the GPU (kernels/dust.hip) unless DAMAR_DUST=host; biased reads and windows the kernel does not hold go to the host
+    routine and are counted (dust_last)."""
+    import numpy as np
+    L = _lib()
+    p = _dust_params(window, thresh, minlen, biased, freq)
+    arrs = [np.ascontiguousarray(s, dtype=np.uint8) for s in seqs]
+    off = np.zeros(len(arrs) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(s) for s in arrs])
+    bases = np.concatenate(arrs + [np.zeros(1, dtype=np.uint8)])
+    out_off = np.zeros(len(arrs) + 1, dtype=np.int64)
+    out = _PI()
+    L.damar_dust_reads.argtypes = [C.POINTER(C.c_ubyte), C.POINTER(c_int64), c_int64, C.POINTER(DustParams), C.POINTER(c_int64),
+                                   C.POINTER(_PI)]
+    if L.damar_dust_reads(bases.ctypes.data_as(C.POINTER(C.c_ubyte)), off.ctypes.data_as(C.POINTER(c_int64)), len(arrs), C.byref(p),
+                          out_off.ctypes.data_as(C.POINTER(c_int64)), C.byref(out)):
+        raise RuntimeError("damar_dust_reads failed")
+    n = int(out_off[-1])
+    flat = np.ctypeslib.as_array(out, shape=(max(n, 1),))[:n].copy()
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    libc.free(C.cast(out, C.c_void_p))
+    return [flat[out_off[i]:out_off[i + 1]].reshape(-1, 2) for i in range(len(arrs))]
+
+
+def dust_host_read(seq, window=64, thresh=2.0, minlen=10, biased=False, freq=None, piece=0, halo=0):
+    """One read through the routine of host/dust.c alone: whole (piece = 0), or cut into pieces of `piece` triplet starts with
+    `halo` triplets run in front of each.  -> (int32 [n, 2] of [beg, end) pairs, the longest the candidate list became
+    -- of the whole read only, else 0)."""
+    import numpy as np
+    L = _lib()
+    p = _dust_params(window, thresh, minlen, biased, freq)
+    s = np.ascontiguousarray(seq, dtype=np.uint8)
+    s = np.concatenate([s, np.zeros(4, dtype=np.uint8)])
+    n = len(s) - 4
+    out = np.zeros(2 * max(n, 1), dtype=np.int32)
+    work = DustList()
+    L.damar_host_dust_read.argtypes = [C.POINTER(C.c_ubyte), C.c_int, C.POINTER(DustParams), C.c_int, C.c_int, _PI, C.POINTER(DustList),
+                                       C.POINTER(c_int64)]
+    L.damar_host_dust_read.restype = c_int64
+    L.damar_host_dust_piece.argtypes = [C.POINTER(C.c_ubyte), C.c_int, C.POINTER(DustParams), C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.POINTER(DustList), C.POINTER(c_int64)]
+    sp = s.ctypes.data_as(C.POINTER(C.c_ubyte))
+    m = L.damar_host_dust_read(sp, n, C.byref(p), int(piece), int(halo), out.ctypes.data_as(_PI), C.byref(work), None)
+    longest = 0
+    if piece <= 0 and n > 2:
+        work.n = 0
+        longest = L.damar_host_dust_piece(sp, n, C.byref(p), 0, 0, n - 2, n - 2, C.byref(work), None)
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    libc.free(C.cast(work.iv, C.c_void_p))
+    return out[:2 * m].reshape(-1, 2).copy(), longest
+
+
+def dust_host_candidates(seq, window=64, thresh=2.0, start=0, own=None, stop=None):
+    """The candidates the routine of host/dust.c retires over the triplets [start, stop) of one read, those that start in
+    own = (beg, end): -> (int32 [n, 2] of (start, last triplet), the longest the candidate list became)."""
+    import numpy as np
+    L = _lib()
+    p = _dust_params(window, thresh, 2, False, None)
+    s = np.concatenate([np.ascontiguousarray(seq, dtype=np.uint8), np.zeros(4, dtype=np.uint8)])
+    n = len(s) - 4
+    own = (0, n) if own is None else own
+    work = DustList()
+    L.damar_host_dust_piece.argtypes = [C.POINTER(C.c_ubyte), C.c_int, C.POINTER(DustParams), C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.POINTER(DustList), C.POINTER(c_int64)]
+    longest = L.damar_host_dust_piece(s.ctypes.data_as(C.POINTER(C.c_ubyte)), n, C.byref(p), int(start), int(own[0]), int(own[1]),
+                                      int(n if stop is None else stop), C.byref(work), None)
+    out = np.ctypeslib.as_array(work.iv, shape=(max(2 * work.n, 1),))[:2 * work.n].copy().reshape(-1, 2) if work.n else \
+        np.zeros((0, 2), dtype=np.int32)
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    libc.free(C.cast(work.iv, C.c_void_p))
+    return out, longest
+
+
+def dust_track(db, window=64, thresh=2.0, minlen=10, biased=False):
+    """DBdust on a database or one of its blocks: .dust.anno / .dust.data written beside it (appended to for a whole database
+    that has them).  -> {reads, host_reads, intervals, bases, steps, walk_steps} of the run."""
+    L = _lib()
+    p = _dust_params(window, thresh, minlen, False, None)
+    p.biased = 1 if biased else 0
+    st = (c_int64 * 6)()
+    L.damar_dust_track.argtypes = [C.c_char_p, C.POINTER(DustParams), C.POINTER(c_int64)]
+    if L.damar_dust_track(db.encode(), C.byref(p), st):
+        raise RuntimeError("damar_dust_track failed")
+    return dict(zip(("reads", "host_reads", "intervals", "bases", "steps", "walk_steps"), list(st)))

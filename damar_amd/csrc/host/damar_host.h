@@ -404,6 +404,26 @@ typedef struct
 int  damar_homogenize_track(const damar_dbinfo *db, const char *las, const damar_homog_params *p, damar_homog_result *res);
 void damar_homog_result_free(damar_homog_result *res);
 
+/* dust.c: DBdust (db/DBdust.c) -- the plain routine behind damar_dust_reads (DAMAR_DUST=host, and the reads the kernel
+   leaves) and the command's work. */
+typedef struct { int *iv; int64 n, cap; } damar_dust_list;       /* n retired candidates: start, last triplet */
+int   damar_dust_on_host(void);                                   /* DAMAR_DUST=host */
+int   damar_dust_params_valid(const damar_dust_params *p);        /* 0 after a message */
+/* the machine over the triplets [start, stop) of seq[0 .. len) from an empty state; the retired candidates that start in
+   [own_beg, own_end) appended to out; steps (or NULL): [0] += steps taken, [1] += steps that entered the walk.  Returns the
+   longest the candidate list became. */
+int   damar_host_dust_piece(const unsigned char *seq, int len, const damar_dust_params *p, int start, int own_beg, int own_end,
+                            int stop, damar_dust_list *out, int64 *steps);
+/* n candidates in order of their starts -> the [beg, end) pairs of the mask in out (room for n of them); their number */
+int64 damar_host_dust_join(const int *cand, int64 n, int minlen, int *out);
+/* one read: whole (piece <= 0) or cut into pieces of `piece` starts with `halo` triplets in front; out needs room for
+   len pairs, work is the caller's scratch list; the number of pairs */
+int64 damar_host_dust_read(const unsigned char *seq, int len, const damar_dust_params *p, int piece, int halo, int *out,
+                           damar_dust_list *work, int64 *steps);
+/* the track of a block, or of a database (appended to where it exists): stats (or NULL) [0 .. 6) += reads, host reads,
+   intervals, bases, steps, walk steps.  0, or 1 after a message */
+int   damar_dust_track(const char *name, const damar_dust_params *p, int64 *stats);
+
 /* masks.c: both tools as calls (the commands and the Python interface are argument handling around them) */
 typedef struct
 { int64 *histo;                /* [max_cov], malloc'ed, NULL when no estimate ran */

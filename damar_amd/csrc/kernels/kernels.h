@@ -439,6 +439,31 @@ typedef struct
 void damar_launch_pile_gaps(const GapArgs *a, u32 grid, hipStream_t st);      /* min(npiles, grid) workgroups */
 u32  damar_pile_gaps_grid(void);      /* workgroups of the largest launch: beyond that many piles a workgroup does several */
 
+/* dust.hip: DBdust's mask, one wavefront per piece of a read (include/damar_hip.h damar_dust_reads; the DAMAR_DUST_* bounds
+   are defined there).  Piece q is the starts from piece_first[q] on of read piece_read[q]; the pieces of read i are
+   [read_piece[i], read_piece[i + 1]).  damar_launch_dust_pieces leaves nint[i] pairs per read at the head of its first
+   stripe (-1: a stripe was too small, the read is the host's); with out_off made from them, damar_launch_dust_gather moves
+   the pairs to out. */
+typedef struct
+{ u32 npieces, nreads;
+  int window, thresh2i, minlen, stripe;
+  double thresh;
+  const u8  *bases;
+  const long long *read_off;          /* [nreads + 1] */
+  const u32 *piece_read;              /* [npieces] */
+  const int *piece_first;             /* [npieces] */
+  const u32 *read_piece;              /* [nreads + 1] */
+  int *cand;                          /* [npieces * stripe * 2] */
+  int *ncand;                         /* [npieces]: candidates retired, beyond `stripe` not written */
+  int *nint;                          /* [nreads] */
+  u64 *steps;                         /* [2]: steps taken, steps that entered the walk; added to */
+  const long long *out_off;           /* [nreads] ints into out */
+  int *out;
+} DustArgs;
+
+void damar_launch_dust_pieces(const DustArgs *a, hipStream_t st);       /* the pieces, then the join per read */
+void damar_launch_dust_gather(const DustArgs *a, hipStream_t st);
+
 /* pile_filter.hip: LAfilter's screens, one wavefront per pile (include/damar_hip.h damar_pile_filter; the DAMAR_FILTER_*
    bounds, the DAMAR_FR_* reason bits and the DAMAR_FC_* counters are defined there).  A pile with status 1 afterwards is the
    host's: a run of more than maxgroup records of one B read, or under -z with -u a read of more than maxlen bases. */

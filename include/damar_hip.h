@@ -560,6 +560,39 @@ void damar_correct_limits(int *seg, int *cols, int *cells);      /* the three li
  * cnt[3] = tiles, tiles the host routine did beside the kernel, bases called */
 void damar_correct_last(double *ms, int64 *cnt);
 
+/* The low-complexity mask of reads (db/DBdust.c, Myers' incremental SDUST): read i is the bases (one per byte, 0 .. 3)
+ * from bases + read_off[i] to bases + read_off[i + 1].  out_off[nreads + 1] (the caller's) receives where each read's
+ * [beg, end) pairs lie in *out, counted in ints; *out is malloc'ed and the caller's to free.  window, thresh and minlen are
+ * the command's -w, -t and -m (minlen >= 2, as there); biased its -b, with the database's four base frequencies.
+ * Runs kernels/dust.hip: a read is cut into pieces of DAMAR_DUST_PIECE triplet starts, one wavefront a piece, each with
+ * DAMAR_DUST_HALO triplets in front of it and `window` behind, which makes the pieces' results those of the whole read
+ * (DESIGN.md section 9l); a second kernel joins a read's intervals and applies minlen.  The routine of host/dust.c does
+ * -- and damar_dust_last counts -- every read with biased set or a window outside 3 .. DAMAR_DUST_MAXWINDOW, and a read
+ * one of whose pieces retires more than DAMAR_DUST_STRIPE candidates.  A start retires at most once, so with a stripe of
+ * DAMAR_DUST_PIECE pairs no read does; DAMAR_TEST_DUST_STRIPE lowers the stripe, for tests of that way out.
+ * With DAMAR_DUST=host that routine does all reads and no GPU is touched.  0 on success, 1 after a message. */
+#define DAMAR_DUST_MAXWINDOW 64
+#define DAMAR_DUST_PIECE     1024
+#define DAMAR_DUST_HALO      (2 * DAMAR_DUST_MAXWINDOW)
+#define DAMAR_DUST_STRIPE    DAMAR_DUST_PIECE
+typedef struct
+{ int    window;                           /* -w (64) */
+  double thresh;                           /* -t (2.) */
+  int    minlen;                           /* -m (10) */
+  int    biased;                           /* -b */
+  float  freq[4];                          /* with biased: HITS_DB.freq */
+} damar_dust_params;
+int  damar_dust_reads(const unsigned char *bases, const int64 *read_off, int64 nreads, const damar_dust_params *p,
+                      int64 *out_off, int **out);
+void damar_dust_release(void);             /* frees the cached device buffers of damar_dust_reads */
+void damar_dust_limits(int *piece, int *halo, int *stripe, int *window);       /* the four limits as the library was built */
+/* of the last call: ms[4] = upload, kernels, download (HIP events; 0 on the host path), whole call (wall);
+ * cnt[3] = reads, reads the host routine did beside the kernel, intervals written */
+void damar_dust_last(double *ms, int64 *cnt);
+/* of the last call, kernel and host routine together: steps[0] = triplets stepped over (halos included), steps[1] = those
+ * that entered the walk over the window's starts */
+void damar_dust_steps(int64 *steps);
+
 /* Phase timings (milliseconds, HIP events on the library's stream) of the last
  * damar_index_build / damar_match: see DAMAR_T_* below. */
 enum { DAMAR_T_TUPLES = 0, DAMAR_T_KSORT, DAMAR_T_TABLE, DAMAR_T_MERGE, DAMAR_T_SSORT,
