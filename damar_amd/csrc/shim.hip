@@ -32,6 +32,7 @@ extern "C" {
 #include "damar_hip.h"
 #include "host/damar_host.h"
 }
+#include "shim_internal.h"     /* what of this file the tool stages (stages/ *.hip) share */
 
 #define MAXGRAM 10000          /* filter.c:71 */
 
@@ -82,7 +83,7 @@ extern "C" int Set_Filter_Params(int kmer, int binshift, int suppress, int hitmi
 /***** device state ***************************************************************************/
 
 static int          G_ready = 0;
-static hipStream_t  G_st;
+hipStream_t         G_st;                   /* the seed stream (shim_internal.h) */
 static hipStream_t   G_copy;                /* record downloads of the asynchronous mode */
 static hipStream_t   G_rep;                 /* report launches of the asynchronous mode: beside the next comparisons' seed stages */
 static hipStream_t   G_ctl;                 /* small downloads (a launch's counters) that must not queue behind anything */
@@ -90,7 +91,7 @@ static std::thread  *G_late = NULL;         /* creates G_copy, G_rep, G_ctl behi
 static std::mutex    G_late_mu;
 static std::atomic<int> G_late_pending(0);
 static hipStream_t preload_stream(void);
-static void late_streams(void)              /* before the first use of G_copy / G_rep / G_ctl */
+void late_streams(void)                     /* before the first use of G_copy / G_rep / G_ctl */
 { if (G_late_pending.load(std::memory_order_acquire) == 0)
     return;
   std::lock_guard<std::mutex> lk(G_late_mu);
@@ -112,14 +113,13 @@ static hipEvent_t    G_report_done;
 static hipEvent_t    G_set_d2h[2];
 static hipEvent_t    G_last_d2h[2] = { NULL, NULL };   /* per set of record buffers: the download the next kernel that writes
                                                           into the set must not overtake */
-static hipDeviceProp_t G_prop;
+hipDeviceProp_t G_prop;
 static hipEvent_t   G_ev[24];
 static double       G_ms[DAMAR_T_COUNT];
 static int          G_limit = 0;          /* the mutual-count cap the last Match_Filter used */
 static double       H_ms[8];              /* host wall clock per phase (DAMAR_HOSTPROF=1 prints them at drain) */
 static const char  *H_name[8] = { "index_build", "match:front", "match:order", "match:report", "match:d2h",
                                   "match:submit", "match:total", "final_drain" };
-static double now_ms(void);
 static int    ilog2_ceil(u64 n);
 
 /* The filter parameters and option globals a comparison was set up under (filter.h:54-62).  A report launch may be made --
@@ -377,7 +377,7 @@ static void hostprof_at_exit(void)
   fprintf(stderr, " | scratch_prepare=%.1f scratch_outputs=%.1f\n", Q_ms[0], Q_ms[1]);
 }
 
-static void ensure_init(void)
+void ensure_init(void)
 { if (!G_ready)
     { const char *d = getenv("DAMAR_DEVICE");
       damar_hip_init(d ? atoi(d) : 0);
@@ -470,17 +470,7 @@ extern "C" int  damar_last_merge_flagged(void)  { return G_merge_flagged; }
 
 /***** blocks ************************************************************************************/
 
-struct damar_dev_block
-{ DevBlock d;
-  float freq[4];           /* base frequencies of the block (-b) */
-  int   minlen;            /* shortest read */
-  u32 *pk_alloc;
-  u32 *moff;
-  int *mdat;
-  u8  *bases_alloc;        /* d.bases = bases_alloc + 64; d.bases[-1] is the leading terminator */
-  u32 *boff, *coarse;
-  int  nreads;
-};
+/* struct damar_dev_block: shim_internal.h */
 
 static damar_dev_block *block_upload_on(const HITS_DB *block, hipStream_t st, const damar_packed *pk = NULL, int comp = 0);
 
@@ -739,7 +729,7 @@ static void sort_verify(void)
       }
   H_nserr = 0;
 }
-static void sort_check(const void *sw)
+void sort_check(const void *sw)
 { if (H_serr == NULL)
     HIP_CHECK(hipHostMalloc((void **) &H_serr, 64 * sizeof(u32), hipHostMallocDefault));
   if (H_nserr == 64)
@@ -1347,7 +1337,7 @@ struct RecOrder
   { return (x.item != y.item) ? (x.item < y.item) : (x.seq < y.seq); }
 };
 
-static double now_ms(void)
+double now_ms(void)
 { struct timespec t;
   clock_gettime(CLOCK_MONOTONIC, &t);
   return t.tv_sec * 1e3 + t.tv_nsec * 1e-6;
@@ -3887,11 +3877,7 @@ extern "C" double damar_bench_sort_u32(uint32_t n, int nbits, int reps, uint32_t
 
 /***** align.h:223-259: Work_Data and the single-call Local_Alignment ***********************************/
 
-struct WorkData
-{ Path   bpath;
-  std::vector<uint16> atrace, btrace;
-  std::vector<int>    script;          /* Compute_Trace_PTS */
-};
+/* struct WorkData: shim_internal.h (Compute_Trace_PTS and _MID, stages/trace.hip, fill its script) */
 
 extern "C" Work_Data *New_Work_Data(void)             /* align.c:135-160 */
 { return (Work_Data *) new WorkData();
@@ -3954,1950 +3940,4 @@ extern "C" Path *Local_Alignment(Alignment *align, Work_Data *work, Align_Spec *
   w->btrace.assign(tr.begin() + toff[1], tr.begin() + toff[1] + paths[11]);
   w->bpath.trace = w->btrace.data();
   return &w->bpath;
-}
-
-/***** (f)4: trace-point expansion, align.c:5577-5692 Compute_Trace_PTS for batches of records *********/
-
-struct DevStage;
-
-struct DBuf                        /* a device buffer kept between calls, grown when a call needs more */
-{ void  *p = nullptr;
-  size_t cap = 0;
-  DBuf  *next;                     /* of the stage's buffers */
-  DBuf(DevStage &s);              /* a buffer is made with the stage it belongs to, so DevStage::release() needs no list */
-  DBuf(const DBuf &) = delete;
-  void *need(size_t n)
-  { if (n > cap)
-      { if (p) HIP_CHECK(hipFree(p));
-        cap = n + n / 4 + 4096;
-        HIP_CHECK(hipMalloc(&p, cap));
-      }
-    return p;
-  }
-  void drop() { if (p) HIP_CHECK(hipFree(p));  p = nullptr;  cap = 0; }
-};
-
-/* What one call family keeps between its calls: the device buffers, the events that time a call's phases on G_st, and the
-   figures of the last call for its damar_*_last.  A family is a static of a struct derived from this one whose members are
-   its buffers by name; damar_homog holds one per handle. */
-struct DevStage
-{ DBuf      *bufs = nullptr;
-  hipEvent_t ev[5] = { NULL, NULL, NULL, NULL, NULL };       /* made on first use, kept like the buffers */
-  double     ms[4] = { 0, 0, 0, 0 };
-  int64      cnt[4] = { 0, 0, 0, 0 };
-
-  void mark(int i)                 /* event i, here on G_st */
-  { if (ev[0] == NULL)
-      for (hipEvent_t &e : ev) HIP_CHECK(hipEventCreate(&e));
-    HIP_CHECK(hipEventRecord(ev[i], G_st));
-  }
-  void laps_add(int first, int n)  /* after the caller's synchronise: the time from event i to event i + 1 added to ms[i], n of them */
-  { for (int i = first; i < first + n; i++)
-      { float t = 0;
-        HIP_CHECK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-        ms[i] += t;
-      }
-  }
-  void laps(int first, int n)      /* the same, written over ms[i] */
-  { for (int i = first; i < first + n; i++) ms[i] = 0;
-    laps_add(first, n);
-  }
-  void last(double *m, int64 *c, int ncnt) const
-  { for (int i = 0; i < 4; i++) m[i] = ms[i];
-    for (int i = 0; i < ncnt; i++) c[i] = cnt[i];
-  }
-  void release()                   /* the buffers and the events; the figures stay */
-  { for (DBuf *b = bufs; b != NULL; b = b->next) b->drop();
-    if (ev[0] != NULL)
-      for (hipEvent_t &e : ev)
-        { (void) hipEventDestroy(e);
-          e = NULL;
-        }
-  }
-};
-
-inline DBuf::DBuf(DevStage &s) : next(s.bufs) { s.bufs = this; }
-
-/* src[0 .. n) into b on G_st: room for it and 16 bytes more (the kernels' wide loads may reach past the last value), the
-   copy where there is something to copy */
-template <typename T>
-static T *up(DBuf &b, const T *src, size_t n)
-{ T *d = (T *) b.need(sizeof(T) * n + 16);
-  if (n > 0)
-    HIP_CHECK(hipMemcpyAsync(d, src, sizeof(T) * n, hipMemcpyHostToDevice, G_st));
-  return d;
-}
-
-/* a track of the database: anno[nreads + 1] byte offsets into data[ndata] */
-struct DevTrack { const u64 *anno;  const int *data; };
-
-static DevTrack up_track(DBuf &anno, DBuf &data, const uint64 *a, size_t nreads, const int *d, int64 ndata)
-{ DevTrack k;
-  k.anno = (const u64 *) up(anno, a, nreads + 1);
-  k.data = up(data, d, (size_t) ndata);
-  return k;
-}
-
-/* A stage whose calls take a damar_pile_batch or a damar_trace_batch, and the batch as pile_up() leaves it on the device:
-   col[i] is the i-th of the record columns the caller named, toff and trace are there for a trace batch */
-struct PileStage : DevStage
-{ DBuf off{*this}, aread{*this}, col[8] = { *this, *this, *this, *this, *this, *this, *this, *this }, toff{*this}, trace{*this};
-};
-
-struct PileDev
-{ const long long *off, *toff;
-  const int *aread, *col[8];
-  const u8  *trace;
-};
-
-static PileDev pile_up(PileStage &S, const damar_pile_batch *b, const damar_trace_batch *t, std::initializer_list<const int *> cols)
-{ const size_t np = (size_t) b->npiles, nrec = (size_t) b->nrec;
-  PileDev d;
-  memset(&d, 0, sizeof(d));
-  d.off = (const long long *) up(S.off, b->pile_off, np + 1);
-  d.aread = up(S.aread, b->pile_aread, np);
-  int i = 0;
-  for (const int *c : cols)
-    { d.col[i] = up(S.col[i], c, nrec);
-      i += 1;
-    }
-  if (t != NULL)
-    { d.toff = (const long long *) up(S.toff, t->trace_off, nrec);
-      d.trace = up(S.trace, t->trace, (size_t) t->trace_bytes);
-    }
-  return d;
-}
-
-/* a limit the library was built with, lowered by a test through the environment: a value below `floor` or not below the
-   limit leaves it as it is */
-static int test_limit(const char *name, int built, int floor)
-{ const char *e = getenv(name);
-  const int v = (e != NULL) ? atoi(e) : built;
-  return (v >= floor && v < built) ? v : built;
-}
-
-/* k more items of `per` values each at the end of a list that grows by realloc (a pile's results behind those of the piles
-   before it); 1 after a message, the list freed */
-template <typename T>
-static int list_append(T **list, int64 *n, int64 *cap, size_t per, const T *src, int64 k, const char *what)
-{ if (*n + k > *cap)
-    { const int64 c = *n + k + *cap / 4 + 256;
-      T *grown = (T *) realloc(*list, sizeof(T) * per * (size_t) c);
-      if (grown == NULL)
-        { fprintf(stderr, "damar: out of memory (%s)\n", what);
-          free(*list);
-          return 1;
-        }
-      *list = grown;
-      *cap = c;
-    }
-  if (k > 0)
-    memcpy(*list + per * (size_t) *n, src, sizeof(T) * per * (size_t) k);
-  *n += k;
-  return 0;
-}
-
-static struct : DevStage         /* ms of the last damar_trace_pts: trace_waves kernel, layout..pack on the device, whole call, inside the
-                                    batches (wall); cnt: records, segments, deferred segments, script values */
-{ DBuf recs{*this}, pts{*this}, segs{*this}, count{*this}, dist{*this}, segoff{*this}, stage{*this}, vf{*this}, hf{*this}, over{*this},
-       ctr{*this}, tlen{*this}, diffs{*this}, script{*this}, scan{*this}, bvf{*this}, bhf{*this}, mid{*this}, segs2{*this}, key{*this},
-       val{*this}, key1{*this}, val1{*this}, sortw{*this};
-} TR;
-
-extern "C" void damar_trace_release(void) { TR.release(); }
-
-extern "C" void damar_trace_last(double *ms, int64 *cnt) { TR.last(ms, cnt, 4); }
-
-/* staging slots one record needs = sum over its segments of dmax + |M - N| (the script of a segment has at
-   most D + |del| <= dmax + |del| values); also dmax and the segment count */
-template <typename PT>
-static void trace_record_shape(const Path *path, const PT *p, int tspace, int *dmax_out, int *nseg_out, int64 *slots_out)
-{ const int tlen = path->tlen;
-  int dmax = 0;
-  for (int d = 0; d + 1 < tlen; d += 2)
-    if ((int) p[d] > dmax) dmax = (int) p[d];
-  const int nseg = tlen >= 2 ? tlen / 2 : 1;
-  int ab = path->abpos, ae = (ab / tspace) * tspace, bb = path->bbpos;
-  int64 slots = 0;
-  for (int s = 0; s < nseg; s++)
-    { int be;
-      if (s + 1 < nseg) { ae += tspace; be = bb + (int) p[2 * s + 1]; }
-      else              { ae = path->aepos; be = path->bepos; }
-      const int del = (ae - ab) - (be - bb);
-      slots += dmax + (del < 0 ? -del : del);
-      ab = ae;
-      bb = be;
-    }
-  *dmax_out = dmax;  *nseg_out = nseg;  *slots_out = slots;
-}
-
-/* One wave phase over `nwork` segments: the slot kernel, then the stripe kernel for what it deferred.
-   kind 0 = scripts, 1 = mid points.  Returns the error flags, or ~0u after a message. */
-static u32 trace_wave_phase(TraceArgs t, int mode, int kind, u32 nwork, u32 rows, u32 maxblocks, u32 *d_ctr,
-                            u32 *d_key, u32 *d_val, hipEvent_t e1, hipEvent_t e2)
-{ const u32 nblocks = std::min(maxblocks, (nwork + 63) / 64);
-  /* work order: segments with equal difference counts side by side in a wavefront */
-  static int ordered = -1;
-  if (ordered < 0)
-    { const char *e = getenv("DAMAR_TRACE_ORDER");
-      ordered = e ? atoi(e) : 1;
-    }
-  const u32 *order = NULL;
-  if (ordered)
-    { u32 *k1 = (u32 *) TR.key1.need(sizeof(u32) * (size_t) nwork), *v1 = (u32 *) TR.val1.need(sizeof(u32) * (size_t) nwork);
-      void *sw = TR.sortw.need(damar_sort_workspace_bytes(nwork));
-      order = damar_radix_sort_u32(d_key, d_val, k1, v1, nwork, 8, sw, G_st) ? v1 : d_val;
-      sort_check(sw);
-    }
-  const size_t area = damar_trace_slot_area_cells();
-  t.vf = (short *) TR.vf.need((size_t) nblocks * damar_trace_slot_vf_bytes(mode, kind));
-  t.hf = (signed char *) TR.hf.need((size_t) nblocks * area);
-  t.cap = rows;
-  t.list = order;  t.nwork = nwork;
-  t.next = d_ctr + 4;
-  HIP_CHECK(hipMemsetAsync(d_ctr, 0, 8, G_st));
-  HIP_CHECK(hipMemsetAsync(d_ctr + 4, 0, 4, G_st));
-  HIP_CHECK(hipEventRecord(e1, G_st));
-  damar_launch_trace_waves_slots(&t, mode, kind, nblocks, G_st);
-  HIP_CHECK(hipEventRecord(e2, G_st));
-  u32 ctr[4];
-  HIP_CHECK(hipMemcpyAsync(ctr, d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, G_st));
-  HIP_CHECK(hipStreamSynchronize(G_st));
-  float wms = 0;
-  HIP_CHECK(hipEventElapsedTime(&wms, e1, e2));
-  TR.ms[0] += wms;
-  if (ctr[0] > 0 && !(ctr[2] & DAMAR_TRACE_ERR_POINTS))
-    { /* segments the slot kernel does not take: one lane each on stripes that hold dmax + 3 rows */
-      const u32 need = ctr[1];
-      size_t bthreads = ((size_t) ctr[0] + 63) / 64 * 64;
-      const size_t budget = (size_t) 8 << 30;
-      while (bthreads > 64 && bthreads * need * 3 > budget) bthreads /= 2;
-      bthreads = (bthreads + 63) / 64 * 64;
-      if (bthreads * need * 3 > ((size_t) 64 << 30))
-        { fprintf(stderr, "damar: trace expansion: a segment needs %u wave cells, more than this build provides\n", need);
-          return ~0u;
-        }
-      t.vf = (short *) TR.bvf.need(sizeof(short) * bthreads * need);
-      t.hf = (signed char *) TR.bhf.need(bthreads * need);
-      t.cap = need;
-      t.list = t.over;  t.nwork = ctr[0];
-      HIP_CHECK(hipMemsetAsync(d_ctr, 0, 8, G_st));
-      HIP_CHECK(hipEventRecord(e1, G_st));
-      damar_launch_trace_waves(&t, mode, kind, (u32) (bthreads / 64), G_st);
-      HIP_CHECK(hipEventRecord(e2, G_st));
-      u32 c2[4];
-      HIP_CHECK(hipMemcpyAsync(c2, d_ctr, sizeof(c2), hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipStreamSynchronize(G_st));
-      HIP_CHECK(hipEventElapsedTime(&wms, e1, e2));
-      TR.ms[0] += wms;
-      TR.cnt[2] += ctr[0];
-      if (c2[0] != 0)
-        { fprintf(stderr, "damar: trace expansion: internal error, %u segments deferred twice\n", c2[0]);
-          return ~0u;
-        }
-      ctr[2] |= c2[2];
-    }
-  if (ctr[2] & DAMAR_TRACE_ERR_POINTS)
-    { fprintf(stderr, "damar: Trace point out of bounds (Compute_Trace), source DB likely incorrect\n");   /* align.c:5575 */
-      return ~0u;
-    }
-  if (ctr[2] & DAMAR_TRACE_ERR_ALIGN)
-    { fprintf(stderr, "damar: Bad alignment between trace points (Compute_Trace), source DB likely incorrect\n");   /* :4890 */
-      return ~0u;
-    }
-  if (ctr[2] & DAMAR_TRACE_ERR_INTERNAL)
-    { fprintf(stderr, "damar: trace expansion: internal error, staging bound of the mid-point pieces violated\n");
-      return ~0u;
-    }
-  return ctr[2];
-}
-
-/* kind 0: Compute_Trace_PTS, the script of every trace-point segment.  kind 1: Compute_Trace_MID: a first
-   wave phase finds the mid point of every segment, the pieces between successive mid points (one more
-   than segments per record) are laid out anew and the script phase runs on those. */
-static int trace_batch(const DevBlock *ad, const DevBlock *bd, int64 r0, int64 r1, int tbytes, int tspace, int mode, int kind,
-                       const std::vector<TraceRecIn> &recs, const std::vector<u8> &pts,
-                       u32 nsegs, u64 nslots, int64 *soff, int *diffs, int **script, int64 *nscript)
-{ const u32 nrecs = (u32) (r1 - r0);
-  static u32 rows = 0, maxblocks = 0;
-  if (rows == 0)
-    { const char *e = getenv("DAMAR_TRACE_ROWS");        /* test hook: fewer rows -> more segments deferred */
-      rows = e ? (u32) atoi(e) : 64u;
-      if (rows < 4) rows = 4;
-      e = getenv("DAMAR_TRACE_BLOCKS");
-      maxblocks = e ? (u32) atoi(e) : (u32) (G_prop.multiProcessorCount * 16);
-      if (maxblocks < 1) maxblocks = 1;
-    }
-  const double h0 = now_ms();
-  const u32 nwork = nsegs + (kind ? nrecs : 0u);             /* segments of the script phase */
-  TraceRecIn *d_recs = (TraceRecIn *) TR.recs.need(sizeof(TraceRecIn) * (size_t) nrecs);
-  void       *d_pts  = TR.pts.need(pts.size() + 64);
-  TraceSeg   *d_segs = (TraceSeg *) TR.segs.need(sizeof(TraceSeg) * (size_t) nsegs);
-  u32 *d_count  = (u32 *) TR.count.need(sizeof(u32) * (size_t) nwork);
-  int *d_dist   = (int *) TR.dist.need(sizeof(int) * (size_t) nwork);
-  u32 *d_segoff = (u32 *) TR.segoff.need(sizeof(u32) * (size_t) nwork);
-  int *d_stage  = (int *) TR.stage.need(sizeof(int) * (size_t) (nslots + 16));
-  u32 *d_over   = (u32 *) TR.over.need(sizeof(u32) * (size_t) nwork);
-  u32 *d_ctr    = (u32 *) TR.ctr.need(256);                    /* [0] deferred, [1] cells needed, [2] error flags; u64 total at +64 */
-  u32 *d_tlen   = (u32 *) TR.tlen.need(sizeof(u32) * (size_t) (nrecs + 1));
-  int *d_diffs  = (int *) TR.diffs.need(sizeof(int) * (size_t) nrecs);
-  void *d_scan  = TR.scan.need(damar_scan_workspace_bytes(nrecs));
-  u32 *d_key    = (u32 *) TR.key.need(sizeof(u32) * (size_t) nwork);
-  u32 *d_val    = (u32 *) TR.val.need(sizeof(u32) * (size_t) nwork);
-
-  struct Events            /* destroyed on every return path */
-  { hipEvent_t e[4];
-    Events()  { for (int i = 0; i < 4; i++) HIP_CHECK(hipEventCreate(&e[i])); }
-    ~Events() { for (int i = 0; i < 4; i++) (void) hipEventDestroy(e[i]); }
-  } evs;
-  hipEvent_t e0 = evs.e[0], e1 = evs.e[1], e2 = evs.e[2], e3 = evs.e[3];
-  HIP_CHECK(hipMemcpyAsync(d_recs, recs.data(), sizeof(TraceRecIn) * (size_t) nrecs, hipMemcpyHostToDevice, G_st));
-  if (!pts.empty())
-    HIP_CHECK(hipMemcpyAsync(d_pts, pts.data(), pts.size(), hipMemcpyHostToDevice, G_st));
-  HIP_CHECK(hipMemsetAsync(d_ctr, 0, 256, G_st));
-  HIP_CHECK(hipEventRecord(e0, G_st));
-  damar_launch_trace_layout(d_recs, nrecs, d_pts, tbytes, tspace, ad, bd, d_segs, d_key, d_val, d_ctr + 2, G_st);
-  TraceArgs t;
-  memset(&t, 0, sizeof(t));
-  t.segs = d_segs;
-  t.abases = ad->bases;  t.bbases = bd->bases;
-  t.apk = ad->pk;  t.bpk = bd->pk;
-  t.stage = d_stage;  t.count = d_count;  t.dist = d_dist;
-  t.over = d_over;  t.over_cap = nwork;  t.nover = d_ctr;  t.need = d_ctr + 1;  t.err = d_ctr + 2;
-  if (kind)
-    { t.mid = (int *) TR.mid.need(sizeof(int) * 2 * (size_t) nsegs);
-      if (trace_wave_phase(t, mode, 1, nsegs, rows, maxblocks, d_ctr, d_key, d_val, e1, e2) == ~0u)
-        return 1;
-      TraceSeg *d_segs2 = (TraceSeg *) TR.segs2.need(sizeof(TraceSeg) * (size_t) nwork);
-      damar_launch_trace_mid_layout(d_recs, nrecs, d_segs, t.mid, ad, bd, d_segs2, d_key, d_val, d_ctr + 2, G_st);
-      t.segs = d_segs = d_segs2;
-    }
-  if (trace_wave_phase(t, mode, 0, nwork, rows, maxblocks, d_ctr, d_key, d_val, e1, e2) == ~0u)
-    return 1;
-  damar_launch_trace_gather(d_recs, nrecs, kind, d_count, d_dist, d_segoff, d_tlen, d_diffs, G_st);
-  u64 *d_tot = (u64 *) ((char *) d_ctr + 64);
-  damar_exclusive_scan_u32(d_tlen, d_tlen, nrecs, d_scan, d_tot, G_st);
-  u64 total = 0;
-  HIP_CHECK(hipMemcpyAsync(&total, d_tot, sizeof(u64), hipMemcpyDeviceToHost, G_st));
-  HIP_CHECK(hipStreamSynchronize(G_st));
-  if (total >= 0xfffffff0ull)
-    { fprintf(stderr, "damar: trace expansion: batch script exceeds 32-bit offsets\n");
-      return 1;
-    }
-  int *d_script = (int *) TR.script.need(sizeof(int) * (size_t) (total + 16));
-  damar_launch_trace_pack(d_segs, nwork, d_count, d_segoff, d_tlen, d_stage, d_script, G_st);
-  HIP_CHECK(hipEventRecord(e3, G_st));
-  std::vector<u32> hoff(nrecs);
-  const size_t base = (size_t) *nscript;
-  { int *grown = (int *) realloc(*script, sizeof(int) * (base + (size_t) total + 1));
-    if (grown == NULL)
-      { fprintf(stderr, "damar: out of memory (edit scripts)\n");
-        return 1;
-      }
-    *script = grown;
-    *nscript = (int64) (base + (size_t) total);
-  }
-  HIP_CHECK(hipMemcpyAsync(hoff.data(), d_tlen, sizeof(u32) * (size_t) nrecs, hipMemcpyDeviceToHost, G_st));
-  HIP_CHECK(hipMemcpyAsync(diffs + r0, d_diffs, sizeof(int) * (size_t) nrecs, hipMemcpyDeviceToHost, G_st));
-  if (total > 0)
-    HIP_CHECK(hipMemcpyAsync(*script + base, d_script, sizeof(int) * (size_t) total, hipMemcpyDeviceToHost, G_st));
-  HIP_CHECK(hipStreamSynchronize(G_st));
-  float dms = 0;
-  HIP_CHECK(hipEventElapsedTime(&dms, e0, e3));
-  TR.ms[1] += dms;
-  for (u32 i = 0; i < nrecs; i++)
-    soff[r0 + i] = (int64) base + hoff[i];
-  soff[r1] = (int64) base + (int64) total;
-  TR.ms[3] += now_ms() - h0;
-  TR.cnt[0] += nrecs;  TR.cnt[1] += nwork;  TR.cnt[3] += (int64) total;
-  return 0;
-}
-
-/* ovls[i].path.trace = the record's trace points as read from the .las (tbytes 1 or 2 per value);
- * aread / bread are DB read ids, afirst / bfirst the ids of the blocks' first reads.  same != 0: A and B of
- * every record are one buffer (align.c:4933-4951; LAshow never is).  On return *script_out is a malloc'ed
- * array holding all edit scripts, record i at [soff[i], soff[i+1]), diffs[i] its summed distance. */
-static int trace_expand(damar_dev_block *ablk, int afirst, damar_dev_block *bblk, int bfirst,
-                        const Overlap *ovls, int64 novl, int tbytes, int tspace, int mode, int same, int kind,
-                        int64 *soff, int *diffs, int **script_out)
-{ ensure_init();
-  const double t0 = now_ms();
-  for (int i = 0; i < 4; i++) { TR.ms[i] = 0;  TR.cnt[i] = 0; }
-  int  *script = NULL;
-  int64 nscript = 0;
-  *script_out = NULL;
-  std::vector<TraceRecIn> recs;
-  std::vector<u8> pts;
-  u32 max_segs = 1u << 24;                                   /* per batch: segments, staging slots */
-  const u64 max_slots = 1ull << 30;
-  { const char *e = getenv("DAMAR_TRACE_MAXSEGS");           /* test hook: many small batches */
-    if (e && atoi(e) > 0) max_segs = (u32) atoi(e);
-  }
-  int64 r0 = 0;
-  u32   nsegs = 0;
-  u64   nslots = 0;
-  soff[0] = 0;
-  for (int64 i = 0; i <= novl; i++)
-    { int dmax = 0, nseg = 0;
-      int64 slots = 0;
-      if (i < novl)
-        { const Overlap *o = ovls + i;
-          const int64 ar = (int64) o->aread - afirst, br = (int64) o->bread - bfirst;
-          if (ar < 0 || ar >= ablk->nreads || br < 0 || br >= bblk->nreads || o->path.tlen < 0 || (o->path.tlen & 1))
-            { fprintf(stderr, "damar: trace expansion: record %lld does not belong to the two blocks\n", (long long) i);
-              free(script);
-              return 1;
-            }
-          if (tbytes == 1) trace_record_shape(&o->path, (const uint8 *) o->path.trace, tspace, &dmax, &nseg, &slots);
-          else             trace_record_shape(&o->path, (const uint16 *) o->path.trace, tspace, &dmax, &nseg, &slots);
-          if (kind)            /* pieces between mid points: |del'| <= |del| of the two segments + 2 (dmax + |del|) drift */
-            slots = 3 * slots + 3 * (int64) dmax;
-        }
-      if (i == novl || nsegs + (u32) nseg > max_segs || nslots + (u64) slots > max_slots)
-        { if (i > r0)
-            { if (trace_batch(&ablk->d, &bblk->d, r0, i, tbytes, tspace, mode, kind, recs, pts,
-                              nsegs, nslots, soff, diffs, &script, &nscript))
-                { free(script);
-                  return 1;
-                }
-            }
-          recs.clear();  pts.clear();
-          r0 = i;  nsegs = 0;  nslots = 0;
-          if (i == novl) break;
-          if ((u64) slots > max_slots || (u32) nseg > max_segs)
-            { fprintf(stderr, "damar: trace expansion: record %lld is larger than a batch\n", (long long) i);
-              free(script);
-              return 1;
-            }
-        }
-      const Overlap *o = ovls + i;
-      TraceRecIn in;
-      in.aread = (u32) (o->aread - afirst);  in.bread = (u32) (o->bread - bfirst);
-      in.flags = (o->flags & COMP_FLAG ? 1u : 0u) | (same ? 2u : 0u);
-      in.abpos = o->path.abpos;  in.bbpos = o->path.bbpos;  in.aepos = o->path.aepos;  in.bepos = o->path.bepos;
-      in.poff = (u32) (pts.size() / (size_t) tbytes);
-      in.tlen = o->path.tlen;
-      in.seg0 = nsegs;
-      in.stage0 = (u32) nslots;
-      in.dmax = dmax;
-      in.slots = (u32) slots;
-      recs.push_back(in);
-      const u8 *src = (const u8 *) o->path.trace;
-      pts.insert(pts.end(), src, src + (size_t) o->path.tlen * (size_t) tbytes);
-      nsegs += (u32) nseg;
-      nslots += (u64) slots;
-    }
-  if (script == NULL)
-    script = (int *) malloc(sizeof(int));
-  *script_out = script;
-  TR.ms[2] = now_ms() - t0;
-  return 0;
-}
-
-extern "C" int damar_trace_pts(damar_dev_block *ablk, int afirst, damar_dev_block *bblk, int bfirst,
-                               const Overlap *ovls, int64 novl, int tbytes, int tspace, int mode, int same,
-                               int64 *soff, int *diffs, int **script_out)
-{ return trace_expand(ablk, afirst, bblk, bfirst, ovls, novl, tbytes, tspace, mode, same, 0, soff, diffs, script_out);
-}
-
-/* the same arguments, Compute_Trace_MID (align.c:5694-5830): the script between the segments' mid points */
-extern "C" int damar_trace_mid(damar_dev_block *ablk, int afirst, damar_dev_block *bblk, int bfirst,
-                               const Overlap *ovls, int64 novl, int tbytes, int tspace, int mode, int same,
-                               int64 *soff, int *diffs, int **script_out)
-{ return trace_expand(ablk, afirst, bblk, bfirst, ovls, novl, tbytes, tspace, mode, same, 1, soff, diffs, script_out);
-}
-
-/* align.c:5577-5692 for one record, through the batch path (the two sequences travel to HBM per call: this
- * entry point is for callers that need the reference's API; LAshow-like loops over a .las belong on
- * damar_trace_pts).  As in the reference, align->path->trace holds 16-bit trace-point pairs on entry (after
- * Decompress_TraceTo16), bseq is already complemented where the record says so, and on return path->trace
- * points to the edit script inside `work`, tlen and diffs are updated.  Returns 0, or 1 after the
- * reference's message where the reference's EXIT(1) paths are. */
-static int compute_trace(Alignment *align, Work_Data *work, int trace_spacing, int mode, int kind)
-{ ensure_init();
-  WorkData *w = (WorkData *) work;
-  HITS_DB   db[2];
-  HITS_READ rd[2][2];
-  std::vector<char> buf[2];
-  const char *seq[2] = { align->aseq, align->bseq };
-  const int   len[2] = { align->alen, align->blen };
-  const int   same = (align->aseq == align->bseq);
-  for (int i = 0; i < 2; i++)
-    { memset(&db[i], 0, sizeof(HITS_DB));
-      memset(rd[i], 0, sizeof(rd[i]));
-      buf[i].assign((size_t) len[i] + 2, 4);
-      memcpy(buf[i].data() + 1, seq[i], (size_t) len[i]);
-      rd[i][0].rlen = len[i];  rd[i][0].boff = 0;  rd[i][1].boff = len[i] + 1;
-      db[i].nreads = db[i].ureads = 1;  db[i].maxlen = len[i];  db[i].totlen = len[i];
-      db[i].bases = buf[i].data() + 1;  db[i].reads = rd[i];
-    }
-  damar_dev_block *ab = damar_block_upload(&db[0]);
-  damar_dev_block *bb = same ? ab : damar_block_upload(&db[1]);
-  Overlap o;
-  memset(&o, 0, sizeof(o));
-  o.path = *align->path;
-  int64 soff[2];
-  int   diffs = 0, *script = NULL;
-  const int rc = trace_expand(ab, 0, bb, 0, &o, 1, 2, trace_spacing, mode, same, kind, soff, &diffs, &script);
-  damar_block_free(ab);
-  if (!same)
-    damar_block_free(bb);
-  if (rc)
-    return 1;
-  w->script.assign(script, script + soff[1]);
-  free(script);
-  align->path->trace = w->script.data();
-  align->path->tlen  = (int) soff[1];
-  align->path->diffs = diffs;
-  return 0;
-}
-
-extern "C" int Compute_Trace_PTS(Alignment *align, Work_Data *work, int trace_spacing, int mode)   /* align.c:5577 */
-{ return compute_trace(align, work, trace_spacing, mode, 0);
-}
-
-extern "C" int Compute_Trace_MID(Alignment *align, Work_Data *work, int trace_spacing, int mode)   /* align.c:5694 */
-{ return compute_trace(align, work, trace_spacing, mode, 1);
-}
-
-/***** mask tracks from piles of overlaps: scrub/LArepeat.c and scrub/TANmask.c (kernels/pile_sweep.hip) **********/
-
-static struct : PileStage       /* ms of the last call: upload, sort, sweep, download; cnt: events sorted, regions (TANDEM: intervals) written */
-{ DBuf rlen{*this}, rflags{*this}, k0{*this}, k1{*this}, kept{*this}, koff{*this}, scan{*this}, sortw{*this}, bases{*this}, active{*this},
-       rb{*this}, re{*this}, rc{*this}, out{*this}, count{*this}, doff{*this}, dst{*this}, misc{*this};
-  std::vector<u64> hsum;         /* COVER's per-pile results on the host: grown, kept */
-  std::vector<int> hact;
-} PL;
-
-extern "C" void damar_pile_release(void)
-{ PL.release();
-  std::vector<u64>().swap(PL.hsum);
-  std::vector<int>().swap(PL.hact);
-}
-
-extern "C" void damar_pile_last(double *ms, int64 *cnt) { PL.last(ms, cnt, 2); }
-
-static int bits_for(u64 v)      /* bits that hold the value v */
-{ int b = 1;
-  while (b < 63 && (v >> b) != 0) b += 1;
-  return b;
-}
-
-/* what the kernels index with: checked here, once, on the host.  The kernels hold record offsets and three ints of data per
-   kept record in 32 bits, so a batch holds fewer than 2^29 records (the reader's batches hold 2^23). */
-static int pile_batch_valid(const damar_pile_batch *b)
-{ if (b->npiles < 0 || b->nrec < 0 || b->npiles > 0x7fffffff || b->nrec > 0x1fffffff || b->nreads <= 0 || b->maxlen < 0)
-    return 0;
-  if (b->npiles == 0)
-    return b->nrec == 0;
-  if (b->pile_off[0] != 0 || b->pile_off[b->npiles] != b->nrec)
-    return 0;
-  for (int64 i = 0; i < b->npiles; i++)
-    if (b->pile_off[i] > b->pile_off[i + 1] || b->pile_aread[i] < 0 || b->pile_aread[i] >= b->nreads)
-      return 0;
-  for (int64 i = 0; i < b->nrec; i++)
-    if (b->bread[i] < 0 || b->bread[i] >= b->nreads)
-      return 0;
-  return 1;
-}
-
-/* One batch through the device.  COVER: bases_out / active_out [npiles].  REPEAT, TANDEM: out. */
-static int pile_device(int mode, const damar_pile_batch *b, const damar_repeat_params *p, int min_len,
-                       u64 *bases_out, int *active_out, damar_pile_track *out)
-{ ensure_init();
-  const u32 np = (u32) b->npiles;
-  const u64 nrec = (u64) b->nrec, nkeys = 2 * nrec;
-  int pbits = bits_for((u64) (b->maxlen > 0 ? b->maxlen : 1));
-  if (pbits > 30)
-    { fprintf(stderr, "damar: piles: reads of %d bases are beyond the event key\n", b->maxlen);
-      return 1;
-    }
-  const int hibit = pbits + 1 + bits_for(np);
-
-  PileArgs a;
-  memset(&a, 0, sizeof(a));
-  a.npiles = np;  a.mode = mode;  a.pbits = pbits;
-  a.min_len = (mode == DAMAR_PILE_TANDEM) ? min_len : p->min_aln_len;
-  if (mode != DAMAR_PILE_TANDEM)
-    { a.inc_identity = p->inc_identity;  a.inccov = p->inccov ? 1 : 0;
-      a.enter = (int) (p->cov * p->xcov_enter);  a.leave = (int) (p->cov * p->xcov_leave);     /* LArepeat.c:328-329 */
-      a.merge_dist = p->merge_dist;
-    }
-  u64 *k0 = (u64 *) PL.k0.need(sizeof(u64) * (size_t) nkeys + 64), *k1 = (u64 *) PL.k1.need(sizeof(u64) * (size_t) nkeys + 64);
-  u32 *d_kept = (u32 *) PL.kept.need(sizeof(u32) * (size_t) np), *d_koff = (u32 *) PL.koff.need(sizeof(u32) * (size_t) np);
-  u32 *d_count = (u32 *) PL.count.need(sizeof(u32) * (size_t) np), *d_doff = (u32 *) PL.doff.need(sizeof(u32) * (size_t) np);
-  void *d_scan = PL.scan.need(damar_scan_workspace_bytes(np));
-  void *d_sortw = PL.sortw.need(damar_sort_workspace_bytes(nkeys));
-  u64 *d_misc = (u64 *) PL.misc.need(256);          /* [0] total kept, [1] total data, [2..3] stats, [4] error word */
-
-  PL.mark(0);
-  const PileDev d = pile_up(PL, b, NULL, { b->abpos, b->aepos, b->bbpos, b->bepos, b->bread, b->flags });
-  a.read_len = up(PL.rlen, b->read_len, (size_t) b->nreads);
-  a.read_flags = up(PL.rflags, b->read_flags, (size_t) b->nreads);
-  HIP_CHECK(hipMemsetAsync(d_misc, 0, 256, G_st));
-  PL.mark(1);
-
-  a.pile_off = d.off;  a.pile_aread = d.aread;
-  a.abpos = d.col[0];  a.aepos = d.col[1];  a.bbpos = d.col[2];  a.bepos = d.col[3];  a.bread = d.col[4];  a.flags = d.col[5];
-  a.keys = k0;  a.kept = d_kept;  a.koff = d_koff;
-  a.stats = d_misc + 2;  a.err = (u32 *) (d_misc + 4);
-  a.count = d_count;
-  if (mode == DAMAR_PILE_COVER)
-    { a.bases = (u64 *) PL.bases.need(sizeof(u64) * (size_t) np);
-      a.active = (int *) PL.active.need(sizeof(int) * (size_t) np);
-    }
-  damar_launch_pile_events(&a, G_st);
-  damar_exclusive_scan_u32(d_kept, d_koff, np, d_scan, d_misc, G_st);
-  const int side = damar_radix_sort_keys_u64(k0, k1, nkeys, 0, hibit, d_sortw, G_st);
-  a.keys = side ? k1 : k0;
-  u64 h_misc[5];
-  u32 h_serr = 0;
-  HIP_CHECK(hipMemcpyAsync(h_misc, d_misc, sizeof(h_misc), hipMemcpyDeviceToHost, G_st));
-  HIP_CHECK(hipMemcpyAsync(&h_serr, damar_sort_error_word(d_sortw), sizeof(u32), hipMemcpyDeviceToHost, G_st));
-  PL.mark(2);
-  HIP_CHECK(hipStreamSynchronize(G_st));
-  if (h_serr != 0)
-    { fprintf(stderr, "damar: piles: the radix sort's look-back timed out\n");
-      return 1;
-    }
-  if ((u32) h_misc[4] & DAMAR_PILE_ERR_RANGE)
-    { fprintf(stderr, "damar: piles: a record's coordinates lie outside its read (longest read %d)\n", b->maxlen);
-      return 1;
-    }
-  const u64 nkept = h_misc[0];
-  PL.cnt[0] = (int64) (2 * nkept);
-  if (mode == DAMAR_PILE_REPEAT)
-    { a.rb = (int *) PL.rb.need(sizeof(int) * (size_t) nkept + 16);
-      a.re = (int *) PL.re.need(sizeof(int) * (size_t) nkept + 16);
-      a.rc = (int *) PL.rc.need(sizeof(int) * (size_t) nkept + 16);
-    }
-  if (mode != DAMAR_PILE_COVER)
-    a.out = (int *) PL.out.need(sizeof(int) * 3 * (size_t) nkept + 16);
-  damar_launch_pile_sweep(&a, G_st);
-  if (mode == DAMAR_PILE_COVER)
-    { PL.mark(3);
-      HIP_CHECK(hipMemcpyAsync(bases_out, a.bases, sizeof(u64) * (size_t) np, hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipMemcpyAsync(active_out, a.active, sizeof(int) * (size_t) np, hipMemcpyDeviceToHost, G_st));
-      PL.cnt[1] = 0;
-    }
-  else
-    { damar_exclusive_scan_u32(d_count, d_doff, np, d_scan, d_misc + 1, G_st);
-      HIP_CHECK(hipMemcpyAsync(h_misc, d_misc, sizeof(h_misc), hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipStreamSynchronize(G_st));
-      const u64 ndata = h_misc[1];
-      int *d_dst = (int *) PL.dst.need(sizeof(int) * (size_t) ndata + 16);
-      damar_launch_pile_gather(a.out, d_koff, d_count, d_doff, np, d_dst, G_st);
-      PL.mark(3);
-      out->data = (int *) malloc(sizeof(int) * (size_t) ndata + 8);
-      if (out->data == NULL)
-        { fprintf(stderr, "damar: out of memory (piles)\n");
-          return 1;
-        }
-      out->ndata = (int64) ndata;
-      out->merged = (int64) h_misc[2];
-      out->repeat_bases = (int64) h_misc[3];
-      if (ndata > 0)
-        HIP_CHECK(hipMemcpyAsync(out->data, d_dst, sizeof(int) * (size_t) ndata, hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipMemcpyAsync(out->count, d_count, sizeof(int) * (size_t) np, hipMemcpyDeviceToHost, G_st));
-    }
-  PL.mark(4);
-  HIP_CHECK(hipStreamSynchronize(G_st));
-  if (mode != DAMAR_PILE_COVER)
-    { const int width = (mode == DAMAR_PILE_REPEAT && a.inccov) ? 3 : 2;       /* a region left open holds its begin alone */
-      int64 regions = 0;
-      for (u32 i = 0; i < np; i++)
-        regions += (out->count[i] + width - 1) / width;
-      PL.cnt[1] = regions;
-    }
-  PL.laps(0, 4);
-  return 0;
-}
-
-static void pile_empty(damar_pile_track *out)
-{ out->data = (int *) malloc(8);
-  out->ndata = out->merged = out->repeat_bases = 0;
-}
-
-extern "C" int damar_pile_coverage(const damar_pile_batch *b, const damar_repeat_params *p, int64 *histo, int64 *bases, int64 *inactive)
-{ if (!pile_batch_valid(b) || p->max_cov <= 0)
-    { fprintf(stderr, "damar: piles: malformed batch\n");
-      return 1;
-    }
-  if (damar_piles_on_host())
-    return damar_host_pile_coverage(b, p, histo, bases, inactive);
-  if (b->npiles == 0)
-    return 0;
-  std::vector<u64> &sum = PL.hsum;
-  std::vector<int> &act = PL.hact;
-  sum.assign((size_t) b->npiles, 0);
-  act.assign((size_t) b->npiles, 0);
-  if (b->nrec > 0)
-    { if (pile_device(DAMAR_PILE_COVER, b, p, 0, sum.data(), act.data(), NULL))
-        return 1;
-    }
-  for (int64 i = 0; i < b->npiles; i++)         /* LArepeat.c:208-223 */
-    { const int   alen = b->read_len[b->pile_aread[i]];
-      const int64 cov = act[i] > 0 ? (int64) sum[i] / act[i] : 0;
-      if (cov < p->max_cov)
-        histo[cov] += 1;
-      *bases += alen;
-      *inactive += alen - act[i];
-    }
-  return 0;
-}
-
-extern "C" int damar_pile_repeats(const damar_pile_batch *b, const damar_repeat_params *p, damar_pile_track *out)
-{ if (!pile_batch_valid(b) || out == NULL || (b->npiles > 0 && out->count == NULL))
-    { fprintf(stderr, "damar: piles: malformed batch\n");
-      return 1;
-    }
-  /* the state after an event is the last setting event's only while span_enter >= span_leave (LArepeat.c:609-613 refuses
-     low > high); below that the device's scan and a sequential walk would part ways */
-  if (p->xcov_enter < p->xcov_leave || (int) (p->cov * p->xcov_enter) < (int) (p->cov * p->xcov_leave))
-    { fprintf(stderr, "damar: piles: coverage %d with enter %.2f below leave %.2f\n", p->cov, p->xcov_enter, p->xcov_leave);
-      return 1;
-    }
-  if (damar_piles_on_host())
-    return damar_host_pile_repeats(b, p, out);
-  if (b->nrec == 0)
-    { for (int64 i = 0; i < b->npiles; i++) out->count[i] = 0;
-      pile_empty(out);
-      return 0;
-    }
-  return pile_device(DAMAR_PILE_REPEAT, b, p, 0, NULL, NULL, out);
-}
-
-extern "C" int damar_pile_tandem(const damar_pile_batch *b, int min_len, damar_pile_track *out)
-{ if (!pile_batch_valid(b) || out == NULL || (b->npiles > 0 && out->count == NULL))
-    { fprintf(stderr, "damar: piles: malformed batch\n");
-      return 1;
-    }
-  if (damar_piles_on_host())
-    return damar_host_pile_tandem(b, min_len, out);
-  if (b->nrec == 0)
-    { for (int64 i = 0; i < b->npiles; i++) out->count[i] = 0;
-      pile_empty(out);
-      return 0;
-    }
-  return pile_device(DAMAR_PILE_TANDEM, b, NULL, min_len, NULL, NULL, out);
-}
-
-/***** LAq's per-tile quality from the traces of piles: scrub/LAq.c handler_annotate (kernels/pile_quality.hip) **********/
-
-static struct : PileStage       /* ms of the last device call: upload, count + scan, scatter + select, download; cnt: segments counted, tiles */
-{ DBuf alen{*this}, tile0{*this}, depth{*this}, run{*this}, vals{*this}, q{*this}, scan{*this}, misc{*this};
-  std::vector<int> halen;        /* per pile: the read's length and where its tiles begin (host arithmetic, kept) */
-  std::vector<u32> htile0;
-} LQ;
-
-extern "C" void damar_q_release(void)
-{ LQ.release();
-  std::vector<int>().swap(LQ.halen);
-  std::vector<u32>().swap(LQ.htile0);
-}
-
-extern "C" void damar_q_last(double *ms, int64 *cnt) { LQ.last(ms, cnt, 2); }
-
-extern "C" int damar_pile_quality(const damar_trace_batch *t, const damar_q_params *p, int *q_out, int64 *ntiles_out)
-{ int64 ntiles = 0;
-  if (t == NULL || p == NULL || ntiles_out == NULL || !damar_trace_batch_valid(t, &ntiles))
-    return 1;
-  if (p->segmin < 1 || p->segmax < p->segmin)
-    { fprintf(stderr, "damar: quality: segmin %d and segmax %d: 1 <= segmin <= segmax is needed\n", p->segmin, p->segmax);
-      return 1;
-    }
-  *ntiles_out = ntiles;
-  if (q_out == NULL || ntiles == 0)
-    return 0;
-  if (damar_piles_on_host())
-    return damar_host_pile_quality(t, p, q_out);
-
-  ensure_init();
-  const damar_pile_batch *b = &t->p;
-  const u32 np = (u32) b->npiles, nt = (u32) ntiles;
-  const size_t nrec = (size_t) b->nrec;
-  u64 segs = 0;                                    /* what the runs hold at most: every segment of every trace */
-  for (size_t i = 0; i < nrec; i++) segs += (u64) (t->tlen[i] / 2);
-  LQ.halen.resize(np);
-  LQ.htile0.resize((size_t) np + 1);
-  LQ.htile0[0] = 0;
-  for (u32 i = 0; i < np; i++)
-    { LQ.halen[i] = b->read_len[b->pile_aread[i]];
-      LQ.htile0[i + 1] = LQ.htile0[i] + (u32) ((LQ.halen[i] + t->tspace - 1) / t->tspace);
-    }
-
-  QArgs a;
-  memset(&a, 0, sizeof(a));
-  a.npiles = np;  a.nrec = (u32) nrec;  a.ntiles = nt;
-  a.tspace = t->tspace;  a.tbytes = t->tbytes;
-  a.segmin = (u32) p->segmin;  a.segmax = (u32) p->segmax;  a.ccs = p->ccs ? 1 : 0;
-  u32 *d_depth = (u32 *) LQ.depth.need(sizeof(u32) * ((size_t) nt + 1));
-  u32 *d_run = (u32 *) LQ.run.need(sizeof(u32) * ((size_t) nt + 1));
-  u16 *d_vals = (u16 *) LQ.vals.need(sizeof(u16) * (size_t) segs + 16);
-  int *d_q = (int *) LQ.q.need(sizeof(int) * (size_t) nt);
-  void *d_scan = LQ.scan.need(damar_scan_workspace_bytes((u64) nt + 1));
-  u64 *d_misc = (u64 *) LQ.misc.need(64);
-
-  LQ.mark(0);
-  a.pile_alen = up(LQ.alen, LQ.halen.data(), (size_t) np);
-  a.pile_tile0 = up(LQ.tile0, LQ.htile0.data(), (size_t) np + 1);
-  const PileDev d = pile_up(LQ, b, t, { b->abpos, b->aepos, b->bread, t->tlen });
-  HIP_CHECK(hipMemsetAsync(d_depth, 0, sizeof(u32) * ((size_t) nt + 1), G_st));
-  LQ.mark(1);
-
-  a.pile_off = d.off;  a.pile_aread = d.aread;
-  a.abpos = d.col[0];  a.aepos = d.col[1];  a.bread = d.col[2];  a.tlen = d.col[3];
-  a.trace_off = d.toff;  a.trace = d.trace;
-  a.depth = d_depth;  a.off = d_run;  a.vals = d_vals;  a.q = d_q;
-  damar_launch_q_count(&a, G_st);
-  damar_exclusive_scan_u32(d_depth, d_run, (u64) nt + 1, d_scan, d_misc, G_st);       /* d_run[nt] = d_misc[0] = segments counted */
-  LQ.mark(2);
-  damar_launch_q_scatter(&a, G_st);
-  damar_launch_q_select(&a, G_st);
-  LQ.mark(3);
-  u64 h_total = 0;
-  HIP_CHECK(hipMemcpyAsync(q_out, d_q, sizeof(int) * (size_t) nt, hipMemcpyDeviceToHost, G_st));
-  HIP_CHECK(hipMemcpyAsync(&h_total, d_misc, sizeof(u64), hipMemcpyDeviceToHost, G_st));
-  LQ.mark(4);
-  HIP_CHECK(hipStreamSynchronize(G_st));
-  LQ.cnt[0] = (int64) h_total;  LQ.cnt[1] = ntiles;
-  LQ.laps(0, 4);
-  return 0;
-}
-
-/***** TKhomogenize's mask of the whole database, kept in HBM across batches of piles (kernels/homogenize.hip) ****************/
-
-struct damar_homog
-{ int   nreads, res;
-  damar_host_homog *hs;          /* DAMAR_PILES=host: the plain routine's state, nothing below is used */
-  std::vector<int> rlen;
-  u32  *d_words;                 /* the mask, nwords of them */
-  u64  *d_woff, *d_cnt;          /* [nreads + 1] word offsets; [0] ranges set */
-  int  *d_rlen;
-  u64   nwords;
-  struct : PileStage             /* the handle's buffers; the events and the figures are HM's */
-  { DBuf ianno{*this}, idata{*this}, trim{*this}, count{*this}, doff{*this}, scan{*this}, out{*this};
-  } S;
-};
-static DevStage HM;              /* the figures outlive the handle.  ms of the last session so far: upload, mark, read-out, download;
-                                    cnt: records seen by add, ranges set, intervals read out */
-
-extern "C" void damar_homog_last(double *ms, int64 *cnt) { HM.last(ms, cnt, 3); }
-
-extern "C" void damar_homog_close(damar_homog *h)
-{ if (h == NULL)
-    return;
-  if (h->hs != NULL)
-    damar_host_homog_close(h->hs);
-  else
-    { h->S.release();
-      HM.release();
-      void *own[] = { h->d_words, h->d_woff, h->d_cnt, h->d_rlen };
-      for (void *p : own)
-        if (p != NULL) HIP_CHECK(hipFree(p));
-    }
-  delete h;
-}
-
-extern "C" damar_homog *damar_homog_open(const int *read_len, int nreads, int res)
-{ if (read_len == NULL || nreads <= 0 || res < 1)
-    { fprintf(stderr, "damar: homogenize: %d reads at resolution %d\n", nreads, res);
-      return NULL;
-    }
-  for (int r = 0; r < nreads; r++)
-    if (read_len[r] < 0)
-      { fprintf(stderr, "damar: homogenize: read %d has length %d\n", r, read_len[r]);
-        return NULL;
-      }
-  damar_homog *h = new damar_homog();
-  h->nreads = nreads;  h->res = res;  h->hs = NULL;
-  h->d_words = NULL;  h->d_woff = NULL;  h->d_cnt = NULL;  h->d_rlen = NULL;
-  for (int i = 0; i < 4; i++) HM.ms[i] = 0;
-  for (int i = 0; i < 3; i++) HM.cnt[i] = 0;
-  h->rlen.assign(read_len, read_len + nreads);
-  if (damar_piles_on_host())
-    { if ((h->hs = damar_host_homog_open(read_len, nreads, res)) == NULL)
-        { delete h;
-          return NULL;
-        }
-      return h;
-    }
-  ensure_init();
-  late_streams();                  /* a tool built on these calls is through soon after the library comes up: see box_scripts */
-  std::vector<u64> woff((size_t) nreads + 1);
-  woff[0] = 0;
-  for (int r = 0; r < nreads; r++)
-    { const u64 bits = (u64) (res > 1 ? (read_len[r] + res - 1) / res : read_len[r]) + 1;
-      woff[(size_t) r + 1] = woff[r] + (bits + 31) / 32;
-    }
-  h->nwords = woff[nreads];
-  const hipError_t e = hipMalloc((void **) &h->d_words, sizeof(u32) * (size_t) h->nwords + 64);
-  if (e != hipSuccess)             /* no smaller mask would do, and there is no other path */
-    { (void) hipGetLastError();
-      fprintf(stderr, "damar: homogenize: no device memory for a mask of %llu bytes (%s)\n", (unsigned long long) (4 * h->nwords),
-              hipGetErrorString(e));
-      h->d_words = NULL;
-      damar_homog_close(h);
-      return NULL;
-    }
-  HIP_CHECK(hipMalloc((void **) &h->d_woff, sizeof(u64) * ((size_t) nreads + 1)));
-  HIP_CHECK(hipMalloc((void **) &h->d_rlen, sizeof(int) * (size_t) nreads));
-  HIP_CHECK(hipMalloc((void **) &h->d_cnt, 64));
-  HM.mark(0);
-  HIP_CHECK(hipMemsetAsync(h->d_words, 0, sizeof(u32) * (size_t) h->nwords + 64, G_st));
-  HIP_CHECK(hipMemsetAsync(h->d_cnt, 0, 64, G_st));
-  HIP_CHECK(hipMemcpyAsync(h->d_woff, woff.data(), sizeof(u64) * ((size_t) nreads + 1), hipMemcpyHostToDevice, G_st));
-  HIP_CHECK(hipMemcpyAsync(h->d_rlen, read_len, sizeof(int) * (size_t) nreads, hipMemcpyHostToDevice, G_st));
-  HM.mark(1);
-  HIP_CHECK(hipStreamSynchronize(G_st));
-  HM.laps_add(0, 1);
-  return h;
-}
-
-/* the interval track goes up with every call: a few ints per read, next to a batch's trace bytes it does not count */
-static void homog_track_up(damar_homog *h, HomArgs *a, const uint64 *anno, const int *data, int64 ndata)
-{ const DevTrack iv = up_track(h->S.ianno, h->S.idata, anno, (size_t) h->nreads, data, ndata);
-  memset(a, 0, sizeof(*a));
-  a->nreads = (u32) h->nreads;  a->res = h->res;  a->ends = -1;
-  a->iv_anno = iv.anno;  a->iv_data = iv.data;
-  a->read_len = h->d_rlen;  a->woff = h->d_woff;  a->words = h->d_words;  a->nranges = h->d_cnt;
-}
-
-static void homog_marked(damar_homog *h)           /* after the kernel: its time and the running count of ranges */
-{ u64 ranges = 0;
-  HIP_CHECK(hipMemcpyAsync(&ranges, h->d_cnt, sizeof(u64), hipMemcpyDeviceToHost, G_st));
-  HIP_CHECK(hipStreamSynchronize(G_st));
-  HM.cnt[1] = (int64) ranges;
-  HM.laps_add(0, 2);
-}
-
-extern "C" int damar_homog_seed(damar_homog *h, const uint64 *anno, const int *data, int64 ndata)
-{ if (h == NULL)
-    return 1;
-  if (!damar_homog_seed_valid(h->rlen.data(), h->nreads, anno, data, ndata))
-    return 1;
-  if (h->hs != NULL)
-    { if (damar_host_homog_seed(h->hs, anno, data))
-        return 1;
-      damar_host_homog_counts(h->hs, HM.cnt);
-      return 0;
-    }
-  HomArgs a;
-  HM.mark(0);
-  homog_track_up(h, &a, anno, data, ndata);
-  HM.mark(1);
-  damar_launch_hom_seed(&a, G_st);
-  HM.mark(2);
-  homog_marked(h);
-  return 0;
-}
-
-extern "C" int damar_homog_add(damar_homog *h, const damar_trace_batch *t, const uint64 *anno, const int *data, int64 ndata, int ends,
-                               const int *trim)
-{ if (h == NULL || t == NULL)
-    return 1;
-  if (!damar_homog_inputs_valid(t, h->nreads, h->rlen.data(), anno, data, ndata, ends, trim))
-    return 1;
-  if (h->hs != NULL)
-    { if (damar_host_homog_add(h->hs, t, anno, data, ends, trim))
-        return 1;
-      damar_host_homog_counts(h->hs, HM.cnt);
-      return 0;
-    }
-  const damar_pile_batch *b = &t->p;
-  HM.cnt[0] += b->nrec;
-  if (b->nrec == 0)
-    return 0;
-  HomArgs a;
-  HM.mark(0);
-  homog_track_up(h, &a, anno, data, ndata);
-  a.npiles = (u32) b->npiles;  a.nrec = (u32) b->nrec;  a.tspace = t->tspace;  a.tbytes = t->tbytes;  a.ends = ends;
-  const PileDev d = pile_up(h->S, b, t, { b->abpos, b->aepos, b->bbpos, b->bepos, b->bread, b->flags, t->tlen });
-  if (ends != -1)
-    a.trim = up(h->S.trim, trim, 2 * (size_t) h->nreads);
-  HM.mark(1);
-  a.pile_off = d.off;  a.pile_aread = d.aread;
-  a.abpos = d.col[0];  a.aepos = d.col[1];  a.bbpos = d.col[2];  a.bepos = d.col[3];  a.bread = d.col[4];  a.flags = d.col[5];
-  a.tlen = d.col[6];  a.trace_off = d.toff;  a.trace = d.trace;
-  damar_launch_hom_mark(&a, G_st);
-  HM.mark(2);
-  homog_marked(h);
-  return 0;
-}
-
-extern "C" int damar_homog_finish(damar_homog *h, uint64 *anno, int **data, int64 *ndata, int64 *tagged)
-{ if (h == NULL || anno == NULL || data == NULL || ndata == NULL || tagged == NULL)
-    return 1;
-  if (h->hs != NULL)
-    { if (damar_host_homog_finish(h->hs, anno, data, ndata, tagged))
-        return 1;
-      damar_host_homog_counts(h->hs, HM.cnt);
-      return 0;
-    }
-  const size_t nr = (size_t) h->nreads;
-  HomArgs a;
-  memset(&a, 0, sizeof(a));
-  a.nreads = (u32) h->nreads;  a.res = h->res;
-  a.read_len = h->d_rlen;  a.woff = h->d_woff;  a.words = h->d_words;
-  u32 *d_count = (u32 *) h->S.count.need(sizeof(u32) * nr), *d_doff = (u32 *) h->S.doff.need(sizeof(u32) * nr);
-  void *d_scan = h->S.scan.need(damar_scan_workspace_bytes(nr));
-  a.count = d_count;  a.off = d_doff;
-  HM.mark(2);
-  damar_launch_hom_count(&a, G_st);
-  damar_exclusive_scan_u32(d_count, d_doff, nr, d_scan, h->d_cnt + 1, G_st);
-  u64 total = 0;
-  HIP_CHECK(hipMemcpyAsync(&total, h->d_cnt + 1, sizeof(u64), hipMemcpyDeviceToHost, G_st));
-  HIP_CHECK(hipStreamSynchronize(G_st));
-  if (total >= ((u64) 1 << 30))
-    { fprintf(stderr, "damar: homogenize: %llu intervals, 2^30 - 1 is the most a track of ints holds here\n", (unsigned long long) total);
-      return 1;
-    }
-  a.out = (int *) h->S.out.need(sizeof(int) * 2 * (size_t) total + 16);
-  damar_launch_hom_emit(&a, G_st);
-  HM.mark(3);
-  std::vector<u32> cnt(nr);
-  int *out = (int *) malloc(sizeof(int) * 2 * (size_t) total + 8);
-  if (out == NULL)
-    { fprintf(stderr, "damar: out of memory (homogenize)\n");
-      return 1;
-    }
-  HIP_CHECK(hipMemcpyAsync(cnt.data(), d_count, sizeof(u32) * nr, hipMemcpyDeviceToHost, G_st));
-  if (total > 0)
-    HIP_CHECK(hipMemcpyAsync(out, a.out, sizeof(int) * 2 * (size_t) total, hipMemcpyDeviceToHost, G_st));
-  HM.mark(4);
-  HIP_CHECK(hipStreamSynchronize(G_st));
-  uint64 off = 0;
-  for (size_t r = 0; r < nr; r++)
-    { anno[r] = off;
-      off += 2 * sizeof(int) * (uint64) cnt[r];
-    }
-  anno[nr] = off;
-  int64 sum = 0;
-  for (u64 k = 0; k < total; k++)
-    sum += out[2 * k + 1] - out[2 * k];
-  *data = out;  *ndata = (int64) (2 * total);  *tagged = sum;
-  HM.cnt[2] = (int64) total;
-  HM.laps_add(2, 2);
-  return 0;
-}
-
-/***** exact alignment of batches of boxes: what damar_align_boxes, damar_align_reads and damar_trace_boxes share **********/
-
-/* A stage whose calls take a batch of boxes: the batch's columns, where a box's output begins (off), and what comes back:
-   the differences, the length of a box's output (-1: the box is the host routine's) and the output itself.
-   ms of the last call: upload, kernel, download (HIP events), whole call (wall);
-   cnt: boxes, boxes the host routine did beside the kernel, values of output */
-struct BoxStage : DevStage
-{ DBuf m{*this}, n{*this}, aoff{*this}, boff{*this}, off{*this}, bases{*this}, diffs{*this}, len{*this}, out{*this};
-  void *room(size_t nb, size_t out_bytes)      /* for what comes back, before the upload is timed: -> the output's */
-  { diffs.need(sizeof(int) * nb);
-    len.need(sizeof(int) * nb);
-    return out.need(out_bytes);
-  }
-};
-
-/* damar_box_batch and damar_tbox_batch as one (abpos is NULL for the first); no batch at all is one of -1 boxes */
-struct BoxBatch
-{ int64 nbox;
-  const int *m, *n, *abpos;
-  const int64 *aoff, *boff;
-  const char *bases;
-  int64 nbases;
-};
-
-static BoxBatch box_batch(const damar_box_batch *b)
-{ return (b == NULL) ? BoxBatch{ -1 } : BoxBatch{ b->nbox, b->m, b->n, NULL, b->aoff, b->boff, b->bases, b->nbases }; }
-
-static BoxBatch box_batch(const damar_tbox_batch *b)
-{ return (b == NULL) ? BoxBatch{ -1 } : BoxBatch{ b->nbox, b->m, b->n, b->abpos, b->aoff, b->boff, b->bases, b->nbases }; }
-
-/* false after a message when a call cannot take the batch.  what: the family's word in its messages; args_ok: what the call
-   asks of its other arguments */
-static bool box_batch_valid(const char *what, const BoxBatch &v, bool args_ok, const int *diffs)
-{ if (!args_ok || v.nbox < 0 || (v.nbox > 0 && diffs == NULL))
-    { fprintf(stderr, "damar: %s: malformed batch\n", what);
-      return false;
-    }
-  if (v.nbox >= ((int64) 1 << 31))
-    { fprintf(stderr, "damar: %s: a batch holds fewer than 2^31 boxes\n", what);
-      return false;
-    }
-  for (size_t i = 0; i < (size_t) v.nbox; i++)
-    if (v.m[i] < 1 || v.n[i] < 1 || (v.abpos != NULL && v.abpos[i] < 0) || v.aoff[i] < 0 || v.boff[i] < 0 || v.aoff[i] + v.m[i] > v.nbases ||
-        v.boff[i] + v.n[i] > v.nbases)
-      { char at[32] = "";
-        if (v.abpos != NULL)
-          snprintf(at, sizeof(at), " at %d", v.abpos[i]);
-        fprintf(stderr, "damar: %s: box %zu (%d x %d%s) does not lie inside the %lld bases\n", what, i, v.m[i], v.n[i], at, (long long) v.nbases);
-        return false;
-      }
-  return true;
-}
-
-struct BoxDev
-{ const int *m, *n;
-  const long long *aoff, *boff, *off;
-  const u8 *bases;
-  int *diffs, *len;
-};
-
-/* after S.room(): the batch onto the device on G_st, off[nbox + 1] with it, and every length that comes back -1 */
-static BoxDev box_up(BoxStage &S, const BoxBatch &v, const long long *off)
-{ const size_t nb = (size_t) v.nbox;
-  BoxDev d;
-  d.m = up(S.m, v.m, nb);
-  d.n = up(S.n, v.n, nb);
-  d.aoff = (const long long *) up(S.aoff, v.aoff, nb);
-  d.boff = (const long long *) up(S.boff, v.boff, nb);
-  d.off = up(S.off, off, nb + 1);
-  d.bases = (const u8 *) up(S.bases, v.bases, (size_t) v.nbases);
-  d.diffs = (int *) S.diffs.p;
-  d.len = (int *) S.len.p;
-  HIP_CHECK(hipMemsetAsync(d.len, 0xff, sizeof(int) * nb, G_st));
-  return d;
-}
-
-static void box_down(const BoxDev &d, size_t nb, int *diffs, int *len)          /* the differences and the lengths back, on G_st */
-{ HIP_CHECK(hipMemcpyAsync(diffs, d.diffs, sizeof(int) * nb, hipMemcpyDeviceToHost, G_st));
-  HIP_CHECK(hipMemcpyAsync(len, d.len, sizeof(int) * nb, hipMemcpyDeviceToHost, G_st));
-}
-
-/* what the kernel left: boxes beyond its bounds (and all of them on the host route), through one(i), the host routine on
-   box i, which sets len[i] and returns the differences; -> how many the host routine did beside the kernel */
-template <typename One>
-static int64 box_rest(std::vector<int> &len, int *diffs, bool host, One one)
-{ int64 fallback = 0;
-  for (size_t i = 0; i < len.size(); i++)
-    if (len[i] < 0)
-      { diffs[i] = one(i);
-        fallback += host ? 0 : 1;
-      }
-  return fallback;
-}
-
-static void box_done(BoxStage &S, int64 nbox, int64 fallback, int64 values, double w0)      /* the figures of a call that succeeded */
-{ S.cnt[0] = nbox;  S.cnt[1] = fallback;  S.cnt[2] = values;
-  S.ms[3] = now_ms() - w0;
-}
-
-/* damar_align_boxes and damar_align_reads.  what: the family's word in its messages; host: its switch to the host routine;
-   order: where the order goes in which the workgroups take the boxes, longest first, or NULL for the order of the batch;
-   launch(a): the family's bound into a and its kernel on G_st */
-template <typename Launch>
-static int box_scripts(BoxStage &S, const char *what, const damar_box_batch *b, int *diffs, int64 *soff, int **script, bool host, DBuf *order,
-                       Launch launch)
-{ const double w0 = now_ms();
-  const BoxBatch v = box_batch(b);
-  if (!box_batch_valid(what, v, soff != NULL && script != NULL, diffs))
-    return 1;
-  const size_t nb = (size_t) v.nbox;
-  /* every box gets max(m, n) values of room; the scripts are moved together at the end */
-  std::vector<long long> room(nb + 1);
-  room[0] = 0;
-  for (size_t i = 0; i < nb; i++)
-    room[i + 1] = room[i] + std::max(v.m[i], v.n[i]);
-  std::vector<int> wide((size_t) room[nb] + 1), slen(nb, -1);
-  for (int i = 0; i < 4; i++) S.ms[i] = 0;
-
-  if (!host && nb > 0)
-    { ensure_init();
-      /* a tool built on this call is through a few milliseconds after the library comes up: its launch, its copies and
-         the frees of the family's release would all run beside the start-up thread, which is inside HIP calls of its own for
-         longer than that.  The process cannot end before that thread does (helpers_join), so waiting here costs nothing. */
-      late_streams();
-      /* longest first: the workgroups take the boxes in this order, and the longest box is the launch's critical path */
-      std::vector<u32> longest;
-      if (order != NULL)
-        { longest.resize(nb);
-          for (size_t i = 0; i < nb; i++) longest[i] = (u32) i;
-          std::stable_sort(longest.begin(), longest.end(), [&](u32 x, u32 y) { return std::max(v.m[x], v.n[x]) > std::max(v.m[y], v.n[y]); });
-        }
-      BoxArgs a;
-      memset(&a, 0, sizeof(a));
-      a.nbox = (u32) nb;
-      a.script = (int *) S.room(nb, sizeof(int) * ((size_t) room[nb] + 1));
-      S.mark(0);
-      const BoxDev d = box_up(S, v, room.data());
-      if (order != NULL)
-        a.order = up(*order, longest.data(), nb);
-      S.mark(1);
-      a.m = d.m;  a.n = d.n;  a.aoff = d.aoff;  a.boff = d.boff;  a.coff = d.off;  a.bases = d.bases;  a.diffs = d.diffs;  a.slen = d.len;
-      launch(&a);
-      HIP_CHECK(hipGetLastError());
-      S.mark(2);
-      box_down(d, nb, diffs, slen.data());
-      if (room[nb] > 0)
-        HIP_CHECK(hipMemcpyAsync(wide.data(), a.script, sizeof(int) * (size_t) room[nb], hipMemcpyDeviceToHost, G_st));
-      S.mark(3);
-      HIP_CHECK(hipStreamSynchronize(G_st));
-      S.laps(0, 3);
-    }
-  const int64 fallback = box_rest(slen, diffs, host, [&](size_t i)
-    { return damar_exact_box(v.bases + v.aoff[i], v.m[i], v.bases + v.boff[i], v.n[i], wide.data() + room[i], &slen[i]); });
-  soff[0] = 0;
-  for (size_t i = 0; i < nb; i++)
-    soff[i + 1] = soff[i] + slen[i];
-  *script = (int *) malloc(sizeof(int) * (size_t) soff[nb] + 8);
-  if (*script == NULL)
-    { fprintf(stderr, "damar: out of memory (%s)\n", what);
-      return 1;
-    }
-  for (size_t i = 0; i < nb; i++)
-    if (slen[i] > 0)
-      memcpy(*script + soff[i], wide.data() + room[i], sizeof(int) * (size_t) slen[i]);
-  box_done(S, v.nbox, fallback, soff[nb], w0);
-  return 0;
-}
-
-/***** exact alignment of a batch of boxes with their edit scripts: Compute_Alignment(DIFF_ALIGN) (kernels/box_align.hip) ******/
-
-static BoxStage BX;
-
-extern "C" void damar_box_release(void) { BX.release(); }
-
-extern "C" unsigned int damar_box_grid(void) { return damar_box_align_grid(); }
-
-extern "C" void damar_box_last(double *ms, int64 *cnt) { BX.last(ms, cnt, 3); }
-
-extern "C" int damar_align_boxes(const damar_box_batch *b, int *diffs, int64 *soff, int **script)
-{ return box_scripts(BX, "boxes", b, diffs, soff, script, damar_trim_on_host() != 0, NULL, [](BoxArgs *a)
-    { a->maxlen = test_limit("DAMAR_TEST_BOX_LIMIT", DAMAR_BOX_MAXLEN, INT_MIN);
-      damar_launch_box_align(a, G_st);
-    });
-}
-
-/***** the same for boxes of read length, LAcorrect's postrace (kernels/read_align.hip) ******/
-
-static struct : BoxStage { DBuf order{*this}; } RD;
-
-extern "C" void damar_read_release(void) { RD.release(); }
-
-extern "C" unsigned int damar_read_grid(void) { return damar_read_align_grid(); }
-
-extern "C" void damar_read_last(double *ms, int64 *cnt) { RD.last(ms, cnt, 3); }
-
-extern "C" int damar_postrace_on_host(void)
-{ const char *e = getenv("DAMAR_POSTRACE");
-  return e != NULL && strcmp(e, "host") == 0;
-}
-
-extern "C" int damar_align_reads(const damar_box_batch *b, int *diffs, int64 *soff, int **script)
-{ return box_scripts(RD, "reads", b, diffs, soff, script, damar_postrace_on_host() != 0, &RD.order, [](BoxArgs *a)
-    { a->maxdiff = test_limit("DAMAR_TEST_READ_DIFFS", DAMAR_READ_MAXDIFF, 0);
-      damar_launch_read_align(a, (u32) test_limit("DAMAR_TEST_READ_GRID", (int) damar_read_align_grid(), 1), G_st);
-    });
-}
-
-/***** exact alignment of a batch of boxes into trace pairs: Compute_Alignment(DIFF_TRACE) (kernels/box_trace.hip) ******/
-
-static struct : BoxStage { DBuf large{*this}, abpos{*this}; } TB;
-
-extern "C" void damar_tbox_release(void) { TB.release(); }
-
-extern "C" unsigned int damar_tbox_grid(void) { return damar_box_trace_grid(); }
-
-extern "C" void damar_tbox_last(double *ms, int64 *cnt) { TB.last(ms, cnt, 3); }
-
-extern "C" int damar_trace_boxes(const damar_tbox_batch *b, int *diffs, int64 *toff, uint16 **trace)
-{ const double w0 = now_ms();
-  const BoxBatch v = box_batch(b);
-  if (!box_batch_valid("trace boxes", v, toff != NULL && trace != NULL && b != NULL && b->tspace >= 1, diffs))
-    return 1;
-  const size_t nb = (size_t) v.nbox;
-  const int    ts = b->tspace;
-  /* a box's number of values follows from where it lies on A's grid: the pairs go straight to their place */
-  toff[0] = 0;
-  for (size_t i = 0; i < nb; i++)
-    toff[i + 1] = toff[i] + 2 * (int64) ((v.abpos[i] % ts + v.m[i] + ts - 1) / ts);
-  *trace = (uint16 *) malloc(sizeof(uint16) * (size_t) toff[nb] + 8);
-  if (*trace == NULL)
-    { fprintf(stderr, "damar: out of memory (trace boxes)\n");
-      return 1;
-    }
-  std::vector<int> tlen(nb, -1);
-  for (int i = 0; i < 4; i++) TB.ms[i] = 0;
-
-  const bool host = damar_stitch_on_host() != 0;
-  if (!host && nb > 0)
-    { ensure_init();
-      late_streams();              /* a tool built on this call is through soon after the library comes up: see box_scripts */
-      TBoxArgs a;
-      memset(&a, 0, sizeof(a));
-      a.nbox = (u32) nb;
-      a.maxlen = test_limit("DAMAR_TEST_BOX_LIMIT", DAMAR_TBOX_MAXLEN, INT_MIN);
-      a.tspace = ts;
-      std::vector<u32> large;
-      for (size_t i = 0; i < nb; i++)
-        if ((u32) std::max(v.m[i], v.n[i]) > damar_box_trace_small())
-          large.push_back((u32) i);
-      a.nlarge = (u32) large.size();
-      a.trace = (u16 *) TB.room(nb, sizeof(u16) * ((size_t) toff[nb] + 4));
-      TB.mark(0);
-      const BoxDev d = box_up(TB, v, (const long long *) toff);
-      a.abpos = up(TB.abpos, v.abpos, nb);
-      a.large = up(TB.large, large.data(), large.size());
-      TB.mark(1);
-      a.m = d.m;  a.n = d.n;  a.aoff = d.aoff;  a.boff = d.boff;  a.toff = d.off;  a.bases = d.bases;  a.diffs = d.diffs;  a.tlen = d.len;
-      damar_launch_box_trace(&a, G_st);
-      HIP_CHECK(hipGetLastError());
-      TB.mark(2);
-      box_down(d, nb, diffs, tlen.data());
-      if (toff[nb] > 0)
-        HIP_CHECK(hipMemcpyAsync(*trace, a.trace, sizeof(u16) * (size_t) toff[nb], hipMemcpyDeviceToHost, G_st));
-      TB.mark(3);
-      HIP_CHECK(hipStreamSynchronize(G_st));
-      TB.laps(0, 3);
-    }
-  const int64 fallback = box_rest(tlen, diffs, host, [&](size_t i)
-    { return damar_trace_box(v.bases + v.aoff[i], v.m[i], v.bases + v.boff[i], v.n[i], v.abpos[i], ts, *trace + toff[i], &tlen[i]); });
-  for (size_t i = 0; i < nb; i++)
-    if (tlen[i] != toff[i + 1] - toff[i])
-      { fprintf(stderr, "damar: trace boxes: box %zu came back with %d values for %lld\n", i, tlen[i], (long long) (toff[i + 1] - toff[i]));
-        free(*trace);
-        *trace = NULL;
-        return 1;
-      }
-  box_done(TB, v.nbox, fallback, toff[nb], w0);
-  return 0;
-}
-
-/***** LAgap's containments, gaps and breaks per pile: scrub/LAgap.c (kernels/pile_gaps.hip) ******************************/
-
-static struct : PileStage       /* ms of the last call: upload, kernel, download (HIP events), whole call (wall);
-                                   cnt: piles, piles the host routine did beside the kernel, break events */
-{ DBuf rlen{*this}, xanno{*this}, xdata{*this}, skip{*this}, flags{*this}, status{*this}, nev{*this}, evs{*this}, pcnt{*this};
-} GP;
-
-extern "C" void damar_gap_release(void) { GP.release(); }
-
-extern "C" void damar_gap_limits(int *bins, int *events)
-{ *bins = DAMAR_GAP_MAXBINS;
-  *events = DAMAR_GAP_MAXEVENTS;
-}
-
-extern "C" void damar_gap_last(double *ms, int64 *cnt) { GP.last(ms, cnt, 3); }
-
-extern "C" int damar_pile_gaps(const damar_pile_batch *b, const damar_gap_params *p, int *flags_out, damar_gap_events *ev)
-{ const double w0 = now_ms();
-  if (ev == NULL || !damar_gap_inputs_valid(b, p) || (b->nrec > 0 && flags_out == NULL) || (b->npiles > 0 && ev->count == NULL))
-    return 1;
-  const size_t np = (size_t) b->npiles, nrec = (size_t) b->nrec;
-  const bool host = damar_piles_on_host() != 0;
-  damar_gap_list L = { NULL, 0, 0 };
-  int64 cnt[3] = { 0, 0, 0 }, fallback = 0;
-  for (int i = 0; i < 4; i++) GP.ms[i] = 0;
-
-  std::vector<u8>  skip(np + 1, 0);
-  std::vector<int> status(np + 1, 1), nev(np + 1, 0), evs, pcnt;
-  if (!host && np > 0)
-    { /* the kernel takes the records of one B read for a run.  The reference's containment loop skips a discarded record
-         before it looks at its B read, so where the B reads do not ascend it can pair records across another read's:
-         such a pile is the host routine's */
-      for (size_t q = 0; q < np; q++)
-        for (int64 i = b->pile_off[q] + 1; i < b->pile_off[q + 1]; i++)
-          if (b->bread[i] < b->bread[i - 1])
-            { skip[q] = 1;
-              break;
-            }
-      ensure_init();
-      late_streams();                /* a tool built on this call is through soon after the library comes up: see box_scripts */
-      GapArgs a;
-      memset(&a, 0, sizeof(a));
-      a.npiles = (u32) np;
-      a.maxbins = test_limit("DAMAR_TEST_GAP_BINS", DAMAR_GAP_MAXBINS, INT_MIN);
-      a.maxev = DAMAR_GAP_MAXEVENTS;  a.stitch = p->stitch;
-      const size_t evints = np * DAMAR_GAP_MAXEVENTS * DAMAR_GAP_EVENT_INTS;
-      int *d_flags = (int *) GP.flags.need(sizeof(int) * nrec + 16);
-      int *d_status = (int *) GP.status.need(sizeof(int) * np + 16), *d_nev = (int *) GP.nev.need(sizeof(int) * np + 16);
-      int *d_ev = (int *) GP.evs.need(sizeof(int) * evints + 16), *d_cnt = (int *) GP.pcnt.need(sizeof(int) * 3 * np + 16);
-      GP.mark(0);
-      if (p->ex_anno != NULL)
-        { const DevTrack ex = up_track(GP.xanno, GP.xdata, p->ex_anno, (size_t) b->nreads, p->ex_data, p->ex_ndata);
-          a.ex_anno = ex.anno;  a.ex_data = ex.data;
-        }
-      a.skip = up(GP.skip, skip.data(), np);
-      const PileDev d = pile_up(GP, b, NULL, { b->abpos, b->aepos, b->bbpos, b->bepos, b->bread, b->flags });
-      a.read_len = up(GP.rlen, b->read_len, (size_t) b->nreads);
-      HIP_CHECK(hipMemsetAsync(d_nev, 0, sizeof(int) * np, G_st));
-      GP.mark(1);
-      a.pile_off = d.off;  a.pile_aread = d.aread;
-      a.abpos = d.col[0];  a.aepos = d.col[1];  a.bbpos = d.col[2];  a.bepos = d.col[3];  a.bread = d.col[4];  a.flags = d.col[5];
-      a.flags_out = d_flags;  a.status = d_status;  a.nev = d_nev;  a.ev = d_ev;  a.cnt = d_cnt;
-      damar_launch_pile_gaps(&a, (u32) test_limit("DAMAR_TEST_GAP_GRID", (int) damar_pile_gaps_grid(), 1), G_st);
-      HIP_CHECK(hipGetLastError());
-      GP.mark(2);
-      evs.resize(evints + 1);
-      pcnt.resize(3 * np + 1);
-      if (nrec > 0)
-        HIP_CHECK(hipMemcpyAsync(flags_out, d_flags, sizeof(int) * nrec, hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipMemcpyAsync(status.data(), d_status, sizeof(int) * np, hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipMemcpyAsync(nev.data(), d_nev, sizeof(int) * np, hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipMemcpyAsync(evs.data(), d_ev, sizeof(int) * evints, hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipMemcpyAsync(pcnt.data(), d_cnt, sizeof(int) * 3 * np, hipMemcpyDeviceToHost, G_st));
-      GP.mark(3);
-      HIP_CHECK(hipStreamSynchronize(G_st));
-      GP.laps(0, 3);
-    }
-  /* the events in pile order; what the kernel left (all piles with DAMAR_PILES=host) is the plain routine's */
-  for (size_t q = 0; q < np; q++)
-    { const int64 before = L.n;
-      if (status[q] != 0)
-        { damar_host_gap_pile(b, (int64) q, p, flags_out, &L, cnt);
-          fallback += host ? 0 : 1;
-        }
-      else
-        { if (nev[q] < 0 || nev[q] > DAMAR_GAP_MAXEVENTS)
-            { fprintf(stderr, "damar: gaps: pile %zu came back with %d events\n", q, nev[q]);
-              free(L.ev);
-              return 1;
-            }
-          if (list_append(&L.ev, &L.n, &L.cap, DAMAR_GAP_EVENT_INTS, evs.data() + q * DAMAR_GAP_MAXEVENTS * DAMAR_GAP_EVENT_INTS, nev[q], "gaps"))
-            return 1;
-          for (int i = 0; i < 3; i++) cnt[i] += pcnt[3 * q + i];
-        }
-      ev->count[q] = (int) (L.n - before);
-    }
-  if (L.ev == NULL && (L.ev = (int *) malloc(sizeof(int) * DAMAR_GAP_EVENT_INTS)) == NULL)       /* no event: still the caller's to free */
-    { fprintf(stderr, "damar: out of memory (gaps)\n");
-      return 1;
-    }
-  ev->ev = L.ev;
-  ev->nev = L.n;
-  ev->contained = cnt[0];  ev->breaks = cnt[1];  ev->dropped = cnt[2];
-  GP.cnt[0] = b->npiles;  GP.cnt[1] = fallback;  GP.cnt[2] = L.n;
-  GP.ms[3] = now_ms() - w0;
-  return 0;
-}
-
-/***** LAfilter's screens per pile: scrub/LAfilter.c filter_handler (kernels/pile_filter.hip) *****************************/
-
-static struct : PileStage       /* ms of the last call: upload, kernel, download (HIP events), whole call (wall);
-                                   cnt: piles, piles the host routine did beside the kernel, records that left discarded */
-{ DBuf rlen{*this}, trim{*this}, ranno{*this}, rdata{*this}, soff{*this}, slen{*this}, sdata{*this}, state{*this},
-       out[7] = { *this, *this, *this, *this, *this, *this, *this }, status{*this}, pcnt{*this};
-} FL;
-
-extern "C" void damar_filter_release(void) { FL.release(); }
-
-extern "C" void damar_filter_limits(int *group, int *len)
-{ *group = DAMAR_FILTER_MAXGROUP;
-  *len = DAMAR_FILTER_MAXLEN;
-}
-
-extern "C" void damar_filter_last(double *ms, int64 *cnt) { FL.last(ms, cnt, 3); }
-
-extern "C" int damar_pile_filter(const damar_trace_batch *t, const int *diffs, const damar_filter_params *p, damar_filter_out *out)
-{ const double w0 = now_ms();
-  if (!damar_filter_inputs_valid(t, diffs, p, out))
-    return 1;
-  const damar_pile_batch *b = &t->p;
-  const size_t np = (size_t) b->npiles, nrec = (size_t) b->nrec, nreads = (size_t) b->nreads;
-  const bool host = damar_piles_on_host() != 0;
-  int64 fallback = 0, gone = 0;
-  for (int i = 0; i < 4; i++) FL.ms[i] = 0;
-
-  std::vector<int> status(np + 1, 1);
-  if (!host && np > 0)
-    { ensure_init();
-      late_streams();                /* a tool built on this call is through soon after the library comes up: see box_scripts */
-      FilterArgs a;
-      memset(&a, 0, sizeof(a));
-      a.npiles = (u32) np;
-      a.steps = p->steps;
-      a.maxgroup = test_limit("DAMAR_TEST_FILTER_GROUP", DAMAR_FILTER_MAXGROUP, 1);
-      a.maxlen = test_limit("DAMAR_TEST_FILTER_LEN", DAMAR_FILTER_MAXLEN, 1);
-      if ((p->steps & DAMAR_FILTER_MAIN) && p->lowcov && p->max_unaligned != -1)
-        { int longest = 0;           /* the coverage bits: room for the longest A read of the batch that the kernel takes */
-          for (size_t q = 0; q < np; q++)
-            { const int alen = b->read_len[b->pile_aread[q]];
-              if (alen <= a.maxlen && alen > longest) longest = alen;
-            }
-          a.mask_words = (longest + 31) / 32 + 2;
-        }
-      a.downsample = p->downsample;  a.max_rid = (int) (p->downsample * b->nreads / 100.0);  a.seg_rate = p->seg_rate;
-      a.stitch = p->stitch;  a.stitch_aggr = p->stitch_aggr;  a.min_rlen = p->min_rlen;  a.min_olen = p->min_olen;
-      a.max_unaligned = p->max_unaligned;  a.min_nonrep = p->min_nonrep;  a.max_diffs = p->max_diffs;  a.merge_tips = p->merge_tips;
-      a.multi = p->multi;  a.lowcov = p->lowcov;  a.remove = p->remove;  a.include = p->include;  a.tbytes = t->tbytes;
-      int *d_out[7];
-      for (int i = 0; i < 7; i++) d_out[i] = (int *) FL.out[i].need(sizeof(int) * nrec + 16);
-      int *d_status = (int *) FL.status.need(sizeof(int) * np + 16);
-      int *d_cnt = (int *) FL.pcnt.need(sizeof(int) * DAMAR_FC_COUNT * np + 16);
-      FL.mark(0);
-      if (p->trim != NULL)
-        a.trim = up(FL.trim, p->trim, 2 * nreads);
-      if (p->min_nonrep != -1)
-        { const DevTrack rep = up_track(FL.ranno, FL.rdata, p->rep_anno, nreads, p->rep_data, p->rep_ndata);
-          a.rep_anno = rep.anno;  a.rep_data = rep.data;
-        }
-      if (p->sym_off != NULL)
-        { a.sym_off = up(FL.soff, p->sym_off, nreads + 1);
-          a.sym_len = up(FL.slen, p->sym_len, nreads + 1);
-          a.sym_data = up(FL.sdata, p->sym_data, (size_t) p->sym_ndata);
-        }
-      if (p->read_state != NULL)
-        a.read_state = up(FL.state, p->read_state, nreads);
-      const PileDev d = pile_up(FL, b, t, { b->abpos, b->aepos, b->bbpos, b->bepos, b->bread, b->flags, diffs, t->tlen });
-      a.read_len = up(FL.rlen, b->read_len, nreads);
-      FL.mark(1);
-      a.pile_off = d.off;  a.pile_aread = d.aread;
-      a.abpos = d.col[0];  a.aepos = d.col[1];  a.bbpos = d.col[2];  a.bepos = d.col[3];  a.bread = d.col[4];  a.flags = d.col[5];
-      a.diffs = d.col[6];  a.tlen = d.col[7];  a.trace_off = d.toff;  a.trace = d.trace;
-      a.o_flags = d_out[0];  a.o_ae = d_out[1];  a.o_be = d_out[2];  a.o_df = d_out[3];  a.o_tl = d_out[4];  a.o_why = d_out[5];  a.o_by = d_out[6];
-      a.status = d_status;  a.cnt = d_cnt;
-      damar_launch_pile_filter(&a, (u32) test_limit("DAMAR_TEST_FILTER_GRID", (int) damar_pile_filter_grid(), 1), G_st);
-      HIP_CHECK(hipGetLastError());
-      FL.mark(2);
-      int *dst[7] = { out->flags, out->aepos, out->bepos, out->diffs, out->tlen, out->reason, out->cont_by };
-      if (nrec > 0)
-        for (int i = 0; i < 7; i++)
-          HIP_CHECK(hipMemcpyAsync(dst[i], d_out[i], sizeof(int) * nrec, hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipMemcpyAsync(status.data(), d_status, sizeof(int) * np, hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipMemcpyAsync(out->cnt, d_cnt, sizeof(int) * DAMAR_FC_COUNT * np, hipMemcpyDeviceToHost, G_st));
-      FL.mark(3);
-      HIP_CHECK(hipStreamSynchronize(G_st));
-      FL.laps(0, 3);
-    }
-  /* what the kernel left (all piles with DAMAR_PILES=host) is the plain routine's */
-  for (size_t q = 0; q < np; q++)
-    if (status[q] != 0)
-      { damar_host_filter_pile(t, diffs, (int64) q, p, out);
-        fallback += host ? 0 : 1;
-      }
-  for (size_t i = 0; i < nrec; i++)
-    gone += (out->flags[i] & 0x2) != 0;
-  FL.cnt[0] = b->npiles;  FL.cnt[1] = fallback;  FL.cnt[2] = gone;
-  FL.ms[3] = now_ms() - w0;
-  return 0;
-}
-
-/***** LAfix's breaks and weak segments per pile: scrub/LAfix.c fix_process (kernels/pile_patch.hip) **********************/
-
-static struct : PileStage       /* ms of the last call: upload, kernel, download (HIP events), whole call (wall);
-                                   cnt: piles, piles the host routine did beside the kernel, repairs */
-{ DBuf trim{*this}, rlen{*this}, qanno{*this}, qdata{*this}, ranno{*this}, rdata{*this}, skip{*this}, slot{*this}, gaps{*this}, status{*this},
-       ngaps{*this};
-} FX;
-
-extern "C" void damar_fix_release(void) { FX.release(); }
-
-extern "C" void damar_fix_limits(int *segs, int *cands)
-{ *segs = DAMAR_FIX_MAXSEGS;
-  *cands = DAMAR_FIX_MAXCAND;
-}
-
-extern "C" void damar_fix_last(double *ms, int64 *cnt) { FX.last(ms, cnt, 3); }
-
-extern "C" int damar_pile_patches(const damar_trace_batch *t, const damar_fix_params *p, const int *trim, damar_fix_gaps *out)
-{ const double w0 = now_ms();
-  if (out == NULL || !damar_fix_inputs_valid(t, p, trim) || (t->p.npiles > 0 && out->count == NULL))
-    return 1;
-  static_assert(sizeof(damar_fix_gap) == 8 * sizeof(int), "the kernel writes a repair as eight ints");
-  const damar_pile_batch *b = &t->p;
-  const size_t np = (size_t) b->npiles, nrec = (size_t) b->nrec;
-  const bool host = damar_piles_on_host() != 0;
-  const int tw = t->tspace;
-  damar_fix_list L = { NULL, 0, 0 };
-  int64 fallback = 0;
-  for (int i = 0; i < 4; i++) FX.ms[i] = 0;
-
-  std::vector<u8>  skip(np + 1, 0);
-  std::vector<int> status(np + 1, 1), ngaps(np + 1, 0);
-  std::vector<long long> slot(np + 1, 0);
-  std::vector<damar_fix_gap> got;
-  if (!host && np > 0)
-    { /* per pile: whether its B reads ascend (a pile where they do not is the host routine's), and the room its repairs
-         need at the most -- a repair is a pair of neighbouring records of one B read or a bad segment inside the trim */
-      for (size_t q = 0; q < np; q++)
-        { const int aread = b->pile_aread[q], tb = trim[2 * q], te = trim[2 * q + 1];
-          long long room = 0;
-          if (tb < te)
-            { for (int64 i = b->pile_off[q] + 1; i < b->pile_off[q + 1]; i++)
-                { if (b->bread[i] < b->bread[i - 1])
-                    skip[q] = 1;
-                  if (b->bread[i] == b->bread[i - 1] && b->aepos[i - 1] < b->abpos[i])
-                    room += 1;
-                }
-              const int64 qa = (int64) (p->q_anno[aread] / 4);
-              for (int s = tb / tw; s < te / tw; s++)
-                { const int v = (qa + s < p->q_ndata) ? p->q_data[qa + s] : 0;
-                  room += (v == 0 || v >= p->lowq) ? 1 : 0;
-                }
-              if (room > DAMAR_FIX_MAXREP)
-                room = DAMAR_FIX_MAXREP;
-            }
-          slot[q + 1] = slot[q] + room;
-        }
-      const size_t nslot = (size_t) slot[np];
-      ensure_init();
-      late_streams();                /* a tool built on this call is through soon after the library comes up: see box_scripts */
-      FixArgs a;
-      memset(&a, 0, sizeof(a));
-      a.npiles = (u32) np;
-      a.maxsegs = test_limit("DAMAR_TEST_FIX_SEGS", DAMAR_FIX_MAXSEGS, INT_MIN);
-      a.tspace = tw;  a.tbytes = t->tbytes;
-      a.lowq = p->lowq;  a.maxgap = p->maxgap;  a.maxspanners = p->maxspanners;  a.minsupport = p->minsupport;
-      a.q_ndata = p->q_ndata;
-      const size_t nreads = (size_t) b->nreads;
-      int *d_gaps = (int *) FX.gaps.need(sizeof(damar_fix_gap) * nslot + 16);
-      int *d_status = (int *) FX.status.need(sizeof(int) * np + 16), *d_ngaps = (int *) FX.ngaps.need(sizeof(int) * np + 16);
-      FX.mark(0);
-      if (p->rep_anno != NULL)
-        { const DevTrack rep = up_track(FX.ranno, FX.rdata, p->rep_anno, nreads, p->rep_data, p->rep_ndata);
-          a.rep_anno = rep.anno;  a.rep_data = rep.data;
-        }
-      a.trim = up(FX.trim, trim, 2 * np);
-      a.skip = up(FX.skip, skip.data(), np);
-      a.slot_off = up(FX.slot, slot.data(), np + 1);
-      const PileDev d = pile_up(FX, b, t, { b->abpos, b->aepos, b->bbpos, b->bepos, b->bread, b->flags, t->tlen });
-      a.read_len = up(FX.rlen, b->read_len, nreads);
-      const DevTrack q = up_track(FX.qanno, FX.qdata, p->q_anno, nreads, p->q_data, p->q_ndata);
-      HIP_CHECK(hipMemsetAsync(d_ngaps, 0, sizeof(int) * np, G_st));
-      FX.mark(1);
-      a.pile_off = d.off;  a.pile_aread = d.aread;
-      a.abpos = d.col[0];  a.aepos = d.col[1];  a.bbpos = d.col[2];  a.bepos = d.col[3];  a.bread = d.col[4];  a.flags = d.col[5];
-      a.tlen = d.col[6];  a.trace_off = d.toff;  a.trace = d.trace;
-      a.q_anno = q.anno;  a.q_data = q.data;
-      a.gaps = d_gaps;  a.status = d_status;  a.ngaps = d_ngaps;
-      damar_launch_pile_patch(&a, G_st);
-      HIP_CHECK(hipGetLastError());
-      FX.mark(2);
-      got.resize(nslot + 1);
-      HIP_CHECK(hipMemcpyAsync(status.data(), d_status, sizeof(int) * np, hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipMemcpyAsync(ngaps.data(), d_ngaps, sizeof(int) * np, hipMemcpyDeviceToHost, G_st));
-      if (nslot > 0)
-        HIP_CHECK(hipMemcpyAsync(got.data(), d_gaps, sizeof(damar_fix_gap) * nslot, hipMemcpyDeviceToHost, G_st));
-      FX.mark(3);
-      HIP_CHECK(hipStreamSynchronize(G_st));
-      FX.laps(0, 3);
-    }
-  /* the repairs in pile order; what the kernel left (all piles with DAMAR_PILES=host) is the plain routine's */
-  for (size_t q = 0; q < np; q++)
-    { const int64 before = L.n;
-      if (status[q] != 0)
-        { damar_host_fix_pile(t, (int64) q, p, trim[2 * q], trim[2 * q + 1], &L);
-          fallback += (host || trim[2 * q] >= trim[2 * q + 1]) ? 0 : 1;
-        }
-      else
-        { if (ngaps[q] < 0 || ngaps[q] > slot[q + 1] - slot[q])
-            { fprintf(stderr, "damar: fix: pile %zu came back with %d repairs\n", q, ngaps[q]);
-              free(L.g);
-              return 1;
-            }
-          if (list_append(&L.g, &L.n, &L.cap, 1, got.data() + slot[q], ngaps[q], "fix"))
-            return 1;
-        }
-      out->count[q] = (int) (L.n - before);
-    }
-  if (L.g == NULL && (L.g = (damar_fix_gap *) malloc(sizeof(damar_fix_gap))) == NULL)       /* no repair: still the caller's to free */
-    { fprintf(stderr, "damar: out of memory (fix)\n");
-      return 1;
-    }
-  out->gaps = L.g;
-  out->ngaps = L.n;
-  FX.cnt[0] = b->npiles;  FX.cnt[1] = fallback;  FX.cnt[2] = L.n;
-  FX.ms[3] = now_ms() - w0;
-  return 0;
-}
-
-/***** LAcorrect's consensus per tile: corrector/consensus.c (kernels/tile_consensus.hip) ************************************/
-
-#define TCN_MAXLANES 32768u    /* stripes of the work area: 512 wavefronts */
-#define TCN_CHUNK    131072u   /* tasks per launch: bounds the staging of the called bases */
-
-static struct : DevStage        /* ms of the last call: upload, kernel, download (HIP events), whole call (wall);
-                                   cnt: tiles, tiles the host routine did beside the kernel, bases called */
-{ DBuf order{*this}, eoff{*this}, soff{*this}, slen{*this}, bases{*this}, work{*this}, out{*this}, status{*this}, len{*this};
-} TCN;
-
-extern "C" void damar_correct_release(void) { TCN.release(); }
-
-extern "C" void damar_correct_limits(int *seg, int *cols, int *cells)
-{ *seg = DAMAR_CORRECT_MAXSEG;
-  *cols = DAMAR_CORRECT_MAXCOLS;
-  *cells = DAMAR_CORRECT_CELLS;
-}
-
-extern "C" void damar_correct_last(double *ms, int64 *cnt) { TCN.last(ms, cnt, 3); }
-
-extern "C" int damar_tile_consensus(const damar_tile_batch *b, int64 *cons_off, unsigned char **cons, int *added)
-{ const double w0 = now_ms();
-  if (cons_off == NULL || cons == NULL || !damar_tile_batch_valid(b) || (b->ntiles > 0 && added == NULL))
-    return 1;
-  static_assert(sizeof(int64) == sizeof(long long), "offsets go to the device as they are");
-  const size_t nt = (size_t) b->ntiles;
-  const bool host = damar_piles_on_host() != 0;
-  int64 fallback = 0;
-  for (int i = 0; i < 4; i++) TCN.ms[i] = 0;
-  for (int i = 0; i < 3; i++) TCN.cnt[i] = 0;       /* a call that fails leaves zeros, not a mixture */
-  if (nt >= ((size_t) 1 << 31))
-    { fprintf(stderr, "damar: correct: %zu tiles in one call (below 2^31 are taken)\n", nt);
-      return 1;
-    }
-
-  /* per tile: where its result lies among the device's (-1: the host routine does it, -2: empty) */
-  std::vector<long long> task_of(nt + 1, -1), comp_off;
-  std::vector<u32> order;
-  std::vector<u8>  compact;
-  for (size_t t = 0; t < nt; t++)
-    { const int64 e0 = b->ent_off[t], e1 = b->ent_off[t + 1];
-      added[t] = (int) (e1 - e0);
-      if (e1 == e0)
-        { task_of[t] = -2;
-          continue;
-        }
-      if (host)
-        continue;
-      bool fits = true;
-      for (int64 e = e0; e < e1; e++)
-        fits = fits && b->seq_len[e] <= DAMAR_CORRECT_MAXSEG;
-      if (fits)
-        order.push_back((u32) t);
-    }
-  if (!order.empty())
-    { const int maxcols = test_limit("DAMAR_TEST_CORRECT_COLS", DAMAR_CORRECT_MAXCOLS, 2) & ~1;
-      auto weight = [&](u32 t) -> long long
-        { if (b->weight != NULL) return b->weight[t];
-          const int64 e0 = b->ent_off[t], e1 = b->ent_off[t + 1];
-          return (long long) (e1 - e0) * (long long) (b->seq_off[e1 - 1] + b->seq_len[e1 - 1] - b->seq_off[e0]);
-        };
-      std::stable_sort(order.begin(), order.end(), [&](u32 x, u32 y) { return weight(x) > weight(y); });
-      const size_t ntask = order.size(), nent = (size_t) b->ent_off[nt];
-      ensure_init();
-      late_streams();
-      TileArgs a;
-      memset(&a, 0, sizeof(a));
-      a.maxcols = maxcols;
-      a.maxscript = maxcols + DAMAR_CORRECT_MAXSEG;
-      a.cells = DAMAR_CORRECT_CELLS;
-      a.stripe = ((size_t) 6 * maxcols + 2 * (size_t) a.maxscript + 3 * (size_t) a.cells + 15) & ~(size_t) 15;
-      const u32 lanes = (u32) std::min<size_t>((ntask + 63) / 64 * 64, TCN_MAXLANES);
-      a.blocks = lanes / 64;
-      const size_t chunk = std::min<size_t>(ntask, TCN_CHUNK);
-      u8  *d_out = (u8 *) TCN.out.need(chunk * (size_t) maxcols);
-      int *d_status = (int *) TCN.status.need(sizeof(int) * chunk), *d_len = (int *) TCN.len.need(sizeof(int) * chunk);
-      a.work = (u8 *) TCN.work.need((size_t) lanes * a.stripe);
-      TCN.mark(0);
-      a.ent_off = (const long long *) up(TCN.eoff, b->ent_off, nt + 1);
-      a.seq_off = (const long long *) up(TCN.soff, b->seq_off, nent);
-      a.seq_len = up(TCN.slen, b->seq_len, nent);
-      a.bases = up(TCN.bases, b->bases, (size_t) b->nbases);
-      const u32 *d_order = up(TCN.order, order.data(), ntask);
-      TCN.mark(1);
-      HIP_CHECK(hipStreamSynchronize(G_st));
-      TCN.laps(0, 1);
-      a.out = d_out;  a.status = d_status;  a.len = d_len;
-      std::vector<int> status(chunk), len(chunk);
-      std::vector<u8>  got(chunk * (size_t) maxcols);
-      comp_off.assign(ntask + 1, 0);
-      for (size_t c0 = 0; c0 < ntask; c0 += chunk)
-        { const size_t n = std::min(chunk, ntask - c0);
-          a.ntasks = (u32) n;
-          a.order = d_order + c0;
-          TCN.mark(1);
-          damar_launch_tile_consensus(&a, G_st);
-          HIP_CHECK(hipGetLastError());
-          TCN.mark(2);
-          HIP_CHECK(hipMemcpyAsync(status.data(), d_status, sizeof(int) * n, hipMemcpyDeviceToHost, G_st));
-          HIP_CHECK(hipMemcpyAsync(len.data(), d_len, sizeof(int) * n, hipMemcpyDeviceToHost, G_st));
-          HIP_CHECK(hipMemcpyAsync(got.data(), d_out, n * (size_t) maxcols, hipMemcpyDeviceToHost, G_st));
-          TCN.mark(3);
-          HIP_CHECK(hipStreamSynchronize(G_st));
-          TCN.laps_add(1, 2);
-          for (size_t i = 0; i < n; i++)
-            { const size_t it = c0 + i;
-              comp_off[it + 1] = comp_off[it];
-              if (status[i] != 0)
-                continue;
-              if (len[i] < 0 || len[i] > maxcols)
-                { fprintf(stderr, "damar: correct: tile %u came back with %d bases\n", order[it], len[i]);
-                  for (int k = 0; k < 4; k++) TCN.ms[k] = 0;
-                  return 1;
-                }
-              task_of[order[it]] = (long long) it;
-              compact.insert(compact.end(), got.begin() + i * (size_t) maxcols, got.begin() + i * (size_t) maxcols + len[i]);
-              comp_off[it + 1] += len[i];
-            }
-        }
-    }
-
-  /* the calls in tile order; what the kernel left (all tiles with DAMAR_PILES=host) is the plain routine's */
-  unsigned char *all = NULL, *one = NULL;
-  int64 cap = 0, n = 0, onecap = 0;
-  for (size_t t = 0; t < nt; t++)
-    { const unsigned char *src = NULL;
-      int64 len = 0;
-      cons_off[t] = n;
-      if (task_of[t] >= 0)
-        { len = comp_off[task_of[t] + 1] - comp_off[task_of[t]];
-          src = compact.data() + comp_off[task_of[t]];
-        }
-      else if (task_of[t] == -1)
-        { const int got = damar_host_tile(b, (int64) t, &one, &onecap);
-          if (got < 0)
-            { free(all);  free(one);
-              return 1;
-            }
-          len = got;
-          src = one;
-          fallback += host ? 0 : 1;
-        }
-      if (n + len > cap)
-        { cap = n + len + cap / 4 + 4096;
-          unsigned char *grown = (unsigned char *) realloc(all, (size_t) cap);
-          if (grown == NULL)
-            { fprintf(stderr, "damar: out of memory (correct)\n");
-              free(all);  free(one);
-              return 1;
-            }
-          all = grown;
-        }
-      if (len > 0)
-        memcpy(all + n, src, (size_t) len);
-      n += len;
-    }
-  cons_off[nt] = n;
-  free(one);
-  if (all == NULL && (all = (unsigned char *) malloc(1)) == NULL)
-    { fprintf(stderr, "damar: out of memory (correct)\n");
-      return 1;
-    }
-  *cons = all;
-  TCN.cnt[0] = b->ntiles;  TCN.cnt[1] = fallback;  TCN.cnt[2] = n;
-  TCN.ms[3] = now_ms() - w0;
-  return 0;
-}
-
-/***** DBdust's low-complexity mask of reads: db/DBdust.c (kernels/dust.hip) **********************************************/
-
-static struct : DevStage        /* ms of the last call: upload, kernels, download (HIP events), whole call (wall);
-                                   cnt: reads, reads the host routine did beside the kernel, intervals written */
-{ DBuf bases{*this}, roff{*this}, pread{*this}, pfirst{*this}, rpiece{*this}, cand{*this}, ncand{*this}, nint{*this},
-       steps{*this}, ooff{*this}, out{*this};
-  int64 stepped[2] = { 0, 0 };
-} DU;
-
-extern "C" void damar_dust_release(void) { DU.release(); }
-
-extern "C" void damar_dust_limits(int *piece, int *halo, int *stripe, int *window)
-{ *piece = DAMAR_DUST_PIECE;
-  *halo = DAMAR_DUST_HALO;
-  *stripe = DAMAR_DUST_STRIPE;
-  *window = DAMAR_DUST_MAXWINDOW;
-}
-
-extern "C" void damar_dust_last(double *ms, int64 *cnt) { DU.last(ms, cnt, 3); }
-
-extern "C" void damar_dust_steps(int64 *steps) { steps[0] = DU.stepped[0];  steps[1] = DU.stepped[1]; }
-
-extern "C" int damar_dust_reads(const unsigned char *bases, const int64 *read_off, int64 nreads, const damar_dust_params *p,
-                                int64 *out_off, int **out)
-{ const double w0 = now_ms();
-  if (!damar_dust_params_valid(p) || nreads < 0 || out_off == NULL || out == NULL || (nreads > 0 && (bases == NULL || read_off == NULL)))
-    return 1;
-  const size_t nr = (size_t) nreads;
-  for (size_t i = 0; i < nr; i++)
-    if (read_off[i + 1] < read_off[i] || read_off[i + 1] - read_off[i] > INT_MAX - 8)
-      { fprintf(stderr, "damar: dust: read %zu has no length\n", i);
-        return 1;
-      }
-  for (int i = 0; i < 4; i++) DU.ms[i] = 0;
-  DU.stepped[0] = DU.stepped[1] = 0;
-  *out = NULL;
-
-  /* what the kernel does not do: the doubles of -b, a window its lanes do not hold */
-  const bool host = damar_dust_on_host() != 0;
-  const bool device = !host && !p->biased && p->window >= 3 && p->window <= DAMAR_DUST_MAXWINDOW && nr > 0;
-  std::vector<int> nint(nr + 1, -1), dev_iv;
-  std::vector<u32> rpiece(nr + 1, 0);
-  int64 fallback = 0;
-  if (device)
-    { std::vector<u32> pread;
-      std::vector<int> pfirst;
-      for (size_t i = 0; i < nr; i++)
-        { const int ntri = (int) (read_off[i + 1] - read_off[i]) - 2;
-          rpiece[i] = (u32) pread.size();
-          for (int a = 0; a < ntri; a += DAMAR_DUST_PIECE)
-            { pread.push_back((u32) i);
-              pfirst.push_back(a);
-            }
-        }
-      rpiece[nr] = (u32) pread.size();
-      const size_t np = pread.size();
-      ensure_init();
-      late_streams();                /* a tool built on this call is through soon after the library comes up: see box_scripts */
-      DustArgs a;
-      memset(&a, 0, sizeof(a));
-      a.npieces = (u32) np;  a.nreads = (u32) nr;
-      a.window = p->window;  a.thresh = p->thresh;  a.thresh2i = (int) ceil(2. * p->thresh);  a.minlen = p->minlen;
-      a.stripe = test_limit("DAMAR_TEST_DUST_STRIPE", DAMAR_DUST_STRIPE, 1);
-      a.cand = (int *) DU.cand.need(sizeof(int) * 2 * (size_t) a.stripe * np + 16);
-      a.ncand = (int *) DU.ncand.need(sizeof(int) * np + 16);
-      a.nint = (int *) DU.nint.need(sizeof(int) * nr + 16);
-      a.steps = (u64 *) DU.steps.need(sizeof(u64) * 2);
-      DU.mark(0);
-      a.bases = up(DU.bases, bases, (size_t) read_off[nr]);
-      a.read_off = (const long long *) up(DU.roff, read_off, nr + 1);
-      a.piece_read = up(DU.pread, pread.data(), np);
-      a.piece_first = up(DU.pfirst, pfirst.data(), np);
-      a.read_piece = up(DU.rpiece, rpiece.data(), nr + 1);
-      HIP_CHECK(hipMemsetAsync(a.steps, 0, sizeof(u64) * 2, G_st));
-      DU.mark(1);
-      damar_launch_dust_pieces(&a, G_st);
-      HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipMemcpyAsync(nint.data(), a.nint, sizeof(int) * nr, hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipStreamSynchronize(G_st));
-      /* where the kernel's reads lie among themselves; the host's reads are put between them below */
-      std::vector<long long> doff(nr + 1, 0);
-      for (size_t i = 0; i < nr; i++)
-        { if (nint[i] > (int) (rpiece[i + 1] - rpiece[i]) * a.stripe)
-            { fprintf(stderr, "damar: dust: read %zu came back with %d intervals\n", i, nint[i]);
-              return 1;
-            }
-          doff[i + 1] = doff[i] + (nint[i] > 0 ? 2 * (long long) nint[i] : 0);
-        }
-      a.out_off = up(DU.ooff, doff.data(), nr);
-      a.out = (int *) DU.out.need(sizeof(int) * (size_t) doff[nr] + 16);
-      damar_launch_dust_gather(&a, G_st);
-      HIP_CHECK(hipGetLastError());
-      DU.mark(2);
-      dev_iv.resize((size_t) doff[nr] + 1);
-      u64 st[2] = { 0, 0 };
-      if (doff[nr] > 0)
-        HIP_CHECK(hipMemcpyAsync(dev_iv.data(), a.out, sizeof(int) * (size_t) doff[nr], hipMemcpyDeviceToHost, G_st));
-      HIP_CHECK(hipMemcpyAsync(st, a.steps, sizeof(st), hipMemcpyDeviceToHost, G_st));
-      DU.mark(3);
-      HIP_CHECK(hipStreamSynchronize(G_st));
-      DU.laps(0, 3);
-      DU.stepped[0] = (int64) st[0];  DU.stepped[1] = (int64) st[1];
-    }
-
-  /* the reads in order; what the kernel left (all reads with DAMAR_DUST=host) is the plain routine's */
-  int64 n = 0, cap = 0, got = 0;
-  int  *all = NULL;
-  damar_dust_list work = { NULL, 0, 0 };
-  for (size_t i = 0; i < nr; i++)
-    { const int len = (int) (read_off[i + 1] - read_off[i]);
-      const int64 need = nint[i] >= 0 ? 2 * (int64) nint[i] : 2 * (int64) len;
-      out_off[i] = n;
-      if (damar_room(&cap, n + need, 4096))
-        all = (int *) damar_grow(all, sizeof(int) * (size_t) cap, "dust intervals");
-      if (nint[i] >= 0)
-        { if (need > 0)
-            memcpy(all + n, dev_iv.data() + got, sizeof(int) * (size_t) need);
-          got += need;
-          n += need;
-        }
-      else
-        { n += 2 * damar_host_dust_read(bases + read_off[i], len, p, 0, 0, all + n, &work, DU.stepped);
-          fallback += host ? 0 : 1;
-        }
-    }
-  out_off[nr] = n;
-  free(work.iv);
-  if (all == NULL)
-    all = (int *) damar_grow(NULL, sizeof(int), "dust intervals");      /* no interval: still the caller's to free */
-  *out = all;
-  DU.cnt[0] = nreads;  DU.cnt[1] = fallback;  DU.cnt[2] = n / 2;
-  DU.ms[3] = now_ms() - w0;
-  return 0;
 }

@@ -1,5 +1,5 @@
 """What damar_align_boxes, damar_align_reads and damar_trace_boxes refuse before any box is aligned, without a GPU: the three
-entry points check a batch with one routine of the shim (damar_amd/csrc/shim.hip, box_batch_valid), and the lines it writes
+entry points check a batch with one routine of the shim (damar_amd/csrc/stages/boxes.hip, box_batch_valid), and the lines it writes
 to stderr are held here word for word.  Every call is on the host route, so nothing reaches a device."""
 import ctypes as C
 

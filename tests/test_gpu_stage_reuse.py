@@ -1,4 +1,4 @@
-"""The stage record of the shim (damar_amd/csrc/shim.hip, struct DevStage) under release and reuse: every call family is
+"""The stage record of the shim (damar_amd/csrc/stage.h, struct DevStage) under release and reuse: every call family is
 called on the first two piles (boxes, tiles) of its smallest input, released, and called on the whole input, so that every
 buffer grows from nothing and the events are made anew.  The result must be the host routine's, the counters of
 damar_*_last those of a call on a fresh stage, and every device phase must have taken time."""
