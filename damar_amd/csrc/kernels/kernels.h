@@ -3,6 +3,7 @@
 #define DAMAR_KERNELS_H
 
 #include "dev_common.h"
+#include "../la_record.h"
 
 /* sort_scan.hip */
 size_t damar_scan_workspace_bytes(u64 n);
@@ -272,13 +273,7 @@ __device__ __forceinline__ int seed_diag(u64 k, const u32 *__restrict__ vals, u6
 #endif
 
 /* report.hip */
-typedef struct
-{ int abpos, bbpos, aepos, bepos, diffs;
-  int atlen, btlen;
-  int aread, bread;       /* block-local ids */
-  u32 item, seq;          /* work item and order of discovery inside it */
-  u32 toff;               /* offset of the A trace in the trace pool; B trace follows */
-} LaRecord;
+/* LaRecord, DAMAR_MAX_JOBS, DAMAR_ITEM_WIDE, DAMAR_SEQ_BITS: la_record.h */
 
 typedef struct
 { /* inputs */
@@ -320,7 +315,6 @@ typedef struct
    wave-uniform reads of a job's fields are scalar loads).  Every wavefront starts with job (block index mod njobs) and
    moves on to the next when a job's queue is empty, so the long alignments of ALL jobs start at once and the tail of
    the launch (waiting for the longest alignment) is paid once per launch, not once per comparison. */
-#define DAMAR_MAX_JOBS 32
 #define DAMAR_MAX_TSPACE 8192     /* consecutive pebbles of a chain then differ by < 2^15 diagonals and < 2^16 waves */
 #define DAMAR_CNT_RECS      1     /* counters[1]: records written (asked for, when DAMAR_ERR_RECS is up) */
 #define DAMAR_CNT_TPOOL     2     /* counters[2]: trace values written (asked for, when DAMAR_ERR_TPOOL is up) */
@@ -330,11 +324,9 @@ typedef struct
 #define DAMAR_CNT_HALFSTEPS 10    /* counters[10..11] (64 bits): wave steps, counted per half-wavefront (= per alignment pass)   */
 #define DAMAR_CNT_ITERS     12    /* counters[12..13] (64 bits): iterations of the wave loop (each steps one or two halves)      */
 #define DAMAR_CNT_WIDE    14      /* counters[14]: read pairs left to the wide kernel (report_wide_kernel) */
-#define DAMAR_ITEM_WIDE   0x80000000u   /* in LaRecord.item: written by the wide kernel */
 #define DAMAR_CNT_CURSOR  16      /* counters[16 + job]: next work item of a job  */
 #define DAMAR_CNT_NFILT   (DAMAR_CNT_CURSOR + DAMAR_MAX_JOBS)      /* counters[.. + job]: its seed hits */
 #define DAMAR_COUNTER_WORDS (DAMAR_CNT_NFILT + DAMAR_MAX_JOBS)
-#define DAMAR_SEQ_BITS 24
 
 #define DAMAR_ERR_CELLS   1u
 #define DAMAR_ERR_RECS    2u

@@ -7,7 +7,7 @@
  *
  * Everything compute-heavy is a HIP kernel (kernels/ *.hip); this file owns device
  * memory, orders the launches on one stream, copies the alignment records back and
- * runs the per-read-pair host tail (host/redundancy.c -> host/las.c).  There is no CPU
+ * hands them to the per-read-pair host tail (host/tail.cpp -> host/redundancy.c -> host/las.c).  There is no CPU
  * fallback: without a HIP device every entry point fails loudly.
  */
 #include <algorithm>
@@ -35,14 +35,6 @@ extern "C" {
 #include "shim_internal.h"     /* what of this file the tool stages (stages/ *.hip) share */
 
 #define MAXGRAM 10000          /* filter.c:71 */
-
-/* Fatal errors end the process like the reference's exit(1) (db/DB.h:84-86), but without
- * running atexit handlers: tearing the HIP runtime down from inside a failed call can hang
- * when the library is embedded (ctypes). */
-static void die(void)
-{ fflush(NULL);
-  _exit(1);
-}
 
 /***** globals shared with the caller (filter.h:54-62 / daligner.c:131-140) *****************/
 
@@ -524,54 +516,17 @@ extern "C" damar_dev_block *damar_block_upload_bg(const HITS_DB *block)
  * reverse complement (comp 1) is unpacked on the device, on the preload stream like damar_block_upload_bg.  The host
  * tail needs the bases of a read pair only where two local alignments have to be bridged by a realignment (filter.c:1950
  * -2059, a few pairs in a thousand): it unpacks those reads out of the registered stretch (host_read). */
-static std::mutex PK_mu;
-static std::vector<std::pair<const HITS_READ *, const damar_packed *>> PK_reg;      /* by the read table: the tail works on COPIES of
-                                                                                       the block records, and a block shares its
-                                                                                       read table with its complement */
-
 extern "C" damar_dev_block *damar_block_upload_packed(const HITS_DB *block, const damar_packed *pk, int comp)
 { ensure_init();
   HIP_CHECK(hipSetDevice(G_device));          /* the current device is a per-thread setting */
   (void) preload_stream();
-  { std::lock_guard<std::mutex> lk(PK_mu);
-    bool have = false;
-    for (auto &e : PK_reg)
-      if (e.first == block->reads)
-        { e.second = pk;  have = true; }
-    if (!have)
-      PK_reg.push_back(std::make_pair((const HITS_READ *) block->reads, pk));
-  }
+  packed_register(block->reads, pk);
   return block_upload_on(block, PL_st, pk, comp);
 }
 
 /* the block is about to be closed: the tail must have drained (damar_async_drain) */
 extern "C" void damar_packed_forget(const HITS_DB *block)
-{ std::lock_guard<std::mutex> lk(PK_mu);
-  for (size_t i = 0; i < PK_reg.size(); i++)
-    if (PK_reg[i].first == block->reads)
-      { PK_reg.erase(PK_reg.begin() + i);
-        break;
-      }
-}
-
-/* read r of a host block, one byte per base with a 4 on either side: straight out of an unpacked block, or unpacked
-   into buf out of a packed one (comp: the record is the block's reverse complement) */
-static const char *host_read(const HITS_DB *block, int r, int comp, std::vector<char> &buf)
-{ if (block->bases != NULL)
-    return (const char *) block->bases + block->reads[r].boff;
-  const damar_packed *pk = NULL;
-  { std::lock_guard<std::mutex> lk(PK_mu);
-    for (auto &e : PK_reg)
-      if (e.first == block->reads)
-        pk = e.second;
-  }
-  if (pk == NULL)
-    { fprintf(stderr, "damar: internal error, a block without bases that was never uploaded packed\n");
-      die();
-    }
-  buf.resize((size_t) block->reads[r].rlen + 2);
-  damar_unpack_read(pk, block, r, comp, buf.data() + 1);
-  return buf.data() + 1;
+{ packed_forget(block->reads);
 }
 
 static damar_dev_block *take_preloaded(const HITS_DB *block)
@@ -1330,33 +1285,22 @@ static bool use_packed(const ReportArgs *ra, int amax, int bmax)
   return true;
 }
 
-/***** host tail (filter.c:2442-2483 per read pair) and its optional worker thread *********************/
+/***** the landing buffers of the host tail (host/tail.cpp) and the asynchronous mode's thin callers *******/
 
-struct RecOrder
+struct RecOrder                                /* (damar_local_alignment_batch_opts lays its traces out in this order) */
 { bool operator()(const LaRecord &x, const LaRecord &y) const
   { return (x.item != y.item) ? (x.item < y.item) : (x.seq < y.seq); }
 };
-
-double now_ms(void)
-{ struct timespec t;
-  clock_gettime(CLOCK_MONOTONIC, &t);
-  return t.tv_sec * 1e3 + t.tv_nsec * 1e-6;
-}
 
 /* Page-locked landing buffers for the records and trace points of one report launch, recycled
  * through a small pool: the download runs at PCIe speed and nothing is allocated or touched
  * for the first time inside the timed loop. */
 static bool   A_on = false;                   /* the asynchronous host pipeline is running (damar_set_async) */
-struct HostBuf
-{ LaRecord *recs;   size_t rec_cap;
-  u16      *tpool;  size_t tp_cap;
-  size_t    nrec, ntp;
+/* what the tail reads of a buffer is the plain part (host/tail.h); the rest is how it gets there */
+struct HostBuf : damar_tail_buf
+{ size_t rec_cap, tp_cap, wmap_cap;
   hipEvent_t e0, e1;               /* around the download; e1 is what the tail thread waits for */
   bool      pending;
-  int       t8;                    /* the trace values are bytes (the launch compressed them: ReportArgs.t8) */
-  u32      *wmap;  size_t wmap_cap;  /* nwide > 0: the jobs' bit maps of the read pairs the wide kernel took over (job j from wm_off[j]) */
-  u32       nwide, wm_off[DAMAR_MAX_JOBS + 1];
-  int       users;                 /* comparisons of the launch whose tails have not run yet */
 };
 static std::mutex             &HB_mu   = *new std::mutex();
 static std::vector<HostBuf *> &HB_free = *new std::vector<HostBuf *>();
@@ -1381,15 +1325,34 @@ static void hostbuf_size(HostBuf *h, size_t nrec, size_t ntp, bool generous)
 }
 
 static std::thread *HB_twin = NULL;           /* allocates the second landing buffer (hostbuf_get); joined by helpers_join() */
+static void hostbuf_put(HostBuf *h)
+{ std::lock_guard<std::mutex> lk(HB_mu);
+  HB_free.push_back(h);
+}
+
+/* the pipeline's two ways back (host/tail.h): the tail thread waits for the download, the last tail returns the buffer */
+static double hostbuf_landed(damar_tail_buf *b)
+{ HostBuf *h = static_cast<HostBuf *>(b);
+  float ms = 0;
+  if (h->pending)
+    { HIP_CHECK(hipSetDevice(G_device));          /* the current device is a per-thread setting */
+      HIP_CHECK(hipEventSynchronize(h->e1));
+      HIP_CHECK(hipEventElapsedTime(&ms, h->e0, h->e1));
+      h->pending = false;                         /* (the other comparisons of the launch share the buffer) */
+    }
+  return ms;
+}
+static void hostbuf_release(damar_tail_buf *b) { hostbuf_put(static_cast<HostBuf *>(b)); }
+
 static HostBuf *hostbuf_new(void)
 { HostBuf *h = new HostBuf();
   memset(h, 0, sizeof(*h));
   HIP_CHECK(hipEventCreate(&h->e0));
   HIP_CHECK(hipEventCreate(&h->e1));
+  h->landed = hostbuf_landed;  h->release = hostbuf_release;
   return h;
 }
 
-static void tail_pool_join(void);
 static void helpers_join(void)
 { late_streams();
   tail_pool_join();
@@ -1436,470 +1399,25 @@ static HostBuf *hostbuf_get(size_t nrec, size_t ntp)
   return h;
 }
 
-static void hostbuf_put(HostBuf *h)
-{ std::lock_guard<std::mutex> lk(HB_mu);
-  HB_free.push_back(h);
-}
-
-/* byte trace values of the device (ReportArgs.t8) into the 16-bit pool the redundancy handling works on */
-static int64 tpool_push8(damar_tpool *tp, const u8 *src, int n)
-{ static thread_local std::vector<uint16> wide;
-  wide.resize((size_t) n);
-  for (int i = 0; i < n; i++)
-    wide[i] = src[i];
-  return damar_tpool_push(tp, wide.data(), n);
-}
-
-/* One contiguous range [lo, hi) of the ordered records (whole read pairs): filter.c:2442-2483
- * per pair, results appended to obuf. */
-static int64 tail_range(const LaRecord *recs, const u32 *ord, const u64 *okey, size_t lo, size_t hi, const u16 *tpool, int t8,
-                        const HITS_DB *ablock, const HITS_DB *bblock, int self, int comp, int ts,
-                        Overlap_IO_Buffer *obuf, int symmetric, int hgap_min)
-{ int64 ncheck = 0;
-  std::vector<damar_path> am, bm;
-  damar_tpool tp = { NULL, 0, 0 };
-  std::vector<char> aread_buf, bread_buf;                       /* (packed host blocks: the reads of a pair that is bridged) */
-  size_t i = lo;
-  while (i < hi)
-    { size_t j = i;
-      /* the records arrive in completion order and are visited in item order: every record and every trace is a
-         cache miss in 300 MB of landing buffer unless it is asked for ahead (records 16 ahead, their traces 8 ahead) */
-      if (i + 16 < hi)
-        __builtin_prefetch(&recs[ord[i + 16]]);
-      if (i + 8 < hi)
-        { const LaRecord &pr = recs[ord[i + 8]];
-          const size_t vb = t8 ? sizeof(u8) : sizeof(u16);
-          const char *pt = (const char *) tpool + vb * (size_t) pr.toff;
-          const size_t nb = vb * (size_t) (pr.atlen + pr.btlen);
-          for (size_t o = 0; o < nb; o += 64)
-            __builtin_prefetch(pt + o);
-        }
-      while (j < hi && (okey[j] >> 32) == (okey[i] >> 32))          /* (the item sits in the key: no record is touched for this) */
-        j += 1;
-      const int ar = recs[ord[i]].aread, br = recs[ord[i]].bread;
-      const int al = ablock->reads[ar].rlen, bl = bblock->reads[br].rlen;
-      const int doA = (al >= hgap_min);
-      const int doB = (symmetric && bl >= hgap_min && (ar != br || !self || !comp));   /* filter.c:2300-2301 */
-      if (j - i == 1)
-        { /* one alignment for the pair -- the common case: nothing for Handle_Redundancies to look at, so the records
-             (filter.c:2470-2483: the A view, then the B view) are written straight from the downloaded traces, which
-             Compress_TraceTo8 may shorten in place (the landing buffer is this comparison's own) */
-          const LaRecord &r = recs[ord[i]];
-          Overlap ovl;
-          memset(&ovl, 0, sizeof(ovl));
-          ovl.flags = (uint32) comp;
-          if (doA)
-            { ovl.aread = ar + ablock->ufirst;  ovl.bread = br + bblock->ufirst;
-              ovl.path.tlen = r.atlen;  ovl.path.diffs = r.diffs;
-              ovl.path.abpos = r.abpos;  ovl.path.bbpos = r.bbpos;  ovl.path.aepos = r.aepos;  ovl.path.bepos = r.bepos;
-              /* (t8: the device has compressed the values already -- and raised DAMAR_ERR_T8 had one not fitted) */
-              ovl.path.trace = t8 ? (void *) ((const u8 *) tpool + r.toff) : (void *) (tpool + r.toff);
-              if (ts <= TRACE_XOVR && !t8)
-                Compress_TraceTo8(&ovl, 1);
-              AddOverlapToBuffer(obuf, &ovl, (ts <= TRACE_XOVR) ? 1 : 2);
-              ncheck += 1;
-            }
-          if (doB)
-            { ovl.aread = br + bblock->ufirst;  ovl.bread = ar + ablock->ufirst;
-              ovl.path.tlen = r.btlen;  ovl.path.diffs = r.diffs;
-              if (comp)                                          /* align.c:2039-2042 */
-                { ovl.path.abpos = bl - r.bepos;  ovl.path.bbpos = al - r.aepos;
-                  ovl.path.aepos = bl - r.bbpos;  ovl.path.bepos = al - r.abpos;
-                }
-              else                                               /* align.c:2059-2062 */
-                { ovl.path.abpos = r.bbpos;  ovl.path.bbpos = r.abpos;  ovl.path.aepos = r.bepos;  ovl.path.bepos = r.aepos; }
-              ovl.path.trace = t8 ? (void *) ((const u8 *) tpool + r.toff + r.atlen) : (void *) (tpool + r.toff + r.atlen);
-              if (ts <= TRACE_XOVR && !t8)
-                Compress_TraceTo8(&ovl, 1);
-              AddOverlapToBuffer(obuf, &ovl, (ts <= TRACE_XOVR) ? 1 : 2);
-              ncheck += 1;
-            }
-          i = j;
-          continue;
-        }
-      am.clear();  bm.clear();  tp.top = 0;
-      for (size_t q = i; q < j; q++)
-        { const LaRecord &r = recs[ord[q]];
-          damar_path p;
-          if (doA)
-            { p.tlen = r.atlen;  p.diffs = r.diffs;
-              p.abpos = r.abpos;  p.bbpos = r.bbpos;  p.aepos = r.aepos;  p.bepos = r.bepos;
-              p.toff = t8 ? tpool_push8(&tp, (const u8 *) tpool + r.toff, r.atlen) : damar_tpool_push(&tp, tpool + r.toff, r.atlen);
-              am.push_back(p);
-            }
-          if (doB)
-            { p.tlen = r.btlen;  p.diffs = r.diffs;
-              if (comp)                                          /* align.c:2039-2042 */
-                { p.abpos = bl - r.bepos;  p.bbpos = al - r.aepos;
-                  p.aepos = bl - r.bbpos;  p.bepos = al - r.abpos;
-                }
-              else                                               /* align.c:2059-2062 */
-                { p.abpos = r.bbpos;  p.bbpos = r.abpos;  p.aepos = r.bepos;  p.bepos = r.aepos; }
-              p.toff = t8 ? tpool_push8(&tp, (const u8 *) tpool + r.toff + r.atlen, r.btlen)
-                          : damar_tpool_push(&tp, tpool + r.toff + r.atlen, r.btlen);
-              bm.push_back(p);
-            }
-        }
-      damar_bridge_ctx bctx;
-      if (am.size() > 1 || bm.size() > 1)      /* (only Handle_Redundancies looks at the sequences) */
-        { bctx.aseq = host_read(ablock, ar, 0, aread_buf);  bctx.bseq = host_read(bblock, br, comp, bread_buf); }
-      else
-        { bctx.aseq = NULL;  bctx.bseq = NULL; }
-      bctx.alen = al;  bctx.blen = bl;
-      damar_emit_pair(am.data(), (int) am.size(), bm.data(), (int) bm.size(), &tp, comp, ts,
-                      ar + ablock->ufirst, br + bblock->ufirst, &bctx, obuf, &ncheck);
-      i = j;
-    }
-  free(tp.val);
-  damar_bridge_release();
-  return ncheck;
-}
-
-static int tail_threads(void)
-{ static int n = 0;
-  if (n == 0)
-    { const char *e = getenv("DAMAR_TAIL_THREADS");
-      n = e ? atoi(e) : 4;
-      if (n < 1) n = 1;
-      if (n > 64) n = 64;
-    }
-  return n;
-}
-
-/* The threads of the tail are kept between calls: a comparison's tail is 0.8 ms of work and four threads created and joined
-   for it were 0.15 ms of that (config 3: 306 tails).  tail_pool_run(n, fn) runs fn(0) .. fn(n - 1), fn(0) on the caller. */
-static struct TailPool
-{ std::mutex              mu, run_mu;
-  std::condition_variable cv_work, cv_done;
-  std::vector<std::thread> th;
-  const std::function<void(int)> *fn = NULL;
-  int      n = 0, left = 0;
-  uint64_t gen = 0;
-  bool     stop = false;
-} TP;
-
-static void tail_pool_worker(int w)
-{ uint64_t seen = 0;
-  for (;;)
-    { const std::function<void(int)> *fn;
-      { std::unique_lock<std::mutex> lk(TP.mu);
-        TP.cv_work.wait(lk, [&] { return TP.stop || TP.gen != seen; });
-        if (TP.stop)
-          return;
-        seen = TP.gen;
-        if (w >= TP.n)
-          continue;
-        fn = TP.fn;
-      }
-      (*fn)(w);
-      { std::lock_guard<std::mutex> lk(TP.mu);
-        if (--TP.left == 0)
-          TP.cv_done.notify_one();
-      }
-    }
-}
-
-static void tail_pool_run(int n, const std::function<void(int)> &fn)
-{ std::lock_guard<std::mutex> one(TP.run_mu);
-  { std::lock_guard<std::mutex> lk(TP.mu);
-    while ((int) TP.th.size() < n - 1)
-      { const int w = (int) TP.th.size() + 1;
-        TP.th.emplace_back(tail_pool_worker, w);
-      }
-    TP.fn = &fn;  TP.n = n;  TP.left = n - 1;  TP.gen += 1;
-  }
-  TP.cv_work.notify_all();
-  fn(0);
-  std::unique_lock<std::mutex> lk(TP.mu);
-  TP.cv_done.wait(lk, [&] { return TP.left == 0; });
-  TP.fn = NULL;  TP.n = 0;
-}
-
-static void tail_pool_join(void)
-{ { std::lock_guard<std::mutex> lk(TP.mu);
-    TP.stop = true;
-  }
-  TP.cv_work.notify_all();
-  for (auto &t : TP.th)
-    t.join();
-  TP.th.clear();
-  TP.stop = false;
-}
-
-static int64 run_tail(LaRecord *recs, size_t nrecs_all, const u16 *tpool, int t8, const u32 *wmap,
-                      const HITS_DB *ablock, const HITS_DB *bblock, int self, int comp, Align_Spec *spec,
-                      const JobParams &jp, int jobid = 0, int njobs = 1)
-{ const int ts = Trace_Spacing(spec);
-  /* (work item, sequence) order = the reference's order of read pairs and of the alignments inside one.  ONE pass over
-     the records (of a launch over several comparisons: those of this one, top byte of seq) collects 8-byte keys
-     item << 32 | seq; everything after that -- a counting sort on the item (a wave emits the records of its item in
-     sequence order; the insertion pass only guards that), the pair boundaries, the thread cuts -- works on the keys,
-     which stay in cache, instead of on 48-byte records scattered over the landing buffer */
-  const bool tprof = getenv("DAMAR_HOSTPROF") != NULL;
-  const double tp0 = tprof ? now_ms() : 0.;
-  std::vector<u64> key;
-  std::vector<u32> idx;
-  key.reserve(nrecs_all);  idx.reserve(nrecs_all);
-  u32 maxitem = 0;
-  for (size_t q = 0; q < nrecs_all; q++)
-    if (njobs <= 1 || (int) (recs[q].seq >> DAMAR_SEQ_BITS) == jobid)
-      { u32 it = recs[q].item;
-        if (it & DAMAR_ITEM_WIDE)                    /* the wide kernel's record */
-          { it &= ~DAMAR_ITEM_WIDE;
-            recs[q].item = it;
-          }
-        else if (wmap != NULL && ((wmap[it >> 5] >> (it & 31)) & 1u))
-          continue;                                   /* what the two-pair kernel wrote for a pair before it gave it up */
-        key.push_back(((u64) it << 32) | (u64) recs[q].seq);
-        idx.push_back((u32) q);
-        if (it > maxitem) maxitem = it;
-      }
-  const size_t nrecs = key.size();
-  const double tp1 = tprof ? now_ms() : 0.;
-  std::vector<u32> ord(nrecs);
-  std::vector<u64> okey(nrecs);
-  { std::vector<u32> first((size_t) maxitem + 2, 0);
-    for (size_t q = 0; q < nrecs; q++)
-      first[(size_t) (key[q] >> 32) + 1] += 1;
-    for (size_t q = 1; q < first.size(); q++)
-      first[q] += first[q - 1];
-    for (size_t q = 0; q < nrecs; q++)
-      { const u32 at = first[(size_t) (key[q] >> 32)]++;
-        ord[at] = idx[q];  okey[at] = key[q];
-      }
-    for (size_t q = 1; q < nrecs; q++)
-      { const u64 x = okey[q];
-        const u32 xi = ord[q];
-        size_t r = q;
-        while (r > 0 && okey[r - 1] > x && (okey[r - 1] >> 32) == (x >> 32))
-          { okey[r] = okey[r - 1];  ord[r] = ord[r - 1];  r -= 1; }
-        okey[r] = x;  ord[r] = xi;
-      }
-  }
-  const double tp2 = tprof ? now_ms() : 0.;
-  Overlap_IO_Buffer *obuf = OVL_IO_Buffer(spec);
-  static size_t tmin = 0;                  /* below this many records one thread does it (DAMAR_TAIL_MIN) */
-  if (tmin == 0)
-    { const char *e = getenv("DAMAR_TAIL_MIN");
-      tmin = (e && atol(e) > 0) ? (size_t) atol(e) : 8192;
-    }
-  const int nthr = (nrecs >= tmin) ? tail_threads() : 1;
-  if (nthr == 1)
-    return tail_range(recs, ord.data(), okey.data(), 0, nrecs, tpool, t8, ablock, bblock, self, comp, ts, obuf, jp.symmetric, jp.hgap_min);
-
-  /* Read pairs are independent: cut the ordered records into nthr ranges at pair boundaries,
-     let each thread fill a private buffer, append the buffers in order. */
-  std::vector<size_t> cut(nthr + 1, nrecs);
-  cut[0] = 0;
-  for (int t = 1; t < nthr; t++)
-    { size_t c = std::max(cut[t - 1], nrecs * (size_t) t / nthr);
-      while (c < nrecs && c > 0 && (okey[c] >> 32) == (okey[c - 1] >> 32))
-        c += 1;
-      cut[t] = c;
-    }
-  /* The Align_Spec holds one buffer per -j thread and the writer gathers them all and sorts (align.c:6166-6200), so tail
-     thread t appends to buffer t: no private buffer to copy over afterwards (a read pair's records stay together in one
-     buffer, which is all the sort's tie-break needs).  With fewer -j buffers than tail threads: private buffers, appended
-     in order. */
-  const bool direct = Num_Threads(spec) >= nthr;
-  std::vector<Overlap_IO_Buffer *> part(nthr, (Overlap_IO_Buffer *) NULL);
-  std::vector<int64> got(nthr, 0);
-  for (int t = 0; t < nthr; t++)
-    { if (direct)
-        part[t] = obuf + t;
-      else
-        { part[t] = CreateOverlapBuffer(4 * nthr, obuf->tbytes ? obuf->tbytes : 1, obuf->no_trace);
-          if (part[t] == NULL)
-            die();
-        }
-    }
-  tail_pool_run(nthr, [&](int t) { got[t] = tail_range(recs, ord.data(), okey.data(), cut[t], cut[t + 1], tpool, t8, ablock, bblock,
-                                                       self, comp, ts, part[t], jp.symmetric, jp.hgap_min); });
-  int64 ncheck = 0;
-  for (int t = 0; t < nthr; t++)
-    { if (!direct)
-        { if (damar_append_overlap_buffer(obuf, part[t]))
-            { fprintf(stderr, "damar: FATAL: out of memory appending overlaps\n");
-              die();
-            }
-          free(part[t]->ovls);
-          free(part[t]->trace);
-          free(part[t]);
-        }
-      ncheck += got[t];
-    }
-  if (tprof)
-    fprintf(stderr, "damar: tail of %zu records: keys %.2f ms, order %.2f ms, %d threads %.2f ms\n", nrecs, tp1 - tp0, tp2 - tp1, nthr, now_ms() - tp2);
-  return ncheck;
-}
-
-/* Asynchronous mode (damar_set_async(1)): the host side runs as a two-stage pipeline behind
- * the GPU.  Stage 1 (one thread) does the tail of each Match_Filter in submission order and,
- * for a write request, detaches the filled overlap buffers from the Align_Spec; stage 2 (a
- * second thread) sorts and writes the detached buffers.  The overlap buffers of an Align_Spec
- * are touched by stage 1 only; damar_async_drain() must be called before the blocks or the
- * Align_Spec involved are released, and before the counters are read. */
+/* Asynchronous mode (damar_set_async(1)): the host side runs as a two-stage pipeline behind the GPU (host/tail.cpp):
+ * tails in submission order, then the sort and write of the files.  damar_async_drain() must be called before the
+ * blocks or the Align_Spec involved are released, and before the counters are read. */
 static bool G_tail_reports = false;          /* a tail job writes its number of confirmed hits into the caller's job struct (damar_match with -v) */
-struct TailJob
-{ int kind;                                  /* 0 = tail of one Match_Filter, 1 = write + reset */
-  HostBuf *hb;
-  int  jobid, njobs;                         /* which comparison of the launch whose records hb holds */
-  HITS_DB ablock, bblock;                    /* copies of the block records: the caller may reuse its structs
-                                                (the read tables and bases they point to must stay alive) */
-  int  self, comp;
-  JobParams jp;                              /* the options the comparison ran under */
-  Align_Spec *spec;
-  std::string d1, d2, a, b;
-  bool has1, has2;
-  int  last;
-  damar_write_params wp;                     /* stage 2 */
-  Overlap_IO_Buffer *bufs;
-  int64 *got;                                /* kind 0, -v only: where the caller wants the number of confirmed hits (it drains before it reads) */
-};
-
-/* Heap objects that are never destroyed: at process exit a worker may still be parked in
- * wait(), and destroying a condition variable with a waiter (static destructors) hangs. */
-struct Stage
-{ std::mutex              mu;
-  std::condition_variable cv, idle;
-  std::deque<TailJob *>   queue;
-  int                     busy;              /* jobs taken off the queue and not finished yet */
-  bool                    quit;
-  std::vector<std::thread *> threads;
-  Stage() : busy(0), quit(false) {}
-};
-static Stage &A_s1 = *new Stage();
-static Stage &A_s2 = *new Stage();
-static std::mutex &A_mu = *new std::mutex();            /* the totals below */
-static int64  A_ncheck = 0;
-static double A_tail_ms = 0, A_write_ms = 0, A_d2h_ms = 0;
-
-static void stage_submit(Stage &st, TailJob *job)
-{ { std::lock_guard<std::mutex> lk(st.mu);
-    st.queue.push_back(job);
-  }
-  st.cv.notify_one();
-}
-
-static TailJob *stage_next(Stage &st)
-{ std::unique_lock<std::mutex> lk(st.mu);
-  st.cv.wait(lk, [&st] { return st.quit || !st.queue.empty(); });
-  if (st.queue.empty())
-    return NULL;
-  TailJob *job = st.queue.front();
-  st.queue.pop_front();
-  st.busy += 1;
-  return job;
-}
-
-static void stage_done(Stage &st)
-{ { std::lock_guard<std::mutex> lk(st.mu);
-    st.busy -= 1;
-  }
-  st.idle.notify_all();
-}
-
-static void stage_drain(Stage &st)
-{ std::unique_lock<std::mutex> lk(st.mu);
-  st.idle.wait(lk, [&st] { return st.queue.empty() && st.busy == 0; });
-}
-
-static void tail_worker(void)
-{ for (;;)
-    { TailJob *job = stage_next(A_s1);
-      if (job == NULL)
-        return;
-      double t0 = now_ms();
-      if (job->kind == 0)
-        { if (job->hb->pending)
-            { float ms = 0;
-              HIP_CHECK(hipSetDevice(G_device));          /* the current device is a per-thread setting */
-              HIP_CHECK(hipEventSynchronize(job->hb->e1));
-              HIP_CHECK(hipEventElapsedTime(&ms, job->hb->e0, job->hb->e1));
-              job->hb->pending = false;                   /* (the other comparisons of the launch share the buffer) */
-              std::lock_guard<std::mutex> lk(A_mu);
-              A_d2h_ms += ms;
-              t0 = now_ms();
-            }
-          int64 n = run_tail(job->hb->recs, job->hb->nrec, job->hb->tpool, job->hb->t8,
-                               job->hb->nwide ? job->hb->wmap + job->hb->wm_off[job->jobid] : (const u32 *) NULL, &job->ablock, &job->bblock,
-                             job->self, job->comp, job->spec, job->jp, job->jobid, job->njobs);
-          if (job->got != NULL)
-            *job->got += n;                    /* (summed over a comparison's slabs) */
-          if (--job->hb->users == 0)
-            hostbuf_put(job->hb);
-          delete job;
-          std::lock_guard<std::mutex> lk(A_mu);
-          A_ncheck += n;
-          A_tail_ms += now_ms() - t0;
-        }
-      else
-        { job->bufs = damar_detach_overlap_buffers(job->spec, &job->wp);
-          stage_submit(A_s2, job);
-          std::lock_guard<std::mutex> lk(A_mu);
-          A_tail_ms += now_ms() - t0;
-        }
-      stage_done(A_s1);
-    }
-}
-
-static void write_worker(void)
-{ for (;;)
-    { TailJob *job = stage_next(A_s2);
-      if (job == NULL)
-        return;
-      double t0 = now_ms();
-      damar_write_detached(&job->wp, job->bufs, job->has1 ? job->d1.c_str() : NULL,
-                           job->has2 ? job->d2.c_str() : NULL, job->a.c_str(), job->b.c_str(), job->last);
-      delete job;
-      { std::lock_guard<std::mutex> lk(A_mu);
-        A_write_ms += now_ms() - t0;
-      }
-      stage_done(A_s2);
-    }
-}
-
-static void async_submit(TailJob *job)
-{ stage_submit(A_s1, job);
-}
-
 extern "C" void damar_async_drain(void)
 { if (!A_on)
     return;
   finish_all();
-  stage_drain(A_s1);           /* stage 1 feeds stage 2: drain in pipeline order */
-  stage_drain(A_s2);
+  tail_drain();
 }
 
 extern "C" void damar_set_async(int on)
 { if (on && !A_on)
-    { A_s1.quit = A_s2.quit = false;
-      A_s1.threads.push_back(new std::thread(tail_worker));      /* one: the tails append to the overlap buffers in order */
-      /* the sort + write of a block pair's files is independent of every other pair's: two writers by default
-         (DAMAR_WRITE_THREADS), so that the files of the last pairs are not written one after the other at the drain */
-      { const char *e = getenv("DAMAR_WRITE_THREADS");
-        int n = e ? atoi(e) : 2;
-        if (n < 1) n = 1;
-        if (n > 16) n = 16;
-        for (int i = 0; i < n; i++)
-          A_s2.threads.push_back(new std::thread(write_worker));
-      }
+    { tail_start();
       A_on = true;
     }
   else if (!on && A_on)
     { damar_async_drain();
-      Stage *st[2] = { &A_s1, &A_s2 };
-      for (int i = 0; i < 2; i++)
-        { { std::lock_guard<std::mutex> lk(st[i]->mu);
-            st[i]->quit = true;
-          }
-          st[i]->cv.notify_all();
-          for (std::thread *th : st[i]->threads)
-            { th->join();
-              delete th;
-            }
-          st[i]->threads.clear();
-        }
+      tail_stop();
       A_on = false;
       helpers_join();
     }
@@ -1920,20 +1438,13 @@ extern "C" void damar_async_totals(int64 *ncheck, double *tail_ms, double *write
               Q_ms[2], Q_ms[3], Q_seg[0], Q_seg[2], Q_seg[3]);
       Q_ms[2] = Q_ms[3] = 0;  Q_exit = 0;  Q_seg[0] = Q_seg[2] = Q_seg[3] = 0;
     }
-  std::lock_guard<std::mutex> lk(A_mu);
-  if (ncheck)   *ncheck = A_ncheck;
-  if (tail_ms)  *tail_ms = A_tail_ms;
-  if (write_ms) *write_ms = A_write_ms;
-  A_ncheck = 0;  A_tail_ms = 0;  A_write_ms = 0;
+  tail_totals(ncheck, tail_ms, write_ms);
 }
 
 /* milliseconds the downloads of the asynchronous mode took since the last call (drains first) */
 extern "C" double damar_async_d2h_ms(void)
 { damar_async_drain();
-  std::lock_guard<std::mutex> lk(A_mu);
-  double v = A_d2h_ms;
-  A_d2h_ms = 0;
-  return v;
+  return tail_d2h_ms();
 }
 
 /***** Match_Filter **********************************************************************************/
@@ -2762,6 +2273,7 @@ static const ReportOpts &report_opts(void)
   return o;
 }
 
+static std::mutex &A_mu = *new std::mutex();      /* the four totals below (the tail keeps its own: host/tail.cpp) */
 static int64   A_nfilt = 0;                        /* totals of the asynchronous mode (damar_async_counts) */
 static int64   W_tot[3] = { 0, 0, 0 };             /* band cells, wave steps per pass, wave-loop iterations (damar_wave_totals) */
 static double  A_report_ms = 0;
@@ -3023,13 +2535,15 @@ static void report_hand_over(Pending &pd, const u32 *hc, HostBuf *hb)
           tj->kind = 0;
           tj->hb = hb;  tj->jobid = j;  tj->njobs = n;
           tj->ablock = *jb.ablock;  tj->bblock = *jb.bblock;
-          tj->self = jb.self;  tj->comp = jb.comp;  tj->spec = jb.spec;  tj->jp = c.fr.jp;
+          tj->self = jb.self;  tj->comp = jb.comp;  tj->spec = jb.spec;
+          tj->symmetric = c.fr.jp.symmetric;  tj->hgap_min = c.fr.jp.hgap_min;
           tj->got = (G_tail_reports && c.orig != NULL) ? &c.orig->counts[2] : NULL;   /* (only for a caller that drains before its job struct goes: damar_match) */
-          async_submit(tj);
+          tail_submit(tj);
         }
       else
         { double t0 = now_ms();
-          const int64 got = run_tail(hb->recs, hb->nrec, hb->tpool, hb->t8, hb->nwide ? hb->wmap + hb->wm_off[j] : (const u32 *) NULL, jb.ablock, jb.bblock, jb.self, jb.comp, jb.spec, c.fr.jp, j, n);
+          const int64 got = damar_host_tail(hb->recs, hb->nrec, hb->tpool, hb->t8, hb->nwide ? hb->wmap + hb->wm_off[j] : (const u32 *) NULL, jb.ablock, jb.bblock,
+                                            jb.self, jb.comp, jb.spec, c.fr.jp.symmetric, c.fr.jp.hgap_min, j, n, 0);
           if (c.orig != NULL)
             c.orig->counts[2] += got;
           if (--hb->users == 0)
@@ -3038,7 +2552,7 @@ static void report_hand_over(Pending &pd, const u32 *hc, HostBuf *hb)
         }
     }
   for (TailJob *w : pd.writes)                   /* the files of these comparisons: behind their tails */
-    async_submit(w);
+    tail_submit(w);
   pd.writes.clear();
 }
 
@@ -3111,7 +2625,7 @@ extern "C" void damar_write_overlaps(Align_Spec *spec, const char *d1, const cha
             return;
           }
     }
-  async_submit(job);
+  tail_submit(job);
 }
 
 /* SURVEY 8(d)'s secondary unit of K6, counted by the packed report kernel itself (scalar adds in its wave loop): band
@@ -3545,29 +3059,7 @@ extern "C" void damar_match_self(const HITS_DB *ablock, damar_dev_block *blk, Al
   damar_index_free(ix);
 
   /* host tail: scrub/tandem.c:1140-1166 (fusion/containment only, A records only) */
-  std::sort(recs.begin(), recs.end(), RecOrder());
-  Overlap_IO_Buffer *obuf = OVL_IO_Buffer(spec);
-  std::vector<damar_path> am;
-  damar_tpool tp = { NULL, 0, 0 };
-  size_t i = 0;
-  while (i < recs.size())
-    { size_t j = i;
-      while (j < recs.size() && recs[j].item == recs[i].item)
-        j += 1;
-      am.clear();  tp.top = 0;
-      for (size_t q = i; q < j; q++)
-        { const LaRecord &r = recs[q];
-          damar_path p;
-          p.tlen = r.atlen;  p.diffs = r.diffs;
-          p.abpos = r.abpos;  p.bbpos = r.bbpos;  p.aepos = r.aepos;  p.bepos = r.bepos;
-          p.toff = damar_tpool_push(&tp, tpool.data() + r.toff, r.atlen);
-          am.push_back(p);
-        }
-      const int ar = recs[i].aread + ablock->ufirst;
-      damar_emit_pair(am.data(), (int) am.size(), NULL, 0, &tp, 0, ts, ar, ar, NULL, obuf, &ncheck);
-      i = j;
-    }
-  free(tp.val);
+  ncheck = damar_host_tail(recs.data(), recs.size(), tpool.data(), 0, NULL, ablock, ablock, 1, 0, spec, 0, 0, 0, 1, 1);
   G_cnt[0] = n;  G_cnt[2] = nfilt;  G_cnt[3] = hc[DAMAR_CNT_RECS];
   if (counts)
     { counts[0] = n;  counts[1] = nfilt;  counts[2] = ncheck; }

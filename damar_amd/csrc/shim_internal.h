@@ -1,5 +1,5 @@
 /* shim_internal.h -- what the tool stages (stage.h, stages/ *.hip) take from the core of the shim (shim.hip): the seed
- * stream, the device's properties, bring-up, the clock, the radix sort's error word, the layout of a block on the
+ * stream, the device's properties, bring-up, the radix sort's error word, the layout of a block on the
  * device and of a Work_Data.  These names are shared inside libdamar_hip.so and are no part of its interface: they
  * are hidden.  Nothing else of shim.hip's file scope belongs here.
  */
@@ -16,6 +16,7 @@ extern "C" {
 #include "damar_hip.h"
 #include "host/damar_host.h"
 }
+#include "host/tail.h"               /* DAMAR_INTERNAL, die(), now_ms() */
 
 struct damar_dev_block
 { DevBlock d;
@@ -35,14 +36,11 @@ struct WorkData                        /* what a Work_Data * points to */
   std::vector<int>    script;          /* Compute_Trace_PTS */
 };
 
-#define DAMAR_INTERNAL __attribute__((visibility("hidden")))      /* shared by the library's sources, not exported */
-
 DAMAR_INTERNAL extern hipStream_t     G_st;       /* the seed stream: every launch and copy of a tool stage is on it */
 DAMAR_INTERNAL extern hipDeviceProp_t G_prop;
 
 DAMAR_INTERNAL void   ensure_init(void);          /* the device brought up, once */
 DAMAR_INTERNAL void   late_streams(void);         /* before the first use of G_copy / G_rep / G_ctl: the start-up thread joined */
-DAMAR_INTERNAL double now_ms(void);               /* wall clock */
 DAMAR_INTERNAL void   sort_check(const void *sw); /* behind a radix sort on G_st: its error word queued for sort_verify */
 
 #endif

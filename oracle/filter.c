@@ -426,6 +426,9 @@ void oracle_report(const HITS_DB *ablock, const HITS_DB *bblock, const OSeed *hi
   damar_tpool tp = { NULL, 0, 0 };
   Overlap_IO_Buffer *obuf = OVL_IO_Buffer(spec);
   int64 nfilt = 0, ncheck = 0;
+#ifdef ORACLE_HOSTTAIL
+  int64 pairno = 0;             /* read pairs in the order of the reference: the records' work item */
+#endif
   int64 beg = 0;
 
 #define PAIR(i) (((uint64) (uint32) hits[i].bread << 32) | (uint32) hits[i].aread)
@@ -512,7 +515,12 @@ void oracle_report(const HITS_DB *ablock, const HITS_DB *bblock, const OSeed *hi
                         if (ae > lasta[d])
                           lasta[d] = ae;
                       if ((apath.aepos - apath.abpos) + (apath.bepos - apath.bbpos) >= prm->minover)
-                        { if (doA)
+                        {
+#ifdef ORACLE_HOSTTAIL          /* the product's tail makes both views of the record itself */
+                          oracle_ht_record(&apath, bpath.tlen, atr, btr, ar, br, (unsigned int) pairno, (unsigned int) na++);
+                          (void) doA; (void) doB; (void) nb; (void) amax; (void) bmax;
+#else
+                          if (doA)
                             { if (na >= amax)
                                 { amax = (int) (1.2 * na) + 100;
                                   am = (damar_path *) realloc(am, sizeof(damar_path) * (size_t) amax);
@@ -534,6 +542,7 @@ void oracle_report(const HITS_DB *ablock, const HITS_DB *bblock, const OSeed *hi
                               bm[nb].toff = damar_tpool_push(&tp, btr, bpath.tlen);
                               nb += 1;
                             }
+#endif
                         }
                     }
                   for (f = lidx; f < nidx; f++)         /* pass 3: reset touched buckets */
@@ -555,13 +564,22 @@ void oracle_report(const HITS_DB *ablock, const HITS_DB *bblock, const OSeed *hi
                 }
             }
           (void) started;
+#ifdef ORACLE_HOSTTAIL
+          pairno += 1;
+          (void) bctx;
+#else
           bctx.aseq = aln.aseq; bctx.bseq = aln.bseq; bctx.alen = alen; bctx.blen = blen;
           damar_emit_pair(am, na, bm, nb, &tp, comp, ts, ar + ablock->ufirst, br + bblock->ufirst,
                           &bctx, obuf, &ncheck);
+#endif
         }
       beg = end;
     }
 #undef PAIR
+#ifdef ORACLE_HOSTTAIL
+  (void) obuf;
+  oracle_ht_compare(ablock, bblock, self, comp, spec, prm->symmetric, prm->hgap_min, 0, &ncheck);
+#endif
   free(store); free(atr); free(btr); free(am); free(bm); free(tp.val);
   if (nfilt_out)  *nfilt_out = nfilt;
   if (ncheck_out) *ncheck_out = ncheck;

@@ -117,6 +117,19 @@ int oracle_compute_trace_mid(const char *aseq, int alen, const char *bseq, int b
 /* Redundancy handling (filter.c:1573-2077): the oracle's own statement in oracle/redundancy.c, behind the interface of
  * damar_amd/csrc/host/damar_host.h (the product's is damar_amd/csrc/host/redundancy.c and is not linked here). */
 
+#ifdef ORACLE_HOSTTAIL
+/* The *_hosttail binaries (oracle/hosttail.cpp): the front above hands every alignment it keeps over as a LaRecord and
+ * the comparison's records go through the PRODUCT's whole tail (damar_amd/csrc/host/tail.cpp); the files are written
+ * through it as well.  How the records are handed over is set from the environment (hosttail.cpp). */
+void oracle_ht_record(const Path *apath, int btlen, const uint16 *atr, const uint16 *btr,
+                      int aread, int bread, unsigned int item, unsigned int seq);
+void oracle_ht_compare(const HITS_DB *ablock, const HITS_DB *bblock, int self, int comp, Align_Spec *spec,
+                       int symmetric, int hgap_min, int no_bridge, int64 *ncheck);
+void oracle_ht_write(Align_Spec *spec, char *d1, char *d2, char *aroot, char *broot, int last);
+void oracle_ht_drain(void);              /* before a block that a comparison read changes or goes */
+int  oracle_ht_spec_threads(void);       /* overlap buffers the Align_Spec is to have */
+#endif
+
 #ifdef __cplusplus
 }
 #endif

@@ -88,7 +88,14 @@ int main(int argc, char *argv[])
     make_dir(d);
     free(d);
   }
+#ifdef ORACLE_HOSTTAIL
+  spec = New_Align_Spec(ecorr, spacing, ablock.freq, oracle_ht_spec_threads(), prm.symmetric, only_id, notrace, 1);
+#define Write_Overlap_Buffer oracle_ht_write          /* (with the reset; behind the tails where they are queued) */
+#define Reset_Overlap_Buffer(spec)
+#else
   spec = New_Align_Spec(ecorr, spacing, ablock.freq, 1, prm.symmetric, only_id, notrace, 1);
+#define oracle_ht_drain()
+#endif
   aidx = oracle_sort_kmers(&ablock, &prm, &alen);
 
   for (i = optind; i < argc; i++)
@@ -108,6 +115,7 @@ int main(int argc, char *argv[])
           oracle_match_filter(&ablock, &bblock, aidx, alen, bidx, blen, 0, 0, &prm, spec, cnt, &st);
           if (verbose) printf("N %s x %s: %lld hits %lld seeds %lld confirmed\n", aroot, broot, (long long) cnt[0], (long long) cnt[1], (long long) cnt[2]);
           free(bidx);
+          oracle_ht_drain();                   /* (the block is complemented in place) */
           damar_complement_block(&bblock, 1);
           bidx = oracle_sort_kmers(&bblock, &prm, &blen);
           oracle_match_filter(&ablock, &bblock, aidx, alen, bidx, blen, 0, 1, &prm, spec, cnt, &st);
@@ -119,6 +127,7 @@ int main(int argc, char *argv[])
           if (bblock.part > 0) d2 = damar_get_dir(runid, bblock.part);
           Write_Overlap_Buffer(spec, d1, d2, aroot, broot, last);
           Reset_Overlap_Buffer(spec);
+          oracle_ht_drain();
           free(d1); free(d2); free(broot);
           damar_close_block(&bblock);
         }
@@ -131,10 +140,12 @@ int main(int argc, char *argv[])
           oracle_match_filter(&ablock, cblock, aidx, alen, bidx, blen, 1, 1, &prm, spec, cnt, &st);
           if (verbose) printf("C %s x %s: %lld hits %lld seeds %lld confirmed\n", aroot, aroot, (long long) cnt[0], (long long) cnt[1], (long long) cnt[2]);
           free(bidx);
+          oracle_ht_drain();
           free(((char *) cblock->bases) - 1);
           if (ablock.part > 0) d1 = damar_get_dir(runid, ablock.part);
           Write_Overlap_Buffer(spec, d1, NULL, aroot, aroot, ablock.ufirst + ablock.nreads - 1);
           Reset_Overlap_Buffer(spec);
+          oracle_ht_drain();
           free(d1);
         }
     }

@@ -43,7 +43,11 @@ int main(int argc, char *argv[])
       if (damar_read_block(argv[i], &blk))
         return 1;
       root = damar_root(argv[i], ".db");
+#ifdef ORACLE_HOSTTAIL
+      spec = New_Align_Spec(ecorr, spacing, blk.freq, oracle_ht_spec_threads(), 1, 0, 0, 0);
+#else
       spec = New_Align_Spec(ecorr, spacing, blk.freq, 1, 1, 0, 0, 0);
+#endif
       oracle_match_self(&blk, &prm, spec, cnt, NULL);
       if (verbose)
         printf("%s: %lld k-mers, %lld seed hits, %lld confirmed\n", root, (long long) cnt[0], (long long) cnt[1], (long long) cnt[2]);

@@ -133,7 +133,12 @@ void oracle_match_self(const HITS_DB *block, const OParams *prm, Align_Spec *spe
                 if (ae > lasta[d])
                   lasta[d] = ae;
               if ((apath.aepos - apath.abpos) + (apath.bepos - apath.bbpos) >= prm->minover)
-                { if (na >= amax)
+                {
+#ifdef ORACLE_HOSTTAIL
+                  oracle_ht_record(&apath, bpath.tlen, atr, btr, r, r, (unsigned int) r, (unsigned int) na++);
+                  continue;
+#endif
+                  if (na >= amax)
                     { amax = (int) (1.2 * na) + 100;
                       am = (damar_path *) realloc(am, sizeof(damar_path) * (size_t) amax);
                     }
@@ -170,8 +175,14 @@ void oracle_match_self(const HITS_DB *block, const OParams *prm, Align_Spec *spe
               lasta[d] = 0;
             }
         }
+#ifndef ORACLE_HOSTTAIL
       damar_emit_pair(am, na, NULL, 0, &tp, 0, ts, r + block->ufirst, r + block->ufirst, NULL, obuf, &ncheck);
+#endif
     }
+#ifdef ORACLE_HOSTTAIL          /* datander's rule: the A block on both sides, A records only, no bridges */
+  (void) obuf;
+  oracle_ht_compare(block, block, 1, 0, spec, 0, 0, 1, &ncheck);
+#endif
   free(dist); free(koff); free(store); free(atr); free(btr); free(am); free(tp.val);
   if (counts)
     { counts[0] = kmers; counts[1] = nfilt; counts[2] = ncheck; }

@@ -27,9 +27,7 @@ def test_product_host_tail_behind_the_oracle_front_matches_reference_las(built, 
     against the reference's files, where there is no GPU (oracle/oracle_daligner_hosttail, oracle/Makefile)."""
     exe = os.path.join(ROOT, "oracle", "oracle_daligner_hosttail")
     case = read_case(name)
-    if case.get("tool", "daligner") != "daligner":
-        pytest.skip("a datander case: no bridges there (scrub/tandem.c:767-850)")
-    run_cli(exe, case, str(tmp_path))
+    run_cli(exe, case, str(tmp_path))          # (through the product's whole tail, host/tail.cpp: tests/test_host_tail.py)
     assert compare_las(case, str(tmp_path)) == []
 
 
