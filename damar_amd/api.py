@@ -1538,3 +1538,58 @@ def dust_track(db, window=64, thresh=2.0, minlen=10, biased=False):
     if L.damar_dust_track(db.encode(), C.byref(p), st):
         raise RuntimeError("damar_dust_track failed")
     return dict(zip(("reads", "host_reads", "intervals", "bases", "steps", "walk_steps"), list(st)))
+
+
+# ---- the overlap graph of a filtered file (OGbuild) ------------------------------------------------------------------
+
+class GraphResult(C.Structure):         # include/damar_graph.h damar_graph_result
+    _fields_ = [("nreads", C.c_int), ("loff", C.POINTER(c_int64)), ("roff", C.POINTER(c_int64)), ("left", _PI), ("right", _PI),
+                ("status", C.POINTER(C.c_ubyte)), ("cnt_left", c_int64), ("cnt_right", c_int64), ("edges", c_int64), ("redges", c_int64),
+                ("symdiscard", c_int64), ("parallel", c_int64), ("removed", c_int64), ("neg_rec", c_int64), ("nneg", c_int64),
+                ("neg", C.POINTER(c_int64))]
+
+
+class OgOpts(C.Structure):              # include/damar_graph.h damar_og_opts
+    _fields_ = [("split", C.c_int), ("contained", C.c_int), ("track", C.c_char_p), ("format", C.c_char_p), ("prio", C.c_char_p)]
+
+
+OG_EDGE_INTS = 9                        # a b ab ae bb be flags ovh diffs
+
+
+def og_build(db, las, out, split=False, contained=0, trim="trim", fmt="graphml", prio="ovl"):
+    """OGbuild on one filtered .las file: the overlap graph written to `out` (split: one file per component), the reference's
+    lines on stdout.  -> its exit status."""
+    L = _lib()
+    L.damar_og_build.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(OgOpts)]
+    o = OgOpts(1 if split else 0, int(contained), trim.encode(), fmt.encode(), prio.encode())
+    return int(L.damar_og_build(db.encode(), las.encode(), out.encode(), C.byref(o)))
+
+
+def og_edges(db, las, trim="trim"):
+    """The edges OGbuild makes of a file before -c: dict of loff, roff (int64[nreads + 1]), left, right (int32[n, 9]: a b ab ae
+    bb be flags ovh diffs), status (uint8[nreads]) and the counters of the run."""
+    import numpy as np
+    L = _lib()
+    L.damar_og_edges.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(GraphResult)]
+    L.damar_graph_result_free.argtypes = [C.POINTER(GraphResult)]
+    r = GraphResult()
+    if L.damar_og_edges(db.encode(), las.encode(), trim.encode(), C.byref(r)):
+        raise RuntimeError("damar_og_edges failed")
+    try:
+        n = r.nreads
+        out = dict(loff=np.ctypeslib.as_array(r.loff, shape=(n + 1,)).copy(), roff=np.ctypeslib.as_array(r.roff, shape=(n + 1,)).copy(),
+                   status=np.ctypeslib.as_array(r.status, shape=(n,)).copy())
+        for k, off in (("left", out["loff"]), ("right", out["roff"])):
+            m = int(off[n])
+            out[k] = (np.ctypeslib.as_array(getattr(r, k), shape=(max(m, 1) * OG_EDGE_INTS,))[:m * OG_EDGE_INTS].copy().reshape(m, OG_EDGE_INTS))
+        for k in ("cnt_left", "cnt_right", "edges", "redges", "symdiscard", "parallel", "removed", "neg_rec"):
+            out[k] = int(getattr(r, k))
+        return out
+    finally:
+        L.damar_graph_result_free(C.byref(r))
+
+
+def og_last():
+    """Of the last OGbuild session, summed over its batches: ({upload, piles, finish, download} ms, records, candidate edges,
+    reads the host routine finished beside the kernel, edges kept)."""
+    return _last("graph", 4, ("upload", "piles", "finish", "download"))

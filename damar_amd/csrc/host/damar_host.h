@@ -226,6 +226,7 @@ int  damar_track_read_a2(const char *dbpath, const char *track, int nreads, uint
 int  damar_exact_box(const char *A, int M, const char *B, int N, int *script, int *slen);
 int  damar_trim_on_host(void);                                   /* DAMAR_TRIM=host */
 void damar_piles_rest(const damar_pile_reader *r, const int **diffs, const int **last_word);
+const int *damar_piles_tlen(const damar_pile_reader *r);
 
 /* trim.c: LAtrim (scrub/LAtrim.c, lib/trim.c) as a call: every record of `las` cut back to what the trim track keeps of
    both reads, written to `out` in file order (purge: without the records that end up discarded).  0, or 1 after a message. */

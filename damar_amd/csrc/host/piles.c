@@ -114,7 +114,8 @@ struct damar_pile_reader
   int    pend_aread;
   int64 *pile_off;
   int   *pile_aread;
-  int   *col[8];               /* abpos aepos bbpos bepos bread flags, then diffs and the record's last word (damar_piles_rest) */
+  int   *col[9];               /* abpos aepos bbpos bepos bread flags, then diffs and the record's last word (damar_piles_rest),
+                                  and the number of trace values (damar_piles_tlen) */
   /* traces on (damar_piles_open_traces): the records' trace bytes as they lie in the file, back to back */
   int    traces;
   int64  tbound;               /* bytes of trace a batch holds at most, a pile alone in its batch excepted */
@@ -206,7 +207,7 @@ void damar_piles_close(damar_pile_reader *r)
     return;
   if (r->f) fclose(r->f);
   free(r->pile_off);  free(r->pile_aread);
-  for (i = 0; i < 8; i++) free(r->col[i]);
+  for (i = 0; i < 9; i++) free(r->col[i]);
   free(r->rtrace);  free(r->tbuf);  free(r->toff);  free(r->tlen);
   free(r);
 }
@@ -221,7 +222,7 @@ static int piles_next(damar_pile_reader *r, damar_pile_batch *b)
   memset(b, 0, sizeof(*b));
   r->ttop = 0;
   if (r->pend > 0)
-    { for (i = 0; i < 8; i++)
+    { for (i = 0; i < 9; i++)
         memmove(r->col[i], r->col[i] + r->pstart, sizeof(int) * (size_t) r->pend);
       if (r->traces)
         { const int64 t0 = r->toff[r->pstart];
@@ -251,7 +252,7 @@ static int piles_next(damar_pile_reader *r, damar_pile_batch *b)
       do
         { if (n >= r->cap)
             { r->cap = r->cap + r->cap / 4 + 1024;
-              for (i = 0; i < 8; i++)
+              for (i = 0; i < 9; i++)
                 r->col[i] = (int *) damar_grow(r->col[i], sizeof(int) * (size_t) r->cap, "piles");
               if (r->traces)
                 { r->toff = (int64 *) damar_grow(r->toff, sizeof(int64) * (size_t) r->cap, "piles");
@@ -274,6 +275,7 @@ static int piles_next(damar_pile_reader *r, damar_pile_batch *b)
           r->col[2][n] = r->rec[3];  r->col[3][n] = r->rec[5];      /* bbpos bepos */
           r->col[4][n] = r->rec[8];  r->col[5][n] = r->rec[6];      /* bread flags */
           r->col[6][n] = r->rec[1];  r->col[7][n] = r->rec[9];      /* diffs, the word behind bread */
+          r->col[8][n] = r->rec[0];
           n += 1;
           got = next_record(r);
           if (got < 0)
@@ -321,6 +323,10 @@ void damar_piles_rest(const damar_pile_reader *r, const int **diffs, const int *
 { *diffs = r->col[6];
   *last_word = r->col[7];
 }
+
+/* the trace values of a batch's records, with or without the traces themselves: with tbytes (1 for a trace spacing of 125
+   or less, else 2) what tells where in the file a record lies (OGbuild's progress lines) */
+const int *damar_piles_tlen(const damar_pile_reader *r) { return r->col[8]; }
 
 /* the next batch with its traces: record i's tlen[i] values of tbytes bytes begin at trace + trace_off[i] */
 int damar_piles_next_traces(damar_pile_reader *r, damar_trace_batch *t)

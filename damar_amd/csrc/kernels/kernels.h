@@ -513,6 +513,42 @@ typedef struct
 
 void damar_launch_pile_patch(const FixArgs *a, hipStream_t st);
 
+/* graph_edges.hip: the edges of OGbuild's overlap graph (touring/OGbuild.c).  A candidate edge as the pile kernel appends it */
+#define GE_INTS 16                  /* e[9] (a b ab ae bb be flags ovh diffs), owner, right | slot << 1 | live << 3, ra, rb, pad, seq lo, seq hi */
+enum { GC_NCAND, GC_NPROBE, GC_NEG, GC_EDGES, GC_REDGES, GC_SYM, GC_PARALLEL, GC_LEFT, GC_COUNT };
+typedef struct
+{ u32 npiles, nrec, nreads;
+  const long long *pile_off;  const int *pile_aread;
+  const int *abpos, *aepos, *bbpos, *bepos, *bread, *flags, *diffs;
+  u64  first_rec;                     /* of the batch, in the file */
+  const int *read_len, *trim;         /* [nreads], [2 * nreads] */
+  /* resident across the batches of a file */
+  u32 *status;                        /* [nreads] DAMAR_OG_CONTAINED, later DAMAR_OG_PROPER or-ed in */
+  int *minfirst, *hasfirst;           /* [nreads] the symmetric discards: smallest B among a pile's, B read seen */
+  int *cand;   u64 cand_cap;          /* GE_INTS per candidate */
+  u64 *probe;  u64 probe_cap;         /* A << 32 | B of the records the building pass asks the discards for */
+  u64 *ctr;                           /* [GC_COUNT] */
+  /* the finishing kernels */
+  u64  ncand, nprobe;
+  u64 *key;  u32 *val;                /* the sort's keys and values */
+  const u32 *val_in;
+  int  rbits;                         /* bits of a read number */
+  u32 *beg, *end;                     /* [2 * nreads] a list's stretch of the sorted candidates: left lists, then right lists */
+  u32 *keep;                          /* [ncand] */
+  const u32 *pos;                     /* exclusive scan of keep */
+  u32 *kcount;                        /* [2 * nreads] edges a list keeps */
+  u32 *hostread;                      /* [nreads] 1: a side over maxdeg, all its edges kept for the host routine */
+  int  maxdeg;
+  int *out;                           /* 9 ints per kept edge */
+} GraphArgs;
+void damar_launch_graph_count(const GraphArgs *a, hipStream_t st);      /* what a batch will append: ctr[GC_NCAND], ctr[GC_NPROBE] += */
+void damar_launch_graph_emit(const GraphArgs *a, hipStream_t st);       /* the same pass, appending (the counters reset to the fill before) */
+void damar_launch_graph_settle(const GraphArgs *a, hipStream_t st);     /* discards applied, statuses, key = file order */
+void damar_launch_graph_keys(const GraphArgs *a, hipStream_t st);       /* key = list, b, zeros first, in the order of val_in */
+void damar_launch_graph_bounds(const GraphArgs *a, hipStream_t st);
+void damar_launch_graph_reads(const GraphArgs *a, hipStream_t st);
+void damar_launch_graph_gather(const GraphArgs *a, hipStream_t st);
+
 /* tile_consensus.hip: the consensus of tiles, one lane per tile.  Task i is tile order[i] of the batch (the host sorts by
    weight and leaves out the empty tiles and those with a sequence over its limit); its sequences are [ent_off[t],
    ent_off[t + 1]).  Lane l of the grid works in work + l * stripe: 5 * maxcols count bytes, maxcols match codes,
