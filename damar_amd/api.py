@@ -488,7 +488,7 @@ def pile_tandem(piles, read_len, read_flags, min_len=0):
 
 
 _PHASES = ("upload", "kernel", "download", "call")
-_STAGES = ("trace", "pile", "q", "box", "tbox", "gap", "fix", "filter", "correct", "read", "dust")
+_STAGES = ("trace", "pile", "q", "box", "tbox", "gap", "fix", "filter", "correct", "read", "dust", "separate")
 
 
 def _last(stage, ncnt, names=_PHASES):
@@ -502,7 +502,7 @@ def _last(stage, ncnt, names=_PHASES):
 
 def release(stage):
     """Frees the device buffers and events a call family keeps between calls: damar_<stage>_release, stage one of
-    trace, pile, q, box, tbox, gap, fix, filter, correct, read, dust (a homogenize session is released by closing it)."""
+    trace, pile, q, box, tbox, gap, fix, filter, correct, read, dust, separate (a homogenize session is released by closing it)."""
     if stage not in _STAGES:
         raise ValueError("no stage %r" % (stage,))
     f = getattr(_lib(), "damar_%s_release" % stage)
@@ -951,6 +951,77 @@ def gap_las(db, las, out, stitch=0, purge=False, trim=None, exclude=None, repeat
     res = {k: int(getattr(st, k)) for k, _ in GapStats._fields_ if k != "trim"}
     res["trim"] = {k: int(getattr(st.trim, k)) for k, _ in TrimStats._fields_}
     return res
+
+
+# ---- the overlaps of a block pair split by their chains (LAseparate) --------------------------------------------------
+
+class SeparateParams(C.Structure):     # include/damar_hip.h damar_separate_params
+    _fields_ = [("rep_anno", C.POINTER(C.c_uint64)), ("rep_data", _PI), ("rep_ndata", c_int64), ("kind", C.c_int), ("twidth", C.c_int), ("rep_checked", C.c_int)]
+
+
+class ChainOut(C.Structure):           # include/damar_hip.h damar_chain_out
+    _fields_ = [(k, _PI) for k in ("flags", "nchains", "proper", "nbest", "best")]
+
+
+class SeparateStats(C.Structure):      # host/damar_host.h damar_separate_stats
+    _fields_ = [(k, c_int64) for k in ("novl", "written", "written_discard", "kept", "discarded", "groups", "host_groups", "multi")]
+
+
+def separate_limits():
+    """(records, chains) a group may have for kernels/pile_chains.hip to do it: DAMAR_SEPARATE_MAXGROUP, DAMAR_SEPARATE_MAXCHAINS"""
+    group, chains = C.c_int(0), C.c_int(0)
+    f = _lib().damar_separate_limits
+    f.argtypes, f.restype = [_PI, _PI], None
+    f(C.byref(group), C.byref(chains))
+    return group.value, chains.value
+
+
+def pile_chains(batch, read_len, rep_anno, rep_data, twidth, kind):
+    """LAseparate's work on a batch of whole piles (the dict of _batch; rep_anno, rep_data: the repeat track of the whole
+    database, byte offsets and {begin, end} pairs, or None for no track): -> (flags int32[nrec] as the reference's first
+    pass leaves them, OVL_TEMP included, and per group in file order (number of chains, members of the best chain in chain
+    order as indices into the group, whether it was found proper)).  On the GPU, a lane per group, unless DAMAR_PILES=host
+    is set."""
+    import numpy as np
+    L = _lib()
+    b, keep = _batch(batch, read_len, np.zeros(len(read_len), dtype=np.int32))
+    p = SeparateParams(None, None, 0, int(kind), int(twidth), 0)
+    if rep_anno is not None:
+        keep["rep_anno"] = np.ascontiguousarray(rep_anno, dtype=np.uint64)
+        keep["rep_data"] = np.ascontiguousarray(rep_data, dtype=np.int32)
+        if len(keep["rep_anno"]) != b.nreads + 1:
+            raise ValueError("the repeat track holds one offset per read and one more")
+        p.rep_anno = keep["rep_anno"].ctypes.data_as(C.POINTER(C.c_uint64))
+        p.rep_data = keep["rep_data"].ctypes.data_as(_PI)
+        p.rep_ndata = len(keep["rep_data"])
+    cols = np.zeros((5, max(b.nrec, 1)), dtype=np.int32)
+    out = ChainOut(*[cols[i].ctypes.data_as(_PI) for i in range(5)])
+    L.damar_pile_chains.argtypes = [C.POINTER(PileBatch), C.POINTER(SeparateParams), C.POINTER(ChainOut)]
+    if L.damar_pile_chains(C.byref(b), C.byref(p), C.byref(out)):
+        raise RuntimeError("damar_pile_chains failed")
+    flags, nchains, proper, nbest, best = (c[:b.nrec] for c in cols)
+    heads = np.flatnonzero(nchains >= 0)
+    ends = np.append(heads[1:], b.nrec)
+    groups = [(int(nchains[g]), [int(x) for x in best[g:g + min(int(nbest[g]), int(e - g))]], bool(proper[g])) for g, e in zip(heads, ends)]
+    return flags.copy(), groups
+
+
+def separate_last():
+    """Of the last pile_chains / of the last batch of separate_las: ({upload, kernel, download, call} ms, groups, groups the
+    host routine did beside the kernel, groups of more than one record)."""
+    return _last("separate", 3)
+
+
+def separate_las(db, las, out, out_discard, kind=0, repeats="rep"):
+    """LAseparate on one .las file: the records the verdict of `kind` (-T) keeps written to `out`, the others to
+    `out_discard`; repeats: the track of repeat intervals.  The reference's lines go to stdout.  -> the counters of the run
+    (host_groups: groups the host routine did beside the kernel)."""
+    L = _lib()
+    st = SeparateStats()
+    L.damar_separate_las.argtypes = [C.c_char_p] * 5 + [C.c_int, C.POINTER(SeparateStats)]
+    if L.damar_separate_las(db.encode(), las.encode(), out.encode(), out_discard.encode(), repeats.encode(), int(kind), C.byref(st)):
+        raise RuntimeError("damar_separate_las failed")
+    return {k: int(getattr(st, k)) for k, _ in SeparateStats._fields_}
 
 
 # ---- reads patched from their piles (LAfix) -------------------------------------------------------------------------

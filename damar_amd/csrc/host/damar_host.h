@@ -274,6 +274,22 @@ typedef struct
 void damar_gap_no_track(const char *track);      /* the reference's two lines for a track that cannot be loaded */
 int  damar_gap_las(const char *db, const char *las, const char *out, const damar_gap_params *p, damar_gap_stats *st);
 
+/* separate.c: LAseparate (scrub/LAseparate.c) -- the plain routine behind damar_pile_chains (DAMAR_PILES=host, and the
+   groups the kernel leaves), the check both paths share, and the pass over a file. */
+int  damar_separate_inputs_valid(const damar_pile_batch *b, const damar_separate_params *p, const damar_chain_out *out);     /* 0 after a message */
+/* one group: the n records from `first` on of pile `pile`; one pile: its groups */
+void damar_host_chain_group(const damar_pile_batch *b, int64 pile, int64 first, int n, const damar_separate_params *p, damar_chain_out *out);
+void damar_host_chain_pile(const damar_pile_batch *b, int64 pile, const damar_separate_params *p, damar_chain_out *out);
+typedef struct
+{ int64 novl, written, written_discard;
+  int64 kept, discarded;                   /* the reference's counters of its first pass */
+  int64 groups, host_groups, multi;        /* summed over the batches: damar_separate_last's counts */
+} damar_separate_stats;
+/* the pass over a file, read once: per batch of whole piles damar_pile_chains, the records the verdict keeps written to
+   `out` and the others to `out_discard`, the reference's lines of both its passes on stdout.  0, or 1 after a message. */
+int  damar_separate_las(const char *db, const char *las, const char *out, const char *out_discard, const char *track, int kind,
+                        damar_separate_stats *st);
+
 /* fix.c: LAfix (scrub/LAfix.c without -X and -f) -- the plain routine behind damar_pile_patches (DAMAR_PILES=host, and the
    piles the kernel leaves), the checks both paths share, and the pass over a file. */
 typedef struct { damar_fix_gap *g; int64 n, cap; } damar_fix_list;

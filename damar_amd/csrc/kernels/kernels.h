@@ -431,6 +431,26 @@ typedef struct
 void damar_launch_pile_gaps(const GapArgs *a, u32 grid, hipStream_t st);      /* min(npiles, grid) workgroups */
 u32  damar_pile_gaps_grid(void);      /* workgroups of the largest launch: beyond that many piles a workgroup does several */
 
+/* pile_chains.hip: LAseparate's chains and verdicts (include/damar_hip.h damar_pile_chains; the DAMAR_SEPARATE_* bounds are
+   defined there).  Two launches over the piles: the first gives every record its repeat counts and the marks of its
+   place in its group and settles the groups of one record, the second chains the groups of two or more.  A group whose
+   first record has status 1 afterwards is the host's: more than maxgroup records, more than maxchains chains. */
+typedef struct
+{ u32 npiles;
+  int kind, twidth, maxgroup, maxchains;
+  const long long *pile_off;          /* [npiles + 1] */
+  const int *pile_aread;              /* [npiles] */
+  const int *abpos, *aepos, *bbpos, *bepos, *bread, *flags;       /* [nrec] */
+  const int *read_len;                /* [nreads] */
+  const u64 *rep_anno;                /* [nreads + 1] byte offsets into rep_data, NULL: no repeat track */
+  const int *rep_data;
+  int *arep, *brep;                   /* [nrec]: the first launch's, for the second */
+  int *o_flags, *o_nchains, *o_proper, *o_nbest, *o_best, *status;     /* [nrec] */
+} ChainArgs;
+
+void damar_launch_pile_chains(const ChainArgs *a, u32 grid, hipStream_t st);    /* both launches, min(npiles, grid) workgroups each */
+u32  damar_pile_chains_grid(void);
+
 /* dust.hip: DBdust's mask, one wavefront per piece of a read (include/damar_hip.h damar_dust_reads; the DAMAR_DUST_* bounds
    are defined there).  Piece q is the starts from piece_first[q] on of read piece_read[q]; the pieces of read i are
    [read_piece[i], read_piece[i + 1]).  damar_launch_dust_pieces leaves nint[i] pairs per read at the head of its first

@@ -426,6 +426,41 @@ void damar_gap_limits(int *bins, int *events);     /* DAMAR_GAP_MAXBINS, DAMAR_G
  * cnt[3] = piles, piles the host routine did beside the kernel, break events */
 void damar_gap_last(double *ms, int64 *cnt);
 
+/* The overlaps of every (A read, B read) chained and judged (scrub/LAseparate.c chain() and separate_handler).  A group is
+ * the run of one B read inside a pile.  Per group of two or more records: the records contained in an earlier one on both
+ * reads marked OVL_CONT, then chains grown greedily from the record with the most non-repeat bases until no record is left,
+ * the chains ordered by length; the best chain decides by `kind` (-T) whether the group is proper.  kind 0: a proper group
+ * is discarded whole, another kept whole (OVL_DISCARD taken off).  kind 1: a group of exactly one, proper chain keeps what
+ * the chaining left, every other group is discarded whole.  A group of one record is judged by that record.  out->flags
+ * receives every record's flags word as the first pass of the reference leaves it, OVL_TEMP included; at the first record
+ * of a group out->nchains, out->proper and out->nbest receive the number of chains, the verdict and the length of the best
+ * chain (-1 at the group's other records), and out->best from there on the best chain's members in chain order as indices
+ * into the group (a chain longer than its group -- a gap filler of under 100 bases taken twice -- is cut to the group's
+ * length there), -1 behind them.  Runs kernels/pile_chains.hip: a lane per record for the repeat counts and the groups of
+ * one, then one wavefront per pile with a lane per group.  A group of more than DAMAR_SEPARATE_MAXGROUP records or with
+ * more than DAMAR_SEPARATE_MAXCHAINS chains is done by the routine of host/separate.c (DAMAR_TEST_SEPARATE_GROUP and
+ * DAMAR_TEST_SEPARATE_CHAINS lower the two, for tests), with DAMAR_PILES=host all are.  A group of two or more records
+ * that all come with OVL_CONT or OVL_DISCARD is refused with a message (the reference aborts on it).  0 on success. */
+#define DAMAR_SEPARATE_MAXGROUP  64        /* records of a group: its working flags are three 64-bit masks */
+#define DAMAR_SEPARATE_MAXCHAINS 16        /* chains of a group the kernel keeps the ends of */
+typedef struct
+{ const uint64 *rep_anno;                  /* -r: [nreads + 1] byte offsets into rep_data, {begin, end} pairs; NULL: none */
+  const int    *rep_data;
+  int64         rep_ndata;
+  int           kind;                      /* -T: 0 for the repeat-aware overlapper, 1 for the forced alignment */
+  int           twidth;                    /* the file's trace spacing */
+  int           rep_checked;               /* the caller has had this track through a call already: its shape is not looked at again */
+} damar_separate_params;
+typedef struct
+{ int *flags, *nchains, *proper, *nbest, *best;      /* [nrec] each, the caller's */
+} damar_chain_out;
+int  damar_pile_chains(const damar_pile_batch *b, const damar_separate_params *p, damar_chain_out *out);
+void damar_separate_release(void);         /* frees the cached device buffers of damar_pile_chains */
+void damar_separate_limits(int *group, int *chains);     /* DAMAR_SEPARATE_MAXGROUP, DAMAR_SEPARATE_MAXCHAINS as the library was built */
+/* of the last call: ms[4] = upload, kernels, download (HIP events; 0 on the host path), whole call (wall);
+ * cnt[3] = groups, groups the host routine did beside the kernel, groups of more than one record */
+void damar_separate_last(double *ms, int64 *cnt);
+
 /* Repairs of piles (scrub/LAfix.c fix_process without its chimer code): per pile of a trace batch, whose A read is kept
  * from trim[2 * pile] to trim[2 * pile + 1] (the trim track's interval after the flip step of host/fix.c; begin >= end: the
  * pile has no repairs),
